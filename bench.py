@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- one JSON line per run (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W [--workload chain|frontend|turbo|uplink|control|sync]
+    python bench.py --gpus N --steps K --warmup W [--workload chain|frontend|turbo|uplink|control|sync] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).  `--full` adds what
+takes work or runs of its own: per-launch HIP events with the per-kernel, per-stage and roofline figures, the result checks against
+the transmitted bits and the CPU checkers, the W3 turbo, host-pipeline and other-configuration legs, and the CPU baselines.
+`--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy (float32 / float64, a fixed sample where the
+whole is larger than 64 MB); the inputs depend on the arguments only, so two builds compare file by file.
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already resident in
 HBM.  Work is sharded by unit (subframes / code blocks) over ranks with no data-path collective
@@ -227,6 +233,13 @@ class TurboWorkload:
     def value_per_unit(self):
         return self.K / 1e6  # information Mbit per code block
 
+    def outputs(self):
+        """--dump-outputs: the decoded bits of a fixed sample of the step's code blocks."""
+        np = self.np
+        blocks = sample_indices(self.n_cb, 1024)
+        bits = np.stack([self.d_out.download(np.uint8, count=self.K, offset=int(b) * self.K) for b in blocks])
+        return {"decoded_bits_sample": bits.astype(np.float32), "decoded_bits_sample_blocks": blocks.astype(np.float64)}
+
     def config(self, world):
         return {"workload": "W3 turbo decode: K=6144 x %d code blocks per GPU, int8 soft in HBM, %s mode" % (self.n_cb, DECODER.upper()),
                 "K": self.K, "blocks_per_gpu": self.n_cb,
@@ -369,6 +382,20 @@ class ChainWorkload:
 
     def value_per_unit(self):
         return 1.0
+
+    def outputs(self):
+        """--dump-outputs: every allocation's CRC verdict, and the decoded transport blocks (one value per bit, up to each one's TBS) of
+        all nine allocations of a fixed sample of the step's subframes."""
+        np = self.np
+        stride = self.plan.out_stride
+        subs = sample_indices(self.n, 256)
+        bits = np.zeros((len(subs), 9, 3240), np.float32)
+        for j, i in enumerate(subs):
+            b = self.d_out.download(np.uint8, count=9 * stride, offset=int(i) * 9 * stride).reshape(9, stride)
+            for a in range(9):
+                bits[j, a, :(3240 if a < 8 else 1064)] = b[a, :(3240 if a < 8 else 1064)]
+        return {"crc_status": self.d_status.download(np.int32).astype(np.float32), "decoded_bits_sample": bits,
+                "decoded_bits_sample_subframes": subs.astype(np.float64)}
 
     def extra(self, value):
         np = self.np
@@ -667,6 +694,19 @@ class ChainMixedWorkload(ChainWorkload):
         self.info_bits_per_step = int((self.rows[:, 3] * self.mult).sum())
         self.info_bits = self.info_bits_per_step / self.n  # per subframe (mean)
 
+    def outputs(self):
+        """--dump-outputs: every allocation's CRC verdict, and the decoded transport blocks (one value per bit, up to each one's TBS,
+        zero beyond) of a fixed sample of the step's allocations (allocation j of the batch is unique allocation j mod len(rows))."""
+        np = self.np
+        stride = self.plan.out_stride
+        rows = sample_indices(self.n_alloc, 2048)
+        tbs = self.rows[rows % len(self.rows), 3]
+        bits = np.zeros((len(rows), int(self.rows[:, 3].max())), np.float32)
+        for j, a in enumerate(rows):
+            bits[j, :tbs[j]] = self.d_out.download(np.uint8, count=int(tbs[j]), offset=int(a) * stride)
+        return {"crc_status": self.d_status.download(np.int32).astype(np.float32), "decoded_bits_sample": bits,
+                "decoded_bits_sample_allocations": rows.astype(np.float64)}
+
     def extra(self, value):
         import ctypes as C
         np = self.np
@@ -866,6 +906,14 @@ class FrontendWorkload:
     def value_per_unit(self):
         return 1.0
 
+    def outputs(self):
+        """--dump-outputs: a fixed sample of the step's device subframes, the 14 symbol rows and every port's 14 estimate rows (re / im)."""
+        np = self.np
+        nf, p = self.ctx.subframe_floats(self.N_ANT), self.N_ANT
+        units = sample_indices(self.n, 48)
+        sub = np.stack([self.d_sub.download(np.float32, count=nf, offset=int(i) * nf * 4).reshape(2 + 2 * p, 16, 1200)[:, :14] for i in units])
+        return {"subframes_sample": sub, "subframes_sample_units": units.astype(np.float64)}
+
     def extra(self, value):
         """After the clock: a sample of the step's device subframes against the CPU restatement of liblte_phy_get_dl_subframe_and_ce
         (the checker, not the product) -- symbol rows within 1e-5, every port's estimate rows within 1e-4, relative L2."""
@@ -997,6 +1045,17 @@ class UplinkWorkload:
     def value_per_unit(self):
         return 1.0
 
+    def outputs(self):
+        """--dump-outputs: every allocation's CRC verdict, the decoded transport blocks of all UEs of a fixed sample of the step's
+        subframes, and every PRACH occasion's (N_det_pre, det_pre, det_ta)."""
+        np = self.np
+        stride = self.plan.out_stride
+        subs = sample_indices(self.n, 256)
+        bits = np.stack([self.d_out.download(np.uint8, count=self.N_UE * stride, offset=int(i) * self.N_UE * stride).reshape(self.N_UE, stride)[:, :self.TBS]
+                         for i in subs])
+        return {"crc_status": self.d_status.download(np.int32).astype(np.float32), "decoded_bits_sample": bits.astype(np.float32),
+                "decoded_bits_sample_subframes": subs.astype(np.float64), "prach_detections": np.stack(self.prach_last, 1).astype(np.float64)}
+
     def extra(self, value):
         np = self.np
         st = self.d_status.download(np.int32)
@@ -1096,6 +1155,18 @@ class ControlWorkload:
     def value_per_unit(self):
         return 1.0
 
+    def outputs(self):
+        """--dump-outputs: per subframe (rc, CFI, control symbols, DCIs found) and per candidate slot the DCI found there (RNTI, format,
+        MCS, N_prb, first PRB, rv; zero where none was)."""
+        np = self.np
+        rc, cfi, nsym, ndci, dci = self.last
+        d = np.zeros((self.n, 6, 6), np.float64)
+        for i in range(self.n):
+            for k in range(int(ndci[i])):
+                x = dci[6 * i + k]
+                d[i, k] = (x.rnti, x.format, x.mcs, x.alloc.N_prb, x.alloc.prb[0][0], x.alloc.rv_idx)
+        return {"per_subframe": np.stack([rc, cfi, nsym, ndci], 1).astype(np.float64), "dcis": d}
+
     def extra(self, value):
         rc, cfi, nsym, ndci, dci = self.last
         ok = sum(1 for i in range(self.n)
@@ -1173,10 +1244,22 @@ class SyncWorkload:
         self.last = None
 
     def step(self):
+        found = []
         for st in self.starts:
             t = self.ctx.coarse_timing_dev(self.cfg, self.d_cap, None, self.N_SLOTS, start=st)
             ss, n2, ps, th, fo = self.ctx.find_pss_dev(self.cfg, self.d_cap, None, list(t.symb_starts[0]), start=st)
             self.last = (t.n_corr_peaks, n2, self.ctx.find_sss_dev(self.cfg, self.d_cap, None, n2, ss, th, start=st))
+            found.append((t, ps, th, fo, self.last))
+        self.found = found
+
+    def outputs(self):
+        """--dump-outputs: per search position of the step, what the three searches returned: coarse peaks, their frequency offsets
+        and symbol starts; N_id_2, the PSS symbol, threshold and frequency offset; SSS found, N_id_1, frame start and symbol starts."""
+        np = self.np
+        rows = []
+        for t, ps, th, fo, (peaks, n2, (ok, n1, fs, ss)) in self.found:
+            rows.append([peaks] + list(t.freq_offset) + [x for r in t.symb_starts for x in r] + [n2, ps, th, fo, ok, n1, fs] + list(ss))
+        return {"searches": np.array(rows, np.float64)}
 
     def units_per_step(self):
         return self.n
@@ -1273,6 +1356,11 @@ class MultiStream:
         c["streams_per_gpu"] = len(self.parts)
         c["units_per_gpu_per_step"] = self.units_per_step()
         return c
+
+    def outputs(self):
+        if len(self.parts) == 1:
+            return self.parts[0].outputs()
+        return {"stream%d_%s" % (k, name): a for k, p in enumerate(self.parts) for name, a in p.outputs().items()}
 
     def extra(self, value):
         if not hasattr(self.parts[0], "extra"):
@@ -1493,6 +1581,32 @@ def roofline_of(wl, prof, steps):
            {k: round(ms / steps, 4) for k, (nl, ms) in sorted(prof.items(), key=lambda kv: -kv[1][1])}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def sample_indices(n, k, seed=20261016):
+    """k of range(n), sorted: a fixed, seeded sample (the same in every run and every build); all of them when n <= k."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(wl, out_dir, rank, world):
+    """--dump-outputs DIR: what the timed path computed in its last step, as a caller of that path receives it (the workload's outputs(),
+    a fixed sample where the whole would exceed the limit), as DIR/<name>.npy in float32 / float64 (DIR/<name>_rank<r>.npy with several
+    ranks).  The inputs are fixed by the arguments, so the files of two builds compare one for one."""
+    import numpy as np
+    outs = wl.outputs()
+    total = sum(a.nbytes for a in outs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), a)
+
+
 def config_leg(cls, ctx, steps, cpu_budget_s):
     """Another BASELINE config inside the default line (after the timed region, like the turbo legs): the workload at its own default
     size on the same context, `steps` steps between two synchronisations with the per-launch HIP events on, its own `roofline` and
@@ -1676,17 +1790,26 @@ def main():
     ap.add_argument("--oversubscribe", action="store_true", help="--strong: map --gpus N onto the visible devices modulo (testing the multi-device path on one GPU)")
     ap.add_argument("--chunk", type=int, default=2048, help="--strong: subframes per chunk")
     ap.add_argument("--lanes", type=int, default=2, help="--strong: lanes per device (the copies have streams of their own: two lanes double-buffer the kernels; more streams than hardware queues serialise)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-launch HIP events and the roofline, the result checks, the turbo, "
+                                                         "host-pipeline and other-configuration legs and the CPU baselines (without it a run sets up, "
+                                                         "warms up, times the steps and prints the headline line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64, "
+                                                          "at most 64 MB: a fixed, seeded sample of larger outputs)")
     args = ap.parse_args()
 
     global DECODER, CE_MODE, NO_HOST_LEG
     DECODER, CE_MODE, NO_HOST_LEG = args.decoder, args.ce, args.no_host_leg
     if args.strong:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is not available with --strong")
         return strong_run(args)
     maybe_relaunch(args.gpus, sys.argv[1:])
     rank, world, barrier, max_reduce = dist_setup(args.gpus)
     if world > 1:
         NO_HOST_LEG = True  # rank 0's host-pipeline leg would keep the other ranks at the closing barrier: the N-rank wall time is the timed region's
     local_rank = int(os.environ.get("LOCAL_RANK", str(rank)))
+    if args.workload in ("selftest", "chain-setup") and args.dump_outputs:
+        raise SystemExit("bench.py: --workload %s computes nothing on the GPU: no --dump-outputs" % args.workload)
     if args.workload == "selftest":
         return selftest(args, rank, world, barrier, max_reduce)
     if args.workload == "chain-setup":
@@ -1703,7 +1826,8 @@ def main():
     for _ in range(args.warmup):
         wl.step()
     wl.sync()
-    wl.profile(not args.no_kernel_events)  # HIP events around every kernel launch, on the launch stream (two event records per launch)
+    events = args.full and not args.no_kernel_events
+    wl.profile(events)  # --full: HIP events around every kernel launch, on the launch stream (two event records per launch)
     barrier()
     wl.sync()
     t0 = time.perf_counter()
@@ -1715,6 +1839,8 @@ def main():
     elapsed = max_reduce(t1 - t0)
     prof = wl.profile_report()
     wl.profile(False)
+    if args.dump_outputs:
+        dump_outputs(wl, args.dump_outputs, rank, world)
     devices = [local_rank]
     if world > 1:
         import torch.distributed as dist
@@ -1724,7 +1850,7 @@ def main():
             raise SystemExit("bench.py: ranks share a device: %s" % (got,))
         devices = [g[1] for g in got]
 
-    if rank == 0 and args.no_kernel_events:
+    if rank == 0 and not events:  # the headline alone (a plain run, or --full --no-kernel-events)
         units = wl.units_per_step() * world * args.steps
         print(json.dumps({"metric": wl.metric, "value": round(units * wl.value_per_unit() / elapsed, 3), "unit": wl.unit, "n_gpus": world, "steps": args.steps,
                           "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",

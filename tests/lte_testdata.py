@@ -1,10 +1,46 @@
 """Seeded synthetic inputs shared by the tests (uses the oracle's encoder -- test side only)."""
+import os
+
 import numpy as np
 import pytest
 
 # Collect a CPU-only checker test twice: unmarked (the `-m "not gpu"` suite) and marked `gpu` (the driver's `-m gpu` run on the GPU
 # box), so that the tests which tie the CPU checkers to the compiled reference are proven where the kernels they underwrite run.
 on_both_boxes = pytest.mark.parametrize("box", ["cpu", pytest.param("gpu_box", marks=pytest.mark.gpu)])
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLDEN_PART_BYTES = 900 * 1024  # a committed file stays below 1 MiB: larger fixtures are stored in numbered parts
+
+
+def save_golden(stem, rec):
+    """Write the arrays of rec as tests/golden/<stem>.<k>.npz (compressed), filling each part in order up to GOLDEN_PART_BYTES."""
+    import io
+    parts, cur, size = [], {}, 0
+    for k, v in rec.items():
+        b = io.BytesIO()
+        np.savez_compressed(b, v)
+        if cur and size + b.tell() > GOLDEN_PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += b.tell()
+    parts.append(cur)
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(GOLDEN, "%s.%d.npz" % (stem, i + 1)), **part)
+    return len(parts)
+
+
+def load_golden(stem):
+    """The arrays of a recorded fixture written by save_golden: tests/golden/<stem>.<k>.npz, k = 1, 2, ... merged into one dict."""
+    out, k = {}, 1
+    while os.path.exists(os.path.join(GOLDEN, "%s.%d.npz" % (stem, k))):
+        with np.load(os.path.join(GOLDEN, "%s.%d.npz" % (stem, k)), allow_pickle=False) as z:
+            out.update({n: z[n] for n in z.files})
+        k += 1
+    if not out:
+        raise FileNotFoundError("tests/golden/%s.1.npz is missing" % stem)
+    return out
 
 
 def turbo_blocks(port, K, n, kind, seed):
@@ -458,7 +494,7 @@ def ref_pbch_decode(R, case):
 
 
 # ---------------------------------------------------------------------------------------------------
-# initial synchronisation: int8 captures written by shim/_build/capture_gen (the reference's TX API), impaired in numpy
+# initial synchronisation: int8 captures written by oracle/_ref/shim/capture_gen (the reference's TX API), impaired in numpy
 
 SYNC_CASES = {
     # name: (fft, N_rb_dl, cell, frames, delay samples prepended, frequency offset Hz, snr_db)
@@ -471,7 +507,7 @@ SYNC_CASES = {
 
 def capture_gen_path():
     import os
-    p = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "shim", "_build", "capture_gen")
+    p = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "shim", "capture_gen")
     return p if os.path.exists(p) else None
 
 

@@ -52,14 +52,14 @@ def test_product_never_touches_the_oracle():
 
 
 def test_own_lifecycle_equals_the_references():
-    """shim/_build/lifecycle_check: the shim's own liblte_phy_init / liblte_phy_update_n_rb_dl / liblte_phy_cleanup against the
+    """oracle/_ref/shim/lifecycle_check: the shim's own liblte_phy_init / liblte_phy_update_n_rb_dl / liblte_phy_cleanup against the
     reference's (linked into the TEST binary under other names): return codes and every field a caller or a replaced entry point reads,
     for every sampling rate x bandwidth x PHICH resource x prefix (liblte_phy.cc:2210-2335, :2592-2647).  Needs no GPU: without one the
     struct simply has no context."""
     import subprocess
-    exe = os.path.join(ROOT, "shim", "_build", "lifecycle_check")
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim", "lifecycle_check")
     if not os.path.exists(exe):
-        pytest.skip("shim/_build/lifecycle_check not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/lifecycle_check not built (needs the reference tree at build time)")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "combinations equal" in r.stdout, r.stdout[-2000:]
 
@@ -70,9 +70,9 @@ def test_scheduler_helpers_equal_the_references():
     desegmentation :9753-9987) against the reference's own, over their whole argument ranges (4.5 million calls): return values and every
     output, including what a failed search leaves untouched and the multi-code-block path's CRC over the caller's buffer.  CPU only."""
     import subprocess
-    exe = os.path.join(ROOT, "shim", "_build", "lifecycle_check")
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim", "lifecycle_check")
     if not os.path.exists(exe):
-        pytest.skip("shim/_build/lifecycle_check not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/lifecycle_check not built (needs the reference tree at build time)")
     r = subprocess.run([exe, "helpers"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "comparisons equal" in r.stdout, r.stdout[-2000:]
 
@@ -85,23 +85,23 @@ def test_transmit_functions_equal_the_references():
     middle for the PBCH; PCFICH + PHICH groups + up to six DCIs per control region for every PHICH resource and port count, with what the call
     writes back into the caller's structs), return codes, and the three transforms (OFDM, SC-FDMA, PRACH) to float rounding.  CPU only."""
     import subprocess
-    exe = os.path.join(ROOT, "shim", "_build", "lifecycle_check")
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim", "lifecycle_check")
     if not os.path.exists(exe):
-        pytest.skip("shim/_build/lifecycle_check not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/lifecycle_check not built (needs the reference tree at build time)")
     r = subprocess.run([exe, "tx"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "comparisons equal" in r.stdout, r.stdout[-3000:]
 
 
 @pytest.mark.parametrize("n_rb,cell,frames", [(6, 17, 4), (25, 301, 3), (100, 77, 2)])
 def test_capture_generator_without_the_references_phy_writes_the_same_file(tmp_path, n_rb, cell, frames):
-    """shim/_build/capture_gen_pure: the capture generator (LTE_fdd_dl_file_gen's sequence of transmit calls: map_pss / _sss / _crs, bch / pdcch /
+    """oracle/_ref/shim/capture_gen_pure: the capture generator (LTE_fdd_dl_file_gen's sequence of transmit calls: map_pss / _sss / _crs, bch / pdcch /
     pdsch channel encode with SIB1, create_dl_subframe, the TBS search) linked with NO object of the reference's PHY -- the shim's own lifecycle
     and the library's host-side transmit functions -- must write the file the all-reference build writes, byte for byte.  CPU only."""
     import subprocess
-    build = os.path.join(ROOT, "shim", "_build")
+    build = os.path.join(ROOT, "oracle", "_ref", "shim")
     ref, own = os.path.join(build, "capture_gen"), os.path.join(build, "capture_gen_pure")
     if not (os.path.exists(ref) and os.path.exists(own)):
-        pytest.skip("shim/_build/capture_gen / capture_gen_pure not built (need the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/capture_gen / capture_gen_pure not built (need the reference tree at build time)")
     a, b = os.path.join(str(tmp_path), "ref.bin"), os.path.join(str(tmp_path), "own.bin")
     subprocess.run([ref, a, str(n_rb), str(cell), str(frames)], check=True, timeout=600, capture_output=True)
     subprocess.run([own, b, str(n_rb), str(cell), str(frames)], check=True, timeout=600, capture_output=True)

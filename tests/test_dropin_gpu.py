@@ -1,6 +1,6 @@
 """GPU: the drop-in claim, end to end.
 
-shim/_build/dropin_gpu is a caller written purely against the reference's liblte_phy API, linked
+oracle/_ref/shim/dropin_gpu is a caller written purely against the reference's liblte_phy API, linked
 against the reference's own objects EXCEPT the three hot-path entry points, which come from
 shim/liblte_phy_shim.cc -> libmi_lte.so (built by shim/Makefile where /root/reference exists; the
 binary travels with the repo snapshot).  Its output must equal what the same caller prints when
@@ -20,9 +20,9 @@ N_PURE_SYMBOLS = 35  # liblte_phy_* functions the build without any reference PH
 
 
 def test_dropin_demo_matches_reference_output():
-    exe = os.path.join(ROOT, "shim", "_build", "dropin_gpu")
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim", "dropin_gpu")
     if not os.path.exists(exe):
-        pytest.skip("shim/_build/dropin_gpu not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/dropin_gpu not built (needs the reference tree at build time)")
     got = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     want = open(os.path.join(ROOT, "tests", "golden", "dropin_demo_reference_cpu.txt")).read().strip().splitlines()
     lines = got.stdout.strip().splitlines()
@@ -229,15 +229,15 @@ def _ul_demo_env(tmp_path):
 def test_uplink_dropin_demo_matches_reference_output(tmp_path):
     """liblte_phy_get_ul_subframe + liblte_phy_pusch_channel_decode + liblte_phy_detect_prach + PUCCH 1/1a/1b through the shim == the
     unmodified reference."""
-    exe = os.path.join(ROOT, "shim", "_build", "dropin_ul_gpu")
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim", "dropin_ul_gpu")
     if not os.path.exists(exe):
-        pytest.skip("shim/_build/dropin_ul_gpu not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/dropin_ul_gpu not built (needs the reference tree at build time)")
     args, env = _ul_demo_args(tmp_path), _ul_demo_env(tmp_path)
     got = subprocess.run([exe] + args, capture_output=True, text=True, timeout=300, env=env)
     assert got.returncode == 0, got.stdout + got.stderr
     lines = got.stdout.strip().splitlines()
     want = open(os.path.join(ROOT, "tests", "golden", "dropin_ul_demo_reference_cpu.txt")).read().strip().splitlines()
-    cpu = os.path.join(ROOT, "shim", "_build", "dropin_ul_cpu")
+    cpu = os.path.join(ROOT, "oracle", "_ref", "shim", "dropin_ul_cpu")
     if os.path.exists(cpu):  # the reference-only build travelled too: it must still print the committed text
         ref_now = subprocess.run([cpu] + args, capture_output=True, text=True, timeout=600, env=env).stdout.strip().splitlines()
         assert ref_now == want
@@ -253,9 +253,9 @@ def test_uplink_dropin_demo_with_no_reference_phy_object_in_the_link(tmp_path):
     root set itself.  Per-UE verdicts, bit counts and hashes of the decoded bits and the PRACH detection must be the all-reference build's.
     (The demo's own PUCCH section BUILDS its resources from the reference's private tables in the struct, which this build leaves empty:
     the PUCCH decoder of this build is checked by `lifecycle_check pucch` below.)"""
-    exe = os.path.join(ROOT, "shim", "_build", "dropin_ul_gpu_pure")
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim", "dropin_ul_gpu_pure")
     if not os.path.exists(exe):
-        pytest.skip("shim/_build/dropin_ul_gpu_pure not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/dropin_ul_gpu_pure not built (needs the reference tree at build time)")
     args, env = _ul_demo_args(tmp_path), _ul_demo_env(tmp_path)
     env.pop("PUCCH_DEMO")
     got = subprocess.run([exe] + args, capture_output=True, text=True, timeout=300, env=env)
@@ -273,9 +273,9 @@ def test_uplink_one_call_per_subframe_prints_the_per_call_lines(tmp_path, exe_na
     """The shim's liblte_phy_ul_subframe_decode (shim/liblte_phy_ext.h: get_ul_subframe + every UE's PUSCH decode as one launch chain with one
     wait, mi_lte_ul_subframe_decode_host) inside the same uplink caller: its per-UE lines -- verdict, bit count, hash of the decoded bits --
     are the per-call sequence's, which are the all-reference build's (the tests above)."""
-    exe = os.path.join(ROOT, "shim", "_build", exe_name)
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim", exe_name)
     if not os.path.exists(exe):
-        pytest.skip("shim/_build/%s not built (needs the reference tree at build time)" % exe_name)
+        pytest.skip("oracle/_ref/shim/%s not built (needs the reference tree at build time)" % exe_name)
     args, env = _ul_demo_args(tmp_path), _ul_demo_env(tmp_path)
     env.pop("PUCCH_DEMO", None)
     env["UL_DEMO_ONE_CALL"] = "1"
@@ -295,10 +295,10 @@ def test_enodeb_tti_receive_and_transmit_prints_the_references_lines(tmp_path, e
     a downlink assignment + an uplink grant sized by the TBS searches, get_n_cce, the SR configuration, PDSCH, create_dl_subframe).  That is every
     liblte_phy function LTE_fdd_enodeb calls.  The build with the receive chains on the GPU, and the build with NO object of the reference's PHY in
     its link (transmit side and helpers from libmi_lte.so's host code), print what the all-reference build prints -- incl. the hash of the samples."""
-    build = os.path.join(ROOT, "shim", "_build")
+    build = os.path.join(ROOT, "oracle", "_ref", "shim")
     exe, cpu = os.path.join(build, exe_name), os.path.join(build, "dropin_ul_cpu")
     if not (os.path.exists(exe) and os.path.exists(cpu)):
-        pytest.skip("shim/_build/%s / dropin_ul_cpu not built (need the reference tree at build time)" % exe_name)
+        pytest.skip("oracle/_ref/shim/%s / dropin_ul_cpu not built (need the reference tree at build time)" % exe_name)
     for sf in (0, 4, 5):
         args, env = _ul_demo_args(tmp_path), _ul_demo_env(tmp_path)
         args[3] = str(sf)  # (the capture was made for another subframe number: the PUSCH verdicts are whatever the reference's are, and the same)
@@ -314,13 +314,13 @@ def test_enodeb_tti_receive_and_transmit_prints_the_references_lines(tmp_path, e
 
 
 def test_pucch_decoder_of_the_build_without_the_reference_phy():
-    """`shim/_build/lifecycle_check pucch` (a TEST binary that links the reference's PHY under other names): 360 PUCCH format 1 / 1a / 1b
+    """`oracle/_ref/shim/lifecycle_check pucch` (a TEST binary that links the reference's PHY under other names): 360 PUCCH format 1 / 1a / 1b
     resources built from the tables the REFERENCE's liblte_phy_ul_init computed, decoded by the reference on its struct and by the
     own-lifecycle shim on a struct of its own, whose decoder asks mi_lte_ul_pucch_tables instead of reading tables out of the struct.
     Error code, bit count and bits equal for every resource (three cell configurations, mixed and unmixed resource blocks)."""
-    exe = os.path.join(ROOT, "shim", "_build", "lifecycle_check")
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim", "lifecycle_check")
     if not os.path.exists(exe):
-        pytest.skip("shim/_build/lifecycle_check not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/lifecycle_check not built (needs the reference tree at build time)")
     r = subprocess.run([exe, "pucch"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "decodes equal" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
 
@@ -331,10 +331,10 @@ def test_cell_scan_matches_reference_output(tmp_path, n_rb, cell, frames, fs):
     coarse timing, PSS, SSS, PBCH, PDCCH, PDSCH -- over an int8 capture written by capture_gen (the reference's TX API).
     scan_gpu = the scanner linked against the reference's objects with the hot-path entry points replaced by the shim;
     its report (cell id, MIB, SIB1, SIB2 fields, transport-block counts) must equal the all-reference build's text."""
-    build = os.path.join(ROOT, "shim", "_build")
+    build = os.path.join(ROOT, "oracle", "_ref", "shim")
     gen, scan_gpu, scan_cpu = (os.path.join(build, n) for n in ("capture_gen", "scan_gpu", "scan_cpu"))
     if not (os.path.exists(gen) and os.path.exists(scan_gpu)):
-        pytest.skip("shim/_build/capture_gen / scan_gpu not built (need the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/capture_gen / scan_gpu not built (need the reference tree at build time)")
     cap = os.path.join(str(tmp_path), "capture.bin")
     subprocess.run([gen, cap, str(n_rb), str(cell), str(frames)], check=True, timeout=600)
     want = open(os.path.join(ROOT, "tests", "golden", "scan_%drb_reference_cpu.txt" % n_rb)).read()
@@ -358,10 +358,10 @@ def test_cell_scan_with_no_reference_phy_object_in_the_link(tmp_path, n_rb, cell
     liblte_phy_cleanup and liblte_phy_update_n_rb_dl are the shim's own (liblte_phy_shim.cc, -DMI_LTE_SHIM_OWN_LIFECYCLE), the other
     seven calls of LTE_fdd_dl_file_scan are the replaced entry points.  Its report must equal the all-reference build's text, and the
     executable must not contain a single function of the reference's PHY besides the ones the shim defines."""
-    build = os.path.join(ROOT, "shim", "_build")
+    build = os.path.join(ROOT, "oracle", "_ref", "shim")
     gen, pure = os.path.join(build, "capture_gen"), os.path.join(build, "scan_gpu_pure")
     if not (os.path.exists(gen) and os.path.exists(pure)):
-        pytest.skip("shim/_build/capture_gen / scan_gpu_pure not built (need the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/capture_gen / scan_gpu_pure not built (need the reference tree at build time)")
     cap = os.path.join(str(tmp_path), "capture.bin")
     subprocess.run([gen, cap, str(n_rb), str(cell), str(frames)], check=True, timeout=600)
     want = open(os.path.join(ROOT, "tests", "golden", "scan_%drb_reference_cpu.txt" % n_rb)).read()
@@ -383,10 +383,10 @@ def test_transmit_and_scan_with_no_reference_phy_object_on_either_side(tmp_path,
     """The whole loop of BASELINE config 1 without liblte_phy.cc: capture_gen_pure (the generator on the library's host-side transmit functions)
     writes the capture, scan_gpu_pure (the scanner on the GPU receive chains) reads it -- and prints what the all-reference scanner printed for
     the all-reference generator's file (tests/golden/scan_*_reference_cpu.txt)."""
-    build = os.path.join(ROOT, "shim", "_build")
+    build = os.path.join(ROOT, "oracle", "_ref", "shim")
     gen, pure = os.path.join(build, "capture_gen_pure"), os.path.join(build, "scan_gpu_pure")
     if not (os.path.exists(gen) and os.path.exists(pure)):
-        pytest.skip("shim/_build/capture_gen_pure / scan_gpu_pure not built (need the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/capture_gen_pure / scan_gpu_pure not built (need the reference tree at build time)")
     cap = os.path.join(str(tmp_path), "capture.bin")
     subprocess.run([gen, cap, str(n_rb), str(cell), str(frames)], check=True, timeout=600, capture_output=True)
     want = open(os.path.join(ROOT, "tests", "golden", "scan_%drb_reference_cpu.txt" % n_rb)).read()
@@ -401,10 +401,10 @@ def test_batch_scanner_with_carrier_offset_matches_reference_output(tmp_path, n_
     subframes of a phase, the capture resident in HBM) over captures with a carrier offset and a frame that does not start at sample 0:
     the frequency correction between the synchronisation stages (LTE_fdd_dl_fs_samp_buf.cc:696-713) runs on the device
     (mi_lte_freq_shift_run).  Its report must equal what the all-reference per-call scanner prints for the same file."""
-    build = os.path.join(ROOT, "shim", "_build")
+    build = os.path.join(ROOT, "oracle", "_ref", "shim")
     gen, scan_batch, scan_cpu = (os.path.join(build, n) for n in ("capture_gen", "scan_batch", "scan_cpu"))
     if not (os.path.exists(gen) and os.path.exists(scan_batch) and os.path.exists(scan_cpu)):
-        pytest.skip("shim/_build/capture_gen / scan_batch / scan_cpu not built (need the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/capture_gen / scan_batch / scan_cpu not built (need the reference tree at build time)")
     cap = os.path.join(str(tmp_path), "capture.bin")
     subprocess.run([gen, cap, str(n_rb), str(cell), str(frames), str(cfo), str(lead)], check=True, timeout=600)
     want = subprocess.run([scan_cpu, cap, fs], capture_output=True, text=True, timeout=900)
@@ -428,9 +428,9 @@ def test_one_call_per_subframe_equals_the_per_call_sequence(tmp_path, n_rb, fft,
     import ctypes as C
     import openlte_amd as m
     from openlte_amd.lib import PdcchDci
-    gen = os.path.join(ROOT, "shim", "_build", "capture_gen")
+    gen = os.path.join(ROOT, "oracle", "_ref", "shim", "capture_gen")
     if not os.path.exists(gen):
-        pytest.skip("shim/_build/capture_gen not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/capture_gen not built (needs the reference tree at build time)")
     cap = os.path.join(str(tmp_path), "capture.bin")
     subprocess.run([gen, cap, str(n_rb), str(cell), str(frames)], check=True, timeout=600)
     raw = np.fromfile(cap, np.int8)
@@ -496,10 +496,10 @@ def test_one_call_per_subframe_equals_the_per_call_sequence(tmp_path, n_rb, fft,
 
 def test_cell_scan_under_the_explicit_cache_contract(tmp_path):
     """The 20 MHz scan through the shim with MI_LTE_SHIM_EXPLICIT_CACHE set (no content hash per decode call): same report."""
-    build = os.path.join(ROOT, "shim", "_build")
+    build = os.path.join(ROOT, "oracle", "_ref", "shim")
     gen, scan_gpu = os.path.join(build, "capture_gen"), os.path.join(build, "scan_gpu")
     if not (os.path.exists(gen) and os.path.exists(scan_gpu)):
-        pytest.skip("shim/_build/capture_gen / scan_gpu not built (need the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/capture_gen / scan_gpu not built (need the reference tree at build time)")
     cap = os.path.join(str(tmp_path), "capture.bin")
     subprocess.run([gen, cap, "100", "77", "12"], check=True, timeout=600)
     want = open(os.path.join(ROOT, "tests", "golden", "scan_100rb_reference_cpu.txt")).read()
@@ -589,10 +589,10 @@ def test_scanners_read_gr_complex_captures(tmp_path):
     """LTE_fdd_dl_file_scan reads int8 pairs or gr_complex (LTE_fdd_dl_fs_samp_buf.cc:657-694); so do the three scanners.  The same capture
     as float32 pairs must give the report of the int8 file -- per-call scanner on the shim, batch scanner on the C-ABI (device-side
     de-interleave, mi_lte_iq_f32_pairs_to_planar), and the all-reference build."""
-    build = os.path.join(ROOT, "shim", "_build")
+    build = os.path.join(ROOT, "oracle", "_ref", "shim")
     gen, scan_gpu, scan_cpu, scan_batch = (os.path.join(build, n) for n in ("capture_gen", "scan_gpu", "scan_cpu", "scan_batch"))
     if not all(os.path.exists(x) for x in (gen, scan_gpu, scan_batch)):
-        pytest.skip("shim/_build not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim not built (needs the reference tree at build time)")
     cap = os.path.join(str(tmp_path), "capture.bin")
     subprocess.run([gen, cap, "25", "301", "24"], check=True, timeout=600)
     capf = os.path.join(str(tmp_path), "capture.fc32")

@@ -464,13 +464,13 @@ def test_prach_fuzz_against_the_compiled_reference(ctx, ref):
 
 
 def test_sync_fuzz_against_the_compiled_reference(ctx, ref, tmp_path):
-    """Initial synchronisation: forty random captures from the reference's transmitter (shim/_build/capture_gen) --
+    """Initial synchronisation: forty random captures from the reference's transmitter (oracle/_ref/shim/capture_gen) --
     bandwidth, cell, delay anywhere in a frame, carrier offset up to +-3 kHz, 0 to 20 dB -- through the three searches.  Coarse timing
     bit for bit (peak count, symbol starts, the float frequency offsets), PSS / SSS decisions identical, the PSS threshold within 1e-4
     (tests/test_sync_gpu.compare), for every coarse peak of every capture."""
     import test_sync_gpu as ts
     if td.capture_gen_path() is None:
-        pytest.skip("shim/_build/capture_gen not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/capture_gen not built (needs the reference tree at build time)")
     rng = np.random.default_rng(62 + 100000 * SEED)
     bws = [(128, 6, 18), (256, 15, 14), (512, 25, 12), (2048, 100, 10)]
     n_peaks = n_cells = near_ties = 0

@@ -41,7 +41,7 @@ def test_pbch_matches_reference(ctx, ref, name):
 
 def test_pbch_golden_fixture(ctx):
     """Against outputs of the reference recorded by tools/gen_golden.py (no oracle at run time)."""
-    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "pbch_ref.npz"), allow_pickle=False)
+    g = td.load_golden("pbch_ref")
     for name in [str(x) for x in g["names"]]:
         fft, nrb = [int(x) for x in g[name + "_cfg"]]
         grids = np.zeros((len(g[name + "_cells"]), 10, 16, 1200), np.float32)

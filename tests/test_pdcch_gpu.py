@@ -54,7 +54,7 @@ def test_pdcch_matches_reference(ctx, ref, name):
 def test_pdcch_golden_fixture(ctx):
     """The same comparison against outputs of the reference recorded by tools/gen_golden.py (no oracle at run time)."""
     import os
-    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "pdcch_ref.npz"), allow_pickle=False)
+    g = td.load_golden("pdcch_ref")
     for name in [str(x) for x in g["names"]]:
         fft, nrb, n_ant, cell = [int(x) for x in g[name + "_cfg"]]
         case = dict(fft=fft, nrb=nrb, n_ant=n_ant, cell=cell, phich_res=float(g[name + "_phich_res"]), sfs=g[name + "_sfs"].tolist(),

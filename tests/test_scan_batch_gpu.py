@@ -20,9 +20,9 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 @pytest.mark.parametrize("n_rb,cell,frames,fft", [(6, 17, 30, 128), (25, 301, 24, 512), (100, 77, 12, 2048)])
 def test_batch_scan_agrees_with_the_reference_scanner(ctx, tmp_path, n_rb, cell, frames, fft):
     import scan_batch
-    gen = os.path.join(ROOT, "shim", "_build", "capture_gen")
+    gen = os.path.join(ROOT, "oracle", "_ref", "shim", "capture_gen")
     if not os.path.exists(gen):
-        pytest.skip("shim/_build/capture_gen not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/capture_gen not built (needs the reference tree at build time)")
     cap = os.path.join(str(tmp_path), "capture.bin")
     subprocess.run([gen, cap, str(n_rb), str(cell), str(frames)], check=True, timeout=600, stdout=subprocess.DEVNULL)
     iq = np.fromfile(cap, np.int8).reshape(-1, 2)

@@ -60,7 +60,7 @@ def compare(got, want):
 @pytest.mark.parametrize("name", list(td.SYNC_CASES))
 def test_sync_matches_reference(ctx, ref, tmp_path, name):
     if td.capture_gen_path() is None:
-        pytest.skip("shim/_build/capture_gen not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/shim/capture_gen not built (needs the reference tree at build time)")
     case = td.sync_case(name, tmp_path)
     want = td.ref_sync(ref, case)
     got = gpu_sync(ctx, case)

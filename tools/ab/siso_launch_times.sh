@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../.."
 W=$1; export MI_LTE_SISO1_LDS=$2 MI_LTE_SISO23_LDS=$3; [ -n "$4" ] && export MI_LTE_SISO_ORDER=$4
 D=$(mktemp -d)
-( cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --output-format csv -d $D -o k -- python $OLDPWD/bench.py --workload $W --steps 8 --warmup 2 --no-cpu-baseline > /dev/null 2>&1 )
+( cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --output-format csv -d $D -o k -- python $OLDPWD/bench.py --full --workload $W --steps 8 --warmup 2 --no-cpu-baseline > /dev/null 2>&1 )
 python - "$D" "$W $2 $3 $4" <<'PY'
 import csv, glob, sys, statistics, collections
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]

@@ -94,8 +94,8 @@ def pdcch_vectors(R):
         rows = [[u] + list(r[:7]) + [r[7][0] if r[7] else 0, r[8][-1] if r[8] else 0] for u, w in enumerate(want) for r in w[3]]
         rec[name + "_dci"] = np.array(rows, np.int64).reshape(len(rows), 10)
     rec["names"] = np.array(names)
-    np.savez_compressed(os.path.join(OUT, "pdcch_ref.npz"), **rec)
-    print("pdcch_ref.npz:", {n: rec[n + "_dci"].shape[0] for n in names})
+    n_parts = td.save_golden("pdcch_ref", rec)  # (numbered parts: every committed file stays below 1 MiB)
+    print("pdcch_ref.*.npz (%d parts):" % n_parts, {n: rec[n + "_dci"].shape[0] for n in names})
 
 
 def pbch_vectors(R):
@@ -112,8 +112,8 @@ def pbch_vectors(R):
         rec[name + "_grids"] = case["grids"][:, :, 7:11, :].astype(np.float32)
         rec[name + "_want"] = td.ref_pbch_decode(R, case)
     rec["names"] = np.array(names)
-    np.savez_compressed(os.path.join(OUT, "pbch_ref.npz"), **rec)
-    print("pbch_ref.npz:", {n: rec[n + "_want"].tolist() for n in names})
+    n_parts = td.save_golden("pbch_ref", rec)  # (numbered parts: every committed file stays below 1 MiB)
+    print("pbch_ref.*.npz (%d parts):" % n_parts, {n: rec[n + "_want"].tolist() for n in names})
 
 
 def sync_vectors(R):
@@ -121,7 +121,7 @@ def sync_vectors(R):
     searches over it, per coarse peak."""
     import tempfile
     if td.capture_gen_path() is None:
-        print("sync_ref.npz: skipped (shim/_build/capture_gen not built)")
+        print("sync_ref.npz: skipped (oracle/_ref/shim/capture_gen not built)")
         return
     with tempfile.TemporaryDirectory() as tmp:
         case = td.sync_case("1p4MHz_offset", tmp)

@@ -6,6 +6,7 @@
 set -u
 TAG=${1:-r06}
 cd "$(dirname "$0")/.."
+DEST=${PROFILE_DEST:-profile_out}  # the bench lines of every workload and a copy of the round's tables
 for w in chain chain-mixed frontend uplink; do
   n=${w//-/_}
   bash tools/profile_bench.sh ${TAG}_$n --workload $w > /dev/null 2>&1
@@ -20,8 +21,8 @@ for w in chain chain-mixed uplink; do
   cp gpurun_out/sq_${TAG}_$n.txt profiles/${TAG}_${n}_sq_counters.txt
 done
 python tools/trace_by_shape.py gpurun_out/prof_${TAG}_chain_mixed/trace | grep -v k_rm_rank > profiles/${TAG}_chain_mixed_by_shape.txt
-mkdir -p gpurun_out/bench_$TAG gpurun_out/profiles_$TAG
-cp profiles/${TAG}_* profiles/pmc_traffic_*.json profiles/sq_counters_*.json gpurun_out/profiles_$TAG/ 2>/dev/null
-for w in chain-mixed uplink turbo frontend frontend2 control sync; do python bench.py --workload $w > gpurun_out/bench_$TAG/${w//-/_}.json 2> gpurun_out/bench_$TAG/${w//-/_}.err; done
-python bench.py > gpurun_out/bench_$TAG/chain.json 2> gpurun_out/bench_$TAG/chain.err
-ls gpurun_out/bench_$TAG gpurun_out/profiles_$TAG
+mkdir -p $DEST/bench_$TAG $DEST/profiles_$TAG
+cp profiles/${TAG}_* profiles/pmc_traffic_*.json profiles/sq_counters_*.json $DEST/profiles_$TAG/ 2>/dev/null
+for w in chain-mixed uplink turbo frontend frontend2 control sync; do python bench.py --full --workload $w > $DEST/bench_$TAG/${w//-/_}.json 2> $DEST/bench_$TAG/${w//-/_}.err; done
+python bench.py --full > $DEST/bench_$TAG/chain.json 2> $DEST/bench_$TAG/chain.err
+ls $DEST/bench_$TAG $DEST/profiles_$TAG

@@ -14,7 +14,7 @@ sys.path.insert(0, ROOT)
 import openlte_amd as m  # noqa: E402
 from openlte_amd.lib import PdcchDci  # noqa: E402
 
-gen = os.path.join(ROOT, "shim", "_build", "capture_gen")
+gen = os.path.join(ROOT, "oracle", "_ref", "shim", "capture_gen")
 for n_rb, fft, cell in ((100, 2048, 77), (25, 512, 301), (6, 128, 17)):
     frames = 10
     cap = os.path.join(tempfile.mkdtemp(), "c.bin")

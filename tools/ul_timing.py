@@ -10,5 +10,5 @@ with tempfile.TemporaryDirectory() as d:
     args = t._ul_demo_args(d)
     env = dict(os.environ, UL_DEMO_REPEAT="200", UL_DEMO_ONE_CALL="1")
     for name in ("dropin_ul_gpu", "dropin_ul_gpu", "dropin_ul_gpu_pure", "dropin_ul_cpu"):
-        r = subprocess.run([os.path.join(root, "shim", "_build", name)] + args, capture_output=True, text=True, env=env, timeout=600)
+        r = subprocess.run([os.path.join(root, "oracle", "_ref", "shim", name)] + args, capture_output=True, text=True, env=env, timeout=600)
         print(name, [l for l in r.stderr.splitlines() if l.startswith("timing")])

@@ -10,7 +10,7 @@ with tempfile.TemporaryDirectory() as d:
     env = dict(os.environ, UL_DEMO_REPEAT=str(reps), TMPDIR="/tmp")
     out = os.path.join(d, "tr")
     r = subprocess.run(["rocprofv3", "--kernel-trace", "--hip-trace", "--output-format", "csv", "-d", out, "-o", "t", "--",
-                        os.path.join(root, "shim", "_build", "dropin_ul_gpu")] + args, capture_output=True, text=True, env=env, timeout=600, cwd="/tmp")
+                        os.path.join(root, "oracle", "_ref", "shim", "dropin_ul_gpu")] + args, capture_output=True, text=True, env=env, timeout=600, cwd="/tmp")
     print([l for l in r.stderr.splitlines() if l.startswith("timing")])
     def rows(pat):
         f = glob.glob(out + "/**/" + pat, recursive=True)
