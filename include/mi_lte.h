@@ -157,7 +157,8 @@ typedef struct {
  * and the CRC24A check.  M_dl_harq = 8 and N_soft = 250368 are fixed as in the reference (:3843-3844).
  *
  * Envelope: one code block per transport block (tbs + 24 <= 6144); larger ones make plan_create
- * return MI_LTE_ERR_UNSUPPORTED (the reference's own multi-block path is broken).
+ * return MI_LTE_ERR_UNSUPPORTED (the reference's own multi-block path is broken).  The opt-in 3GPP transport-block
+ * mode below (mi_lte_pdsch_plan_create_3gpp) decodes them as 36.212 specifies.
  *
  * A plan holds the device copy of the allocation list and its grouping by code-block size, so a
  * repeated schedule (the benchmark, or a semi-static grant pattern) pays for planning once.
@@ -204,6 +205,65 @@ int      mi_lte_pdsch_decode_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *plan, const
 /* stage tap: device pointers to the descrambled soft bits (int8) of one allocation and to their count */
 int      mi_lte_pdsch_plan_soft_bits(const mi_lte_pdsch_plan *plan, uint32_t alloc, const int8_t **d_e,
                                      const uint32_t **d_len);
+
+/* ---------------------------------------------------------------- PDSCH, 3GPP transport-block mode (opt-in)
+ * Transport blocks of any size in 36.213 Table 7.1.7.2.1-1, processed as 36.212 specifies rather than as the reference does (its C > 1
+ * path is broken, SURVEY F4, so there is nothing to be bit-exact against).  The plans above keep their single-code-block envelope.
+ *
+ * Segmentation (36.212 5.1.2): B = tbs + 24 (CRC24A, gCRC24A = D^24+D^23+D^18+D^17+D^14+D^11+D^10+D^7+D^6+D^5+D^4+D^3+D+1);
+ *   C = ceil(B / 6120) when B > 6144, else 1; B' = B + 24 C when C > 1; K = the smallest of the 188 turbo sizes with C K >= B'.
+ *   Only F = 0 and C- = 0 is supported (every block has the same K, K C = B', no filler bits), which every size of Table 7.1.7.2.1-1
+ *   satisfies; any other tbs, and tbs > 75376, is MI_LTE_ERR_UNSUPPORTED.  When C > 1 every block ends in CRC24B
+ *   (gCRC24B = D^24+D^23+D^6+D^5+D+1) over its first K - 24 bits; block r carries bits r (K - 24) .. (r + 1)(K - 24) - 1 of the B-bit
+ *   transport block with its CRC24A.
+ * Code-block concatenation (36.212 5.1.4.1.2), N_L = 1 (single-port cells only): G = the allocation's soft-bit count (e_len of the tap
+ *   below; not the reference's E, which is rounded down to a multiple of 2 Q_m), G' = G / Q_m, gamma = G' mod C,
+ *   E_r = Q_m floor(G' / C) for r <= C - gamma - 1, Q_m ceil(G' / C) otherwise; block r reads soft bits [sum_{r' < r} E_r', + E_r).
+ *   G depends on the subframe number (PBCH / PSS / SSS exclusions), so E_r and the offsets are computed on the device at run time.
+ * Soft buffer (36.212 5.1.4.1.2): N_IR = floor(N_soft / (K_MIMO min(M_dl_harq, 8))) (K_C = 1; liblte_phy.cc:11381-11386),
+ *   N_cb = min(floor(N_IR / C), K_w), k0 = R (2 ceil(N_cb / (8 R)) rv + 2), R = ceil((K + 4) / 32), K_w = 96 R.
+ *   N_soft and M_dl_harq are the caller's (mi_lte_dlsch_cfg): there is no default -- the reference's fixed 250368 is a category-1 soft
+ *   buffer, with which a 13-block transport block keeps ~2 400 of its ~17 500 circular-buffer positions and cannot be decoded.
+ * Channel values: every block is rate-un-matched into the interleaved int8 layout d[i*3+x] of mi_lte_turbo_decode_batch (MI_LTE_SOFT_I8):
+ *   repeats summed, then saturated to +-127; positions no soft bit reaches are 0.
+ * Decoder: MI_LTE_TURBO_BCJR (default, 8 iterations), MI_LTE_TURBO_BCJR_EARLY or MI_LTE_TURBO_BCJR_BLOCK, always with the exact 3GPP
+ *   interleaver; mi_lte_pdsch_plan_set_decoder returns MI_LTE_ERR_UNSUPPORTED for MI_LTE_TURBO_REF and MI_LTE_ERR_INVALID_ARG for
+ *   qpp_spec = 0 on such a plan.  The blocks are decoded by the kernels of mi_lte_turbo_decode_batch, one launch set per block size.
+ * Verdict: d_status[a] = 0 when every block's CRC24B and the transport block's CRC24A pass, else 2.  The output row holds the decoded
+ *   payload (tbs bits) whatever the verdict, one bit per byte or packed (mi_lte_pdsch_plan_set_output). */
+typedef struct {
+    uint32_t N_soft;    /* total soft channel bits of the UE category (36.306 Table 4.1-1), e.g. 250368, 1237248, 1827072 */
+    uint32_t M_dl_harq; /* maximum number of DL HARQ processes (8 for FDD) */
+} mi_lte_dlsch_cfg;
+
+#define MI_LTE_DLSCH_MAX_CB 13 /* code blocks of the largest single-layer transport block (75376 bits) */
+typedef struct {
+    uint32_t C, K;                        /* code blocks, their size */
+    uint32_t B;                           /* tbs + 24 */
+    uint32_t N_cb, k0;                    /* soft-buffer size per block and the rv's starting position (k0 before reduction mod N_cb) */
+    uint32_t E[MI_LTE_DLSCH_MAX_CB];      /* E_r */
+    uint32_t off[MI_LTE_DLSCH_MAX_CB];    /* first soft bit of block r in the allocation's stream */
+} mi_lte_dlsch_layout_t;
+
+/* Host arithmetic only: the segmentation and concatenation above for one transport block of tbs bits sent with G soft bits of Q_m bits per
+ * symbol (1, 2, 4, 6; G a multiple of Q_m), transmission mode tx_mode (3, 4, 8, 9: K_MIMO = 2) and redundancy version rv (0..3).
+ * MI_LTE_ERR_UNSUPPORTED for tbs = 0, tbs > 75376 or F != 0; MI_LTE_ERR_INVALID_ARG for malformed arguments or a soft buffer of fewer than
+ * two positions. */
+int mi_lte_dlsch_layout(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t tx_mode, uint32_t rv, const mi_lte_dlsch_cfg *dlsch,
+                        mi_lte_dlsch_layout_t *out);
+/* A static plan in this mode.  mi_lte_pdsch_decode_run, _set_decoder, _set_output, _out_stride, _n_alloc, _soft_bits and _destroy work on
+ * it as on any plan; the output stride covers the plan's largest tbs.  MI_LTE_ERR_UNSUPPORTED: cfg->N_ant != 1, an allocation with
+ * mod_type 0 (BPSK), or a tbs the segmentation above refuses; the other conditions are those of mi_lte_pdsch_plan_create. */
+int mi_lte_pdsch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t N_pdcch_symbs, const mi_lte_dlsch_cfg *dlsch,
+                                  const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, mi_lte_pdsch_plan **out);
+/* 1 when mi_lte_pdsch_plan_create_3gpp accepts this allocation, 0 when it refuses it */
+int mi_lte_pdsch_alloc_decodable_3gpp(const mi_lte_dl_cfg *cfg, const mi_lte_dlsch_cfg *dlsch, const mi_lte_pdsch_alloc *alloc,
+                                      uint32_t N_pdcch_symbs);
+/* stage taps of a 3GPP plan, valid after a run; device pointers owned by the plan.
+ * _cb_soft: allocation alloc's C rate-un-matched blocks, block r at *d_blocks + r * 3 (K + 4), the decoder's int8 input.
+ * _cb_ok:   one uint32 per allocation; bit r set when block r's CRC24B passed (C = 1: bit 0 = the CRC24A verdict). */
+int mi_lte_pdsch_plan_cb_soft(const mi_lte_pdsch_plan *plan, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K);
+int mi_lte_pdsch_plan_cb_ok(const mi_lte_pdsch_plan *plan, const uint32_t **d_mask);
 
 /* ---------------------------------------------------------------- turbo decode
  * Replaces turbo_decode() (liblte/src/liblte_phy.cc:10620-10845) for a batch of code blocks of one
@@ -799,6 +859,17 @@ int    mi_lte_synth_dl_units_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, cons
                                 const uint32_t *h_n_id_cell, uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs,
                                 uint32_t n_alloc, const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits,
                                 uint32_t tbs_stride);
+
+/* DL-SCH transmit side of the 3GPP transport-block mode (36.212 5.1.1-5.1.4.1, the layout of mi_lte_dlsch_layout): CRC24A, segmentation,
+ * CRC24B per block when C > 1, turbo encoding with the exact QPP interleaver, limited-buffer rate matching (N_cb of the layout) and
+ * concatenation of the blocks' E_r bits.  bits: tbs payload bits, one per byte; e_out: G bits, one per byte. */
+int mi_lte_dlsch_encode_3gpp(uint32_t tbs, const uint8_t *bits, uint32_t G, uint32_t Q_m, uint32_t tx_mode, uint32_t rv,
+                             const mi_lte_dlsch_cfg *dlsch, uint8_t *e_out);
+/* mi_lte_synth_dl_units_i8 with that encoder and every resource element of an allocation used (E = G): the input of the 3GPP plans.
+ * Same arguments plus the soft-buffer configuration; any tbs mi_lte_dlsch_layout accepts. */
+int mi_lte_synth_dl_units_3gpp_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
+                                  uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, const mi_lte_dlsch_cfg *dlsch,
+                                  const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride);
 
 /* control regions: PCFICH + n_dci format-1A DCIs (rnti = 0: slot unused) at aggregation level 4 in candidates 0..n_dci-1,
  * standard transmit diversity on cfg->N_ant ports, through a smooth random channel per port (gain_min..gain_max) and

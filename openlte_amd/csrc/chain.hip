@@ -337,6 +337,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
 // ------------------------------------------------------------------------------------------------
 // host side: plans
 
+// the 3GPP transport-block mode's part of a plan (dlsch3gpp.hip)
+struct MiDlsch3;
+int             mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out);
+void            mi_dlsch3_free(MiDlsch3 *g);
+int             mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, const mi_lte_pdsch_alloc *d_allocs, const int8_t *d_e, const uint32_t *d_e_off,
+                              const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t decoder, uint32_t n_iter,
+                              uint32_t packed);
+int             mi_dlsch3_cb_soft(const MiDlsch3 *g, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K);
+const uint32_t *mi_dlsch3_cb_ok(const MiDlsch3 *g);
+
 struct mi_lte_pdsch_plan {
     mi_lte_dl_cfg cfg;
     uint32_t      decoder = MI_LTE_TURBO_REF, n_iter = 8; // MI_LTE_TURBO_BCJR: mi_lte_pdsch_plan_set_decoder
@@ -361,6 +371,7 @@ struct mi_lte_pdsch_plan {
     std::vector<Group>    groups;
     std::vector<uint32_t> h_e_off;
     MiMultiCache          multi; // the merged decode's device tables for `groups` (turbo.hip: mi_turbo_ref_multi)
+    MiDlsch3             *g3 = nullptr; // 3GPP transport-block mode (mi_lte_pdsch_plan_create_3gpp): its code blocks and buffers (dlsch3gpp.hip)
 };
 
 static uint32_t qpp_size_at_least(uint32_t B);
@@ -550,6 +561,68 @@ int mi_lte_pdsch_alloc_decodable(const mi_lte_dl_cfg *cfg, const mi_lte_pdsch_al
     return 1;
 }
 
+int mi_lte_pdsch_alloc_decodable_3gpp(const mi_lte_dl_cfg *cfg, const mi_lte_dlsch_cfg *dlsch, const mi_lte_pdsch_alloc *al, uint32_t N_pdcch_symbs)
+{ // mi_lte_pdsch_alloc_decodable's conditions with the 3GPP segmentation in place of the single-block one
+    if (!cfg || !dlsch || !al || cfg->N_ant != 1 || al->mod_type == 0 || al->mod_type > 3) return 0;
+    mi_lte_dlsch_layout_t lay;
+    if (mi_lte_dlsch_layout(al->tbs, 0, 2, al->tx_mode, al->rv_idx & 3u, dlsch, &lay) != MI_LTE_OK) return 0;
+    mi_lte_pdsch_alloc one = *al;
+    one.tbs = 16;
+    return mi_lte_pdsch_alloc_decodable(cfg, &one, N_pdcch_symbs);
+}
+
+// A static plan in the 3GPP transport-block mode: the demodulator's layout is that of any plan -- it does not depend on the transport block
+// size, so plan_layout lays out a copy of the list with a one-block size in every entry -- and the code blocks are dlsch3gpp.hip's.
+int mi_lte_pdsch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t N_pdcch_symbs, const mi_lte_dlsch_cfg *dlsch,
+                                  const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, mi_lte_pdsch_plan **out)
+{
+    if (!ctx || !cfg || !dlsch || !h_allocs || !out || n_alloc == 0 || N_pdcch_symbs < 1 || N_pdcch_symbs > 4 || dlsch->M_dl_harq == 0) return MI_LTE_ERR_INVALID_ARG;
+    if (cfg->N_ant != 1) { ctx->err = "3GPP transport-block mode: single-port cells only"; return MI_LTE_ERR_UNSUPPORTED; }
+    uint32_t max_tbs = 0;
+    std::vector<mi_lte_pdsch_alloc> one(h_allocs, h_allocs + n_alloc);
+    for (uint32_t a = 0; a < n_alloc; a++) {
+        mi_lte_dlsch_layout_t lay;
+        const int rc = h_allocs[a].mod_type == 0 ? MI_LTE_ERR_UNSUPPORTED : mi_lte_dlsch_layout(h_allocs[a].tbs, 0, 2, h_allocs[a].tx_mode, h_allocs[a].rv_idx & 3u, dlsch, &lay);
+        if (rc != MI_LTE_OK) { ctx->err = "allocation outside the 3GPP transport-block mode (BPSK, F != 0, tbs > 75376 or a soft buffer under 2 positions)"; return rc; }
+        max_tbs  = std::max(max_tbs, h_allocs[a].tbs);
+        one[a].tbs = 16;
+    }
+    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    auto *pl    = new mi_lte_pdsch_plan();
+    auto  guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_lte_pdsch_plan_destroy(nullptr, pl); });
+    pl->cfg     = *cfg;
+    std::vector<uint32_t> cb_alloc;
+    int rc = plan_layout(ctx, pl, N_pdcch_symbs, one.data(), n_alloc, cb_alloc);
+    if (rc != MI_LTE_OK) return rc;
+    pl->groups.clear(); // (the single-block decode's grouping: not used)
+    pl->max_tbs = max_tbs;
+    pl->decoder = MI_LTE_TURBO_BCJR; pl->n_iter = 8; pl->qpp_spec = 1;
+    (void)mi_lte_pdsch_plan_set_output(pl, 0);
+    rc = plan_device_arrays(ctx, pl, n_alloc, pl->e_bytes);
+    if (rc != MI_LTE_OK) return rc;
+    rc = mi_dlsch3_create(ctx, dlsch, h_allocs, n_alloc, &pl->g3);
+    if (rc != MI_LTE_OK) return rc;
+    MI_H2D(ctx, pl->d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
+    MI_H2D(ctx, pl->d_e_off, pl->h_e_off.data(), sizeof(uint32_t) * n_alloc);
+    MI_HIP_CHECK(ctx, mi_stream_wait_polling(ctx));
+    guard.armed = false;
+    *out = pl;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pdsch_plan_cb_soft(const mi_lte_pdsch_plan *pl, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K)
+{
+    if (!pl || !pl->g3) return MI_LTE_ERR_INVALID_ARG;
+    return mi_dlsch3_cb_soft(pl->g3, alloc, d_blocks, C, K);
+}
+
+int mi_lte_pdsch_plan_cb_ok(const mi_lte_pdsch_plan *pl, const uint32_t **d_mask)
+{
+    if (!pl || !pl->g3 || !d_mask) return MI_LTE_ERR_INVALID_ARG;
+    *d_mask = mi_dlsch3_cb_ok(pl->g3);
+    return MI_LTE_OK;
+}
+
 int mi_lte_pdsch_plan_assign(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc)
 {
     if (!ctx || !pl || !pl->dynamic || !h_allocs || n_alloc == 0 || N_pdcch_symbs < 1 || N_pdcch_symbs > 4) return MI_LTE_ERR_INVALID_ARG;
@@ -647,6 +720,7 @@ void mi_lte_pdsch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl)
     if (pl->h_stage) (void)hipHostFree(pl->h_stage);
     if (pl->staged) (void)hipEventDestroy(pl->staged);
     mi_multi_cache_free(&pl->multi);
+    mi_dlsch3_free(pl->g3);
     delete pl;
 }
 
@@ -672,6 +746,8 @@ int mi_lte_pdsch_plan_set_decoder(mi_lte_pdsch_plan *pl, uint32_t mode, uint32_t
 {
     const bool bcjr = mode == MI_LTE_TURBO_BCJR || mode == MI_LTE_TURBO_BCJR_BLOCK || mode == MI_LTE_TURBO_BCJR_EARLY;
     if (!pl || !(mode == MI_LTE_TURBO_REF || bcjr) || (bcjr && (n_iter == 0 || n_iter > 64))) return MI_LTE_ERR_INVALID_ARG;
+    if (pl->g3 && mode == MI_LTE_TURBO_REF) return MI_LTE_ERR_UNSUPPORTED; // (the 3GPP mode: BCJR decoders, exact interleaver)
+    if (pl->g3 && !qpp_spec) return MI_LTE_ERR_INVALID_ARG;
     pl->decoder = mode; pl->n_iter = n_iter; pl->qpp_spec = qpp_spec;
     return MI_LTE_OK;
 }
@@ -715,6 +791,9 @@ int mi_lte_pdsch_decode_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float 
         MI_LAUNCH(ctx, "k_pdsch_demod", k_pdsch_demod<false>, dim3(pl->n_alloc), dim3(threads), lds, d_subframes, g, pl->d_allocs, d_subfr_num,
                   d_n_id_cell, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->max_pairs, words_al, e_cap);
     MI_HIP_CHECK(ctx, hipGetLastError());
+    if (pl->g3)
+        return mi_dlsch3_run(ctx, pl->g3, pl->d_allocs, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits, pl->out_stride, d_status, pl->decoder, pl->n_iter,
+                             pl->packed);
     const bool bcjr = pl->decoder == MI_LTE_TURBO_BCJR || pl->decoder == MI_LTE_TURBO_BCJR_BLOCK || pl->decoder == MI_LTE_TURBO_BCJR_EARLY;
     if (bcjr) {
         size_t soft = 0, bits = 0;

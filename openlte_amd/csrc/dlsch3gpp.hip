@@ -1,0 +1,343 @@
+// 3GPP transport-block mode of the PDSCH plans (mi_lte_pdsch_plan_create_3gpp, include/mi_lte.h): DL-SCH decoding of transport blocks of
+// one to thirteen code blocks as 36.212 5.1.2 (segmentation, CRC24B), 5.1.3 (turbo code) and 5.1.4.1 (rate matching, concatenation)
+// specify.  The reference's own C > 1 path is broken, so this mode is specified by 36.212 alone; the rate-matching geometry
+// is the reference's liblte_phy_rate_unmatch_turbo (liblte_phy.cc:11246-11490) with N_codeblocks = C, which the tests pin it to.
+//
+// After the plan's demodulator (chain.hip, unchanged) has written every allocation's soft bits and their count G:
+//   k_dl3_desc       one thread per code-block slot: E_r, its offset, N_cb and k0 from G (G depends on the subframe: device side)
+//   k_dl3_rm_i8      one workgroup per code block: rate un-matching into the interleaved int8 block the BCJR decoders take
+//   (decode)         mi_lte_turbo_decode_batch's BCJR kernels, one launch set per block size (bcjr.hip, unchanged)
+//   k_dl3_cb_finish  one workgroup per code block: CRC24B, the block's payload into the transport block's output row, its share of the CRC24A
+//   k_dl3_tb_finish  one thread per transport block: the shares combined, status and the per-block CRC mask
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "ctx.hpp"
+
+namespace {
+
+constexpr uint32_t G_CRC24A = 0x1864CFBu; // 36.212 5.1.1, x^24 included
+constexpr uint32_t G_CRC24B = 0x1800063u;
+constexpr uint32_t DL3_E_CAP = 48 * 1024; // LDS a code block stages its soft bits in (larger E_r: read from global memory)
+
+__device__ inline uint32_t k_mimo(uint32_t tx_mode) { return (tx_mode == 3 || tx_mode == 4 || tx_mode == 8 || tx_mode == 9) ? 2u : 1u; }
+__device__ inline uint32_t q_m(uint32_t mod_type) { return mod_type == 3 ? 6u : mod_type == 2 ? 4u : mod_type == 1 ? 2u : 1u; }
+// 36.212 5.1.4.1.2: soft-buffer size per code block and the redundancy version's start, K_C = 1 (the host's copy: mi_lte_dlsch_layout, synth.cc)
+__device__ inline void soft_buffer(uint32_t K, uint32_t C, uint32_t tx_mode, uint32_t rv, uint32_t N_soft, uint32_t M_dl_harq,
+                                            uint32_t &N_cb, uint32_t &k0)
+{
+    const uint32_t R = (K + 4 + 31) / 32, K_w = 96 * R;
+    const uint32_t N_ir = N_soft / (k_mimo(tx_mode) * (M_dl_harq < 8 ? M_dl_harq : 8));
+    N_cb = N_ir / C < K_w ? N_ir / C : K_w;
+    k0   = R * (2 * ((N_cb + 8 * R - 1) / (8 * R)) * rv + 2);
+}
+// x * w mod g for a remainder w < 2^24
+__host__ __device__ inline uint32_t mulx(uint32_t w, uint32_t g) { w <<= 1; return (w & 0x1000000u) ? w ^ g : w; }
+// a * b mod g (Horner over the bits of b)
+__host__ __device__ inline uint32_t mulmod(uint32_t a, uint32_t b, uint32_t g)
+{
+    uint32_t s = 0;
+    for (int i = 23; i >= 0; i--) s = mulx(s, g) ^ (((b >> i) & 1u) ? a : 0u);
+    return s;
+}
+// x^s mod g by squaring
+inline uint32_t xpow(uint32_t s, uint32_t g)
+{
+    uint32_t r = 1, p = 2; // p = x^(2^i)
+    for (; s; s >>= 1, p = mulmod(p, p, g))
+        if (s & 1u) r = mulmod(r, p, g);
+    return r;
+}
+
+// Everything the per-code-block kernels need: the static part from the plan (alloc .. bits_off8), the rest from k_dl3_desc
+struct Dl3Slot { uint32_t alloc, r, C, K, xs, soft_off4, bits_off8, pad; };
+struct Dl3Desc {
+    uint32_t alloc, r, C, K;
+    uint32_t E, off, N_cb, k0;
+    uint32_t tbs, xs, soft_off4, bits_off8; // xs = x^s mod gCRC24A, s = transport-block bits after the block's last payload bit
+};
+
+__global__ __launch_bounds__(256) void k_dl3_desc(const Dl3Slot *__restrict__ slots, uint32_t n_slot, const mi_lte_pdsch_alloc *__restrict__ allocs,
+                                                  const uint32_t *__restrict__ e_len, uint32_t N_soft, uint32_t M_dl_harq, Dl3Desc *__restrict__ out)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_slot) return;
+    const Dl3Slot             sl = slots[s];
+    const mi_lte_pdsch_alloc &al = allocs[sl.alloc];
+    const uint32_t Qm = q_m(al.mod_type), Gp = e_len[sl.alloc] / Qm, gam = Gp % sl.C, lo = Gp / sl.C, C = sl.C, r = sl.r;
+    Dl3Desc d;
+    d.alloc = sl.alloc; d.r = r; d.C = C; d.K = sl.K;
+    d.E   = Qm * (r + gam < C ? lo : lo + 1);                    // r <= C - gamma - 1: floor(G' / C), else ceil
+    d.off = Qm * (r * lo + (r > C - gam ? r - (C - gam) : 0u)); // blocks C - gamma .. r - 1 have one symbol more
+    soft_buffer(sl.K, C, al.tx_mode, al.rv_idx & 3u, N_soft, M_dl_harq, d.N_cb, d.k0);
+    d.tbs = al.tbs; d.xs = sl.xs; d.soft_off4 = sl.soft_off4; d.bits_off8 = sl.bits_off8;
+    out[s] = d;
+}
+
+// Circular-buffer geometry of a block (36.212 5.1.4.1.1-2): the sub-block-interleaved streams column by column, and for every d element
+// its position p and the number of non-NULL positions below it.  Only row 0 of a stream's R x 32 matrix holds NULLs (the N_d head-padding
+// bits), so the count is a popcount over the columns.  The same geometry as turbo.hip's RmGeom, with N_cb and k0 given.
+struct Rm3 {
+    uint32_t R, K_pi, N_d, N_cb, k0m, Nnn, cnt_k0, mask0, mask2;
+    __device__ static uint32_t lowmask(uint32_t n) { return n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u); }
+    __device__ uint32_t nulls_below(uint32_t p) const
+    {
+        if (p <= K_pi) return __popc(mask0 & lowmask((p + R - 1) / R));
+        const uint32_t q = p - K_pi, a = (q + 1) >> 1, b = q >> 1;
+        return __popc(mask0) + __popc(mask0 & lowmask((a + R - 1) / R)) + __popc(mask2 & lowmask((b + R - 1) / R)) + ((b > K_pi - 1) ? 1u : 0u);
+    }
+    __device__ void init(uint32_t D, uint32_t N_cb_, uint32_t k0)
+    {
+        R = (D + 31) / 32; K_pi = 32 * R; N_d = K_pi - D; N_cb = N_cb_; k0m = k0 % N_cb;
+        mask0 = mask2 = 0;
+        for (uint32_t c = 0; c < 32; c++) {
+            const uint32_t P = __brev(c) >> 27; // inter-column permutation = 5-bit reversal (36.212 table 5.1.4-1)
+            if (P < N_d) mask0 |= 1u << c;
+            if (P + 1 < N_d) mask2 |= 1u << c;
+        }
+        Nnn    = N_cb - nulls_below(N_cb);
+        cnt_k0 = k0m - nulls_below(k0m);
+    }
+    // d[i*3+x] -> its position p and the non-NULL count below it
+    __device__ void pos_cnt(uint32_t i, int x, uint32_t &p, uint32_t &cn) const
+    {
+        const uint32_t n = i + N_d - (x == 2 ? 1u : 0u), c = __brev(n & 31) >> 27, r = n >> 5, ii = c * R + r, cc = c + (r > 0 ? 1u : 0u);
+        uint32_t nulls;
+        if (x == 0)      { p = ii;              nulls = __popc(mask0 & lowmask(cc)); }
+        else if (x == 1) { p = K_pi + 2 * ii;     nulls = __popc(mask0) + __popc(mask0 & lowmask(cc)) + __popc(mask2 & lowmask(cc)); }
+        else             { p = K_pi + 2 * ii + 1; nulls = __popc(mask0) + __popc(mask0 & lowmask(c + 1)) + __popc(mask2 & lowmask(cc)); }
+        cn = p - nulls;
+    }
+};
+
+// Rate un-matching of one code block into the decoder's int8 layout d[i*3+x], tail included: position p of the circular buffer receives
+// e[rank(p) + t Nnn], t = 0, 1, .. (rank = non-NULL positions between k0 and p in walk order), summed and then saturated to +-127; a
+// position no soft bit reaches is 0.  The block's E_r soft bits are staged in LDS (aligned dwords) when they fit.
+__global__ __launch_bounds__(256) void k_dl3_rm_i8(const Dl3Desc *__restrict__ desc, const int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off,
+                                                   int8_t *__restrict__ soft, uint32_t e_cap)
+{
+    extern __shared__ __attribute__((aligned(16))) int8_t e_lds[];
+    const Dl3Desc &d = desc[blockIdx.x];
+    const uint32_t K = d.K, D = K + 4, E = d.E, n = 3 * D;
+    Rm3 rm;
+    rm.init(D, d.N_cb, d.k0);
+    const int8_t  *e     = e_base + (size_t)e_off[d.alloc] * 64 + d.off; // (an allocation's slot is 64-byte aligned and padded to 64 bytes)
+    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(e) & 3u);
+    const bool     staged = shift + E <= e_cap;
+    if (staged) {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(e - shift);
+        for (uint32_t w = threadIdx.x; w < (shift + E + 3) / 4; w += blockDim.x) reinterpret_cast<uint32_t *>(e_lds)[w] = src[w];
+    }
+    __syncthreads();
+    const int8_t *es = staged ? e_lds + shift : e;
+    int8_t       *db = soft + (size_t)d.soft_off4 * 4;
+    for (uint32_t t = threadIdx.x; t < n; t += blockDim.x) {
+        const uint32_t i = t / 3;
+        uint32_t       p, cn;
+        rm.pos_cnt(i, (int)(t - 3 * i), p, cn);
+        int v = 0;
+        if (p < rm.N_cb)
+            for (uint32_t k = p >= rm.k0m ? cn - rm.cnt_k0 : rm.Nnn - rm.cnt_k0 + cn; k < E; k += rm.Nnn) v += es[k];
+        db[t] = (int8_t)max(-127, min(127, v));
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
+{
+    for (int o = 32; o > 0; o >>= 1) v ^= (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+// One code block's decisions: CRC24B over its K bits (C > 1), its payload into the output row, and its share of the transport block's
+// CRC24A -- the remainder of its payload bits times x^s, s = the bits that follow them in the transport block -- so that the shares of a
+// transport block XOR to its CRC24A remainder.  tab_a / tab_b: x^e mod g for e < 6144.
+__global__ __launch_bounds__(256) void k_dl3_cb_finish(const Dl3Desc *__restrict__ desc, const uint8_t *__restrict__ c_bits, const uint32_t *__restrict__ tab_a,
+                                                       const uint32_t *__restrict__ tab_b, uint8_t *__restrict__ out_bits, uint32_t out_stride, uint32_t packed,
+                                                       uint32_t *__restrict__ part, uint32_t *__restrict__ ok)
+{
+    __shared__ uint32_t red[2][4];
+    const Dl3Desc &d = desc[blockIdx.x];
+    const uint32_t K = d.K, C = d.C, tbs = d.tbs, nb = C > 1 ? K - 24 : K, q0 = d.r * (K - 24); // (C = 1: q0 = 0)
+    const uint8_t *c = c_bits + (size_t)d.bits_off8 * 8;
+    uint8_t       *o = out_bits + (size_t)d.alloc * out_stride;
+    uint32_t crc_a = 0, crc_b = 0;
+    // eight bits per thread and step (K, nb, q0 and tbs are multiples of 8): one 8-byte read, the weight of the last bit from the table and
+    // the other seven by "times x"
+    for (uint32_t g8 = threadIdx.x; g8 < K / 8; g8 += blockDim.x) {
+        const uint32_t j0 = 8 * g8;
+        const uint2    bb = *reinterpret_cast<const uint2 *>(c + j0);
+        const uint32_t lo = bb.x & 0x01010101u, hi = bb.y & 0x01010101u;
+        const bool     in_a = j0 < nb;
+        uint32_t       wa = in_a ? tab_a[nb - 8 - j0] : 0u, wb = tab_b[K - 8 - j0];
+#pragma unroll
+        for (int k = 7; k >= 0; k--) {
+            const uint32_t m = 0u - (((k < 4 ? lo : hi) >> (8 * (k & 3))) & 1u);
+            crc_a ^= wa & m;
+            crc_b ^= wb & m;
+            if (k > 0) { wa = mulx(wa, G_CRC24A); wb = mulx(wb, G_CRC24B); }
+        }
+        const uint32_t q = q0 + j0; // position in the transport block
+        if (in_a && q < tbs) {
+            if (packed) o[q >> 3] = (uint8_t)((((lo * 0x08040201u) >> 24) & 0xFu) << 4 | (((hi * 0x08040201u) >> 24) & 0xFu)); // first bit most significant
+            else        *reinterpret_cast<uint2 *>(o + q) = make_uint2(lo, hi);
+        }
+    }
+    crc_a = wave_xor(crc_a);
+    crc_b = wave_xor(crc_b);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = crc_a; red[1][threadIdx.x >> 6] = crc_b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t a = 0, b = 0;
+        for (uint32_t w = 0; w < blockDim.x / 64; w++) { a ^= red[0][w]; b ^= red[1][w]; }
+        part[blockIdx.x] = mulmod(a, d.xs, G_CRC24A);
+        ok[blockIdx.x]   = (C == 1 || b == 0) ? 1u : 0u;
+    }
+}
+
+// One thread per transport block: CRC24A = XOR of its blocks' shares, the blocks' CRC24B verdicts as a mask, the status word
+__global__ __launch_bounds__(256) void k_dl3_tb_finish(const uint32_t *__restrict__ a_slot, const uint32_t *__restrict__ a_nc, uint32_t n_alloc,
+                                                       const uint32_t *__restrict__ part, const uint32_t *__restrict__ ok, int32_t *__restrict__ status,
+                                                       uint32_t *__restrict__ cb_ok)
+{
+    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_alloc) return;
+    const uint32_t s0 = a_slot[a], C = a_nc[a];
+    uint32_t rem = 0, mask = 0;
+    for (uint32_t r = 0; r < C; r++) {
+        rem ^= part[s0 + r];
+        mask |= ok[s0 + r] << r;
+    }
+    const bool crc_a = rem == 0;
+    if (C == 1) mask = crc_a ? 1u : 0u;
+    status[a] = (crc_a && mask == (1u << C) - 1u) ? 0 : 2;
+    cb_ok[a]  = mask;
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------
+// host side
+
+struct MiDlsch3 {
+    mi_lte_dlsch_cfg cfg{};
+    uint32_t n_alloc = 0, n_slot = 0;
+    struct Group { uint32_t K, n_cb; size_t soft_off, bits_off; }; // a block size's slots, contiguous; byte offsets into d_soft / d_bits
+    std::vector<Group>    groups;
+    std::vector<uint32_t> a_slot, a_nc, a_K;   // per allocation: first slot, C, K
+    std::vector<size_t>   a_soft;              // per allocation: byte offset of its first block in d_soft
+    Dl3Slot  *d_slot = nullptr;
+    Dl3Desc  *d_desc = nullptr;
+    int8_t   *d_soft = nullptr;
+    uint8_t  *d_bits = nullptr;
+    uint32_t *d_tab = nullptr;                 // x^e mod gCRC24A [6144] | x^e mod gCRC24B [6144]
+    uint32_t *d_a_slot = nullptr, *d_a_nc = nullptr, *d_part = nullptr, *d_ok = nullptr, *d_cb_ok = nullptr;
+};
+
+void mi_dlsch3_free(MiDlsch3 *g)
+{
+    if (!g) return;
+    for (void *p : {(void *)g->d_slot, (void *)g->d_desc, (void *)g->d_soft, (void *)g->d_bits, (void *)g->d_tab, (void *)g->d_a_slot, (void *)g->d_a_nc,
+                    (void *)g->d_part, (void *)g->d_ok, (void *)g->d_cb_ok})
+        if (p) (void)hipFree(p);
+    delete g;
+}
+
+// The plan's code-block slots: grouped by block size (ascending), inside a size allocation after allocation, block after block.
+// mi_lte_pdsch_plan_create_3gpp has checked every allocation against mi_lte_dlsch_layout.
+int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out)
+{
+    auto *g   = new MiDlsch3();
+    auto guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_dlsch3_free(g); });
+    g->cfg     = *cfg;
+    g->n_alloc = n_alloc;
+    g->a_slot.resize(n_alloc); g->a_nc.resize(n_alloc); g->a_K.resize(n_alloc); g->a_soft.resize(n_alloc);
+    for (uint32_t a = 0; a < n_alloc; a++) {
+        mi_lte_dlsch_layout_t lay;
+        const int rc = mi_lte_dlsch_layout(h_allocs[a].tbs, 0, 2, h_allocs[a].tx_mode, h_allocs[a].rv_idx & 3u, cfg, &lay);
+        if (rc != MI_LTE_OK) { ctx->err = "transport block size outside the 3GPP mode (F != 0 or tbs > 75376)"; return rc; }
+        g->a_nc[a] = lay.C; g->a_K[a] = lay.K;
+    }
+    std::vector<uint32_t> order(n_alloc);
+    for (uint32_t a = 0; a < n_alloc; a++) order[a] = a;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return g->a_K[x] < g->a_K[y]; });
+    std::vector<Dl3Slot> slots;
+    size_t soft = 0, bits = 0;
+    for (uint32_t i = 0; i < n_alloc; i++) {
+        const uint32_t a = order[i], K = g->a_K[a], C = g->a_nc[a];
+        if (g->groups.empty() || g->groups.back().K != K) { // a new size: its arrays start on 256 bytes
+            soft = (soft + 255) & ~(size_t)255; bits = (bits + 255) & ~(size_t)255;
+            g->groups.push_back({K, 0, soft, bits});
+        }
+        g->a_slot[a] = (uint32_t)slots.size();
+        g->a_soft[a] = soft;
+        const uint32_t B = h_allocs[a].tbs + 24;
+        for (uint32_t r = 0; r < C; r++) {
+            // x^s mod gCRC24A, s = B - (r + 1)(K - 24) for C > 1 (0 for C = 1): the transport-block bits behind the block's payload
+            const uint32_t xs = xpow(C == 1 ? 0u : B - (r + 1) * (K - 24), G_CRC24A);
+            slots.push_back({a, r, C, K, xs, (uint32_t)(soft / 4), (uint32_t)(bits / 8), 0});
+            soft += 3 * (size_t)(K + 4);
+            bits += K;
+            g->groups.back().n_cb++;
+        }
+        if (soft / 4 > 0xFFFFFFFFull || bits / 8 > 0xFFFFFFFFull) { ctx->err = "3GPP plan too large"; return MI_LTE_ERR_UNSUPPORTED; }
+    }
+    g->n_slot = (uint32_t)slots.size();
+    std::vector<uint32_t> tab(2 * 6144);
+    for (uint32_t e = 0, wa = 1, wb = 1; e < 6144; e++, wa = mulx(wa, G_CRC24A), wb = mulx(wb, G_CRC24B)) { tab[e] = wa; tab[6144 + e] = wb; }
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_slot, sizeof(Dl3Slot) * g->n_slot));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_desc, sizeof(Dl3Desc) * g->n_slot));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_soft, std::max<size_t>(soft, 256)));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_bits, std::max<size_t>(bits, 256)));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_tab, sizeof(uint32_t) * tab.size()));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_a_slot, sizeof(uint32_t) * n_alloc));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_a_nc, sizeof(uint32_t) * n_alloc));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_part, sizeof(uint32_t) * g->n_slot));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_ok, sizeof(uint32_t) * g->n_slot));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_cb_ok, sizeof(uint32_t) * n_alloc));
+    MI_HIP_CHECK(ctx, hipMemsetAsync(g->d_soft, 0, std::max<size_t>(soft, 256), ctx->stream)); // (the taps read defined bytes before a first run)
+    MI_HIP_CHECK(ctx, hipMemsetAsync(g->d_cb_ok, 0, sizeof(uint32_t) * n_alloc, ctx->stream));
+    MI_H2D(ctx, g->d_slot, slots.data(), sizeof(Dl3Slot) * g->n_slot);
+    MI_H2D(ctx, g->d_tab, tab.data(), sizeof(uint32_t) * tab.size());
+    MI_H2D(ctx, g->d_a_slot, g->a_slot.data(), sizeof(uint32_t) * n_alloc);
+    MI_H2D(ctx, g->d_a_nc, g->a_nc.data(), sizeof(uint32_t) * n_alloc);
+    MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    guard.armed = false;
+    *out = g;
+    return MI_LTE_OK;
+}
+
+// everything after the demodulator (chain.hip: mi_lte_pdsch_decode_run on a 3GPP plan)
+int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, const mi_lte_pdsch_alloc *d_allocs, const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len,
+                  uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t decoder, uint32_t n_iter, uint32_t packed)
+{
+    MI_LAUNCH(ctx, "k_dl3_desc", k_dl3_desc, dim3((g->n_slot + 255) / 256), dim3(256), 0, (const Dl3Slot *)g->d_slot, g->n_slot, d_allocs, d_e_len,
+              g->cfg.N_soft, g->cfg.M_dl_harq, g->d_desc);
+    MI_LAUNCH(ctx, "k_dl3_rm_i8", k_dl3_rm_i8, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, d_e, d_e_off, g->d_soft, DL3_E_CAP);
+    MI_HIP_CHECK(ctx, hipGetLastError());
+    for (const auto &gr : g->groups) {
+        const int8_t *s = g->d_soft + gr.soft_off;
+        uint8_t      *b = g->d_bits + gr.bits_off;
+        const int rc = decoder == MI_LTE_TURBO_BCJR_BLOCK ? mi_turbo_bcjr_block_batch(ctx, s, gr.K, gr.n_cb, n_iter, 1, b)
+                                                          : mi_turbo_bcjr_batch(ctx, s, gr.K, gr.n_cb, n_iter, 1, b, decoder == MI_LTE_TURBO_BCJR_EARLY);
+        if (rc != MI_LTE_OK) return rc;
+    }
+    MI_LAUNCH(ctx, "k_dl3_cb_finish", k_dl3_cb_finish, dim3(g->n_slot), dim3(256), 0, (const Dl3Desc *)g->d_desc, (const uint8_t *)g->d_bits,
+              (const uint32_t *)g->d_tab, (const uint32_t *)(g->d_tab + 6144), d_out_bits, out_stride, packed, g->d_part, g->d_ok);
+    MI_LAUNCH(ctx, "k_dl3_tb_finish", k_dl3_tb_finish, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const uint32_t *)g->d_a_slot,
+              (const uint32_t *)g->d_a_nc, g->n_alloc, (const uint32_t *)g->d_part, (const uint32_t *)g->d_ok, d_status, g->d_cb_ok);
+    MI_HIP_CHECK(ctx, hipGetLastError());
+    ctx->last_kernels = "k_pdsch_demod:1,k_dl3_desc:1,k_dl3_rm_i8:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1";
+    return MI_LTE_OK;
+}
+
+int mi_dlsch3_cb_soft(const MiDlsch3 *g, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K)
+{
+    if (!g || alloc >= g->n_alloc || !d_blocks || !C || !K) return MI_LTE_ERR_INVALID_ARG;
+    *d_blocks = g->d_soft + g->a_soft[alloc];
+    *C = g->a_nc[alloc];
+    *K = g->a_K[alloc];
+    return MI_LTE_OK;
+}
+
+const uint32_t *mi_dlsch3_cb_ok(const MiDlsch3 *g) { return g ? g->d_cb_ok : nullptr; }

@@ -44,6 +44,17 @@ void crc24a(const uint8_t *bits, uint32_t n, uint8_t p[24])
     for (int i = 0; i < 24; i++) p[i] = (uint8_t)((rem >> (23 - i)) & 1u);
 }
 
+// 36.212 5.1.1, gCRC24B = D^24+D^23+D^6+D^5+D+1: the parity of a code block of a segmented transport block
+static void crc24b(const uint8_t *bits, uint32_t n, uint8_t p[24])
+{
+    uint32_t rem = 0;
+    for (uint32_t i = 0; i < n + 24; i++) {
+        rem = (rem << 1) | (i < n ? bits[i] : 0u);
+        if (rem & 0x1000000u) rem ^= 0x1800063u;
+    }
+    for (int i = 0; i < 24; i++) p[i] = (uint8_t)((rem >> (23 - i)) & 1u);
+}
+
 bool qpp_params(uint32_t K, uint32_t *f1, uint32_t *f2)
 {
     for (int r = 0; r < LTE_QPP_N_SIZES; r++)
@@ -211,23 +222,82 @@ void idft(std::vector<double> &xr, std::vector<double> &xi)
 
 extern "C" {
 
+// 36.212 5.1.2 (segmentation with F = 0 and C- = 0: C blocks of one size K, K C = B') and 5.1.4.1.2 (soft buffer, code-block concatenation)
+// for the 3GPP transport-block mode: what the transmitter below, the 3GPP plans (chain.hip, dlsch3gpp.hip) and the tests lay a block out by
+int mi_lte_dlsch_layout(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t tx_mode, uint32_t rv, const mi_lte_dlsch_cfg *dlsch, mi_lte_dlsch_layout_t *out)
+{
+    if (!dlsch || !out || !(Q_m == 1 || Q_m == 2 || Q_m == 4 || Q_m == 6) || G % Q_m || rv > 3 || dlsch->M_dl_harq == 0) return MI_LTE_ERR_INVALID_ARG;
+    if (tbs == 0 || tbs > 75376) return MI_LTE_ERR_UNSUPPORTED; // the largest single-layer size of 36.213 Table 7.1.7.2.1-1 (13 blocks)
+    const uint32_t B = tbs + 24, C = B <= 6144 ? 1u : (B + 6119) / 6120, Bp = C == 1 ? B : B + 24 * C;
+    uint32_t K = 0;
+    for (int r = 0; r < LTE_QPP_N_SIZES && !K; r++)
+        if (C * LTE_QPP_ROWS[r].K >= Bp) K = LTE_QPP_ROWS[r].K;
+    if (C * K != Bp) return MI_LTE_ERR_UNSUPPORTED; // filler bits, or blocks of two sizes
+    memset(out, 0, sizeof(*out));
+    out->C = C; out->K = K; out->B = B;
+    const uint32_t R = (K + 4 + 31) / 32, K_w = 96 * R, K_mimo = (tx_mode == 3 || tx_mode == 4 || tx_mode == 8 || tx_mode == 9) ? 2 : 1;
+    const uint32_t N_ir = dlsch->N_soft / (K_mimo * std::min(dlsch->M_dl_harq, 8u));
+    out->N_cb = std::min(N_ir / C, K_w);
+    out->k0   = R * (2 * ((out->N_cb + 8 * R - 1) / (8 * R)) * rv + 2);
+    if (out->N_cb < 2) return MI_LTE_ERR_INVALID_ARG; // (position 1 of the buffer is the first that is never NULL)
+    const uint32_t Gp = G / Q_m, gam = Gp % C, lo = Gp / C;
+    for (uint32_t r = 0, off = 0; r < C; r++) {
+        out->E[r]   = Q_m * (r + gam < C ? lo : lo + 1); // r <= C - gamma - 1: floor(G' / C), else ceil
+        out->off[r] = off;
+        off += out->E[r];
+    }
+    return MI_LTE_OK;
+}
+
+// 36.212 5.1.1-5.1.4.1 for one transport block in the 3GPP mode (include/mi_lte.h): CRC24A, C blocks of K bits (each with CRC24B when
+// C > 1), turbo encoding with the exact interleaver, rate matching with the layout's N_cb and E_r, concatenation
+int mi_lte_dlsch_encode_3gpp(uint32_t tbs, const uint8_t *bits, uint32_t G, uint32_t Q_m, uint32_t tx_mode, uint32_t rv, const mi_lte_dlsch_cfg *dlsch,
+                             uint8_t *e_out)
+{
+    if (!bits || !e_out) return MI_LTE_ERR_INVALID_ARG;
+    mi_lte_dlsch_layout_t lay;
+    const int rc = mi_lte_dlsch_layout(tbs, G, Q_m, tx_mode, rv, dlsch, &lay);
+    if (rc != MI_LTE_OK) return rc;
+    const uint32_t K = lay.K, C = lay.C, nb = C == 1 ? K : K - 24;
+    std::vector<uint8_t> b(lay.B), c(K), d(3 * (K + 4));
+    for (uint32_t i = 0; i < tbs; i++) b[i] = bits[i] & 1u;
+    synth::crc24a(b.data(), tbs, b.data() + tbs);
+    for (uint32_t r = 0; r < C; r++) {
+        memcpy(c.data(), b.data() + (size_t)r * nb, nb);
+        if (C > 1) synth::crc24b(c.data(), nb, c.data() + nb);
+        synth::turbo_encode(c.data(), K, false, d.data());
+        synth::rate_match(d.data(), K + 4, lay.N_cb, rv, lay.E[r], e_out + lay.off[r]);
+    }
+    return MI_LTE_OK;
+}
+
 size_t mi_lte_synth_unit_len(uint32_t fft_size)
 {
     const size_t s = 2048 / (fft_size ? fft_size : 2048);
     return ((30720 + 4400) / s + 15) / 16 * 16;
 }
 
-int mi_lte_synth_dl_units_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num,
-                             const uint32_t *h_n_id_cell, uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs,
-                             uint32_t n_alloc, const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits,
-                             uint32_t tbs_stride)
+} // extern "C"
+
+// The downlink generator behind mi_lte_synth_dl_units_i8 (dlsch == nullptr: the reference transmitter's single-block DL-SCH, E rounded
+// down to a multiple of 2 Q_m) and mi_lte_synth_dl_units_3gpp_i8 (mi_lte_dlsch_encode_3gpp, E = G)
+static int synth_dl_units(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell, uint32_t N_pdcch_symbs,
+                          const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, const mi_lte_dlsch_cfg *dlsch, const mi_lte_synth_channel *chan,
+                          int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride)
 {
     if (!cfg || !h_subfr_num || !h_n_id_cell || !chan || !h_iq || cfg->N_ant != 1 || (n_alloc && !h_allocs)) return MI_LTE_ERR_INVALID_ARG;
     if (!synth::valid_grid(cfg->fft_size, cfg->N_rb_dl) || N_pdcch_symbs < 1 || N_pdcch_symbs > 4) return MI_LTE_ERR_INVALID_ARG;
+    auto valid = [&](const mi_lte_pdsch_alloc &al) {
+        if (!dlsch) return synth::valid_alloc(al, cfg->N_rb_dl);
+        mi_lte_pdsch_alloc one = al;
+        one.tbs = 16; // the grid conditions; the transport block's are the layout's
+        mi_lte_dlsch_layout_t lay;
+        return synth::valid_alloc(one, cfg->N_rb_dl) && al.mod_type != 0 && mi_lte_dlsch_layout(al.tbs, 0, 2, al.tx_mode, al.rv_idx, dlsch, &lay) == MI_LTE_OK;
+    };
     for (uint32_t u = 0; u < n_units; u++) {
         if (h_n_id_cell[u] > 503) return MI_LTE_ERR_INVALID_ARG;
         for (uint32_t a = 0; a < n_alloc; a++)
-            if (!synth::valid_alloc(h_allocs[(size_t)u * n_alloc + a], cfg->N_rb_dl) || (h_tx_bits && h_allocs[(size_t)u * n_alloc + a].tbs > tbs_stride))
+            if (!valid(h_allocs[(size_t)u * n_alloc + a]) || (h_tx_bits && h_allocs[(size_t)u * n_alloc + a].tbs > tbs_stride))
                 return MI_LTE_ERR_INVALID_ARG;
     }
     const uint32_t N = cfg->fft_size, sc = 2048 / N, cp0 = 160 / sc, cpe = 144 / sc, N_rb = cfg->N_rb_dl, half = 6 * N_rb, N_sc = 12 * N_rb;
@@ -270,6 +340,20 @@ int mi_lte_synth_dl_units_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const u
                         const uint32_t scx = al.prb[L / 7][pi] * 12 + j;
                         if (!synth::pdsch_re_excluded(1, cell, sf, L, j, scx, first_sc, last_sc)) res.push_back(L * N_sc + scx);
                     }
+            if (dlsch) { // 3GPP mode: every resource element carries a soft bit
+                const uint32_t G = (uint32_t)res.size() * Qm;
+                std::vector<uint8_t> b(al.tbs), e(G), c(G);
+                for (uint32_t i = 0; i < al.tbs; i++) b[i] = (uint8_t)(rng.next() & 1u);
+                if (h_tx_bits) memcpy(h_tx_bits + ((size_t)u * n_alloc + a) * tbs_stride, b.data(), al.tbs);
+                const int rc = mi_lte_dlsch_encode_3gpp(al.tbs, b.data(), G, Qm, al.tx_mode, al.rv_idx, dlsch, e.data());
+                if (rc != MI_LTE_OK) return rc;
+                synth::gold((al.rnti << 14) | (sf << 9) | cell, G, c.data());
+                for (uint32_t i = 0; i < G; i++) e[i] ^= c[i];
+                std::vector<float> m_re(res.size()), m_im(res.size());
+                synth::modulate(e.data(), (uint32_t)res.size(), al.mod_type, m_re.data(), m_im.data());
+                for (size_t i = 0; i < res.size(); i++) { g_re[res[i]] = m_re[i]; g_im[res[i]] = m_im[i]; }
+                continue;
+            }
             const uint32_t G = (uint32_t)res.size() * Qm, E = G / (2 * Qm) * (2 * Qm); // dlsch_channel_encode with N_l = 2 (:3572-3584)
             const uint32_t B = al.tbs + 24;
             uint32_t       K = 0, f1, f2;
@@ -347,6 +431,24 @@ int mi_lte_synth_dl_units_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const u
         }
     }
     return MI_LTE_OK;
+}
+
+extern "C" {
+
+int mi_lte_synth_dl_units_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num,
+                             const uint32_t *h_n_id_cell, uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs,
+                             uint32_t n_alloc, const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits,
+                             uint32_t tbs_stride)
+{
+    return synth_dl_units(cfg, n_units, h_subfr_num, h_n_id_cell, N_pdcch_symbs, h_allocs, n_alloc, nullptr, chan, h_iq, h_tx_bits, tbs_stride);
+}
+
+int mi_lte_synth_dl_units_3gpp_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
+                                  uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, const mi_lte_dlsch_cfg *dlsch,
+                                  const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride)
+{
+    if (!dlsch) return MI_LTE_ERR_INVALID_ARG;
+    return synth_dl_units(cfg, n_units, h_subfr_num, h_n_id_cell, N_pdcch_symbs, h_allocs, n_alloc, dlsch, chan, h_iq, h_tx_bits, tbs_stride);
 }
 
 

@@ -40,6 +40,27 @@ class PdschAlloc(C.Structure):
                [("prb", (C.c_uint8 * 112) * 2)]
 
 
+class DlschCfg(C.Structure):
+    """mi_lte_dlsch_cfg: the soft-buffer parameters of the 3GPP transport-block mode"""
+    _fields_ = [("N_soft", C.c_uint32), ("M_dl_harq", C.c_uint32)]
+
+
+class DlschLayout(C.Structure):
+    """mi_lte_dlsch_layout_t"""
+    _fields_ = [(n, C.c_uint32) for n in ("C", "K", "B", "N_cb", "k0")] + [("E", C.c_uint32 * 13), ("off", C.c_uint32 * 13)]
+
+
+def dlsch_layout(tbs, G, Q_m, tx_mode=1, rv=0, n_soft=1237248, m_dl_harq=8):
+    """mi_lte_dlsch_layout (host arithmetic): 36.212 segmentation and code-block concatenation of one transport block.  Returns a dict
+    {C, K, B, N_cb, k0, E: [C], off: [C]}; raises MiLteError with the status on a refusal."""
+    L = load_library()
+    out = DlschLayout()
+    rc = L.mi_lte_dlsch_layout(tbs, G, Q_m, tx_mode, rv, C.byref(DlschCfg(n_soft, m_dl_harq)), C.byref(out))
+    if rc != 0:
+        raise MiLteError("mi_lte_dlsch_layout(%d, %d, %d) failed: %d" % (tbs, G, Q_m, rc), rc)
+    return {"C": out.C, "K": out.K, "B": out.B, "N_cb": out.N_cb, "k0": out.k0, "E": list(out.E[:out.C]), "off": list(out.off[:out.C])}
+
+
 def make_alloc(unit, mod_type, tbs, prbs, rnti, rv_idx=0, tx_mode=1, prbs_slot1=None, n_pdcch_symbs=0):
     a = PdschAlloc()
     a.unit, a.mod_type, a.tbs, a.rv_idx, a.tx_mode, a.rnti, a.N_prb = unit, mod_type, tbs, rv_idx, tx_mode, rnti, len(prbs)
@@ -182,6 +203,12 @@ def load_library():
     L.mi_lte_pdsch_plan_out_stride.restype = u32
     L.mi_lte_pdsch_decode_run.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.mi_lte_pdsch_plan_soft_bits.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(vp)]
+    L.mi_lte_dlsch_layout.argtypes = [u32, u32, u32, u32, u32, C.POINTER(DlschCfg), C.POINTER(DlschLayout)]
+    L.mi_lte_pdsch_plan_create_3gpp.argtypes = [vp, C.POINTER(DlCfg), u32, C.POINTER(DlschCfg), vp, u32, C.POINTER(vp)]
+    L.mi_lte_pdsch_alloc_decodable_3gpp.argtypes = [C.POINTER(DlCfg), C.POINTER(DlschCfg), C.POINTER(PdschAlloc), u32]
+    L.mi_lte_pdsch_alloc_decodable_3gpp.restype = C.c_int
+    L.mi_lte_pdsch_plan_cb_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
+    L.mi_lte_pdsch_plan_cb_ok.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_ul_subframe_floats.restype = sz
     L.mi_lte_ul_frontend_batch.argtypes = [vp, C.POINTER(DlCfg), vp, vp, vp, u32, vp]
     f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
@@ -275,10 +302,17 @@ class PdschPlan:
     """mi_lte_pdsch_plan: device copy of an allocation list, grouped by code-block size.  allocs=None: a dynamic plan of the given
     capacity (mi_lte_pdsch_plan_create_dynamic), filled and re-filled by assign()."""
 
-    def __init__(self, ctx, cfg, n_pdcch_symbs, allocs, max_alloc=0, max_soft_bytes=0):
+    def __init__(self, ctx, cfg, n_pdcch_symbs, allocs, max_alloc=0, max_soft_bytes=0, dlsch=None):
+        """dlsch: a DlschCfg -- a plan in the 3GPP transport-block mode (mi_lte_pdsch_plan_create_3gpp)."""
         self.ctx = ctx
         h = C.c_void_p()
-        if allocs is None:
+        if dlsch is not None:
+            self.n_alloc = len(allocs)
+            arr = (PdschAlloc * len(allocs))(*allocs)
+            ctx._check(ctx.L.mi_lte_pdsch_plan_create_3gpp(ctx.h, C.byref(cfg), n_pdcch_symbs, C.byref(dlsch), C.cast(arr, C.c_void_p),
+                                                           len(allocs), C.byref(h)))
+            self.h, self.tbs, self._arr = h, [a.tbs for a in allocs], arr
+        elif allocs is None:
             ctx._check(ctx.L.mi_lte_pdsch_plan_create_dynamic(ctx.h, C.byref(cfg), max_alloc, max_soft_bytes, C.byref(h)))
             self.h, self.n_alloc, self.tbs = h, 0, []
         else:
@@ -342,6 +376,22 @@ class PdschPlan:
         self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, n.ctypes.data, pn.value, 4))
         out = np.empty(int(n[0]), np.int8)
         self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, pe.value, out.nbytes))
+        return out
+
+    def cb_soft(self, alloc):
+        """3GPP mode, after a run: the C rate-un-matched code blocks of one allocation, int8 [C, 3 (K + 4)] (stage tap)."""
+        p, nc, k = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        self.ctx._check(self.ctx.L.mi_lte_pdsch_plan_cb_soft(self.h, alloc, C.byref(p), C.byref(nc), C.byref(k)))
+        out = np.empty((nc.value, 3 * (k.value + 4)), np.int8)
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
+        return out
+
+    def cb_ok(self):
+        """3GPP mode, after a run: uint32 [n_alloc], bit r set when code block r's CRC24B passed (one block: bit 0 = the CRC24A verdict)."""
+        p = C.c_void_p()
+        self.ctx._check(self.ctx.L.mi_lte_pdsch_plan_cb_ok(self.h, C.byref(p)))
+        out = np.empty(self.n_alloc, np.uint32)
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
         return out
 
     def close(self):
@@ -848,6 +898,11 @@ class Context:
     # ---- PDSCH ------------------------------------------------------------------------------
     def pdsch_plan(self, cfg, n_pdcch_symbs, allocs):
         return PdschPlan(self, cfg, n_pdcch_symbs, allocs)
+
+    def pdsch_plan_3gpp(self, cfg, n_pdcch_symbs, allocs, n_soft, m_dl_harq=8):
+        """A plan in the 3GPP transport-block mode (36.212 segmentation, any tbs of Table 7.1.7.2.1-1): BCJR x 8 with the exact interleaver
+        by default; n_soft / m_dl_harq size the soft buffer (no default: the UE category's N_soft)."""
+        return PdschPlan(self, cfg, n_pdcch_symbs, allocs, dlsch=DlschCfg(n_soft, m_dl_harq))
 
     def pdsch_plan_dynamic(self, cfg, max_alloc, max_soft_bytes):
         return PdschPlan(self, cfg, 0, None, max_alloc, max_soft_bytes)

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .lib import load_library, MiLteError, DlCfg, UlCfg, PrachCfg, PdschAlloc
+from .lib import load_library, MiLteError, DlCfg, UlCfg, PrachCfg, PdschAlloc, DlschCfg
 
 _i8p = np.ctypeslib.ndpointer(np.int8, flags="C_CONTIGUOUS")
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
@@ -29,6 +29,9 @@ def _lib():
         L.mi_lte_synth_unit_len.restype = C.c_size_t
         L.mi_lte_synth_dl_units_i8.argtypes = [C.POINTER(DlCfg), C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                C.POINTER(SynthChannel), _i8p, _u8p, C.c_uint32]
+        L.mi_lte_synth_dl_units_3gpp_i8.argtypes = [C.POINTER(DlCfg), C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                    C.POINTER(DlschCfg), C.POINTER(SynthChannel), _i8p, _u8p, C.c_uint32]
+        L.mi_lte_dlsch_encode_3gpp.argtypes = [C.c_uint32, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DlschCfg), _u8p]
         L.mi_lte_synth_ul_unit_len.argtypes = [C.c_uint32]
         L.mi_lte_synth_ul_unit_len.restype = C.c_size_t
         L.mi_lte_synth_ul_units_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(UlCfg), C.c_uint32, _u32p, _u32p, C.c_void_p, C.c_uint32,
@@ -84,6 +87,33 @@ def dl_units(cfg, subfr_num, n_id_cell, allocs, n_alloc, n_pdcch_symbs=2, gain=(
     if rc != 0:
         raise MiLteError("mi_lte_synth_dl_units_i8 failed: %d" % rc)
     return iq, tx
+
+
+def dl_units_3gpp(cfg, subfr_num, n_id_cell, allocs, n_alloc, n_soft, m_dl_harq=8, n_pdcch_symbs=2, gain=(0.5, 1.5), max_delay=8,
+                  snr_db=30.0, peak=100.0, seed=1):
+    """dl_units with the 3GPP transport-block transmitter (mi_lte_synth_dl_units_3gpp_i8): any tbs of Table 7.1.7.2.1-1, E = G."""
+    n = len(subfr_num)
+    iq = np.zeros((n, unit_len(cfg.fft_size), 2), np.int8)
+    max_tbs = max([a.tbs for a in allocs], default=8)
+    tx = np.zeros((n, max(n_alloc, 1), max_tbs), np.uint8)
+    arr = (PdschAlloc * max(len(allocs), 1))(*allocs)
+    ch = SynthChannel(gain[0], gain[1], float(max_delay), float(snr_db), float(peak), int(seed))
+    rc = _lib().mi_lte_synth_dl_units_3gpp_i8(C.byref(cfg), n, np.ascontiguousarray(subfr_num, np.uint32), np.ascontiguousarray(n_id_cell, np.uint32),
+                                              n_pdcch_symbs, C.cast(arr, C.c_void_p), n_alloc, C.byref(DlschCfg(n_soft, m_dl_harq)), C.byref(ch), iq,
+                                              tx, max_tbs)
+    if rc != 0:
+        raise MiLteError("mi_lte_synth_dl_units_3gpp_i8 failed: %d" % rc)
+    return iq, tx
+
+
+def dlsch_encode_3gpp(bits, G, Q_m, tx_mode=1, rv=0, n_soft=1237248, m_dl_harq=8):
+    """mi_lte_dlsch_encode_3gpp: the G rate-matched bits (one per byte) of the transport block `bits`."""
+    bits = np.ascontiguousarray(bits, np.uint8)
+    e = np.zeros(max(G, 1), np.uint8)
+    rc = _lib().mi_lte_dlsch_encode_3gpp(len(bits), bits, G, Q_m, tx_mode, rv, C.byref(DlschCfg(n_soft, m_dl_harq)), e)
+    if rc != 0:
+        raise MiLteError("mi_lte_dlsch_encode_3gpp failed: %d" % rc, rc)
+    return e[:G]
 
 
 def ul_unit_len(fft_size=2048):
