@@ -265,6 +265,56 @@ int mi_lte_pdsch_alloc_decodable_3gpp(const mi_lte_dl_cfg *cfg, const mi_lte_dls
 int mi_lte_pdsch_plan_cb_soft(const mi_lte_pdsch_plan *plan, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K);
 int mi_lte_pdsch_plan_cb_ok(const mi_lte_pdsch_plan *plan, const uint32_t **d_mask);
 
+/* ---------------------------------------------------------------- PDSCH, 3GPP mode: HARQ soft combining
+ * Incremental-redundancy combining of the retransmissions of a transport block in device-resident soft buffers (36.212 5.1.4.1.2: the
+ * circular buffer of N_cb positions per code block that every redundancy version reads from; 36.321 5.3.2.2: when a buffer is flushed).
+ *
+ * Pool: n_buf soft buffers on the context's device, each sized for the largest C * 3 (K + 4) over the sizes of 36.213 Table 7.1.7.2.1-1 up
+ *   to max_tbs (mi_lte_harq_buffer_bytes), as int16 in the decoder's interleaved layout d[i*3+x], block r at r * 3 (K + 4), plus a state
+ *   record (mi_lte_harq_state).  What a buffer index means -- typically one (UE, HARQ process) pair -- is the caller's.  The pool belongs to
+ *   a context, outlives any plan and serves every 3GPP plan of that context.  It is zeroed at creation; an empty buffer has n_tx = 0.
+ * Binding: mi_lte_pdsch_decode_run_harq takes one host mi_lte_harq_bind per allocation of the plan.  buf = MI_LTE_HARQ_NONE decodes the
+ *   allocation exactly as mi_lte_pdsch_decode_run does and leaves the pool alone; flags & MI_LTE_HARQ_NEW_DATA is the toggled NDI.
+ * Flush rule (36.321 5.3.2.2): before combining, a bound buffer is emptied when NEW_DATA is set, when its n_tx is 0, or when its held tbs or
+ *   N_cb differs from this transmission's (N_cb follows from the plan's mi_lte_dlsch_cfg and the allocation's tx_mode; C and K from tbs).
+ * Combining, at every decoder position t of block r: v = the exact integer sum of this transmission's soft bits that rate un-matching maps
+ *   to t (the sum the plain run saturates; 0 where none does, positions >= N_cb included), buf[t] = sat16(buf[t] + sat16(v)), and the
+ *   decoder's input (and the _cb_soft tap) is clamp(buf[t], -127, 127).  From an empty buffer this is the plain run's clamp(v) byte for
+ *   byte.  Modulation, N_prb, subframe (so G, E_r and the offsets) and rv may all differ between the transmissions of a transport block.
+ * After the run the state holds n_tx (transmissions since the last flush, this one included) and the transport block's verdict (status,
+ *   the value written to d_status).  A passing CRC does not empty the buffer: only the flush rule and mi_lte_harq_pool_reset do.
+ * Refusals, returned before anything is launched, leaving pool and plan usable: MI_LTE_ERR_UNSUPPORTED for a plan not in the 3GPP mode;
+ *   MI_LTE_ERR_INVALID_ARG for a NULL binding, buf >= n_buf, one buf bound twice in a run, or an allocation whose tbs exceeds the pool's
+ *   max_tbs.
+ * Ordering: runs on one context's stream combine in stream order.  The call does not wait for the decode; at most it waits for the previous
+ *   HARQ run's binding copy to leave the pool's pinned staging block. */
+typedef struct mi_lte_harq_pool mi_lte_harq_pool;
+#define MI_LTE_HARQ_NONE     0xFFFFFFFFu
+#define MI_LTE_HARQ_NEW_DATA 1u
+typedef struct {
+    uint32_t buf;   /* buffer index, or MI_LTE_HARQ_NONE */
+    uint32_t flags; /* MI_LTE_HARQ_NEW_DATA */
+} mi_lte_harq_bind;
+typedef struct {
+    uint32_t tbs, C, K, N_cb; /* the transport block the buffer holds (0 when empty) */
+    uint32_t n_tx;            /* transmissions combined since the last flush; 0: empty */
+    int32_t  status;          /* the last run's verdict (d_status) */
+} mi_lte_harq_state;
+/* host arithmetic: soft-buffer bytes per buffer of a pool for max_tbs (2 * the largest C * 3 (K + 4) over Table 7.1.7.2.1-1 sizes <= max_tbs);
+ * 0 when no size of the table is <= max_tbs */
+size_t mi_lte_harq_buffer_bytes(uint32_t max_tbs);
+/* MI_LTE_ERR_INVALID_ARG: n_buf = 0 or > 2^24, or mi_lte_harq_buffer_bytes(max_tbs) = 0 */
+int  mi_lte_harq_pool_create(mi_lte_ctx *ctx, uint32_t n_buf, uint32_t max_tbs, mi_lte_harq_pool **out);
+void mi_lte_harq_pool_destroy(mi_lte_ctx *ctx, mi_lte_harq_pool *pool);
+/* empties buffer buf (MI_LTE_HARQ_NONE: every buffer): soft bytes and state zeroed, on the context's stream */
+int  mi_lte_harq_pool_reset(mi_lte_ctx *ctx, mi_lte_harq_pool *pool, uint32_t buf);
+/* mi_lte_pdsch_decode_run on a 3GPP plan with the allocations' soft bits combined into the pool's buffers as above */
+int  mi_lte_pdsch_decode_run_harq(mi_lte_ctx *ctx, mi_lte_pdsch_plan *plan, mi_lte_harq_pool *pool, const mi_lte_harq_bind *h_bind,
+                                  const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell, uint8_t *d_out_bits,
+                                  int32_t *d_status);
+/* tap: device pointers to buffer buf's int16 blocks (mi_lte_harq_buffer_bytes(max_tbs) bytes) and to its state; either may be NULL */
+int  mi_lte_harq_pool_soft(const mi_lte_harq_pool *pool, uint32_t buf, const int16_t **d_soft, const mi_lte_harq_state **d_state);
+
 /* ---------------------------------------------------------------- turbo decode
  * Replaces turbo_decode() (liblte/src/liblte_phy.cc:10620-10845) for a batch of code blocks of one
  * size K.  Input layout is the reference's: per block 3*(K+4) soft values INTERLEAVED d[i*3+x]
@@ -870,6 +920,13 @@ int mi_lte_dlsch_encode_3gpp(uint32_t tbs, const uint8_t *bits, uint32_t G, uint
 int mi_lte_synth_dl_units_3gpp_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
                                   uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, const mi_lte_dlsch_cfg *dlsch,
                                   const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride);
+/* mi_lte_synth_dl_units_3gpp_i8 with the caller's transport blocks: h_payload[(u * n_alloc + a) * tbs_stride + i], i < tbs, one bit per
+ * byte.  The random numbers the payload would have taken are still drawn and discarded, so given the bits mi_lte_synth_dl_units_3gpp_i8
+ * drew with the same seed, it writes the same IQ byte for byte; a HARQ retransmission is the same payload with another rv and another seed. */
+int mi_lte_synth_dl_units_3gpp_payload_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
+                                          uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                          const mi_lte_dlsch_cfg *dlsch, const mi_lte_synth_channel *chan, const uint8_t *h_payload,
+                                          uint32_t tbs_stride, int8_t *h_iq);
 
 /* control regions: PCFICH + n_dci format-1A DCIs (rnti = 0: slot unused) at aggregation level 4 in candidates 0..n_dci-1,
  * standard transmit diversity on cfg->N_ant ports, through a smooth random channel per port (gain_min..gain_max) and

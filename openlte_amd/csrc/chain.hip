@@ -346,6 +346,10 @@ int             mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, const mi_lte_pdsch_a
                               uint32_t packed);
 int             mi_dlsch3_cb_soft(const MiDlsch3 *g, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K);
 const uint32_t *mi_dlsch3_cb_ok(const MiDlsch3 *g);
+int             mi_dlsch3_harq_check(mi_lte_ctx *ctx, const MiDlsch3 *g, const mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind);
+int             mi_dlsch3_run_harq(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const mi_lte_pdsch_alloc *d_allocs,
+                                   const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride,
+                                   int32_t *d_status, uint32_t decoder, uint32_t n_iter, uint32_t packed);
 
 struct mi_lte_pdsch_plan {
     mi_lte_dl_cfg cfg;
@@ -761,11 +765,61 @@ int mi_lte_pdsch_plan_set_output(mi_lte_pdsch_plan *pl, uint32_t packed)
     return MI_LTE_OK;
 }
 
+} // extern "C"
+
+// the demodulator of a HARQ run: every allocation's descrambled soft bits and their count -- the launch mi_lte_pdsch_decode_run makes (its own copy
+// below is left as it was)
+static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell)
+{
+    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    int rc = mi_ctx_gold_tables(ctx);
+    if (rc != MI_LTE_OK) return rc;
+    DemodGeom  g{pl->cfg.N_rb_dl, pl->cfg.N_ant, pl->cfi, (uint32_t)mi_lte_subframe_floats(pl->cfg.N_ant)};
+    GoldTables gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
+    // LDS: pair table | scrambling words | (when it fits in 32 KiB) the allocation's soft bits
+    const uint32_t words_al = (pl->max_words + 1u + 3u) & ~3u, e_bytes = (pl->max_words * 32 + 63u) & ~63u;
+    const uint32_t e_cap = (e_bytes <= 32 * 1024) ? e_bytes : 0;
+    const uint32_t pairs_al = ((2 * (pl->max_pairs + 1) + 3u) & ~3u);
+    const size_t lds = sizeof(uint32_t) * ((size_t)pairs_al + words_al) + e_cap;
+    uint32_t threads = 256;
+    if (const char *ev = getenv("MI_LTE_PDSCH_THREADS")) { // (tuning aid)
+        const int t = atoi(ev);
+        if (t >= 64 && t <= 256 && t % 64 == 0) threads = (uint32_t)t;
+    }
+    if (g.N_ant == 1 && (pl->cfg.sample_format & MI_LTE_CE_COMPACT))
+        MI_LAUNCH(ctx, "k_pdsch_demod", (k_pdsch_demod<true, true>), dim3(pl->n_alloc), dim3(threads), lds, d_subframes, g, pl->d_allocs, d_subfr_num,
+                  d_n_id_cell, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->max_pairs, words_al, e_cap);
+    else if (g.N_ant == 1)
+        MI_LAUNCH(ctx, "k_pdsch_demod", k_pdsch_demod<true>, dim3(pl->n_alloc), dim3(threads), lds, d_subframes, g, pl->d_allocs, d_subfr_num,
+                  d_n_id_cell, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->max_pairs, words_al, e_cap);
+    else
+        MI_LAUNCH(ctx, "k_pdsch_demod", k_pdsch_demod<false>, dim3(pl->n_alloc), dim3(threads), lds, d_subframes, g, pl->d_allocs, d_subfr_num,
+                  d_n_id_cell, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->max_pairs, words_al, e_cap);
+    MI_HIP_CHECK(ctx, hipGetLastError());
+    return MI_LTE_OK;
+}
+
+extern "C" {
+
+int mi_lte_pdsch_decode_run_harq(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *pool, const mi_lte_harq_bind *h_bind, const float *d_subframes,
+                                 const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell, uint8_t *d_out_bits, int32_t *d_status)
+{
+    if (!ctx || !pl || !pool || !h_bind || !d_subframes || !d_subfr_num || !d_n_id_cell || !d_out_bits || !d_status) return MI_LTE_ERR_INVALID_ARG;
+    if (!pl->g3) { ctx->err = "HARQ soft combining needs a plan in the 3GPP transport-block mode"; return MI_LTE_ERR_UNSUPPORTED; }
+    int rc = mi_dlsch3_harq_check(ctx, pl->g3, pool, h_bind);
+    if (rc != MI_LTE_OK) return rc;
+    rc = pdsch_demod(ctx, pl, d_subframes, d_subfr_num, d_n_id_cell);
+    if (rc != MI_LTE_OK) return rc;
+    return mi_dlsch3_run_harq(ctx, pl->g3, pool, h_bind, pl->d_allocs, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits, pl->out_stride, d_status, pl->decoder,
+                              pl->n_iter, pl->packed);
+}
+
 int mi_lte_pdsch_decode_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_subframes, const uint32_t *d_subfr_num,
                             const uint32_t *d_n_id_cell, uint8_t *d_out_bits, int32_t *d_status)
 {
     if (!ctx || !pl || !d_subframes || !d_subfr_num || !d_n_id_cell || !d_out_bits || !d_status) return MI_LTE_ERR_INVALID_ARG;
     if (pl->n_alloc == 0) { ctx->err = "the dynamic plan holds no allocations (mi_lte_pdsch_plan_assign)"; return MI_LTE_ERR_INVALID_ARG; }
+
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     int rc = mi_ctx_gold_tables(ctx);
     if (rc != MI_LTE_OK) return rc;

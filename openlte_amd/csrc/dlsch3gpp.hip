@@ -9,6 +9,11 @@
 //   (decode)         mi_lte_turbo_decode_batch's BCJR kernels, one launch set per block size (bcjr.hip, unchanged)
 //   k_dl3_cb_finish  one workgroup per code block: CRC24B, the block's payload into the transport block's output row, its share of the CRC24A
 //   k_dl3_tb_finish  one thread per transport block: the shares combined, status and the per-block CRC mask
+// A HARQ run (mi_lte_pdsch_decode_run_harq) adds the soft combining of the pool's buffers (include/mi_lte.h):
+//   k_harq_bind      one thread per allocation, after k_dl3_desc: the flush rule against the buffer's state, the state's new tbs .. n_tx,
+//                    and the buffer / flush word of the allocation's code-block slots
+//   k_harq_rm        k_dl3_rm_i8's place: the same gather sums, combined into the int16 buffer (saturating), the decoder's int8 input from it
+//   k_harq_commit    one thread per allocation, after k_dl3_tb_finish: the transport block's verdict into the state
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -214,6 +219,94 @@ __global__ __launch_bounds__(256) void k_dl3_tb_finish(const uint32_t *__restric
     cb_ok[a]  = mask;
 }
 
+// ------------------------------------------------------------------------------------------------ HARQ soft combining
+
+constexpr uint32_t HARQ_FLUSH = 0x80000000u; // in a slot's word: the buffer starts empty in this run (buffer index below it)
+
+// One thread per allocation of the plan: buffer and flush rule (36.321 5.3.2.2) for a bound one, MI_LTE_HARQ_NONE for the others, written to
+// every code-block slot of the allocation.  No buffer is bound twice in a run (the host refuses it), so the state updates do not race.
+__global__ __launch_bounds__(256) void k_harq_bind(const Dl3Desc *__restrict__ desc, const uint32_t *__restrict__ a_slot, uint32_t n_alloc,
+                                                   const mi_lte_harq_bind *__restrict__ bind, mi_lte_harq_state *__restrict__ state,
+                                                   uint32_t *__restrict__ slot_buf)
+{
+    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_alloc) return;
+    const uint32_t      s0 = a_slot[a];
+    const Dl3Desc      &d  = desc[s0];
+    const mi_lte_harq_bind b = bind[a];
+    uint32_t w = MI_LTE_HARQ_NONE;
+    if (b.buf != MI_LTE_HARQ_NONE) {
+        mi_lte_harq_state st = state[b.buf];
+        const bool flush = (b.flags & MI_LTE_HARQ_NEW_DATA) || st.n_tx == 0 || st.tbs != d.tbs || st.N_cb != d.N_cb;
+        st.tbs = d.tbs; st.C = d.C; st.K = d.K; st.N_cb = d.N_cb;
+        st.n_tx = flush ? 1u : (st.n_tx < 0xFFFFFFFFu ? st.n_tx + 1u : st.n_tx);
+        state[b.buf] = st;
+        w = b.buf | (flush ? HARQ_FLUSH : 0u);
+    }
+    for (uint32_t r = 0; r < d.C; r++) slot_buf[s0 + r] = w;
+}
+
+__device__ __forceinline__ int sat16(int v) { return max(-32768, min(32767, v)); }
+__device__ __forceinline__ int clamp127(int v) { return max(-127, min(127, v)); }
+
+// k_dl3_rm_i8 with soft combining: a slot bound to a buffer sums position t's soft bits as k_dl3_rm_i8 does (v), then
+// buf[t] = sat16(buf[t] + sat16(v)) (buf[t] = 0 when the slot's buffer was flushed) and the decoder's input is clamp(buf[t], +-127).
+// Two positions per lane: one dword of the buffer read and written (block r starts at an even position), one int16 of the int8 output.
+// An unbound slot takes k_dl3_rm_i8's own path.
+__global__ __launch_bounds__(256) void k_harq_rm(const Dl3Desc *__restrict__ desc, const int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off,
+                                                 int8_t *__restrict__ soft, uint32_t e_cap, const uint32_t *__restrict__ slot_buf,
+                                                 int16_t *__restrict__ pool, size_t buf_elems)
+{
+    extern __shared__ __attribute__((aligned(16))) int8_t e_lds[];
+    const Dl3Desc &d = desc[blockIdx.x];
+    const uint32_t K = d.K, D = K + 4, E = d.E, n = 3 * D;
+    Rm3 rm;
+    rm.init(D, d.N_cb, d.k0);
+    const int8_t  *e     = e_base + (size_t)e_off[d.alloc] * 64 + d.off;
+    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(e) & 3u);
+    const bool     staged = shift + E <= e_cap;
+    if (staged) {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(e - shift);
+        for (uint32_t w = threadIdx.x; w < (shift + E + 3) / 4; w += blockDim.x) reinterpret_cast<uint32_t *>(e_lds)[w] = src[w];
+    }
+    __syncthreads();
+    const int8_t *es = staged ? e_lds + shift : e;
+    int8_t       *db = soft + (size_t)d.soft_off4 * 4;
+    auto gather = [&](uint32_t t) {
+        const uint32_t i = t / 3;
+        uint32_t       p, cn;
+        rm.pos_cnt(i, (int)(t - 3 * i), p, cn);
+        int v = 0;
+        if (p < rm.N_cb)
+            for (uint32_t k = p >= rm.k0m ? cn - rm.cnt_k0 : rm.Nnn - rm.cnt_k0 + cn; k < E; k += rm.Nnn) v += es[k];
+        return v;
+    };
+    const uint32_t sb = slot_buf[blockIdx.x];
+    if (sb == MI_LTE_HARQ_NONE) {
+        for (uint32_t t = threadIdx.x; t < n; t += blockDim.x) db[t] = (int8_t)clamp127(gather(t));
+        return;
+    }
+    const bool flush = (sb & HARQ_FLUSH) != 0;
+    uint32_t  *hb    = reinterpret_cast<uint32_t *>(pool + (size_t)(sb & ~HARQ_FLUSH) * buf_elems + (size_t)d.r * n);
+    for (uint32_t t2 = threadIdx.x; t2 < n / 2; t2 += blockDim.x) {
+        const int      v0 = sat16(gather(2 * t2)), v1 = sat16(gather(2 * t2 + 1));
+        const uint32_t w  = flush ? 0u : hb[t2];
+        const int      b0 = sat16((int)(int16_t)(w & 0xFFFFu) + v0), b1 = sat16((int)(int16_t)(w >> 16) + v1);
+        hb[t2] = (uint32_t)(uint16_t)b0 | ((uint32_t)(uint16_t)b1 << 16);
+        reinterpret_cast<uint16_t *>(db)[t2] = (uint16_t)((uint8_t)(int8_t)clamp127(b0) | ((uint32_t)(uint8_t)(int8_t)clamp127(b1) << 8));
+    }
+}
+
+// One thread per allocation, after k_dl3_tb_finish: a bound transport block's verdict into its buffer's state
+__global__ __launch_bounds__(256) void k_harq_commit(const mi_lte_harq_bind *__restrict__ bind, uint32_t n_alloc, const int32_t *__restrict__ status,
+                                                     mi_lte_harq_state *__restrict__ state)
+{
+    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_alloc) return;
+    const uint32_t buf = bind[a].buf;
+    if (buf != MI_LTE_HARQ_NONE) state[buf].status = status[a];
+}
+
 } // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -224,7 +317,7 @@ struct MiDlsch3 {
     uint32_t n_alloc = 0, n_slot = 0;
     struct Group { uint32_t K, n_cb; size_t soft_off, bits_off; }; // a block size's slots, contiguous; byte offsets into d_soft / d_bits
     std::vector<Group>    groups;
-    std::vector<uint32_t> a_slot, a_nc, a_K;   // per allocation: first slot, C, K
+    std::vector<uint32_t> a_slot, a_nc, a_K, a_tbs; // per allocation: first slot, C, K, tbs
     std::vector<size_t>   a_soft;              // per allocation: byte offset of its first block in d_soft
     Dl3Slot  *d_slot = nullptr;
     Dl3Desc  *d_desc = nullptr;
@@ -232,13 +325,14 @@ struct MiDlsch3 {
     uint8_t  *d_bits = nullptr;
     uint32_t *d_tab = nullptr;                 // x^e mod gCRC24A [6144] | x^e mod gCRC24B [6144]
     uint32_t *d_a_slot = nullptr, *d_a_nc = nullptr, *d_part = nullptr, *d_ok = nullptr, *d_cb_ok = nullptr;
+    uint32_t *d_slot_buf = nullptr;            // HARQ runs: per slot, the bound buffer | HARQ_FLUSH, or MI_LTE_HARQ_NONE (k_harq_bind)
 };
 
 void mi_dlsch3_free(MiDlsch3 *g)
 {
     if (!g) return;
     for (void *p : {(void *)g->d_slot, (void *)g->d_desc, (void *)g->d_soft, (void *)g->d_bits, (void *)g->d_tab, (void *)g->d_a_slot, (void *)g->d_a_nc,
-                    (void *)g->d_part, (void *)g->d_ok, (void *)g->d_cb_ok})
+                    (void *)g->d_part, (void *)g->d_ok, (void *)g->d_cb_ok, (void *)g->d_slot_buf})
         if (p) (void)hipFree(p);
     delete g;
 }
@@ -251,12 +345,12 @@ int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_
     auto guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_dlsch3_free(g); });
     g->cfg     = *cfg;
     g->n_alloc = n_alloc;
-    g->a_slot.resize(n_alloc); g->a_nc.resize(n_alloc); g->a_K.resize(n_alloc); g->a_soft.resize(n_alloc);
+    g->a_slot.resize(n_alloc); g->a_nc.resize(n_alloc); g->a_K.resize(n_alloc); g->a_tbs.resize(n_alloc); g->a_soft.resize(n_alloc);
     for (uint32_t a = 0; a < n_alloc; a++) {
         mi_lte_dlsch_layout_t lay;
         const int rc = mi_lte_dlsch_layout(h_allocs[a].tbs, 0, 2, h_allocs[a].tx_mode, h_allocs[a].rv_idx & 3u, cfg, &lay);
         if (rc != MI_LTE_OK) { ctx->err = "transport block size outside the 3GPP mode (F != 0 or tbs > 75376)"; return rc; }
-        g->a_nc[a] = lay.C; g->a_K[a] = lay.K;
+        g->a_nc[a] = lay.C; g->a_K[a] = lay.K; g->a_tbs[a] = h_allocs[a].tbs;
     }
     std::vector<uint32_t> order(n_alloc);
     for (uint32_t a = 0; a < n_alloc; a++) order[a] = a;
@@ -295,6 +389,7 @@ int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_
     MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_part, sizeof(uint32_t) * g->n_slot));
     MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_ok, sizeof(uint32_t) * g->n_slot));
     MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_cb_ok, sizeof(uint32_t) * n_alloc));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_slot_buf, sizeof(uint32_t) * g->n_slot));
     MI_HIP_CHECK(ctx, hipMemsetAsync(g->d_soft, 0, std::max<size_t>(soft, 256), ctx->stream)); // (the taps read defined bytes before a first run)
     MI_HIP_CHECK(ctx, hipMemsetAsync(g->d_cb_ok, 0, sizeof(uint32_t) * n_alloc, ctx->stream));
     MI_H2D(ctx, g->d_slot, slots.data(), sizeof(Dl3Slot) * g->n_slot);
@@ -307,14 +402,10 @@ int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_
     return MI_LTE_OK;
 }
 
-// everything after the demodulator (chain.hip: mi_lte_pdsch_decode_run on a 3GPP plan)
-int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, const mi_lte_pdsch_alloc *d_allocs, const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len,
-                  uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t decoder, uint32_t n_iter, uint32_t packed)
+// the decode and the finish of a run, after the rate un-matching
+static int dlsch3_decode_finish(mi_lte_ctx *ctx, MiDlsch3 *g, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t decoder,
+                                uint32_t n_iter, uint32_t packed)
 {
-    MI_LAUNCH(ctx, "k_dl3_desc", k_dl3_desc, dim3((g->n_slot + 255) / 256), dim3(256), 0, (const Dl3Slot *)g->d_slot, g->n_slot, d_allocs, d_e_len,
-              g->cfg.N_soft, g->cfg.M_dl_harq, g->d_desc);
-    MI_LAUNCH(ctx, "k_dl3_rm_i8", k_dl3_rm_i8, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, d_e, d_e_off, g->d_soft, DL3_E_CAP);
-    MI_HIP_CHECK(ctx, hipGetLastError());
     for (const auto &gr : g->groups) {
         const int8_t *s = g->d_soft + gr.soft_off;
         uint8_t      *b = g->d_bits + gr.bits_off;
@@ -327,7 +418,151 @@ int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, const mi_lte_pdsch_alloc *d_allo
     MI_LAUNCH(ctx, "k_dl3_tb_finish", k_dl3_tb_finish, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const uint32_t *)g->d_a_slot,
               (const uint32_t *)g->d_a_nc, g->n_alloc, (const uint32_t *)g->d_part, (const uint32_t *)g->d_ok, d_status, g->d_cb_ok);
     MI_HIP_CHECK(ctx, hipGetLastError());
+    return MI_LTE_OK;
+}
+
+// everything after the demodulator (chain.hip: mi_lte_pdsch_decode_run on a 3GPP plan)
+int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, const mi_lte_pdsch_alloc *d_allocs, const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len,
+                  uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t decoder, uint32_t n_iter, uint32_t packed)
+{
+    MI_LAUNCH(ctx, "k_dl3_desc", k_dl3_desc, dim3((g->n_slot + 255) / 256), dim3(256), 0, (const Dl3Slot *)g->d_slot, g->n_slot, d_allocs, d_e_len,
+              g->cfg.N_soft, g->cfg.M_dl_harq, g->d_desc);
+    MI_LAUNCH(ctx, "k_dl3_rm_i8", k_dl3_rm_i8, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, d_e, d_e_off, g->d_soft, DL3_E_CAP);
+    MI_HIP_CHECK(ctx, hipGetLastError());
+    const int rc = dlsch3_decode_finish(ctx, g, d_out_bits, out_stride, d_status, decoder, n_iter, packed);
+    if (rc != MI_LTE_OK) return rc;
     ctx->last_kernels = "k_pdsch_demod:1,k_dl3_desc:1,k_dl3_rm_i8:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1";
+    return MI_LTE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// HARQ soft-buffer pool (include/mi_lte.h)
+
+struct mi_lte_harq_pool {
+    int                device = -1;
+    uint32_t           n_buf = 0, max_tbs = 0;
+    size_t             buf_bytes = 0, buf_elems = 0; // a buffer's soft bytes (mi_lte_harq_buffer_bytes), its stride in int16 (a multiple of 128)
+    int16_t           *d_soft = nullptr;
+    mi_lte_harq_state *d_state = nullptr;
+    // the bindings of a run: pinned staging block -> device copy, cap of each; `staged` guards the block against the previous run's copy
+    mi_lte_harq_bind  *h_bind = nullptr, *d_bind = nullptr;
+    uint32_t           cap_bind = 0;
+    hipEvent_t         staged = nullptr;
+};
+
+static void harq_pool_free(mi_lte_harq_pool *p)
+{
+    if (!p) return;
+    if (p->d_soft) (void)hipFree(p->d_soft);
+    if (p->d_state) (void)hipFree(p->d_state);
+    if (p->d_bind) (void)hipFree(p->d_bind);
+    if (p->h_bind) (void)hipHostFree(p->h_bind);
+    if (p->staged) (void)hipEventDestroy(p->staged);
+    delete p;
+}
+
+extern "C" {
+
+int mi_lte_harq_pool_create(mi_lte_ctx *ctx, uint32_t n_buf, uint32_t max_tbs, mi_lte_harq_pool **out)
+{
+    if (!ctx || !out || n_buf == 0 || n_buf > (1u << 24)) return MI_LTE_ERR_INVALID_ARG;
+    const size_t bytes = mi_lte_harq_buffer_bytes(max_tbs);
+    if (bytes == 0) { ctx->err = "HARQ pool: no transport block size of the table is <= max_tbs"; return MI_LTE_ERR_INVALID_ARG; }
+    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    auto *p    = new mi_lte_harq_pool();
+    auto guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); harq_pool_free(p); });
+    p->device = ctx->device; p->n_buf = n_buf; p->max_tbs = max_tbs; p->buf_bytes = bytes;
+    p->buf_elems = (bytes / 2 + 127) & ~(size_t)127;
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&p->d_soft, 2 * p->buf_elems * n_buf));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&p->d_state, sizeof(mi_lte_harq_state) * n_buf));
+    MI_HIP_CHECK(ctx, hipEventCreateWithFlags(&p->staged, hipEventDisableTiming));
+    MI_HIP_CHECK(ctx, hipMemsetAsync(p->d_soft, 0, 2 * p->buf_elems * n_buf, ctx->stream));
+    MI_HIP_CHECK(ctx, hipMemsetAsync(p->d_state, 0, sizeof(mi_lte_harq_state) * n_buf, ctx->stream));
+    MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    guard.armed = false;
+    *out = p;
+    return MI_LTE_OK;
+}
+
+void mi_lte_harq_pool_destroy(mi_lte_ctx *ctx, mi_lte_harq_pool *p)
+{
+    if (!p) return;
+    if (ctx) (void)hipStreamSynchronize(ctx->stream); // (runs that combine into it may still be queued)
+    harq_pool_free(p);
+}
+
+int mi_lte_harq_pool_reset(mi_lte_ctx *ctx, mi_lte_harq_pool *p, uint32_t buf)
+{
+    if (!ctx || !p || (buf != MI_LTE_HARQ_NONE && buf >= p->n_buf)) return MI_LTE_ERR_INVALID_ARG;
+    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const uint32_t b0 = buf == MI_LTE_HARQ_NONE ? 0u : buf, nb = buf == MI_LTE_HARQ_NONE ? p->n_buf : 1u;
+    MI_HIP_CHECK(ctx, hipMemsetAsync(p->d_soft + (size_t)b0 * p->buf_elems, 0, 2 * p->buf_elems * nb, ctx->stream));
+    MI_HIP_CHECK(ctx, hipMemsetAsync(p->d_state + b0, 0, sizeof(mi_lte_harq_state) * nb, ctx->stream));
+    return MI_LTE_OK;
+}
+
+int mi_lte_harq_pool_soft(const mi_lte_harq_pool *p, uint32_t buf, const int16_t **d_soft, const mi_lte_harq_state **d_state)
+{
+    if (!p || buf >= p->n_buf) return MI_LTE_ERR_INVALID_ARG;
+    if (d_soft) *d_soft = p->d_soft + (size_t)buf * p->buf_elems;
+    if (d_state) *d_state = p->d_state + buf;
+    return MI_LTE_OK;
+}
+
+} // extern "C"
+
+// The bindings of a HARQ run against the plan and the pool, on the host, before anything is launched
+int mi_dlsch3_harq_check(mi_lte_ctx *ctx, const MiDlsch3 *g, const mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind)
+{
+    if (!g || !p || !h_bind) return MI_LTE_ERR_INVALID_ARG;
+    if (p->device != ctx->device) { ctx->err = "HARQ pool of another device"; return MI_LTE_ERR_INVALID_ARG; }
+    std::vector<uint32_t> seen;
+    for (uint32_t a = 0; a < g->n_alloc; a++) {
+        const uint32_t b = h_bind[a].buf;
+        if (b == MI_LTE_HARQ_NONE) continue;
+        if (b >= p->n_buf) { ctx->err = "HARQ binding: buffer index past the pool"; return MI_LTE_ERR_INVALID_ARG; }
+        if (g->a_tbs[a] > p->max_tbs || (size_t)g->a_nc[a] * 3 * (g->a_K[a] + 4) * 2 > p->buf_bytes) {
+            ctx->err = "HARQ binding: transport block larger than the pool's max_tbs";
+            return MI_LTE_ERR_INVALID_ARG;
+        }
+        seen.push_back(b);
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { ctx->err = "HARQ binding: one buffer bound twice in a run"; return MI_LTE_ERR_INVALID_ARG; }
+    return MI_LTE_OK;
+}
+
+// everything after the demodulator in a HARQ run (chain.hip: mi_lte_pdsch_decode_run_harq); mi_dlsch3_harq_check has passed
+int mi_dlsch3_run_harq(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const mi_lte_pdsch_alloc *d_allocs,
+                       const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
+                       uint32_t decoder, uint32_t n_iter, uint32_t packed)
+{
+    if (g->n_alloc > p->cap_bind) { // (a larger plan than any before: the queued runs that read the old blocks finish first)
+        MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (p->d_bind) { (void)hipFree(p->d_bind); p->d_bind = nullptr; }
+        if (p->h_bind) { (void)hipHostFree(p->h_bind); p->h_bind = nullptr; }
+        p->cap_bind = 0;
+        MI_HIP_CHECK(ctx, hipMalloc((void **)&p->d_bind, sizeof(mi_lte_harq_bind) * g->n_alloc));
+        MI_HIP_CHECK(ctx, hipHostMalloc((void **)&p->h_bind, sizeof(mi_lte_harq_bind) * g->n_alloc, hipHostMallocDefault));
+        p->cap_bind = g->n_alloc;
+    }
+    MI_HIP_CHECK(ctx, hipEventSynchronize(p->staged)); // the previous run's binding copy has left the staging block
+    memcpy(p->h_bind, h_bind, sizeof(mi_lte_harq_bind) * g->n_alloc);
+    MI_HIP_CHECK(ctx, hipMemcpyAsync(p->d_bind, p->h_bind, sizeof(mi_lte_harq_bind) * g->n_alloc, hipMemcpyHostToDevice, ctx->stream));
+    MI_HIP_CHECK(ctx, hipEventRecord(p->staged, ctx->stream));
+    MI_LAUNCH(ctx, "k_dl3_desc", k_dl3_desc, dim3((g->n_slot + 255) / 256), dim3(256), 0, (const Dl3Slot *)g->d_slot, g->n_slot, d_allocs, d_e_len,
+              g->cfg.N_soft, g->cfg.M_dl_harq, g->d_desc);
+    MI_LAUNCH(ctx, "k_harq_bind", k_harq_bind, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const Dl3Desc *)g->d_desc, (const uint32_t *)g->d_a_slot,
+              g->n_alloc, (const mi_lte_harq_bind *)p->d_bind, p->d_state, g->d_slot_buf);
+    MI_LAUNCH(ctx, "k_harq_rm", k_harq_rm, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, d_e, d_e_off, g->d_soft, DL3_E_CAP,
+              (const uint32_t *)g->d_slot_buf, p->d_soft, p->buf_elems);
+    MI_HIP_CHECK(ctx, hipGetLastError());
+    const int rc = dlsch3_decode_finish(ctx, g, d_out_bits, out_stride, d_status, decoder, n_iter, packed);
+    if (rc != MI_LTE_OK) return rc;
+    MI_LAUNCH(ctx, "k_harq_commit", k_harq_commit, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const mi_lte_harq_bind *)p->d_bind, g->n_alloc,
+              (const int32_t *)d_status, p->d_state);
+    MI_HIP_CHECK(ctx, hipGetLastError());
+    ctx->last_kernels = "k_pdsch_demod:1,k_dl3_desc:1,k_harq_bind:1,k_harq_rm:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1,k_harq_commit:1";
     return MI_LTE_OK;
 }
 

@@ -249,6 +249,21 @@ int mi_lte_dlsch_layout(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t tx_mode
     return MI_LTE_OK;
 }
 
+// The HARQ pool's buffer (include/mi_lte.h): the largest C * 3 (K + 4) int16 positions over the sizes of 36.213 Table 7.1.7.2.1-1 up to max_tbs
+size_t mi_lte_harq_buffer_bytes(uint32_t max_tbs)
+{
+    const mi_lte_dlsch_cfg any{1u << 30, 8};
+    size_t best = 0;
+    for (uint32_t i = 0; i < 27; i++)
+        for (uint32_t n = 0; n < 110; n++) {
+            const uint32_t tbs = 8u * LTE_TBS_DIV8[i][n];
+            mi_lte_dlsch_layout_t lay;
+            if (tbs == 0 || tbs > max_tbs || mi_lte_dlsch_layout(tbs, 0, 2, 1, 0, &any, &lay) != MI_LTE_OK) continue;
+            best = std::max(best, (size_t)lay.C * 3 * (lay.K + 4));
+        }
+    return 2 * best;
+}
+
 // 36.212 5.1.1-5.1.4.1 for one transport block in the 3GPP mode (include/mi_lte.h): CRC24A, C blocks of K bits (each with CRC24B when
 // C > 1), turbo encoding with the exact interleaver, rate matching with the layout's N_cb and E_r, concatenation
 int mi_lte_dlsch_encode_3gpp(uint32_t tbs, const uint8_t *bits, uint32_t G, uint32_t Q_m, uint32_t tx_mode, uint32_t rv, const mi_lte_dlsch_cfg *dlsch,
@@ -283,7 +298,7 @@ size_t mi_lte_synth_unit_len(uint32_t fft_size)
 // down to a multiple of 2 Q_m) and mi_lte_synth_dl_units_3gpp_i8 (mi_lte_dlsch_encode_3gpp, E = G)
 static int synth_dl_units(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell, uint32_t N_pdcch_symbs,
                           const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, const mi_lte_dlsch_cfg *dlsch, const mi_lte_synth_channel *chan,
-                          int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride)
+                          int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride, const uint8_t *h_payload = nullptr)
 {
     if (!cfg || !h_subfr_num || !h_n_id_cell || !chan || !h_iq || cfg->N_ant != 1 || (n_alloc && !h_allocs)) return MI_LTE_ERR_INVALID_ARG;
     if (!synth::valid_grid(cfg->fft_size, cfg->N_rb_dl) || N_pdcch_symbs < 1 || N_pdcch_symbs > 4) return MI_LTE_ERR_INVALID_ARG;
@@ -297,7 +312,7 @@ static int synth_dl_units(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint
     for (uint32_t u = 0; u < n_units; u++) {
         if (h_n_id_cell[u] > 503) return MI_LTE_ERR_INVALID_ARG;
         for (uint32_t a = 0; a < n_alloc; a++)
-            if (!valid(h_allocs[(size_t)u * n_alloc + a]) || (h_tx_bits && h_allocs[(size_t)u * n_alloc + a].tbs > tbs_stride))
+            if (!valid(h_allocs[(size_t)u * n_alloc + a]) || ((h_tx_bits || h_payload) && h_allocs[(size_t)u * n_alloc + a].tbs > tbs_stride))
                 return MI_LTE_ERR_INVALID_ARG;
     }
     const uint32_t N = cfg->fft_size, sc = 2048 / N, cp0 = 160 / sc, cpe = 144 / sc, N_rb = cfg->N_rb_dl, half = 6 * N_rb, N_sc = 12 * N_rb;
@@ -344,6 +359,8 @@ static int synth_dl_units(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint
                 const uint32_t G = (uint32_t)res.size() * Qm;
                 std::vector<uint8_t> b(al.tbs), e(G), c(G);
                 for (uint32_t i = 0; i < al.tbs; i++) b[i] = (uint8_t)(rng.next() & 1u);
+                if (h_payload) // the caller's transport block; the draws above keep the rest of the stream where the generator has it
+                    for (uint32_t i = 0; i < al.tbs; i++) b[i] = h_payload[((size_t)u * n_alloc + a) * tbs_stride + i] & 1u;
                 if (h_tx_bits) memcpy(h_tx_bits + ((size_t)u * n_alloc + a) * tbs_stride, b.data(), al.tbs);
                 const int rc = mi_lte_dlsch_encode_3gpp(al.tbs, b.data(), G, Qm, al.tx_mode, al.rv_idx, dlsch, e.data());
                 if (rc != MI_LTE_OK) return rc;
@@ -449,6 +466,15 @@ int mi_lte_synth_dl_units_3gpp_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, co
 {
     if (!dlsch) return MI_LTE_ERR_INVALID_ARG;
     return synth_dl_units(cfg, n_units, h_subfr_num, h_n_id_cell, N_pdcch_symbs, h_allocs, n_alloc, dlsch, chan, h_iq, h_tx_bits, tbs_stride);
+}
+
+int mi_lte_synth_dl_units_3gpp_payload_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
+                                          uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                          const mi_lte_dlsch_cfg *dlsch, const mi_lte_synth_channel *chan, const uint8_t *h_payload,
+                                          uint32_t tbs_stride, int8_t *h_iq)
+{
+    if (!dlsch || (n_alloc && n_units && !h_payload)) return MI_LTE_ERR_INVALID_ARG;
+    return synth_dl_units(cfg, n_units, h_subfr_num, h_n_id_cell, N_pdcch_symbs, h_allocs, n_alloc, dlsch, chan, h_iq, nullptr, tbs_stride, h_payload);
 }
 
 

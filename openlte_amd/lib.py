@@ -61,6 +61,38 @@ def dlsch_layout(tbs, G, Q_m, tx_mode=1, rv=0, n_soft=1237248, m_dl_harq=8):
     return {"C": out.C, "K": out.K, "B": out.B, "N_cb": out.N_cb, "k0": out.k0, "E": list(out.E[:out.C]), "off": list(out.off[:out.C])}
 
 
+HARQ_NONE, HARQ_NEW_DATA = 0xFFFFFFFF, 1
+
+
+class HarqBind(C.Structure):
+    """mi_lte_harq_bind"""
+    _fields_ = [("buf", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class HarqState(C.Structure):
+    """mi_lte_harq_state"""
+    _fields_ = [(n, C.c_uint32) for n in ("tbs", "C", "K", "N_cb", "n_tx")] + [("status", C.c_int32)]
+
+
+def harq_buffer_bytes(max_tbs):
+    """mi_lte_harq_buffer_bytes (host arithmetic): soft bytes per buffer of a HARQ pool for max_tbs."""
+    return int(load_library().mi_lte_harq_buffer_bytes(max_tbs))
+
+
+def harq_binds(n_alloc, bufs, new_data=False):
+    """A ctypes array of n_alloc mi_lte_harq_bind: bufs[a] is a buffer index or None (MI_LTE_HARQ_NONE); new_data a bool or one per
+    allocation (MI_LTE_HARQ_NEW_DATA)."""
+    bufs = list(bufs)
+    nd = list(new_data) if isinstance(new_data, (list, tuple, np.ndarray)) else [new_data] * n_alloc
+    if len(bufs) != n_alloc or len(nd) != n_alloc:
+        raise ValueError("one binding per allocation: %d allocations, %d buffers, %d flags" % (n_alloc, len(bufs), len(nd)))
+    arr = (HarqBind * max(n_alloc, 1))()
+    for a in range(n_alloc):
+        arr[a].buf = HARQ_NONE if bufs[a] is None else int(bufs[a])
+        arr[a].flags = HARQ_NEW_DATA if nd[a] else 0
+    return arr
+
+
 def make_alloc(unit, mod_type, tbs, prbs, rnti, rv_idx=0, tx_mode=1, prbs_slot1=None, n_pdcch_symbs=0):
     a = PdschAlloc()
     a.unit, a.mod_type, a.tbs, a.rv_idx, a.tx_mode, a.rnti, a.N_prb = unit, mod_type, tbs, rv_idx, tx_mode, rnti, len(prbs)
@@ -209,6 +241,14 @@ def load_library():
     L.mi_lte_pdsch_alloc_decodable_3gpp.restype = C.c_int
     L.mi_lte_pdsch_plan_cb_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
     L.mi_lte_pdsch_plan_cb_ok.argtypes = [vp, C.POINTER(vp)]
+    L.mi_lte_harq_buffer_bytes.argtypes = [u32]
+    L.mi_lte_harq_buffer_bytes.restype = sz
+    L.mi_lte_harq_pool_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
+    L.mi_lte_harq_pool_destroy.argtypes = [vp, vp]
+    L.mi_lte_harq_pool_destroy.restype = None
+    L.mi_lte_harq_pool_reset.argtypes = [vp, vp, u32]
+    L.mi_lte_harq_pool_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(vp)]
+    L.mi_lte_pdsch_decode_run_harq.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mi_lte_ul_subframe_floats.restype = sz
     L.mi_lte_ul_frontend_batch.argtypes = [vp, C.POINTER(DlCfg), vp, vp, vp, u32, vp]
     f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
@@ -346,14 +386,25 @@ class PdschPlan:
         self.ctx._check(self.ctx.L.mi_lte_pdsch_decode_run(self.ctx.h, self.h, d_subframes.ptr, d_sf.ptr, d_cell.ptr,
                                                            d_out.ptr, d_status.ptr))
 
-    def run(self, d_subframes, subfr_num, n_id_cell):
-        """Returns (status int32 [n_alloc], list of uint8 bit arrays)."""
+    def run_harq_dev(self, pool, binds, d_subframes, d_sf, d_cell, d_out, d_status):
+        """mi_lte_pdsch_decode_run_harq (3GPP mode): binds is a ctypes array of HarqBind, one per allocation (harq_binds), or None -- a NULL
+        binding, which the library refuses."""
+        self.ctx._check(self.ctx.L.mi_lte_pdsch_decode_run_harq(self.ctx.h, self.h, pool.h, None if binds is None else C.cast(binds, C.c_void_p),
+                                                                d_subframes.ptr, d_sf.ptr, d_cell.ptr, d_out.ptr, d_status.ptr))
+
+    def run(self, d_subframes, subfr_num, n_id_cell, harq=None):
+        """Returns (status int32 [n_alloc], list of uint8 bit arrays).  harq = (pool, bufs, new_data): a HARQ run (3GPP mode) that combines
+        allocation a into pool buffer bufs[a] (None: not combined); new_data a bool or one per allocation."""
         ctx = self.ctx
+        binds = None if harq is None else harq_binds(self.n_alloc, harq[1], harq[2] if len(harq) > 2 else False)
         d_sf, d_cell = ctx.to_device(np.asarray(subfr_num, np.uint32)), ctx.to_device(np.asarray(n_id_cell, np.uint32))
         d_out, d_st = ctx.alloc(self.n_alloc * self.out_stride), ctx.alloc(4 * self.n_alloc)
         d_out.zero()
         try:
-            self.run_dev(d_subframes, d_sf, d_cell, d_out, d_st)
+            if harq is None:
+                self.run_dev(d_subframes, d_sf, d_cell, d_out, d_st)
+            else:
+                self.run_harq_dev(harq[0], binds, d_subframes, d_sf, d_cell, d_out, d_st)
             st = d_st.download(np.int32)
             bits = d_out.download(np.uint8).reshape(self.n_alloc, self.out_stride)
             if getattr(self, "packed", False):  # back to one bit per byte for the caller
@@ -397,6 +448,49 @@ class PdschPlan:
     def close(self):
         if self.h:
             self.ctx.L.mi_lte_pdsch_plan_destroy(self.ctx.h, self.h)
+            self.h = None
+
+
+class HarqPool:
+    """mi_lte_harq_pool: n_buf device soft buffers for HARQ combining in the 3GPP mode, owned by a Context and shared by its plans."""
+
+    def __init__(self, ctx, n_buf, max_tbs=75376):
+        self.ctx, self.n_buf, self.max_tbs = ctx, int(n_buf), int(max_tbs)
+        h = C.c_void_p()
+        ctx._check(ctx.L.mi_lte_harq_pool_create(ctx.h, self.n_buf, self.max_tbs, C.byref(h)))
+        self.h = h
+        self.buffer_bytes = harq_buffer_bytes(self.max_tbs)
+
+    def reset(self, buf=None):
+        """Empty buffer buf, or every buffer (None)."""
+        self.ctx._check(self.ctx.L.mi_lte_harq_pool_reset(self.ctx.h, self.h, HARQ_NONE if buf is None else int(buf)))
+
+    def _ptrs(self, buf):
+        ps, pst = C.c_void_p(), C.c_void_p()
+        self.ctx._check(self.ctx.L.mi_lte_harq_pool_soft(self.h, int(buf), C.byref(ps), C.byref(pst)))
+        return ps.value, pst.value
+
+    def state(self, buf):
+        """The buffer's state record as a dict {tbs, C, K, N_cb, n_tx, status}."""
+        st = HarqState()
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, C.addressof(st), self._ptrs(buf)[1], C.sizeof(st)))
+        return {n: getattr(st, n) for n, _ in HarqState._fields_}
+
+    def soft_raw(self, buf):
+        """The whole int16 buffer (buffer_bytes / 2 positions), whatever it holds."""
+        out = np.empty(self.buffer_bytes // 2, np.int16)
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, self._ptrs(buf)[0], out.nbytes))
+        return out
+
+    def soft(self, buf):
+        """The held transport block's code blocks, int16 [C, 3 (K + 4)] (C and K from the state; [0, 0] when empty)."""
+        st = self.state(buf)
+        n = st["C"] * 3 * (st["K"] + 4)
+        return self.soft_raw(buf)[:n].reshape(st["C"], 3 * (st["K"] + 4) if st["C"] else 0)
+
+    def close(self):
+        if self.h:
+            self.ctx.L.mi_lte_harq_pool_destroy(self.ctx.h, self.h)
             self.h = None
 
 
@@ -903,6 +997,10 @@ class Context:
         """A plan in the 3GPP transport-block mode (36.212 segmentation, any tbs of Table 7.1.7.2.1-1): BCJR x 8 with the exact interleaver
         by default; n_soft / m_dl_harq size the soft buffer (no default: the UE category's N_soft)."""
         return PdschPlan(self, cfg, n_pdcch_symbs, allocs, dlsch=DlschCfg(n_soft, m_dl_harq))
+
+    def harq_pool(self, n_buf, max_tbs=75376):
+        """A HARQ soft-buffer pool (mi_lte_harq_pool_create) for the 3GPP plans of this context."""
+        return HarqPool(self, n_buf, max_tbs)
 
     def pdsch_plan_dynamic(self, cfg, max_alloc, max_soft_bytes):
         return PdschPlan(self, cfg, 0, None, max_alloc, max_soft_bytes)

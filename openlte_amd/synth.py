@@ -31,6 +31,8 @@ def _lib():
                                                C.POINTER(SynthChannel), _i8p, _u8p, C.c_uint32]
         L.mi_lte_synth_dl_units_3gpp_i8.argtypes = [C.POINTER(DlCfg), C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                     C.POINTER(DlschCfg), C.POINTER(SynthChannel), _i8p, _u8p, C.c_uint32]
+        L.mi_lte_synth_dl_units_3gpp_payload_i8.argtypes = [C.POINTER(DlCfg), C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                            C.POINTER(DlschCfg), C.POINTER(SynthChannel), C.c_void_p, C.c_uint32, _i8p]
         L.mi_lte_dlsch_encode_3gpp.argtypes = [C.c_uint32, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DlschCfg), _u8p]
         L.mi_lte_synth_ul_unit_len.argtypes = [C.c_uint32]
         L.mi_lte_synth_ul_unit_len.restype = C.c_size_t
@@ -90,14 +92,26 @@ def dl_units(cfg, subfr_num, n_id_cell, allocs, n_alloc, n_pdcch_symbs=2, gain=(
 
 
 def dl_units_3gpp(cfg, subfr_num, n_id_cell, allocs, n_alloc, n_soft, m_dl_harq=8, n_pdcch_symbs=2, gain=(0.5, 1.5), max_delay=8,
-                  snr_db=30.0, peak=100.0, seed=1):
-    """dl_units with the 3GPP transport-block transmitter (mi_lte_synth_dl_units_3gpp_i8): any tbs of Table 7.1.7.2.1-1, E = G."""
+                  snr_db=30.0, peak=100.0, seed=1, payload=None):
+    """dl_units with the 3GPP transport-block transmitter (mi_lte_synth_dl_units_3gpp_i8): any tbs of Table 7.1.7.2.1-1, E = G.
+    payload: the transport blocks to send, uint8 [n_units, n_alloc, >= max tbs] one bit per byte (mi_lte_synth_dl_units_3gpp_payload_i8:
+    a HARQ retransmission is the same payload with another rv and seed); returned as tx."""
     n = len(subfr_num)
     iq = np.zeros((n, unit_len(cfg.fft_size), 2), np.int8)
     max_tbs = max([a.tbs for a in allocs], default=8)
     tx = np.zeros((n, max(n_alloc, 1), max_tbs), np.uint8)
     arr = (PdschAlloc * max(len(allocs), 1))(*allocs)
     ch = SynthChannel(gain[0], gain[1], float(max_delay), float(snr_db), float(peak), int(seed))
+    if payload is not None:
+        pl = np.ascontiguousarray(payload, np.uint8)
+        if pl.ndim != 3 or pl.shape[0] != n or pl.shape[1] != max(n_alloc, 1):
+            raise ValueError("payload: uint8 [n_units, n_alloc, >= max tbs]")
+        rc = _lib().mi_lte_synth_dl_units_3gpp_payload_i8(C.byref(cfg), n, np.ascontiguousarray(subfr_num, np.uint32),
+                                                          np.ascontiguousarray(n_id_cell, np.uint32), n_pdcch_symbs, C.cast(arr, C.c_void_p), n_alloc,
+                                                          C.byref(DlschCfg(n_soft, m_dl_harq)), C.byref(ch), pl.ctypes.data, pl.shape[2], iq)
+        if rc != 0:
+            raise MiLteError("mi_lte_synth_dl_units_3gpp_payload_i8 failed: %d" % rc, rc)
+        return iq, pl[:, :, :max_tbs].copy()
     rc = _lib().mi_lte_synth_dl_units_3gpp_i8(C.byref(cfg), n, np.ascontiguousarray(subfr_num, np.uint32), np.ascontiguousarray(n_id_cell, np.uint32),
                                               n_pdcch_symbs, C.cast(arr, C.c_void_p), n_alloc, C.byref(DlschCfg(n_soft, m_dl_harq)), C.byref(ch), iq,
                                               tx, max_tbs)
