@@ -341,15 +341,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
 struct MiDlsch3;
 int             mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out);
 void            mi_dlsch3_free(MiDlsch3 *g);
-int             mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, const mi_lte_pdsch_alloc *d_allocs, const int8_t *d_e, const uint32_t *d_e_off,
-                              const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t decoder, uint32_t n_iter,
-                              uint32_t packed);
+int             mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const mi_lte_pdsch_alloc *d_allocs,
+                              const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
+                              uint32_t decoder, uint32_t n_iter, uint32_t packed);
 int             mi_dlsch3_cb_soft(const MiDlsch3 *g, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K);
 const uint32_t *mi_dlsch3_cb_ok(const MiDlsch3 *g);
 int             mi_dlsch3_harq_check(mi_lte_ctx *ctx, const MiDlsch3 *g, const mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind);
-int             mi_dlsch3_run_harq(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const mi_lte_pdsch_alloc *d_allocs,
-                                   const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride,
-                                   int32_t *d_status, uint32_t decoder, uint32_t n_iter, uint32_t packed);
 
 struct mi_lte_pdsch_plan {
     mi_lte_dl_cfg cfg;
@@ -371,10 +368,9 @@ struct mi_lte_pdsch_plan {
     // pinned staging for re-assignments: allocs | e_off | cb_alloc, copied with one command each on the context's stream
     void       *h_stage = nullptr;
     hipEvent_t  staged = nullptr;
-    using Group = MiKGroup; // { K, n_cb, cb_base, e_max }
-    std::vector<Group>    groups;
+    std::vector<MiKGroup> groups;
     std::vector<uint32_t> h_e_off;
-    MiMultiCache          multi; // the merged decode's device tables for `groups` (turbo.hip: mi_turbo_ref_multi)
+    MiMultiCache          multi; // the merged decode's device tables for `groups` (turbo.hip: mi_turbo_ref_dispatch)
     MiDlsch3             *g3 = nullptr; // 3GPP transport-block mode (mi_lte_pdsch_plan_create_3gpp): its code blocks and buffers (dlsch3gpp.hip)
 };
 
@@ -767,8 +763,7 @@ int mi_lte_pdsch_plan_set_output(mi_lte_pdsch_plan *pl, uint32_t packed)
 
 } // extern "C"
 
-// the demodulator of a HARQ run: every allocation's descrambled soft bits and their count -- the launch mi_lte_pdsch_decode_run makes (its own copy
-// below is left as it was)
+// the plan's demodulator: every allocation's descrambled soft bits and their count
 static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell)
 {
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -799,144 +794,64 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
     return MI_LTE_OK;
 }
 
-extern "C" {
-
-int mi_lte_pdsch_decode_run_harq(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *pool, const mi_lte_harq_bind *h_bind, const float *d_subframes,
-                                 const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell, uint8_t *d_out_bits, int32_t *d_status)
+// A plan run: demodulation, then the 3GPP mode's decode (dlsch3gpp.hip) or the code blocks size by size (BCJR decoders) or through the REF
+// dispatch (turbo.hip).  pool / h_bind: a HARQ run (mi_lte_pdsch_decode_run_harq), nullptr otherwise.  Every refusal returns before a launch.
+static int pdsch_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *pool, const mi_lte_harq_bind *h_bind, const float *d_subframes,
+                     const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell, uint8_t *d_out_bits, int32_t *d_status)
 {
-    if (!ctx || !pl || !pool || !h_bind || !d_subframes || !d_subfr_num || !d_n_id_cell || !d_out_bits || !d_status) return MI_LTE_ERR_INVALID_ARG;
-    if (!pl->g3) { ctx->err = "HARQ soft combining needs a plan in the 3GPP transport-block mode"; return MI_LTE_ERR_UNSUPPORTED; }
-    int rc = mi_dlsch3_harq_check(ctx, pl->g3, pool, h_bind);
-    if (rc != MI_LTE_OK) return rc;
-    rc = pdsch_demod(ctx, pl, d_subframes, d_subfr_num, d_n_id_cell);
-    if (rc != MI_LTE_OK) return rc;
-    return mi_dlsch3_run_harq(ctx, pl->g3, pool, h_bind, pl->d_allocs, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits, pl->out_stride, d_status, pl->decoder,
-                              pl->n_iter, pl->packed);
+    if (!ctx || !pl || !d_subframes || !d_subfr_num || !d_n_id_cell || !d_out_bits || !d_status) return MI_LTE_ERR_INVALID_ARG;
+    int rc;
+    if (pool) {
+        if (!pl->g3) { ctx->err = "HARQ soft combining needs a plan in the 3GPP transport-block mode"; return MI_LTE_ERR_UNSUPPORTED; }
+        if ((rc = mi_dlsch3_harq_check(ctx, pl->g3, pool, h_bind)) != MI_LTE_OK) return rc;
+    }
+    if (pl->n_alloc == 0) { ctx->err = "the dynamic plan holds no allocations (mi_lte_pdsch_plan_assign)"; return MI_LTE_ERR_INVALID_ARG; }
+    if ((rc = pdsch_demod(ctx, pl, d_subframes, d_subfr_num, d_n_id_cell)) != MI_LTE_OK) return rc;
+    if (pl->g3)
+        return mi_dlsch3_run(ctx, pl->g3, pool, h_bind, pl->d_allocs, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits, pl->out_stride, d_status, pl->decoder,
+                             pl->n_iter, pl->packed);
+    const bool bcjr = pl->decoder == MI_LTE_TURBO_BCJR || pl->decoder == MI_LTE_TURBO_BCJR_BLOCK || pl->decoder == MI_LTE_TURBO_BCJR_EARLY;
+    if (!bcjr) {
+        rc = mi_turbo_ref_dispatch(ctx, pl->groups.data(), (uint32_t)pl->groups.size(), pl->d_allocs, pl->d_cb_alloc, pl->d_e, pl->d_e_off, pl->d_e_len,
+                                   d_out_bits, pl->out_stride, d_status, false, pl->packed != 0, &pl->multi);
+        if (rc != MI_LTE_OK) return rc;
+        ctx->last_kernels.insert(0, "k_pdsch_demod:1,");
+        return MI_LTE_OK;
+    }
+    size_t soft = 0, bits = 0;
+    for (auto &gr : pl->groups) { soft = std::max(soft, (size_t)gr.n_cb * 3 * (gr.K + 4)); bits = std::max(bits, (size_t)gr.n_cb * gr.K); }
+    if (soft > pl->bcjr_soft_cap || bits > pl->bcjr_bits_cap) { // first run, or a re-assigned plan that needs more
+        MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (pl->d_bcjr_soft) (void)hipFree(pl->d_bcjr_soft);
+        if (pl->d_bcjr_bits) (void)hipFree(pl->d_bcjr_bits);
+        pl->d_bcjr_soft = nullptr; pl->d_bcjr_bits = nullptr;
+        MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_bcjr_soft, soft));
+        MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_bcjr_bits, bits));
+        pl->bcjr_soft_cap = soft; pl->bcjr_bits_cap = bits;
+    }
+    for (auto &gr : pl->groups) {
+        rc = mi_turbo_bcjr_group(ctx, gr.K, gr.n_cb, pl->d_allocs, pl->d_cb_alloc + gr.cb_base, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits,
+                                 pl->out_stride, d_status, false, pl->d_bcjr_soft, pl->d_bcjr_bits, pl->n_iter, pl->qpp_spec, pl->packed != 0, gr.e_max,
+                                 pl->decoder == MI_LTE_TURBO_BCJR_BLOCK, pl->decoder == MI_LTE_TURBO_BCJR_EARLY);
+        if (rc != MI_LTE_OK) return rc;
+    }
+    ctx->last_kernels = "k_pdsch_demod:1,k_rm_to_i8,k_bcjr_*,k_crc_finish per block size";
+    return MI_LTE_OK;
 }
+
+extern "C" {
 
 int mi_lte_pdsch_decode_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_subframes, const uint32_t *d_subfr_num,
                             const uint32_t *d_n_id_cell, uint8_t *d_out_bits, int32_t *d_status)
 {
-    if (!ctx || !pl || !d_subframes || !d_subfr_num || !d_n_id_cell || !d_out_bits || !d_status) return MI_LTE_ERR_INVALID_ARG;
-    if (pl->n_alloc == 0) { ctx->err = "the dynamic plan holds no allocations (mi_lte_pdsch_plan_assign)"; return MI_LTE_ERR_INVALID_ARG; }
+    return pdsch_run(ctx, pl, nullptr, nullptr, d_subframes, d_subfr_num, d_n_id_cell, d_out_bits, d_status);
+}
 
-    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    int rc = mi_ctx_gold_tables(ctx);
-    if (rc != MI_LTE_OK) return rc;
-    DemodGeom  g{pl->cfg.N_rb_dl, pl->cfg.N_ant, pl->cfi, (uint32_t)mi_lte_subframe_floats(pl->cfg.N_ant)};
-    GoldTables gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
-    // LDS: pair table | scrambling words | (when it fits in 32 KiB) the allocation's soft bits
-    const uint32_t words_al = (pl->max_words + 1u + 3u) & ~3u, e_bytes = (pl->max_words * 32 + 63u) & ~63u;
-    const uint32_t e_cap = (e_bytes <= 32 * 1024) ? e_bytes : 0;
-    const uint32_t pairs_al = ((2 * (pl->max_pairs + 1) + 3u) & ~3u);
-    const size_t lds = sizeof(uint32_t) * ((size_t)pairs_al + words_al) + e_cap;
-    uint32_t threads = 256;
-    if (const char *ev = getenv("MI_LTE_PDSCH_THREADS")) { // (tuning aid)
-        const int t = atoi(ev);
-        if (t >= 64 && t <= 256 && t % 64 == 0) threads = (uint32_t)t;
-    }
-    if (g.N_ant == 1 && (pl->cfg.sample_format & MI_LTE_CE_COMPACT))
-        MI_LAUNCH(ctx, "k_pdsch_demod", (k_pdsch_demod<true, true>), dim3(pl->n_alloc), dim3(threads), lds, d_subframes, g, pl->d_allocs, d_subfr_num,
-                  d_n_id_cell, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->max_pairs, words_al, e_cap);
-    else if (g.N_ant == 1)
-        MI_LAUNCH(ctx, "k_pdsch_demod", k_pdsch_demod<true>, dim3(pl->n_alloc), dim3(threads), lds, d_subframes, g, pl->d_allocs, d_subfr_num,
-                  d_n_id_cell, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->max_pairs, words_al, e_cap);
-    else
-        MI_LAUNCH(ctx, "k_pdsch_demod", k_pdsch_demod<false>, dim3(pl->n_alloc), dim3(threads), lds, d_subframes, g, pl->d_allocs, d_subfr_num,
-                  d_n_id_cell, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->max_pairs, words_al, e_cap);
-    MI_HIP_CHECK(ctx, hipGetLastError());
-    if (pl->g3)
-        return mi_dlsch3_run(ctx, pl->g3, pl->d_allocs, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits, pl->out_stride, d_status, pl->decoder, pl->n_iter,
-                             pl->packed);
-    const bool bcjr = pl->decoder == MI_LTE_TURBO_BCJR || pl->decoder == MI_LTE_TURBO_BCJR_BLOCK || pl->decoder == MI_LTE_TURBO_BCJR_EARLY;
-    if (bcjr) {
-        size_t soft = 0, bits = 0;
-        for (auto &gr : pl->groups) { soft = std::max(soft, (size_t)gr.n_cb * 3 * (gr.K + 4)); bits = std::max(bits, (size_t)gr.n_cb * gr.K); }
-        if (soft > pl->bcjr_soft_cap || bits > pl->bcjr_bits_cap) { // first run, or a re-assigned plan that needs more
-            MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            if (pl->d_bcjr_soft) (void)hipFree(pl->d_bcjr_soft);
-            if (pl->d_bcjr_bits) (void)hipFree(pl->d_bcjr_bits);
-            pl->d_bcjr_soft = nullptr; pl->d_bcjr_bits = nullptr;
-            MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_bcjr_soft, soft));
-            MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_bcjr_bits, bits));
-            pl->bcjr_soft_cap = soft; pl->bcjr_bits_cap = bits;
-        }
-    }
-    auto run_group = [&](const mi_lte_pdsch_plan::Group &gr) -> int {
-        if (bcjr)
-            return mi_turbo_bcjr_group(ctx, gr.K, gr.n_cb, pl->d_allocs, pl->d_cb_alloc + gr.cb_base, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits,
-                                       pl->out_stride, d_status, false, pl->d_bcjr_soft, pl->d_bcjr_bits, pl->n_iter, pl->qpp_spec, pl->packed != 0, gr.e_max,
-                                       pl->decoder == MI_LTE_TURBO_BCJR_BLOCK, pl->decoder == MI_LTE_TURBO_BCJR_EARLY);
-        return mi_turbo_ref_group(ctx, gr.K, gr.n_cb, pl->d_allocs, pl->d_cb_alloc + gr.cb_base, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits,
-                                  pl->out_stride, d_status, gr.e_max, false, pl->packed != 0);
-    };
-    // The block-size groups of a decode are independent of each other (own code blocks, own status words and output rows).  In a batch the
-    // groups differ widely in size -- W4: 65 536 blocks of K = 1088 next to 524 288 of K = 3264 -- and the small ones do not fill the device
-    // (the K = 1088 trellis walk is one or two wavefronts per SIMD: 0.46 ms of latency for 3 % of the work), so with the reference-faithful
-    // decoder every group but the largest can run on a side stream, in a scratch block of its own, next to the largest one.
-    size_t big = 0, total_cb = 0;
-    for (size_t i = 0; i < pl->groups.size(); i++) {
-        total_cb += pl->groups[i].n_cb;
-        if ((size_t)pl->groups[i].n_cb * pl->groups[i].K > (size_t)pl->groups[big].n_cb * pl->groups[big].K) big = i;
-    }
-    // Opt-in (MI_LTE_GROUP_STREAMS=1): worth 1 % of the W4 step (24.77 -> 24.55 ms), and it stretches the launches that overlap -- the
-    // per-launch times the roofline accounting of bench.py and the rocprof summaries are built on stop describing a kernel alone.
-    static const bool side_ok = [] { const char *e = getenv("MI_LTE_GROUP_STREAMS"); return e && atoi(e) != 0; }();
-    // A decode with several block sizes -- a batch, or a per-call caller's subframe with a handful of transport blocks: ONE launch set over all sizes
-    // (turbo.hip: KSeg).  A cell's TTIs hold dozens of the 188 sizes; size by size that is ~7 launches per size in series, each a sliver
-    // of the device -- 65 536 mixed subframes took 72.6 ms that way, 48.8 of them in the decoder (profiles/r06_chain_mixed_per_size.json).
-    // MI_LTE_NO_MERGED_DECODE=1 keeps the per-size launches (A/B).
-    static const bool merged_off = [] { const char *e = getenv("MI_LTE_NO_MERGED_DECODE"); return e && atoi(e) != 0; }();
-    if (!bcjr && !merged_off && ctx->merged_decode && !side_ok && pl->groups.size() >= 2) {
-        // (MI_LTE_MERGE_MAX_TILES=n, tuning aid: a size with more than n tiles of 64 blocks keeps its own launches.  No limit by default: W4's two
-        // sizes run 23.6-23.9 ms merged -- the trellis kernel's two launches instead of four, 6.5 against 6.8 ms -- and 24.0-24.3 size by size,
-        // profiles/r06_variants_merged_prep.txt)
-        static const uint32_t max_tiles = [] { const char *e = getenv("MI_LTE_MERGE_MAX_TILES"); return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 0xFFFFFFFFu; }();
-        auto merged = [&](const MiKGroup &gr) { return mi_turbo_ref_multi_takes(gr.K, gr.e_max) && (gr.n_cb + 63) / 64 <= max_tiles; };
-        std::vector<MiKGroup> take;
-        for (auto &gr : pl->groups)
-            if (merged(gr)) take.push_back(gr);
-        if (take.size() >= 2) {
-            rc = mi_turbo_ref_multi(ctx, take.data(), (uint32_t)take.size(), pl->d_allocs, pl->d_cb_alloc, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits, pl->out_stride, d_status,
-                                    false, pl->packed != 0, &pl->multi);
-            if (rc != MI_LTE_OK) return rc;
-            for (auto &gr : pl->groups) // (an allocation repeated over more than 258 laps of its circular buffer: 32-bit sums, the per-size path)
-                if (!merged(gr) && (rc = run_group(gr)) != MI_LTE_OK) return rc;
-            ctx->last_kernels = take.size() == pl->groups.size() ? "k_pdsch_demod:1,k_cb_desc:1,k_turbo_prep,k_turbo_siso:2,k_turbo_perm,k_turbo_vote per workgroup width over all block sizes"
-                                                                  : "k_pdsch_demod:1,k_cb_desc:1,k_turbo_prep,k_turbo_siso:2,k_turbo_perm,k_turbo_vote per workgroup width over all block sizes but the per-size ones";
-            return MI_LTE_OK;
-        }
-    }
-    if (!bcjr && side_ok && pl->groups.size() >= 2 && total_cb >= 16384) {
-        if (!ctx->side_stream) {
-            MI_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
-            MI_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            MI_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
-        MI_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream)); // the soft bits are there, the previous run's side work was joined
-        MI_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
-        auto swap_side = [&] { std::swap(ctx->stream, ctx->side_stream); std::swap(ctx->scratch, ctx->side_scratch); std::swap(ctx->scratch_bytes, ctx->side_scratch_bytes); };
-        swap_side(); // the launch helpers take the stream and the scratch from the context
-        for (size_t i = 0; i < pl->groups.size() && rc == MI_LTE_OK; i++)
-            if (i != big) rc = run_group(pl->groups[i]);
-        swap_side();
-        // whatever happened on the side stream is joined before this function returns, on every path: groups already launched there
-        // still write d_out_bits / d_status / the side scratch, and a later mi_lte_sync only waits for ctx->stream
-        const hipError_t e_rec = hipEventRecord(ctx->ev_join, ctx->side_stream);
-        if (rc == MI_LTE_OK && e_rec == hipSuccess) rc = run_group(pl->groups[big]);
-        const hipError_t e_join = e_rec == hipSuccess ? hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0) : hipStreamSynchronize(ctx->side_stream);
-        if (rc != MI_LTE_OK) return rc;
-        MI_HIP_CHECK(ctx, e_rec);
-        MI_HIP_CHECK(ctx, e_join);
-    } else {
-        for (auto &gr : pl->groups) {
-            rc = run_group(gr);
-            if (rc != MI_LTE_OK) return rc;
-        }
-    }
-    ctx->last_kernels = bcjr ? "k_pdsch_demod:1,k_rm_to_i8,k_bcjr_*,k_crc_finish per block size"
-                                                         : "k_pdsch_demod:1,k_turbo_prep,k_turbo_siso,k_turbo_perm,k_turbo_vote per block size";
-    return MI_LTE_OK;
+int mi_lte_pdsch_decode_run_harq(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *pool, const mi_lte_harq_bind *h_bind, const float *d_subframes,
+                                 const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell, uint8_t *d_out_bits, int32_t *d_status)
+{
+    if (!pool || !h_bind) return MI_LTE_ERR_INVALID_ARG;
+    return pdsch_run(ctx, pl, pool, h_bind, d_subframes, d_subfr_num, d_n_id_cell, d_out_bits, d_status);
 }
 
 } // extern "C"

@@ -36,6 +36,9 @@ int mi_lte_ctx_create(int device, mi_lte_ctx **out)
     }
     mi_lte_ctx *ctx = new mi_lte_ctx();
     ctx->device     = device;
+    // MI_LTE_NO_MERGED_DECODE=1: every context starts with the per-size launches (mi_lte_set_turbo_merged; the only way to reach the host
+    // pipeline's own contexts)
+    if (const char *e = getenv("MI_LTE_NO_MERGED_DECODE")) ctx->merged_decode = atoi(e) == 0;
     hipDeviceProp_t prop;
     if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) {
         delete ctx;
@@ -65,11 +68,6 @@ void mi_lte_ctx_destroy(mi_lte_ctx *ctx)
     for (void *p : ctx->owned) (void)hipFree(p);
     for (hipEvent_t e : ctx->prof_pool) (void)hipEventDestroy(e);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->side_stream) (void)hipStreamSynchronize(ctx->side_stream);
-    if (ctx->side_scratch) (void)hipFree(ctx->side_scratch);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-    if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
     if (ctx->h_small) (void)hipHostFree(ctx->h_small);
     if (ctx->h_bounce) (void)hipHostFree(ctx->h_bounce);
     for (int k = 0; k < 2; k++)

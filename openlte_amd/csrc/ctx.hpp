@@ -44,11 +44,6 @@ struct mi_lte_ctx {
     double             copy_rates[3] = {0, 0, 0}; // mi_lte_device_copy_rate's three kernel shapes, GB/s of the last call
     void              *scratch       = nullptr;
     size_t             scratch_bytes = 0;
-    // a second stream with its own scratch: the smaller block-size groups of a PDSCH decode run there next to the largest one (chain.hip)
-    hipStream_t        side_stream = nullptr;
-    hipEvent_t         ev_fork = nullptr, ev_join = nullptr;
-    void              *side_scratch       = nullptr;
-    size_t             side_scratch_bytes = 0;
     uint32_t          *h_flag = nullptr, *d_flag = nullptr; // the completion word of the per-call waits (mi_stream_wait_polling) and its sequence number
     uint32_t           flag_seq = 0;
     uint32_t *bcjr_early_buf = nullptr; size_t bcjr_early_cap = 0; // ctx-owned copy of the change words (the scratch they are counted in is shared with every other kernel family)
@@ -136,10 +131,7 @@ hipError_t mi_stream_wait_polling(mi_lte_ctx *ctx); // the per-call forms' wait:
 int   mi_ctx_gold_tables(mi_lte_ctx *ctx);
 int   mi_ctx_crc_table(mi_lte_ctx *ctx);
 int   mi_ctx_fft_twiddles(mi_lte_ctx *ctx);
-int   mi_turbo_ref_group(mi_lte_ctx *ctx, uint32_t K, uint32_t n_cb, const mi_lte_pdsch_alloc *d_allocs,
-                         const uint32_t *d_cb_alloc, const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len,
-                         uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t e_max_bytes, bool ul = false, bool packed = false);
-// the merged REF decode of a batch with many code-block sizes (turbo.hip: KSeg, mi_turbo_ref_multi)
+// the REF decode of a plan's block-size groups: many sizes in one launch set (turbo.hip: KSeg, mi_turbo_ref_multi) or size by size
 struct MiKGroup { uint32_t K, n_cb, cb_base, e_max; }; // a block size's code blocks: slots cb_base .. cb_base + n_cb of the batch's code-block order; e_max: its longest allocation's soft bits
 struct MiMultiGeom { // launch geometry derived from the groups; classes = workgroup widths 64 (c + 1)
     uint64_t arr_bytes = 0;                           // bytes of one scratch array over all sizes
@@ -154,10 +146,9 @@ struct MiMultiGeom { // launch geometry derived from the groups; classes = workg
     size_t   map_off = 0;                             // bytes from the table's start to the maps
 };
 struct MiMultiCache { void *d_tab = nullptr; size_t cap = 0; std::vector<MiKGroup> built_for; MiMultiGeom geom; };
-bool  mi_turbo_ref_multi_takes(uint32_t K, uint32_t e_max_bytes);
-int   mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_groups, const mi_lte_pdsch_alloc *d_allocs, const uint32_t *d_cb_alloc,
-                         const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
-                         bool ul, bool packed, MiMultiCache *cache);
+int   mi_turbo_ref_dispatch(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_groups, const mi_lte_pdsch_alloc *d_allocs, const uint32_t *d_cb_alloc,
+                            const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
+                            bool ul, bool packed, MiMultiCache *cache);
 void  mi_multi_cache_free(MiMultiCache *cache);
 int   mi_turbo_bcjr_group(mi_lte_ctx *ctx, uint32_t K, uint32_t n_cb, const mi_lte_pdsch_alloc *d_allocs, const uint32_t *d_cb_alloc, const int8_t *d_e,
                           const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, bool ul,

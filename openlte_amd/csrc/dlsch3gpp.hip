@@ -116,36 +116,53 @@ struct Rm3 {
     }
 };
 
-// Rate un-matching of one code block into the decoder's int8 layout d[i*3+x], tail included: position p of the circular buffer receives
-// e[rank(p) + t Nnn], t = 0, 1, .. (rank = non-NULL positions between k0 and p in walk order), summed and then saturated to +-127; a
-// position no soft bit reaches is 0.  The block's E_r soft bits are staged in LDS (aligned dwords) when they fit.
-__global__ __launch_bounds__(256) void k_dl3_rm_i8(const Dl3Desc *__restrict__ desc, const int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off,
-                                                   int8_t *__restrict__ soft, uint32_t e_cap)
-{
-    extern __shared__ __attribute__((aligned(16))) int8_t e_lds[];
-    const Dl3Desc &d = desc[blockIdx.x];
-    const uint32_t K = d.K, D = K + 4, E = d.E, n = 3 * D;
-    Rm3 rm;
-    rm.init(D, d.N_cb, d.k0);
-    const int8_t  *e     = e_base + (size_t)e_off[d.alloc] * 64 + d.off; // (an allocation's slot is 64-byte aligned and padded to 64 bytes)
-    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(e) & 3u);
-    const bool     staged = shift + E <= e_cap;
-    if (staged) {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(e - shift);
-        for (uint32_t w = threadIdx.x; w < (shift + E + 3) / 4; w += blockDim.x) reinterpret_cast<uint32_t *>(e_lds)[w] = src[w];
+__device__ __forceinline__ int sat16(int v) { return max(-32768, min(32767, v)); }
+__device__ __forceinline__ int clamp127(int v) { return max(-127, min(127, v)); }
+
+// Rate un-matching of one code block into the decoder's int8 layout d[i*3+x], tail included, the part k_dl3_rm_i8 and k_harq_rm share:
+// stage() puts the block's E_r soft bits in LDS (aligned dwords) when they fit; sum(t) is what position p of d[t] in the circular buffer
+// receives, e[rank(p) + t Nnn], t = 0, 1, .. (rank = non-NULL positions between k0 and p in walk order), summed; 0 where no soft bit reaches.
+struct Dl3Gather {
+    Rm3           rm;
+    const int8_t *es;
+    uint32_t      E, n; // E_r; the block's 3 (K + 4) positions
+    __device__ void stage(const Dl3Desc &d, const int8_t *e_base, const uint32_t *e_off, int8_t *e_lds, uint32_t e_cap)
+    {
+        const uint32_t D = d.K + 4;
+        E = d.E; n = 3 * D;
+        rm.init(D, d.N_cb, d.k0);
+        const int8_t  *e      = e_base + (size_t)e_off[d.alloc] * 64 + d.off; // (an allocation's slot is 64-byte aligned and padded to 64 bytes)
+        const uint32_t shift  = (uint32_t)(reinterpret_cast<uintptr_t>(e) & 3u);
+        const bool     staged = shift + E <= e_cap;
+        if (staged) {
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(e - shift);
+            for (uint32_t w = threadIdx.x; w < (shift + E + 3) / 4; w += blockDim.x) reinterpret_cast<uint32_t *>(e_lds)[w] = src[w];
+        }
+        __syncthreads();
+        es = staged ? e_lds + shift : e;
     }
-    __syncthreads();
-    const int8_t *es = staged ? e_lds + shift : e;
-    int8_t       *db = soft + (size_t)d.soft_off4 * 4;
-    for (uint32_t t = threadIdx.x; t < n; t += blockDim.x) {
+    __device__ int sum(uint32_t t) const
+    {
         const uint32_t i = t / 3;
         uint32_t       p, cn;
         rm.pos_cnt(i, (int)(t - 3 * i), p, cn);
         int v = 0;
         if (p < rm.N_cb)
             for (uint32_t k = p >= rm.k0m ? cn - rm.cnt_k0 : rm.Nnn - rm.cnt_k0 + cn; k < E; k += rm.Nnn) v += es[k];
-        db[t] = (int8_t)max(-127, min(127, v));
+        return v;
     }
+};
+
+// the sums saturated to +-127
+__global__ __launch_bounds__(256) void k_dl3_rm_i8(const Dl3Desc *__restrict__ desc, const int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off,
+                                                   int8_t *__restrict__ soft, uint32_t e_cap)
+{
+    extern __shared__ __attribute__((aligned(16))) int8_t e_lds[];
+    const Dl3Desc &d = desc[blockIdx.x];
+    Dl3Gather      g;
+    g.stage(d, e_base, e_off, e_lds, e_cap);
+    int8_t *db = soft + (size_t)d.soft_off4 * 4;
+    for (uint32_t t = threadIdx.x; t < g.n; t += blockDim.x) db[t] = (int8_t)clamp127(g.sum(t));
 }
 
 __device__ __forceinline__ uint32_t wave_xor(uint32_t v)
@@ -246,9 +263,6 @@ __global__ __launch_bounds__(256) void k_harq_bind(const Dl3Desc *__restrict__ d
     for (uint32_t r = 0; r < d.C; r++) slot_buf[s0 + r] = w;
 }
 
-__device__ __forceinline__ int sat16(int v) { return max(-32768, min(32767, v)); }
-__device__ __forceinline__ int clamp127(int v) { return max(-127, min(127, v)); }
-
 // k_dl3_rm_i8 with soft combining: a slot bound to a buffer sums position t's soft bits as k_dl3_rm_i8 does (v), then
 // buf[t] = sat16(buf[t] + sat16(v)) (buf[t] = 0 when the slot's buffer was flushed) and the decoder's input is clamp(buf[t], +-127).
 // Two positions per lane: one dword of the buffer read and written (block r starts at an even position), one int16 of the int8 output.
@@ -259,37 +273,18 @@ __global__ __launch_bounds__(256) void k_harq_rm(const Dl3Desc *__restrict__ des
 {
     extern __shared__ __attribute__((aligned(16))) int8_t e_lds[];
     const Dl3Desc &d = desc[blockIdx.x];
-    const uint32_t K = d.K, D = K + 4, E = d.E, n = 3 * D;
-    Rm3 rm;
-    rm.init(D, d.N_cb, d.k0);
-    const int8_t  *e     = e_base + (size_t)e_off[d.alloc] * 64 + d.off;
-    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(e) & 3u);
-    const bool     staged = shift + E <= e_cap;
-    if (staged) {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(e - shift);
-        for (uint32_t w = threadIdx.x; w < (shift + E + 3) / 4; w += blockDim.x) reinterpret_cast<uint32_t *>(e_lds)[w] = src[w];
-    }
-    __syncthreads();
-    const int8_t *es = staged ? e_lds + shift : e;
-    int8_t       *db = soft + (size_t)d.soft_off4 * 4;
-    auto gather = [&](uint32_t t) {
-        const uint32_t i = t / 3;
-        uint32_t       p, cn;
-        rm.pos_cnt(i, (int)(t - 3 * i), p, cn);
-        int v = 0;
-        if (p < rm.N_cb)
-            for (uint32_t k = p >= rm.k0m ? cn - rm.cnt_k0 : rm.Nnn - rm.cnt_k0 + cn; k < E; k += rm.Nnn) v += es[k];
-        return v;
-    };
-    const uint32_t sb = slot_buf[blockIdx.x];
+    Dl3Gather      g;
+    g.stage(d, e_base, e_off, e_lds, e_cap);
+    int8_t        *db = soft + (size_t)d.soft_off4 * 4;
+    const uint32_t sb = slot_buf[blockIdx.x], n = g.n;
     if (sb == MI_LTE_HARQ_NONE) {
-        for (uint32_t t = threadIdx.x; t < n; t += blockDim.x) db[t] = (int8_t)clamp127(gather(t));
+        for (uint32_t t = threadIdx.x; t < n; t += blockDim.x) db[t] = (int8_t)clamp127(g.sum(t));
         return;
     }
     const bool flush = (sb & HARQ_FLUSH) != 0;
     uint32_t  *hb    = reinterpret_cast<uint32_t *>(pool + (size_t)(sb & ~HARQ_FLUSH) * buf_elems + (size_t)d.r * n);
     for (uint32_t t2 = threadIdx.x; t2 < n / 2; t2 += blockDim.x) {
-        const int      v0 = sat16(gather(2 * t2)), v1 = sat16(gather(2 * t2 + 1));
+        const int      v0 = sat16(g.sum(2 * t2)), v1 = sat16(g.sum(2 * t2 + 1));
         const uint32_t w  = flush ? 0u : hb[t2];
         const int      b0 = sat16((int)(int16_t)(w & 0xFFFFu) + v0), b1 = sat16((int)(int16_t)(w >> 16) + v1);
         hb[t2] = (uint32_t)(uint16_t)b0 | ((uint32_t)(uint16_t)b1 << 16);
@@ -402,39 +397,6 @@ int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_
     return MI_LTE_OK;
 }
 
-// the decode and the finish of a run, after the rate un-matching
-static int dlsch3_decode_finish(mi_lte_ctx *ctx, MiDlsch3 *g, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t decoder,
-                                uint32_t n_iter, uint32_t packed)
-{
-    for (const auto &gr : g->groups) {
-        const int8_t *s = g->d_soft + gr.soft_off;
-        uint8_t      *b = g->d_bits + gr.bits_off;
-        const int rc = decoder == MI_LTE_TURBO_BCJR_BLOCK ? mi_turbo_bcjr_block_batch(ctx, s, gr.K, gr.n_cb, n_iter, 1, b)
-                                                          : mi_turbo_bcjr_batch(ctx, s, gr.K, gr.n_cb, n_iter, 1, b, decoder == MI_LTE_TURBO_BCJR_EARLY);
-        if (rc != MI_LTE_OK) return rc;
-    }
-    MI_LAUNCH(ctx, "k_dl3_cb_finish", k_dl3_cb_finish, dim3(g->n_slot), dim3(256), 0, (const Dl3Desc *)g->d_desc, (const uint8_t *)g->d_bits,
-              (const uint32_t *)g->d_tab, (const uint32_t *)(g->d_tab + 6144), d_out_bits, out_stride, packed, g->d_part, g->d_ok);
-    MI_LAUNCH(ctx, "k_dl3_tb_finish", k_dl3_tb_finish, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const uint32_t *)g->d_a_slot,
-              (const uint32_t *)g->d_a_nc, g->n_alloc, (const uint32_t *)g->d_part, (const uint32_t *)g->d_ok, d_status, g->d_cb_ok);
-    MI_HIP_CHECK(ctx, hipGetLastError());
-    return MI_LTE_OK;
-}
-
-// everything after the demodulator (chain.hip: mi_lte_pdsch_decode_run on a 3GPP plan)
-int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, const mi_lte_pdsch_alloc *d_allocs, const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len,
-                  uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t decoder, uint32_t n_iter, uint32_t packed)
-{
-    MI_LAUNCH(ctx, "k_dl3_desc", k_dl3_desc, dim3((g->n_slot + 255) / 256), dim3(256), 0, (const Dl3Slot *)g->d_slot, g->n_slot, d_allocs, d_e_len,
-              g->cfg.N_soft, g->cfg.M_dl_harq, g->d_desc);
-    MI_LAUNCH(ctx, "k_dl3_rm_i8", k_dl3_rm_i8, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, d_e, d_e_off, g->d_soft, DL3_E_CAP);
-    MI_HIP_CHECK(ctx, hipGetLastError());
-    const int rc = dlsch3_decode_finish(ctx, g, d_out_bits, out_stride, d_status, decoder, n_iter, packed);
-    if (rc != MI_LTE_OK) return rc;
-    ctx->last_kernels = "k_pdsch_demod:1,k_dl3_desc:1,k_dl3_rm_i8:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1";
-    return MI_LTE_OK;
-}
-
 // ------------------------------------------------------------------------------------------------
 // HARQ soft-buffer pool (include/mi_lte.h)
 
@@ -532,37 +494,54 @@ int mi_dlsch3_harq_check(mi_lte_ctx *ctx, const MiDlsch3 *g, const mi_lte_harq_p
     return MI_LTE_OK;
 }
 
-// everything after the demodulator in a HARQ run (chain.hip: mi_lte_pdsch_decode_run_harq); mi_dlsch3_harq_check has passed
-int mi_dlsch3_run_harq(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const mi_lte_pdsch_alloc *d_allocs,
-                       const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
-                       uint32_t decoder, uint32_t n_iter, uint32_t packed)
+// Everything after the demodulator (chain.hip: a plan run on a 3GPP plan).  p: the pool of a HARQ run and h_bind its bindings
+// (mi_dlsch3_harq_check has passed); nullptr: a plain run.
+int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const mi_lte_pdsch_alloc *d_allocs,
+                  const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
+                  uint32_t decoder, uint32_t n_iter, uint32_t packed)
 {
-    if (g->n_alloc > p->cap_bind) { // (a larger plan than any before: the queued runs that read the old blocks finish first)
-        MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (p->d_bind) { (void)hipFree(p->d_bind); p->d_bind = nullptr; }
-        if (p->h_bind) { (void)hipHostFree(p->h_bind); p->h_bind = nullptr; }
-        p->cap_bind = 0;
-        MI_HIP_CHECK(ctx, hipMalloc((void **)&p->d_bind, sizeof(mi_lte_harq_bind) * g->n_alloc));
-        MI_HIP_CHECK(ctx, hipHostMalloc((void **)&p->h_bind, sizeof(mi_lte_harq_bind) * g->n_alloc, hipHostMallocDefault));
-        p->cap_bind = g->n_alloc;
+    if (p) {
+        if (g->n_alloc > p->cap_bind) { // (a larger plan than any before: the queued runs that read the old blocks finish first)
+            MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+            if (p->d_bind) { (void)hipFree(p->d_bind); p->d_bind = nullptr; }
+            if (p->h_bind) { (void)hipHostFree(p->h_bind); p->h_bind = nullptr; }
+            p->cap_bind = 0;
+            MI_HIP_CHECK(ctx, hipMalloc((void **)&p->d_bind, sizeof(mi_lte_harq_bind) * g->n_alloc));
+            MI_HIP_CHECK(ctx, hipHostMalloc((void **)&p->h_bind, sizeof(mi_lte_harq_bind) * g->n_alloc, hipHostMallocDefault));
+            p->cap_bind = g->n_alloc;
+        }
+        MI_HIP_CHECK(ctx, hipEventSynchronize(p->staged)); // the previous run's binding copy has left the staging block
+        memcpy(p->h_bind, h_bind, sizeof(mi_lte_harq_bind) * g->n_alloc);
+        MI_HIP_CHECK(ctx, hipMemcpyAsync(p->d_bind, p->h_bind, sizeof(mi_lte_harq_bind) * g->n_alloc, hipMemcpyHostToDevice, ctx->stream));
+        MI_HIP_CHECK(ctx, hipEventRecord(p->staged, ctx->stream));
     }
-    MI_HIP_CHECK(ctx, hipEventSynchronize(p->staged)); // the previous run's binding copy has left the staging block
-    memcpy(p->h_bind, h_bind, sizeof(mi_lte_harq_bind) * g->n_alloc);
-    MI_HIP_CHECK(ctx, hipMemcpyAsync(p->d_bind, p->h_bind, sizeof(mi_lte_harq_bind) * g->n_alloc, hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP_CHECK(ctx, hipEventRecord(p->staged, ctx->stream));
     MI_LAUNCH(ctx, "k_dl3_desc", k_dl3_desc, dim3((g->n_slot + 255) / 256), dim3(256), 0, (const Dl3Slot *)g->d_slot, g->n_slot, d_allocs, d_e_len,
               g->cfg.N_soft, g->cfg.M_dl_harq, g->d_desc);
-    MI_LAUNCH(ctx, "k_harq_bind", k_harq_bind, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const Dl3Desc *)g->d_desc, (const uint32_t *)g->d_a_slot,
-              g->n_alloc, (const mi_lte_harq_bind *)p->d_bind, p->d_state, g->d_slot_buf);
-    MI_LAUNCH(ctx, "k_harq_rm", k_harq_rm, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, d_e, d_e_off, g->d_soft, DL3_E_CAP,
-              (const uint32_t *)g->d_slot_buf, p->d_soft, p->buf_elems);
+    if (p) {
+        MI_LAUNCH(ctx, "k_harq_bind", k_harq_bind, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const Dl3Desc *)g->d_desc, (const uint32_t *)g->d_a_slot,
+                  g->n_alloc, (const mi_lte_harq_bind *)p->d_bind, p->d_state, g->d_slot_buf);
+        MI_LAUNCH(ctx, "k_harq_rm", k_harq_rm, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, d_e, d_e_off, g->d_soft, DL3_E_CAP,
+                  (const uint32_t *)g->d_slot_buf, p->d_soft, p->buf_elems);
+    } else
+        MI_LAUNCH(ctx, "k_dl3_rm_i8", k_dl3_rm_i8, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, d_e, d_e_off, g->d_soft, DL3_E_CAP);
     MI_HIP_CHECK(ctx, hipGetLastError());
-    const int rc = dlsch3_decode_finish(ctx, g, d_out_bits, out_stride, d_status, decoder, n_iter, packed);
-    if (rc != MI_LTE_OK) return rc;
-    MI_LAUNCH(ctx, "k_harq_commit", k_harq_commit, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const mi_lte_harq_bind *)p->d_bind, g->n_alloc,
-              (const int32_t *)d_status, p->d_state);
+    for (const auto &gr : g->groups) {
+        const int8_t *s = g->d_soft + gr.soft_off;
+        uint8_t      *b = g->d_bits + gr.bits_off;
+        const int rc = decoder == MI_LTE_TURBO_BCJR_BLOCK ? mi_turbo_bcjr_block_batch(ctx, s, gr.K, gr.n_cb, n_iter, 1, b)
+                                                          : mi_turbo_bcjr_batch(ctx, s, gr.K, gr.n_cb, n_iter, 1, b, decoder == MI_LTE_TURBO_BCJR_EARLY);
+        if (rc != MI_LTE_OK) return rc;
+    }
+    MI_LAUNCH(ctx, "k_dl3_cb_finish", k_dl3_cb_finish, dim3(g->n_slot), dim3(256), 0, (const Dl3Desc *)g->d_desc, (const uint8_t *)g->d_bits,
+              (const uint32_t *)g->d_tab, (const uint32_t *)(g->d_tab + 6144), d_out_bits, out_stride, packed, g->d_part, g->d_ok);
+    MI_LAUNCH(ctx, "k_dl3_tb_finish", k_dl3_tb_finish, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const uint32_t *)g->d_a_slot,
+              (const uint32_t *)g->d_a_nc, g->n_alloc, (const uint32_t *)g->d_part, (const uint32_t *)g->d_ok, d_status, g->d_cb_ok);
+    if (p)
+        MI_LAUNCH(ctx, "k_harq_commit", k_harq_commit, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const mi_lte_harq_bind *)p->d_bind, g->n_alloc,
+                  (const int32_t *)d_status, p->d_state);
     MI_HIP_CHECK(ctx, hipGetLastError());
-    ctx->last_kernels = "k_pdsch_demod:1,k_dl3_desc:1,k_harq_bind:1,k_harq_rm:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1,k_harq_commit:1";
+    ctx->last_kernels = p ? "k_pdsch_demod:1,k_dl3_desc:1,k_harq_bind:1,k_harq_rm:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1,k_harq_commit:1"
+                          : "k_pdsch_demod:1,k_dl3_desc:1,k_dl3_rm_i8:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1";
     return MI_LTE_OK;
 }
 

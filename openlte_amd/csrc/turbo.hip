@@ -2075,11 +2075,10 @@ static int rm_rank_tables(mi_lte_ctx *ctx, uint32_t K, RmTables *out)
     return MI_LTE_OK;
 }
 
-// used by the PDSCH chain (chain.hip): decode the code blocks of one size K straight from the
-// demodulator's soft bits
-int mi_turbo_ref_group(mi_lte_ctx *ctx, uint32_t K, uint32_t n_cb, const mi_lte_pdsch_alloc *d_allocs,
-                       const uint32_t *d_cb_alloc, const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len,
-                       uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t e_max_bytes, bool ul, bool packed)
+// the per-size path of mi_turbo_ref_dispatch: decode the code blocks of one size K straight from the demodulator's soft bits
+static int mi_turbo_ref_group(mi_lte_ctx *ctx, uint32_t K, uint32_t n_cb, const mi_lte_pdsch_alloc *d_allocs,
+                              const uint32_t *d_cb_alloc, const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len,
+                              uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t e_max_bytes, bool ul, bool packed)
 {
     int rc = mi_ctx_crc_table(ctx);
     if (rc != MI_LTE_OK) return rc;
@@ -2107,15 +2106,15 @@ int mi_turbo_ref_group(mi_lte_ctx *ctx, uint32_t K, uint32_t n_cb, const mi_lte_
 
 // Can the block-size group join a merged decode?  The merged kernels keep the rate un-matching sums as int16 pairs (SrcRateUnmatchPk): a
 // group whose longest allocation makes more than 258 laps of the circular buffer takes the per-size path with 32-bit sums instead.
-bool mi_turbo_ref_multi_takes(uint32_t K, uint32_t e_max_bytes) { return (e_max_bytes + (3 * K - 81) - 1) / (3 * K - 81) <= 258; }
+static bool mi_turbo_ref_multi_takes(uint32_t K, uint32_t e_max_bytes) { return (e_max_bytes + (3 * K - 81) - 1) / (3 * K - 81) <= 258; }
 
 // A whole PDSCH batch -- the code blocks of MANY sizes -- through the REF decoder with every kernel launched once (the per-code-block
 // kernels once per workgroup width): see KSeg.  `groups` in ascending K, cb_base = the group's first slot in d_cb_alloc.  The tables the
 // kernels read are rebuilt only when the groups differ from the ones `cache` was built for (a static plan: once; a dynamic plan: per
 // assignment).
-int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_groups, const mi_lte_pdsch_alloc *d_allocs, const uint32_t *d_cb_alloc,
-                       const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
-                       bool ul, bool packed, MiMultiCache *cache)
+static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_groups, const mi_lte_pdsch_alloc *d_allocs, const uint32_t *d_cb_alloc,
+                              const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
+                              bool ul, bool packed, MiMultiCache *cache)
 {
     if (!groups || n_groups == 0 || n_groups > 0xFFFF || !cache) return MI_LTE_ERR_INVALID_ARG;
     int rc = mi_ctx_crc_table(ctx);
@@ -2127,6 +2126,7 @@ int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_group
     auto cls_of = [](uint32_t K) { return (int)((((kpad64(K) >> 4) + 63) >> 6) - 1); };
     const bool same = cache->built_for.size() == n_groups && memcmp(cache->built_for.data(), groups, sizeof(MiKGroup) * n_groups) == 0;
     if (!same) {
+        cache->built_for.clear(); // (until the upload below has succeeded: a rebuild that fails part-way leaves no key next to its tables)
         std::vector<KSeg>     segs(n_groups);
         std::vector<uint32_t> map;
         MiMultiGeom          &G = cache->geom;
@@ -2213,43 +2213,28 @@ int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_group
         // a compute unit's four resident workgroups are neighbours in the sorted order and the unit that got the four longest decides when the
         // launch ends.  Dealt out in rounds of 256 (one workgroup per compute unit and round), every other round backwards, each unit gets the
         // r-th longest of one round with the r-th shortest of the next: equal sums (0.07 ms of the mixed batch's 3.6; a scatter that gives up
-        // "longest first" costs 1.3).  Batches of a few sizes (W4) keep the sorted order.  (MI_LTE_SISO_ORDER=0 / 1: A/B.)
+        // "longest first" costs 1.3).  Batches of a few sizes (W4) keep the sorted order.
         // And how many of them a compute unit holds at a time.  The registers allow four (16 walks per unit, 4096 in all): right for W4, whose
         // walks are equally long and come in more than two rounds of that.  A mixed batch of this size has 1.2 rounds (pass 1) and 2.3 (passes
         // 2 + 3) of walks between 44 and 4612 steps: the units that drew short ones run dry and nothing is left to hand them.  Half as many
         // resident workgroups are twice as many rounds -- the queue stays non-empty until close to the end -- at the price of fewer wavefronts to
         // hide latency behind; measured on the mixed batch (gpurun_out/occ*.log): 2 per unit for pass 1 and 3 for passes 2 + 3 take 0.12-0.15 ms
         // off the trellis kernel's 3.6, one per unit costs 0.15.  The limit is set with dynamic LDS that the kernel never touches.
-        G.n_ord1 = G.n_ord23 = 0;
-        G.siso_pad1 = G.siso_pad23 = 0;
         const bool many_sizes = n_groups >= 8;
         if (many_sizes) { G.siso_pad1 = 60000; G.siso_pad23 = 45000; } // (+ the kernel's own 8 KB: two / three of them in a unit's 160 KB)
-        if (getenv("MI_LTE_SISO1_LDS")) G.siso_pad1 = (uint32_t)atoi(getenv("MI_LTE_SISO1_LDS"));
-        if (getenv("MI_LTE_SISO23_LDS")) G.siso_pad23 = (uint32_t)atoi(getenv("MI_LTE_SISO23_LDS"));
-        {
-            const char *eo = getenv("MI_LTE_SISO_ORDER");
-            const int   mode = eo ? atoi(eo) : (many_sizes ? 1 : 0);
-            auto deal = [&](uint32_t n_wv, uint32_t *at, uint32_t *n_out) {
-                const uint32_t n_wg = (n_wv + 3) / 4;
-                if (mode == 0 || n_wg < 512) { *n_out = 0; return; }
-                *at = (uint32_t)map.size();
-                for (uint32_t j = 0; j < n_wg; j++) {
-                    const uint32_t round = j / 256, c = j % 256, in_round = std::min(256u, n_wg - 256 * round);
-                    uint32_t       src = j;
-                    if (mode == 1 && (round & 1u)) src = 256 * round + (in_round - 1 - std::min(c, in_round - 1));
-                    if (mode == 2) { // (a scatter by a stride coprime to the count, for comparison)
-                        uint32_t st = (uint32_t)(0.618 * n_wg) | 1u;
-                        auto gcd = [](uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; };
-                        while (gcd(st, n_wg) != 1) st += 2;
-                        src = (uint32_t)(((uint64_t)j * st) % n_wg);
-                    }
-                    for (uint32_t t = 0; t < 4; t++) map.push_back(4 * src + t < n_wv ? 4 * src + t : 0xFFFFFFFFu);
-                }
-                *n_out = 4 * n_wg;
-            };
-            deal(G.n_wv1, &G.ord_wv1, &G.n_ord1);
-            deal(G.n_wv23, &G.ord_wv23, &G.n_ord23);
-        }
+        auto deal = [&](uint32_t n_wv, uint32_t *at, uint32_t *n_out) {
+            const uint32_t n_wg = (n_wv + 3) / 4;
+            if (!many_sizes || n_wg < 512) return; // (*n_out stays 0: the sorted order)
+            *at = (uint32_t)map.size();
+            for (uint32_t j = 0; j < n_wg; j++) {
+                const uint32_t round = j / 256, c = j % 256, in_round = std::min(256u, n_wg - 256 * round);
+                const uint32_t src = (round & 1u) ? 256 * round + (in_round - 1 - std::min(c, in_round - 1)) : j;
+                for (uint32_t t = 0; t < 4; t++) map.push_back(4 * src + t < n_wv ? 4 * src + t : 0xFFFFFFFFu);
+            }
+            *n_out = 4 * n_wg;
+        };
+        deal(G.n_wv1, &G.ord_wv1, &G.n_ord1);
+        deal(G.n_wv23, &G.ord_wv23, &G.n_ord23);
         // ... and of the state-parallel trellis kernel (a handful of code blocks in all): workgroup = wavefront = up to gpw trellises of one size
         auto gpw_of = [](uint32_t n_tr) { return n_tr <= 2048 ? 1u : n_tr <= 4096 ? 2u : n_tr <= 8192 ? 4u : SMALL_G; };
         uint32_t tot = 0, kp_all = 0;
@@ -2360,7 +2345,37 @@ int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_group
             MI_LAUNCH(ctx, "k_turbo_vote", (k_turbo_vote<true, 1, true>), dim3(G.grid_cb[c]), dim3(64 * (c + 1)), 3 * G.kp_max[c] + 64, va, 0u, 0u, (const uint16_t *)nullptr,
                       (uint8_t *)nullptr, gd, (MultiArgs{d_segs, d_map + G.map_cb[c]}));
     MI_HIP_CHECK(ctx, hipGetLastError());
-    ctx->last_kernels = "k_cb_desc:1,k_turbo_prep,k_turbo_siso:2,k_turbo_perm,k_turbo_vote per workgroup width over all block sizes";
+    return MI_LTE_OK;
+}
+
+// The REF decode of a plan's block-size groups (chain.hip: PDSCH plans, uplink.hip: PUSCH plans; `groups` in ascending K).  Several block
+// sizes -- a batch, or a per-call caller's subframe with a handful of transport blocks -- take ONE launch set over all of them
+// (mi_turbo_ref_multi, see KSeg): a cell's TTIs hold dozens of the 188 sizes, and size by size that is ~7 launches per size in series, each a
+// sliver of the device -- 65 536 mixed subframes took 72.6 ms that way, 48.8 of them in the decoder (profiles/r06_chain_mixed_per_size.json).
+// That needs ctx->merged_decode and two groups the merged kernels take; every other group (more than 258 laps: 32-bit sums), and every group
+// when the merged launches do not run, takes its own launches.  Sets the decoder's part of ctx->last_kernels.
+int mi_turbo_ref_dispatch(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_groups, const mi_lte_pdsch_alloc *d_allocs, const uint32_t *d_cb_alloc,
+                          const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
+                          bool ul, bool packed, MiMultiCache *cache)
+{
+    std::vector<MiKGroup> take;
+    if (ctx->merged_decode)
+        for (uint32_t i = 0; i < n_groups; i++)
+            if (mi_turbo_ref_multi_takes(groups[i].K, groups[i].e_max)) take.push_back(groups[i]);
+    const bool merged = take.size() >= 2;
+    int        rc;
+    if (merged && (rc = mi_turbo_ref_multi(ctx, take.data(), (uint32_t)take.size(), d_allocs, d_cb_alloc, d_e, d_e_off, d_e_len, d_out_bits, out_stride,
+                                           d_status, ul, packed, cache)) != MI_LTE_OK)
+        return rc;
+    for (uint32_t i = 0; i < n_groups; i++) {
+        const MiKGroup &gr = groups[i];
+        if (merged && mi_turbo_ref_multi_takes(gr.K, gr.e_max)) continue;
+        rc = mi_turbo_ref_group(ctx, gr.K, gr.n_cb, d_allocs, d_cb_alloc + gr.cb_base, d_e, d_e_off, d_e_len, d_out_bits, out_stride, d_status, gr.e_max, ul, packed);
+        if (rc != MI_LTE_OK) return rc;
+    }
+    ctx->last_kernels = !merged                 ? "k_turbo_prep,k_turbo_siso,k_turbo_perm,k_turbo_vote per block size"
+                        : take.size() == n_groups ? "k_cb_desc:1,k_turbo_prep,k_turbo_siso:2,k_turbo_perm,k_turbo_vote per workgroup width over all block sizes"
+                                                  : "k_cb_desc:1,k_turbo_prep,k_turbo_siso:2,k_turbo_perm,k_turbo_vote per workgroup width over all block sizes but the per-size ones";
     return MI_LTE_OK;
 }
 

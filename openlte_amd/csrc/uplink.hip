@@ -454,10 +454,9 @@ struct mi_lte_pusch_plan {
     float              *d_dmrs   = nullptr;
     uint32_t *d_e_off = nullptr, *d_e_len = nullptr, *d_cb_alloc = nullptr;
     int8_t   *d_e = nullptr;
-    struct Group { uint32_t K, n_cb, cb_base, e_max; };
-    std::vector<Group>    groups;
+    std::vector<MiKGroup> groups;
     std::vector<uint32_t> h_e_off, h_e_len;
-    MiMultiCache          multi; // the merged decode's device tables for `groups` (turbo.hip: mi_turbo_ref_multi)
+    MiMultiCache          multi; // the merged decode's device tables for `groups` (turbo.hip: mi_turbo_ref_dispatch)
 };
 
 // the float next above or equal to 1 / d (see quot)
@@ -670,24 +669,11 @@ int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float 
     if (threads == 64) MI_PUSCH_LAUNCH(64); else if (threads == 128) MI_PUSCH_LAUNCH(128); else if (threads == 192) MI_PUSCH_LAUNCH(192); else MI_PUSCH_LAUNCH(256);
 #undef MI_PUSCH_LAUNCH
     MI_HIP_CHECK(ctx, hipGetLastError());
-    // several block sizes (the UEs of a subframe rarely share one): one launch set over all of them (turbo.hip: KSeg), as in the PDSCH chain
-    std::vector<MiKGroup> take;
-    if (ctx->merged_decode && pl->groups.size() >= 2)
-        for (auto &gr : pl->groups)
-            if (mi_turbo_ref_multi_takes(gr.K, gr.e_max)) take.push_back(MiKGroup{gr.K, gr.n_cb, gr.cb_base, gr.e_max});
-    if (take.size() >= 2) {
-        rc = mi_turbo_ref_multi(ctx, take.data(), (uint32_t)take.size(), pl->d_allocs, pl->d_cb_alloc, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits, pl->out_stride, d_status,
-                                /*ul=*/true, false, &pl->multi);
-        if (rc != MI_LTE_OK) return rc;
-    }
-    for (auto &gr : pl->groups) {
-        if (take.size() >= 2 && mi_turbo_ref_multi_takes(gr.K, gr.e_max)) continue;
-        rc = mi_turbo_ref_group(ctx, gr.K, gr.n_cb, pl->d_allocs, pl->d_cb_alloc + gr.cb_base, pl->d_e, pl->d_e_off, pl->d_e_len,
-                                d_out_bits, pl->out_stride, d_status, gr.e_max, /*ul=*/true);
-        if (rc != MI_LTE_OK) return rc;
-    }
-    ctx->last_kernels = take.size() >= 2 ? "k_pusch_demod:1,k_cb_desc:1,k_turbo_prep,k_turbo_siso:2,k_turbo_perm,k_turbo_vote per workgroup width over all block sizes"
-                                         : "k_pusch_demod:1,k_turbo_prep,k_turbo_siso,k_turbo_perm,k_turbo_vote per block size";
+    // several block sizes (the UEs of a subframe rarely share one): one launch set over all of them, as in the PDSCH chain
+    rc = mi_turbo_ref_dispatch(ctx, pl->groups.data(), (uint32_t)pl->groups.size(), pl->d_allocs, pl->d_cb_alloc, pl->d_e, pl->d_e_off, pl->d_e_len,
+                               d_out_bits, pl->out_stride, d_status, /*ul=*/true, false, &pl->multi);
+    if (rc != MI_LTE_OK) return rc;
+    ctx->last_kernels.insert(0, "k_pusch_demod:1,");
     return MI_LTE_OK;
 }
 
