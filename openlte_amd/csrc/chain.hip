@@ -6,10 +6,9 @@
 // SURVEY F4).
 #include <algorithm>
 #include <cstring>
-#include <map>
 #include <type_traits>
 
-#include "ctx.hpp"
+#include "plan_core.hpp"
 #include "phy_dev.hpp"
 
 namespace {
@@ -337,82 +336,50 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
 // ------------------------------------------------------------------------------------------------
 // host side: plans
 
-// the 3GPP transport-block mode's part of a plan (dlsch3gpp.hip)
-struct MiDlsch3;
-int             mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out);
-void            mi_dlsch3_free(MiDlsch3 *g);
-int             mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const mi_lte_pdsch_alloc *d_allocs,
-                              const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
-                              uint32_t decoder, uint32_t n_iter, uint32_t packed);
-int             mi_dlsch3_cb_soft(const MiDlsch3 *g, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K);
-const uint32_t *mi_dlsch3_cb_ok(const MiDlsch3 *g);
-int             mi_dlsch3_harq_check(mi_lte_ctx *ctx, const MiDlsch3 *g, const mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind);
-
 struct mi_lte_pdsch_plan {
     mi_lte_dl_cfg cfg;
+    MiPlanCore    core;
     uint32_t      decoder = MI_LTE_TURBO_REF, n_iter = 8; // MI_LTE_TURBO_BCJR: mi_lte_pdsch_plan_set_decoder
     int           qpp_spec = 0;
     int8_t       *d_bcjr_soft = nullptr;                  // [max n_cb][3(K+4)] int8 channel values of the group being decoded
     uint8_t      *d_bcjr_bits = nullptr;                  // [max n_cb][K] its hard decisions
     size_t        bcjr_soft_cap = 0, bcjr_bits_cap = 0;
-    uint32_t      cfi = 0, n_alloc = 0, out_stride = 0, max_pairs = 0, max_words = 0, max_tbs = 0, packed = 0;
-    size_t        e_bytes = 0;
-    // capacity of the device arrays (a dynamic plan is re-assigned within it; a static plan's capacity is its first assignment)
-    uint32_t      cap_alloc = 0;
-    size_t        cap_e_bytes = 0;
+    uint32_t      cfi = 0, max_pairs = 0, max_words = 0, max_tbs = 0;
     bool          dynamic = false, wide = false; // wide: the output stride of the largest single-code-block transport block, whatever is held
     bool          mapped = false; // the descriptor arrays ARE the pinned staging block, mapped into the device (mi_pdsch_plan_create_mapped)
-    mi_lte_pdsch_alloc *d_allocs = nullptr;
-    uint32_t *d_e_off = nullptr, *d_e_len = nullptr, *d_cb_alloc = nullptr;
-    int8_t   *d_e = nullptr;
     // pinned staging for re-assignments: allocs | e_off | cb_alloc, copied with one command each on the context's stream
     void       *h_stage = nullptr;
     hipEvent_t  staged = nullptr;
-    std::vector<MiKGroup> groups;
-    std::vector<uint32_t> h_e_off;
-    MiMultiCache          multi; // the merged decode's device tables for `groups` (turbo.hip: mi_turbo_ref_dispatch)
-    MiDlsch3             *g3 = nullptr; // 3GPP transport-block mode (mi_lte_pdsch_plan_create_3gpp): its code blocks and buffers (dlsch3gpp.hip)
+    std::vector<uint8_t>  h_row;    // plan_layout's per-allocation scratch: kept, so that a re-assignment (tens of thousands of allocations per
+    std::vector<uint32_t> h_e_bits; // chunk of a capture) allocates nothing
+    MiDlsch3   *g3 = nullptr; // 3GPP transport-block mode (mi_lte_pdsch_plan_create_3gpp): its code blocks and buffers (dlsch3gpp.hip)
 };
 
-static uint32_t qpp_size_at_least(uint32_t B);
-#include "lte_tables.h"
-static uint32_t qpp_size_at_least(uint32_t B)
-{
-    for (int r = 0; r < LTE_QPP_N_SIZES; r++)
-        if (LTE_QPP_ROWS[r].K >= B) return LTE_QPP_ROWS[r].K;
-    return 0;
+static void plan_set_stride(mi_lte_pdsch_plan *pl)
+{ // a dynamic plan keeps ONE output stride over its assignments: the largest single-code-block size
+    pl->core.out_stride = mi_out_stride((pl->dynamic || pl->wide) ? 6120u : pl->max_tbs, pl->core.packed != 0);
 }
 
-// Host side of a plan: group the allocations by code-block size, lay their soft bits out.  Fills everything but the device arrays;
-// cb_alloc receives the allocation index of every code-block slot, group after group.
+// Host side of a plan: check the allocations, lay their soft bits out and group them by code-block size.  Fills everything but the device arrays;
+// cb_alloc receives the allocation index of every code-block slot, group after group.  cb_alloc == nullptr: the soft-bit layout alone (the 3GPP
+// mode: its code blocks are dlsch3gpp.hip's, and no allocation is outside the envelope for its transport block size).
 static int plan_layout(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
-                       std::vector<uint32_t> &cb_alloc, bool prbs_checked = false)
+                       std::vector<uint32_t> *cb_alloc, bool prbs_checked = false)
 {
+    std::vector<uint8_t>  &row    = pl->h_row;
+    std::vector<uint32_t> &e_bits = pl->h_e_bits;
+    row.resize(n_alloc);
+    e_bits.resize(n_alloc);
     const mi_lte_dl_cfg *cfg = &pl->cfg;
-    pl->cfi       = N_pdcch_symbs;
-    pl->n_alloc   = n_alloc;
-    pl->max_pairs = pl->max_words = 0;
-    pl->groups.clear();
-    // two passes and a counting sort by code-block size (188 sizes): a capture's chunk re-plans tens of thousands of allocations per call
-    static_assert(LTE_QPP_N_SIZES <= 256, "size index fits a byte");
-    uint32_t cnt[LTE_QPP_N_SIZES] = {0}, emax[LTE_QPP_N_SIZES] = {0};
-    std::vector<uint8_t> kidx(n_alloc);
-    uint32_t max_tbs = 0;
-    size_t   off = 0;
-    pl->h_e_off.resize(n_alloc);
+    pl->cfi          = N_pdcch_symbs;
+    pl->core.n_alloc = n_alloc;
+    pl->max_pairs = pl->max_words = pl->max_tbs = 0;
+    pl->core.groups.clear();
     for (uint32_t a = 0; a < n_alloc; a++) {
         const mi_lte_pdsch_alloc &al = h_allocs[a];
-        const uint32_t B = al.tbs + 24;
-        int            r = -1;
-        if (B <= 6144) { // first size >= B: the sizes step by 8, 16, 32, 64 (36.212 table 5.1.3-3)
-            r = B <= 40 ? 0 : B <= 512 ? (int)((B - 40 + 7) / 8) : B <= 1024 ? 59 + (int)((B - 512 + 15) / 16) : B <= 2048 ? 91 + (int)((B - 1024 + 31) / 32)
-                                                                                                                              : 123 + (int)((B - 2048 + 63) / 64);
-            if (r >= LTE_QPP_N_SIZES || LTE_QPP_ROWS[r].K < B || (r > 0 && LTE_QPP_ROWS[r - 1].K >= B)) r = -2; // (table and closed form disagree: fall back)
-            if (r == -2)
-                for (r = 0; r < LTE_QPP_N_SIZES && LTE_QPP_ROWS[r].K < B; r++) {}
-        }
+        const int      r   = cb_alloc ? mi_qpp_row_at_least(al.tbs + 24) : 0;
         const uint32_t cfi = al.n_pdcch_symbs ? al.n_pdcch_symbs : N_pdcch_symbs;
-        if (r < 0 || r >= LTE_QPP_N_SIZES || al.N_prb == 0 || al.N_prb > cfg->N_rb_dl || al.mod_type > 3 || cfi < 1 || cfi > 4) {
+        if (r < 0 || al.N_prb == 0 || al.N_prb > cfg->N_rb_dl || al.mod_type > 3 || cfi < 1 || cfi > 4) {
             // multi-code-block transport blocks: the reference's own C > 1 path is broken
             ctx->err = "allocation outside the single-code-block envelope (tbs + 24 > 6144) or malformed";
             return MI_LTE_ERR_UNSUPPORTED;
@@ -423,45 +390,21 @@ static int plan_layout(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t N_pdcch_
                     ctx->err = "allocation names a resource block outside the carrier";
                     return MI_LTE_ERR_INVALID_ARG;
                 }
-        kidx[a] = (uint8_t)r;
-        cnt[r]++;
-        max_tbs = std::max(max_tbs, al.tbs);
+        row[a]      = (uint8_t)r;
+        pl->max_tbs = std::max(pl->max_tbs, al.tbs);
         const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : al.mod_type == 1 ? 2 : 1;
         const uint32_t pairs = (14 - cfi) * al.N_prb, e_max = pairs * 12 * Qm;
         pl->max_pairs = std::max(pl->max_pairs, 14 * al.N_prb); // the demodulator's pair table spans all 14 symbols
         pl->max_words = std::max(pl->max_words, (e_max + 31) / 32);
-        emax[r]        = std::max(emax[r], e_max);
-        pl->h_e_off[a] = (uint32_t)(off >> 6); // in 64-byte units
-        off += (e_max + 63) & ~63u;
+        e_bits[a]     = e_max;
     }
     if (pl->max_words > 4095) { // the demodulator reads one word past the allocation's last scrambling word
         ctx->err = "allocation larger than the scrambling table";
         return MI_LTE_ERR_UNSUPPORTED;
     }
-    pl->e_bytes    = off;
-    pl->max_tbs    = max_tbs;
-    const uint32_t st_tbs = (pl->dynamic || pl->wide) ? 6120u : max_tbs; // a dynamic plan keeps ONE output stride over its assignments: the largest single-code-block size
-    pl->out_stride = pl->packed ? (((st_tbs + 7) / 8 + 63) & ~63u) : ((st_tbs + 63) & ~63u);
-    cb_alloc.resize(n_alloc);
-    uint32_t base[LTE_QPP_N_SIZES], run = 0;
-    for (int r = 0; r < LTE_QPP_N_SIZES; r++) { // groups in ascending block size, allocations inside a group in their own order
-        base[r] = run;
-        if (cnt[r]) pl->groups.push_back({LTE_QPP_ROWS[r].K, cnt[r], run, emax[r]});
-        run += cnt[r];
-    }
-    for (uint32_t a = 0; a < n_alloc; a++) cb_alloc[base[kidx[a]]++] = a;
-    return MI_LTE_OK;
-}
-
-static int plan_device_arrays(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t cap_alloc, size_t cap_e_bytes)
-{
-    pl->cap_alloc   = cap_alloc;
-    pl->cap_e_bytes = cap_e_bytes ? cap_e_bytes : 64;
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_allocs, sizeof(mi_lte_pdsch_alloc) * cap_alloc));
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_e_off, sizeof(uint32_t) * cap_alloc));
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_e_len, sizeof(uint32_t) * cap_alloc));
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_cb_alloc, sizeof(uint32_t) * cap_alloc));
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_e, pl->cap_e_bytes));
+    pl->core.e_bytes = mi_plan_soft_layout(e_bits.data(), n_alloc, pl->core.h_e_off);
+    plan_set_stride(pl);
+    if (cb_alloc) mi_plan_group(row.data(), nullptr, e_bits.data(), n_alloc, pl->core.groups, *cb_alloc);
     return MI_LTE_OK;
 }
 
@@ -480,13 +423,12 @@ int mi_lte_pdsch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t
     auto  guard   = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_lte_pdsch_plan_destroy(nullptr, pl); });
     pl->cfg       = *cfg;
     std::vector<uint32_t> cb_alloc;
-    int rc = plan_layout(ctx, pl, N_pdcch_symbs, h_allocs, n_alloc, cb_alloc);
+    int rc = plan_layout(ctx, pl, N_pdcch_symbs, h_allocs, n_alloc, &cb_alloc);
     if (rc != MI_LTE_OK) return rc;
-    rc = plan_device_arrays(ctx, pl, n_alloc, pl->e_bytes);
-    if (rc != MI_LTE_OK) return rc;
-    MI_H2D(ctx, pl->d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
-    MI_H2D(ctx, pl->d_e_off, pl->h_e_off.data(), sizeof(uint32_t) * n_alloc);
-    MI_H2D(ctx, pl->d_cb_alloc, cb_alloc.data(), sizeof(uint32_t) * n_alloc);
+    MI_HIP_CHECK(ctx, pl->core.allocate(n_alloc, pl->core.e_bytes));
+    MI_H2D(ctx, pl->core.d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
+    MI_H2D(ctx, pl->core.d_e_off, pl->core.h_e_off.data(), sizeof(uint32_t) * n_alloc);
+    MI_H2D(ctx, pl->core.d_cb_alloc, cb_alloc.data(), sizeof(uint32_t) * n_alloc);
     MI_HIP_CHECK(ctx, mi_stream_wait_polling(ctx));
     guard.armed = false;
     *out = pl;
@@ -509,8 +451,7 @@ int mi_lte_pdsch_plan_create_dynamic(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, 
     // the capacity a multiple of four entries: the staging block's three arrays (260-byte structs, then two uint32 arrays) then all start on 16
     // bytes whatever the caller asked for, which is what the copy kernel of mi_pdsch_plan_assign_slice needs (otherwise three copy commands)
     max_alloc = (max_alloc + 3u) & ~3u;
-    int rc = plan_device_arrays(ctx, pl, max_alloc, (max_soft_bytes + 63) & ~(size_t)63);
-    if (rc != MI_LTE_OK) return rc;
+    MI_HIP_CHECK(ctx, pl->core.allocate(max_alloc, (max_soft_bytes + 63) & ~(size_t)63));
     MI_HIP_CHECK(ctx, hipHostMalloc(&pl->h_stage, (sizeof(mi_lte_pdsch_alloc) + 2 * sizeof(uint32_t)) * (size_t)max_alloc, hipHostMallocDefault));
     MI_HIP_CHECK(ctx, hipEventCreateWithFlags(&pl->staged, hipEventDisableTiming));
     guard.armed = false;
@@ -532,33 +473,32 @@ int mi_pdsch_plan_create_mapped(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint3
     auto  guard = on_fail([&] { mi_lte_pdsch_plan_destroy(nullptr, pl); });
     pl->cfg     = *cfg;
     pl->dynamic = pl->mapped = true;
-    pl->cap_alloc   = max_alloc;
-    pl->cap_e_bytes = std::max<size_t>((max_soft_bytes + 63) & ~(size_t)63, 64);
     MI_HIP_CHECK(ctx, hipHostMalloc(&pl->h_stage, (sizeof(mi_lte_pdsch_alloc) + 2 * sizeof(uint32_t)) * (size_t)max_alloc, hipHostMallocMapped | hipHostMallocCoherent));
     void *d_stage = nullptr;
     MI_HIP_CHECK(ctx, hipHostGetDevicePointer(&d_stage, pl->h_stage, 0));
-    pl->d_allocs   = (mi_lte_pdsch_alloc *)d_stage;
-    pl->d_e_off    = (uint32_t *)(pl->d_allocs + max_alloc);
-    pl->d_cb_alloc = pl->d_e_off + max_alloc;
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_e_len, sizeof(uint32_t) * max_alloc));
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_e, pl->cap_e_bytes));
+    MI_HIP_CHECK(ctx, pl->core.allocate(max_alloc, (max_soft_bytes + 63) & ~(size_t)63, d_stage));
     guard.armed = false;
     *out = pl;
     return MI_LTE_OK;
+}
+
+// what the demodulator asks of one allocation, whatever its transport block is cut into
+static bool alloc_geometry_ok(const mi_lte_dl_cfg *cfg, const mi_lte_pdsch_alloc *al, uint32_t N_pdcch_symbs)
+{
+    const uint32_t cfi = al->n_pdcch_symbs ? al->n_pdcch_symbs : N_pdcch_symbs;
+    if (al->N_prb == 0 || al->N_prb > cfg->N_rb_dl || al->N_prb > 110 || al->mod_type > 3 || cfi < 1 || cfi > 4) return false;
+    if ((14 - cfi) * al->N_prb * 12 * (al->mod_type == 3 ? 6u : al->mod_type == 2 ? 4u : al->mod_type == 1 ? 2u : 1u) > 4095u * 32u) return false; // the scrambling table
+    for (uint32_t s = 0; s < 2; s++)
+        for (uint32_t i = 0; i < al->N_prb; i++)
+            if (al->prb[s][i] >= cfg->N_rb_dl) return false;
+    return true;
 }
 
 extern "C" {
 
 int mi_lte_pdsch_alloc_decodable(const mi_lte_dl_cfg *cfg, const mi_lte_pdsch_alloc *al, uint32_t N_pdcch_symbs)
 { // the per-allocation conditions of plan_layout, for callers that must not lose a whole list to one chance-CRC DCI
-    if (!cfg || !al) return 0;
-    const uint32_t cfi = al->n_pdcch_symbs ? al->n_pdcch_symbs : N_pdcch_symbs;
-    if (al->tbs + 24 > 6144 || al->tbs + 24 < al->tbs || al->N_prb == 0 || al->N_prb > cfg->N_rb_dl || al->N_prb > 110 || al->mod_type > 3 || cfi < 1 || cfi > 4) return 0;
-    if ((14 - cfi) * al->N_prb * 12 * (al->mod_type == 3 ? 6u : al->mod_type == 2 ? 4u : al->mod_type == 1 ? 2u : 1u) > 4095u * 32u) return 0; // the scrambling table
-    for (uint32_t s = 0; s < 2; s++)
-        for (uint32_t i = 0; i < al->N_prb; i++)
-            if (al->prb[s][i] >= cfg->N_rb_dl) return 0;
-    return 1;
+    return cfg && al && al->tbs + 24 <= 6144 && al->tbs + 24 >= al->tbs && alloc_geometry_ok(cfg, al, N_pdcch_symbs);
 }
 
 int mi_lte_pdsch_alloc_decodable_3gpp(const mi_lte_dl_cfg *cfg, const mi_lte_dlsch_cfg *dlsch, const mi_lte_pdsch_alloc *al, uint32_t N_pdcch_symbs)
@@ -566,44 +506,33 @@ int mi_lte_pdsch_alloc_decodable_3gpp(const mi_lte_dl_cfg *cfg, const mi_lte_dls
     if (!cfg || !dlsch || !al || cfg->N_ant != 1 || al->mod_type == 0 || al->mod_type > 3) return 0;
     mi_lte_dlsch_layout_t lay;
     if (mi_lte_dlsch_layout(al->tbs, 0, 2, al->tx_mode, al->rv_idx & 3u, dlsch, &lay) != MI_LTE_OK) return 0;
-    mi_lte_pdsch_alloc one = *al;
-    one.tbs = 16;
-    return mi_lte_pdsch_alloc_decodable(cfg, &one, N_pdcch_symbs);
+    return alloc_geometry_ok(cfg, al, N_pdcch_symbs);
 }
 
 // A static plan in the 3GPP transport-block mode: the demodulator's layout is that of any plan -- it does not depend on the transport block
-// size, so plan_layout lays out a copy of the list with a one-block size in every entry -- and the code blocks are dlsch3gpp.hip's.
+// size -- and the code blocks are dlsch3gpp.hip's.
 int mi_lte_pdsch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t N_pdcch_symbs, const mi_lte_dlsch_cfg *dlsch,
                                   const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, mi_lte_pdsch_plan **out)
 {
     if (!ctx || !cfg || !dlsch || !h_allocs || !out || n_alloc == 0 || N_pdcch_symbs < 1 || N_pdcch_symbs > 4 || dlsch->M_dl_harq == 0) return MI_LTE_ERR_INVALID_ARG;
     if (cfg->N_ant != 1) { ctx->err = "3GPP transport-block mode: single-port cells only"; return MI_LTE_ERR_UNSUPPORTED; }
-    uint32_t max_tbs = 0;
-    std::vector<mi_lte_pdsch_alloc> one(h_allocs, h_allocs + n_alloc);
     for (uint32_t a = 0; a < n_alloc; a++) {
         mi_lte_dlsch_layout_t lay;
         const int rc = h_allocs[a].mod_type == 0 ? MI_LTE_ERR_UNSUPPORTED : mi_lte_dlsch_layout(h_allocs[a].tbs, 0, 2, h_allocs[a].tx_mode, h_allocs[a].rv_idx & 3u, dlsch, &lay);
         if (rc != MI_LTE_OK) { ctx->err = "allocation outside the 3GPP transport-block mode (BPSK, F != 0, tbs > 75376 or a soft buffer under 2 positions)"; return rc; }
-        max_tbs  = std::max(max_tbs, h_allocs[a].tbs);
-        one[a].tbs = 16;
     }
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     auto *pl    = new mi_lte_pdsch_plan();
     auto  guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_lte_pdsch_plan_destroy(nullptr, pl); });
     pl->cfg     = *cfg;
-    std::vector<uint32_t> cb_alloc;
-    int rc = plan_layout(ctx, pl, N_pdcch_symbs, one.data(), n_alloc, cb_alloc);
-    if (rc != MI_LTE_OK) return rc;
-    pl->groups.clear(); // (the single-block decode's grouping: not used)
-    pl->max_tbs = max_tbs;
     pl->decoder = MI_LTE_TURBO_BCJR; pl->n_iter = 8; pl->qpp_spec = 1;
-    (void)mi_lte_pdsch_plan_set_output(pl, 0);
-    rc = plan_device_arrays(ctx, pl, n_alloc, pl->e_bytes);
+    int rc = plan_layout(ctx, pl, N_pdcch_symbs, h_allocs, n_alloc, nullptr);
     if (rc != MI_LTE_OK) return rc;
+    MI_HIP_CHECK(ctx, pl->core.allocate(n_alloc, pl->core.e_bytes));
     rc = mi_dlsch3_create(ctx, dlsch, h_allocs, n_alloc, &pl->g3);
     if (rc != MI_LTE_OK) return rc;
-    MI_H2D(ctx, pl->d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
-    MI_H2D(ctx, pl->d_e_off, pl->h_e_off.data(), sizeof(uint32_t) * n_alloc);
+    MI_H2D(ctx, pl->core.d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
+    MI_H2D(ctx, pl->core.d_e_off, pl->core.h_e_off.data(), sizeof(uint32_t) * n_alloc);
     MI_HIP_CHECK(ctx, mi_stream_wait_polling(ctx));
     guard.armed = false;
     *out = pl;
@@ -626,27 +555,27 @@ int mi_lte_pdsch_plan_cb_ok(const mi_lte_pdsch_plan *pl, const uint32_t **d_mask
 int mi_lte_pdsch_plan_assign(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc)
 {
     if (!ctx || !pl || !pl->dynamic || !h_allocs || n_alloc == 0 || N_pdcch_symbs < 1 || N_pdcch_symbs > 4) return MI_LTE_ERR_INVALID_ARG;
-    if (n_alloc > pl->cap_alloc) { ctx->err = "more allocations than the dynamic plan was created for"; return MI_LTE_ERR_INVALID_ARG; }
+    if (n_alloc > pl->core.cap_alloc) { ctx->err = "more allocations than the dynamic plan was created for"; return MI_LTE_ERR_INVALID_ARG; }
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     std::vector<uint32_t> cb_alloc;
-    int rc = plan_layout(ctx, pl, N_pdcch_symbs, h_allocs, n_alloc, cb_alloc);
-    if (rc != MI_LTE_OK) { pl->n_alloc = 0; return rc; }
-    if (pl->e_bytes > pl->cap_e_bytes) { pl->n_alloc = 0; ctx->err = "more soft bits than the dynamic plan was created for"; return MI_LTE_ERR_INVALID_ARG; }
+    int rc = plan_layout(ctx, pl, N_pdcch_symbs, h_allocs, n_alloc, &cb_alloc);
+    if (rc != MI_LTE_OK) { pl->core.n_alloc = 0; return rc; }
+    if (pl->core.e_bytes > pl->core.cap_e_bytes) { pl->core.n_alloc = 0; ctx->err = "more soft bits than the dynamic plan was created for"; return MI_LTE_ERR_INVALID_ARG; }
     if (!pl->mapped) MI_HIP_CHECK(ctx, hipEventSynchronize(pl->staged)); // the previous assignment's copies have left the staging block
     auto *sa = (mi_lte_pdsch_alloc *)pl->h_stage;
-    auto *so = (uint32_t *)(sa + pl->cap_alloc), *sc = so + pl->cap_alloc;
+    auto *so = (uint32_t *)(sa + pl->core.cap_alloc), *sc = so + pl->core.cap_alloc;
     memcpy(sa, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
-    memcpy(so, pl->h_e_off.data(), sizeof(uint32_t) * n_alloc);
+    memcpy(so, pl->core.h_e_off.data(), sizeof(uint32_t) * n_alloc);
     memcpy(sc, cb_alloc.data(), sizeof(uint32_t) * n_alloc);
     if (pl->mapped) return MI_LTE_OK; // the kernels read the block itself (mi_pdsch_plan_create_mapped: the caller has waited for the last run)
-    MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->d_allocs, sa, sizeof(mi_lte_pdsch_alloc) * n_alloc, hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->d_e_off, so, sizeof(uint32_t) * n_alloc, hipMemcpyHostToDevice, ctx->stream));
-    MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->d_cb_alloc, sc, sizeof(uint32_t) * n_alloc, hipMemcpyHostToDevice, ctx->stream));
+    MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->core.d_allocs, sa, sizeof(mi_lte_pdsch_alloc) * n_alloc, hipMemcpyHostToDevice, ctx->stream));
+    MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->core.d_e_off, so, sizeof(uint32_t) * n_alloc, hipMemcpyHostToDevice, ctx->stream));
+    MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->core.d_cb_alloc, sc, sizeof(uint32_t) * n_alloc, hipMemcpyHostToDevice, ctx->stream));
     MI_HIP_CHECK(ctx, hipEventRecord(pl->staged, ctx->stream));
     return MI_LTE_OK;
 }
 
-uint32_t mi_lte_pdsch_plan_n_alloc(const mi_lte_pdsch_plan *pl) { return pl ? pl->n_alloc : 0; }
+uint32_t mi_lte_pdsch_plan_n_alloc(const mi_lte_pdsch_plan *pl) { return pl ? pl->core.n_alloc : 0; }
 } // extern "C"
 
 // The host pipeline's assignment (pipeline.cc: one per chunk of a capture, tens of thousands of allocations each, on the thread that also
@@ -660,11 +589,11 @@ int mi_pdsch_plan_assign_slice(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t 
 {
     if (!ctx || !pl || !pl->dynamic || pl->mapped || !h_src || n_alloc == 0 || N_pdcch_symbs < 1 || N_pdcch_symbs > 4) return MI_LTE_ERR_INVALID_ARG;
     const hipStream_t cs = copy_stream ? copy_stream : ctx->stream;
-    if (n_alloc > pl->cap_alloc) { ctx->err = "more allocations than the dynamic plan was created for"; return MI_LTE_ERR_INVALID_ARG; }
+    if (n_alloc > pl->core.cap_alloc) { ctx->err = "more allocations than the dynamic plan was created for"; return MI_LTE_ERR_INVALID_ARG; }
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     MI_HIP_CHECK(ctx, hipEventSynchronize(pl->staged)); // the previous assignment's copies have left the staging block
     auto *sa = (mi_lte_pdsch_alloc *)pl->h_stage;
-    auto *so = (uint32_t *)(sa + pl->cap_alloc), *sc = so + pl->cap_alloc;
+    auto *so = (uint32_t *)(sa + pl->core.cap_alloc), *sc = so + pl->core.cap_alloc;
     for (uint32_t i = 0; i < n_alloc; i++) {
         mi_lte_pdsch_alloc &a = sa[i];
         a = h_src[i];
@@ -677,10 +606,10 @@ int mi_pdsch_plan_assign_slice(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t 
         }
     }
     std::vector<uint32_t> cb_alloc;
-    int rc = plan_layout(ctx, pl, N_pdcch_symbs, sa, n_alloc, cb_alloc, true);
-    if (rc != MI_LTE_OK) { pl->n_alloc = 0; return rc; }
-    if (pl->e_bytes > pl->cap_e_bytes) { pl->n_alloc = 0; ctx->err = "more soft bits than the dynamic plan was created for"; return MI_LTE_ERR_INVALID_ARG; }
-    memcpy(so, pl->h_e_off.data(), sizeof(uint32_t) * n_alloc);
+    int rc = plan_layout(ctx, pl, N_pdcch_symbs, sa, n_alloc, &cb_alloc, true);
+    if (rc != MI_LTE_OK) { pl->core.n_alloc = 0; return rc; }
+    if (pl->core.e_bytes > pl->core.cap_e_bytes) { pl->core.n_alloc = 0; ctx->err = "more soft bits than the dynamic plan was created for"; return MI_LTE_ERR_INVALID_ARG; }
+    memcpy(so, pl->core.h_e_off.data(), sizeof(uint32_t) * n_alloc);
     memcpy(sc, cb_alloc.data(), sizeof(uint32_t) * n_alloc);
     // The three arrays leave the (pinned) staging block with a copy KERNEL on the same stream, not with copy commands: the runtime rotates its
     // copy engines from command to command, and three small commands per chunk between the sample copies put every third chunk's samples on
@@ -688,17 +617,17 @@ int mi_pdsch_plan_assign_slice(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t 
     // (profiles/r05_host_pipeline_profile.txt section 6, and section 7 for this)
     static const bool slice_by_engine = getenv("MI_LTE_SLICE_COPY_COMMANDS") != nullptr; // (A/B switch)
     if (slice_by_engine) {
-        MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->d_allocs, sa, sizeof(mi_lte_pdsch_alloc) * n_alloc, hipMemcpyHostToDevice, cs));
-        MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->d_e_off, so, sizeof(uint32_t) * n_alloc, hipMemcpyHostToDevice, cs));
-        MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->d_cb_alloc, sc, sizeof(uint32_t) * n_alloc, hipMemcpyHostToDevice, cs));
+        MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->core.d_allocs, sa, sizeof(mi_lte_pdsch_alloc) * n_alloc, hipMemcpyHostToDevice, cs));
+        MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->core.d_e_off, so, sizeof(uint32_t) * n_alloc, hipMemcpyHostToDevice, cs));
+        MI_HIP_CHECK(ctx, hipMemcpyAsync(pl->core.d_cb_alloc, sc, sizeof(uint32_t) * n_alloc, hipMemcpyHostToDevice, cs));
     } else {
-        const MiCopySeg segs[3] = {{pl->d_allocs, sa, sizeof(mi_lte_pdsch_alloc) * n_alloc}, {pl->d_e_off, so, sizeof(uint32_t) * n_alloc}, {pl->d_cb_alloc, sc, sizeof(uint32_t) * n_alloc}};
+        const MiCopySeg segs[3] = {{pl->core.d_allocs, sa, sizeof(mi_lte_pdsch_alloc) * n_alloc}, {pl->core.d_e_off, so, sizeof(uint32_t) * n_alloc}, {pl->core.d_cb_alloc, sc, sizeof(uint32_t) * n_alloc}};
         MI_HIP_CHECK(ctx, mi_pinned_segments_to_device(ctx, segs, 3, cs));
     }
     MI_HIP_CHECK(ctx, hipEventRecord(pl->staged, cs));
     return MI_LTE_OK;
 }
-void mi_pdsch_plan_wide_stride(mi_lte_pdsch_plan *pl) { pl->wide = true; (void)mi_lte_pdsch_plan_set_output(pl, pl->packed); }
+void mi_pdsch_plan_wide_stride(mi_lte_pdsch_plan *pl) { pl->wide = true; plan_set_stride(pl); }
 extern "C" {
 
 void mi_lte_pdsch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl)
@@ -708,23 +637,16 @@ void mi_lte_pdsch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl)
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    if (!pl->mapped) { // (mapped: the three are views of h_stage)
-        (void)hipFree(pl->d_allocs);
-        (void)hipFree(pl->d_e_off);
-        (void)hipFree(pl->d_cb_alloc);
-    }
-    (void)hipFree(pl->d_e_len);
-    (void)hipFree(pl->d_e);
+    pl->core.release(); // (mapped: the three descriptor arrays are views of h_stage)
     if (pl->d_bcjr_soft) (void)hipFree(pl->d_bcjr_soft);
     if (pl->d_bcjr_bits) (void)hipFree(pl->d_bcjr_bits);
     if (pl->h_stage) (void)hipHostFree(pl->h_stage);
     if (pl->staged) (void)hipEventDestroy(pl->staged);
-    mi_multi_cache_free(&pl->multi);
     mi_dlsch3_free(pl->g3);
     delete pl;
 }
 
-uint32_t mi_lte_pdsch_plan_out_stride(const mi_lte_pdsch_plan *pl) { return pl ? pl->out_stride : 0; }
+uint32_t mi_lte_pdsch_plan_out_stride(const mi_lte_pdsch_plan *pl) { return pl ? pl->core.out_stride : 0; }
 
 // the de-mappers' atan2f (phy_dev.hpp: the host libm's algorithm restated) evaluated on the host, for the test that pins it to libm
 int mi_lte_model_atan2f(const float *h_y, const float *h_x, float *h_out, size_t n)
@@ -736,15 +658,15 @@ int mi_lte_model_atan2f(const float *h_y, const float *h_x, float *h_out, size_t
 
 int mi_lte_pdsch_plan_soft_bits(const mi_lte_pdsch_plan *pl, uint32_t alloc, const int8_t **d_e, const uint32_t **d_len)
 {
-    if (!pl || alloc >= pl->n_alloc || !d_e || !d_len) return MI_LTE_ERR_INVALID_ARG;
-    *d_e   = pl->d_e + (size_t)pl->h_e_off[alloc] * 64;
-    *d_len = pl->d_e_len + alloc;
+    if (!pl || alloc >= pl->core.n_alloc || !d_e || !d_len) return MI_LTE_ERR_INVALID_ARG;
+    *d_e   = pl->core.d_e + (size_t)pl->core.h_e_off[alloc] * 64;
+    *d_len = pl->core.d_e_len + alloc;
     return MI_LTE_OK;
 }
 
 int mi_lte_pdsch_plan_set_decoder(mi_lte_pdsch_plan *pl, uint32_t mode, uint32_t n_iter, int qpp_spec)
 {
-    const bool bcjr = mode == MI_LTE_TURBO_BCJR || mode == MI_LTE_TURBO_BCJR_BLOCK || mode == MI_LTE_TURBO_BCJR_EARLY;
+    const bool bcjr = mi_is_bcjr(mode);
     if (!pl || !(mode == MI_LTE_TURBO_REF || bcjr) || (bcjr && (n_iter == 0 || n_iter > 64))) return MI_LTE_ERR_INVALID_ARG;
     if (pl->g3 && mode == MI_LTE_TURBO_REF) return MI_LTE_ERR_UNSUPPORTED; // (the 3GPP mode: BCJR decoders, exact interleaver)
     if (pl->g3 && !qpp_spec) return MI_LTE_ERR_INVALID_ARG;
@@ -755,9 +677,8 @@ int mi_lte_pdsch_plan_set_decoder(mi_lte_pdsch_plan *pl, uint32_t mode, uint32_t
 int mi_lte_pdsch_plan_set_output(mi_lte_pdsch_plan *pl, uint32_t packed)
 {
     if (!pl) return MI_LTE_ERR_INVALID_ARG;
-    pl->packed     = packed ? 1u : 0u;
-    const uint32_t st_tbs = (pl->dynamic || pl->wide) ? 6120u : pl->max_tbs;
-    pl->out_stride = packed ? (((st_tbs + 7) / 8 + 63) & ~63u) : ((st_tbs + 63) & ~63u);
+    pl->core.packed = packed ? 1u : 0u;
+    plan_set_stride(pl);
     return MI_LTE_OK;
 }
 
@@ -781,15 +702,13 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
         const int t = atoi(ev);
         if (t >= 64 && t <= 256 && t % 64 == 0) threads = (uint32_t)t;
     }
-    if (g.N_ant == 1 && (pl->cfg.sample_format & MI_LTE_CE_COMPACT))
-        MI_LAUNCH(ctx, "k_pdsch_demod", (k_pdsch_demod<true, true>), dim3(pl->n_alloc), dim3(threads), lds, d_subframes, g, pl->d_allocs, d_subfr_num,
-                  d_n_id_cell, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->max_pairs, words_al, e_cap);
-    else if (g.N_ant == 1)
-        MI_LAUNCH(ctx, "k_pdsch_demod", k_pdsch_demod<true>, dim3(pl->n_alloc), dim3(threads), lds, d_subframes, g, pl->d_allocs, d_subfr_num,
-                  d_n_id_cell, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->max_pairs, words_al, e_cap);
-    else
-        MI_LAUNCH(ctx, "k_pdsch_demod", k_pdsch_demod<false>, dim3(pl->n_alloc), dim3(threads), lds, d_subframes, g, pl->d_allocs, d_subfr_num,
-                  d_n_id_cell, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->max_pairs, words_al, e_cap);
+    auto launch = [&](auto kernel) {
+        MI_LAUNCH(ctx, "k_pdsch_demod", kernel, dim3(pl->core.n_alloc), dim3(threads), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt,
+                  pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap);
+    };
+    if (g.N_ant == 1 && (pl->cfg.sample_format & MI_LTE_CE_COMPACT)) launch(k_pdsch_demod<true, true>);
+    else if (g.N_ant == 1) launch(k_pdsch_demod<true>);
+    else launch(k_pdsch_demod<false>);
     MI_HIP_CHECK(ctx, hipGetLastError());
     return MI_LTE_OK;
 }
@@ -805,21 +724,18 @@ static int pdsch_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *p
         if (!pl->g3) { ctx->err = "HARQ soft combining needs a plan in the 3GPP transport-block mode"; return MI_LTE_ERR_UNSUPPORTED; }
         if ((rc = mi_dlsch3_harq_check(ctx, pl->g3, pool, h_bind)) != MI_LTE_OK) return rc;
     }
-    if (pl->n_alloc == 0) { ctx->err = "the dynamic plan holds no allocations (mi_lte_pdsch_plan_assign)"; return MI_LTE_ERR_INVALID_ARG; }
+    if (pl->core.n_alloc == 0) { ctx->err = "the dynamic plan holds no allocations (mi_lte_pdsch_plan_assign)"; return MI_LTE_ERR_INVALID_ARG; }
     if ((rc = pdsch_demod(ctx, pl, d_subframes, d_subfr_num, d_n_id_cell)) != MI_LTE_OK) return rc;
-    if (pl->g3)
-        return mi_dlsch3_run(ctx, pl->g3, pool, h_bind, pl->d_allocs, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits, pl->out_stride, d_status, pl->decoder,
-                             pl->n_iter, pl->packed);
-    const bool bcjr = pl->decoder == MI_LTE_TURBO_BCJR || pl->decoder == MI_LTE_TURBO_BCJR_BLOCK || pl->decoder == MI_LTE_TURBO_BCJR_EARLY;
-    if (!bcjr) {
-        rc = mi_turbo_ref_dispatch(ctx, pl->groups.data(), (uint32_t)pl->groups.size(), pl->d_allocs, pl->d_cb_alloc, pl->d_e, pl->d_e_off, pl->d_e_len,
-                                   d_out_bits, pl->out_stride, d_status, false, pl->packed != 0, &pl->multi);
+    const MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/false);
+    if (pl->g3) return mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter);
+    if (!mi_is_bcjr(pl->decoder)) {
+        rc = mi_turbo_ref_dispatch(ctx, pl->core.groups.data(), (uint32_t)pl->core.groups.size(), io, &pl->core.multi);
         if (rc != MI_LTE_OK) return rc;
         ctx->last_kernels.insert(0, "k_pdsch_demod:1,");
         return MI_LTE_OK;
     }
     size_t soft = 0, bits = 0;
-    for (auto &gr : pl->groups) { soft = std::max(soft, (size_t)gr.n_cb * 3 * (gr.K + 4)); bits = std::max(bits, (size_t)gr.n_cb * gr.K); }
+    for (auto &gr : pl->core.groups) { soft = std::max(soft, (size_t)gr.n_cb * 3 * (gr.K + 4)); bits = std::max(bits, (size_t)gr.n_cb * gr.K); }
     if (soft > pl->bcjr_soft_cap || bits > pl->bcjr_bits_cap) { // first run, or a re-assigned plan that needs more
         MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         if (pl->d_bcjr_soft) (void)hipFree(pl->d_bcjr_soft);
@@ -829,10 +745,8 @@ static int pdsch_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *p
         MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_bcjr_bits, bits));
         pl->bcjr_soft_cap = soft; pl->bcjr_bits_cap = bits;
     }
-    for (auto &gr : pl->groups) {
-        rc = mi_turbo_bcjr_group(ctx, gr.K, gr.n_cb, pl->d_allocs, pl->d_cb_alloc + gr.cb_base, pl->d_e, pl->d_e_off, pl->d_e_len, d_out_bits,
-                                 pl->out_stride, d_status, false, pl->d_bcjr_soft, pl->d_bcjr_bits, pl->n_iter, pl->qpp_spec, pl->packed != 0, gr.e_max,
-                                 pl->decoder == MI_LTE_TURBO_BCJR_BLOCK, pl->decoder == MI_LTE_TURBO_BCJR_EARLY);
+    for (auto &gr : pl->core.groups) {
+        rc = mi_turbo_bcjr_group(ctx, gr, io, pl->d_bcjr_soft, pl->d_bcjr_bits, pl->decoder, pl->n_iter, pl->qpp_spec);
         if (rc != MI_LTE_OK) return rc;
     }
     ctx->last_kernels = "k_pdsch_demod:1,k_rm_to_i8,k_bcjr_*,k_crc_finish per block size";

@@ -18,7 +18,7 @@
 #include <cstring>
 #include <vector>
 
-#include "ctx.hpp"
+#include "plan_core.hpp"
 
 namespace {
 
@@ -310,8 +310,8 @@ __global__ __launch_bounds__(256) void k_harq_commit(const mi_lte_harq_bind *__r
 struct MiDlsch3 {
     mi_lte_dlsch_cfg cfg{};
     uint32_t n_alloc = 0, n_slot = 0;
-    struct Group { uint32_t K, n_cb; size_t soft_off, bits_off; }; // a block size's slots, contiguous; byte offsets into d_soft / d_bits
-    std::vector<Group>    groups;
+    std::vector<MiKGroup> groups;              // a block size's slots, contiguous; ...
+    std::vector<size_t>   g_soft, g_bits;      // ... and where they start in d_soft / d_bits (bytes, on 256)
     std::vector<uint32_t> a_slot, a_nc, a_K, a_tbs; // per allocation: first slot, C, K, tbs
     std::vector<size_t>   a_soft;              // per allocation: byte offset of its first block in d_soft
     Dl3Slot  *d_slot = nullptr;
@@ -341,37 +341,32 @@ int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_
     g->cfg     = *cfg;
     g->n_alloc = n_alloc;
     g->a_slot.resize(n_alloc); g->a_nc.resize(n_alloc); g->a_K.resize(n_alloc); g->a_tbs.resize(n_alloc); g->a_soft.resize(n_alloc);
+    std::vector<uint8_t> row(n_alloc);
     for (uint32_t a = 0; a < n_alloc; a++) {
         mi_lte_dlsch_layout_t lay;
         const int rc = mi_lte_dlsch_layout(h_allocs[a].tbs, 0, 2, h_allocs[a].tx_mode, h_allocs[a].rv_idx & 3u, cfg, &lay);
         if (rc != MI_LTE_OK) { ctx->err = "transport block size outside the 3GPP mode (F != 0 or tbs > 75376)"; return rc; }
         g->a_nc[a] = lay.C; g->a_K[a] = lay.K; g->a_tbs[a] = h_allocs[a].tbs;
+        row[a] = (uint8_t)mi_qpp_row_at_least(lay.K);
     }
-    std::vector<uint32_t> order(n_alloc);
-    for (uint32_t a = 0; a < n_alloc; a++) order[a] = a;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return g->a_K[x] < g->a_K[y]; });
-    std::vector<Dl3Slot> slots;
+    std::vector<uint32_t> slot_alloc;
+    mi_plan_group(row.data(), g->a_nc.data(), nullptr, n_alloc, g->groups, slot_alloc);
+    g->n_slot = (uint32_t)slot_alloc.size();
+    std::vector<Dl3Slot> slots(g->n_slot);
     size_t soft = 0, bits = 0;
-    for (uint32_t i = 0; i < n_alloc; i++) {
-        const uint32_t a = order[i], K = g->a_K[a], C = g->a_nc[a];
-        if (g->groups.empty() || g->groups.back().K != K) { // a new size: its arrays start on 256 bytes
-            soft = (soft + 255) & ~(size_t)255; bits = (bits + 255) & ~(size_t)255;
-            g->groups.push_back({K, 0, soft, bits});
-        }
-        g->a_slot[a] = (uint32_t)slots.size();
-        g->a_soft[a] = soft;
-        const uint32_t B = h_allocs[a].tbs + 24;
-        for (uint32_t r = 0; r < C; r++) {
+    for (const MiKGroup &gr : g->groups) { // a size's arrays start on 256 bytes
+        soft = (soft + 255) & ~(size_t)255; bits = (bits + 255) & ~(size_t)255;
+        g->g_soft.push_back(soft); g->g_bits.push_back(bits);
+        for (uint32_t s = gr.cb_base, r = 0; s < gr.cb_base + gr.n_cb; s++, soft += 3 * (size_t)(gr.K + 4), bits += gr.K) {
+            const uint32_t a = slot_alloc[s], C = g->a_nc[a], B = h_allocs[a].tbs + 24;
+            r = (s > gr.cb_base && slot_alloc[s - 1] == a) ? r + 1 : 0; // an allocation's blocks are adjacent
+            if (r == 0) { g->a_slot[a] = s; g->a_soft[a] = soft; }
             // x^s mod gCRC24A, s = B - (r + 1)(K - 24) for C > 1 (0 for C = 1): the transport-block bits behind the block's payload
-            const uint32_t xs = xpow(C == 1 ? 0u : B - (r + 1) * (K - 24), G_CRC24A);
-            slots.push_back({a, r, C, K, xs, (uint32_t)(soft / 4), (uint32_t)(bits / 8), 0});
-            soft += 3 * (size_t)(K + 4);
-            bits += K;
-            g->groups.back().n_cb++;
+            const uint32_t xs = xpow(C == 1 ? 0u : B - (r + 1) * (gr.K - 24), G_CRC24A);
+            slots[s] = {a, r, C, gr.K, xs, (uint32_t)(soft / 4), (uint32_t)(bits / 8), 0};
         }
         if (soft / 4 > 0xFFFFFFFFull || bits / 8 > 0xFFFFFFFFull) { ctx->err = "3GPP plan too large"; return MI_LTE_ERR_UNSUPPORTED; }
     }
-    g->n_slot = (uint32_t)slots.size();
     std::vector<uint32_t> tab(2 * 6144);
     for (uint32_t e = 0, wa = 1, wb = 1; e < 6144; e++, wa = mulx(wa, G_CRC24A), wb = mulx(wb, G_CRC24B)) { tab[e] = wa; tab[6144 + e] = wb; }
     MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_slot, sizeof(Dl3Slot) * g->n_slot));
@@ -496,9 +491,7 @@ int mi_dlsch3_harq_check(mi_lte_ctx *ctx, const MiDlsch3 *g, const mi_lte_harq_p
 
 // Everything after the demodulator (chain.hip: a plan run on a 3GPP plan).  p: the pool of a HARQ run and h_bind its bindings
 // (mi_dlsch3_harq_check has passed); nullptr: a plain run.
-int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const mi_lte_pdsch_alloc *d_allocs,
-                  const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
-                  uint32_t decoder, uint32_t n_iter, uint32_t packed)
+int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const MiDecodeIO &io, uint32_t decoder, uint32_t n_iter)
 {
     if (p) {
         if (g->n_alloc > p->cap_bind) { // (a larger plan than any before: the queued runs that read the old blocks finish first)
@@ -515,30 +508,31 @@ int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lt
         MI_HIP_CHECK(ctx, hipMemcpyAsync(p->d_bind, p->h_bind, sizeof(mi_lte_harq_bind) * g->n_alloc, hipMemcpyHostToDevice, ctx->stream));
         MI_HIP_CHECK(ctx, hipEventRecord(p->staged, ctx->stream));
     }
-    MI_LAUNCH(ctx, "k_dl3_desc", k_dl3_desc, dim3((g->n_slot + 255) / 256), dim3(256), 0, (const Dl3Slot *)g->d_slot, g->n_slot, d_allocs, d_e_len,
+    MI_LAUNCH(ctx, "k_dl3_desc", k_dl3_desc, dim3((g->n_slot + 255) / 256), dim3(256), 0, (const Dl3Slot *)g->d_slot, g->n_slot, io.d_allocs, io.d_e_len,
               g->cfg.N_soft, g->cfg.M_dl_harq, g->d_desc);
     if (p) {
         MI_LAUNCH(ctx, "k_harq_bind", k_harq_bind, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const Dl3Desc *)g->d_desc, (const uint32_t *)g->d_a_slot,
                   g->n_alloc, (const mi_lte_harq_bind *)p->d_bind, p->d_state, g->d_slot_buf);
-        MI_LAUNCH(ctx, "k_harq_rm", k_harq_rm, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, d_e, d_e_off, g->d_soft, DL3_E_CAP,
+        MI_LAUNCH(ctx, "k_harq_rm", k_harq_rm, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, io.d_e, io.d_e_off, g->d_soft, DL3_E_CAP,
                   (const uint32_t *)g->d_slot_buf, p->d_soft, p->buf_elems);
     } else
-        MI_LAUNCH(ctx, "k_dl3_rm_i8", k_dl3_rm_i8, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, d_e, d_e_off, g->d_soft, DL3_E_CAP);
+        MI_LAUNCH(ctx, "k_dl3_rm_i8", k_dl3_rm_i8, dim3(g->n_slot), dim3(256), DL3_E_CAP, (const Dl3Desc *)g->d_desc, io.d_e, io.d_e_off, g->d_soft, DL3_E_CAP);
     MI_HIP_CHECK(ctx, hipGetLastError());
-    for (const auto &gr : g->groups) {
-        const int8_t *s = g->d_soft + gr.soft_off;
-        uint8_t      *b = g->d_bits + gr.bits_off;
+    for (size_t i = 0; i < g->groups.size(); i++) {
+        const MiKGroup &gr = g->groups[i];
+        const int8_t   *s  = g->d_soft + g->g_soft[i];
+        uint8_t        *b  = g->d_bits + g->g_bits[i];
         const int rc = decoder == MI_LTE_TURBO_BCJR_BLOCK ? mi_turbo_bcjr_block_batch(ctx, s, gr.K, gr.n_cb, n_iter, 1, b)
                                                           : mi_turbo_bcjr_batch(ctx, s, gr.K, gr.n_cb, n_iter, 1, b, decoder == MI_LTE_TURBO_BCJR_EARLY);
         if (rc != MI_LTE_OK) return rc;
     }
     MI_LAUNCH(ctx, "k_dl3_cb_finish", k_dl3_cb_finish, dim3(g->n_slot), dim3(256), 0, (const Dl3Desc *)g->d_desc, (const uint8_t *)g->d_bits,
-              (const uint32_t *)g->d_tab, (const uint32_t *)(g->d_tab + 6144), d_out_bits, out_stride, packed, g->d_part, g->d_ok);
+              (const uint32_t *)g->d_tab, (const uint32_t *)(g->d_tab + 6144), io.d_out_bits, io.out_stride, io.packed ? 1u : 0u, g->d_part, g->d_ok);
     MI_LAUNCH(ctx, "k_dl3_tb_finish", k_dl3_tb_finish, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const uint32_t *)g->d_a_slot,
-              (const uint32_t *)g->d_a_nc, g->n_alloc, (const uint32_t *)g->d_part, (const uint32_t *)g->d_ok, d_status, g->d_cb_ok);
+              (const uint32_t *)g->d_a_nc, g->n_alloc, (const uint32_t *)g->d_part, (const uint32_t *)g->d_ok, io.d_status, g->d_cb_ok);
     if (p)
         MI_LAUNCH(ctx, "k_harq_commit", k_harq_commit, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const mi_lte_harq_bind *)p->d_bind, g->n_alloc,
-                  (const int32_t *)d_status, p->d_state);
+                  (const int32_t *)io.d_status, p->d_state);
     MI_HIP_CHECK(ctx, hipGetLastError());
     ctx->last_kernels = p ? "k_pdsch_demod:1,k_dl3_desc:1,k_harq_bind:1,k_harq_rm:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1,k_harq_commit:1"
                           : "k_pdsch_demod:1,k_dl3_desc:1,k_dl3_rm_i8:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1";

@@ -23,7 +23,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "ctx.hpp"
+#include "plan_core.hpp"
 
 namespace {
 
@@ -1979,6 +1979,35 @@ static bool no_static_lds(const void *kernel)
     return hipFuncGetAttributes(&a, kernel) == hipSuccess && a.sharedSizeBytes == 0;
 }
 
+// The scratch of one REF decode carved up -- eleven byte arrays of arr_bytes each, three arrays of traceback words of half that, the
+// per-block descriptors -- and the kernels' arguments wired from it
+struct RefScratch {
+    uint8_t *base;
+    CbDesc  *d_desc;
+    PrepOut  po;
+    SisoArgs s1, s23;
+    PermArgs pa;
+    VoteArgs va;
+    RefScratch(void *scratch, size_t arr_bytes) : base((uint8_t *)scratch)
+    {
+        uint8_t *arr[N_BYTE_ARRAYS];
+        for (int a = 0; a < N_BYTE_ARRAYS; a++) arr[a] = base + a * arr_bytes;
+        uint32_t *dec[3];
+        for (int p = 0; p < 3; p++) dec[p] = (uint32_t *)(base + N_BYTE_ARRAYS * arr_bytes + p * (arr_bytes / 2));
+        d_desc = (CbDesc *)(base + N_BYTE_ARRAYS * arr_bytes + 3 * (arr_bytes / 2));
+        po.arr[0] = arr[AX0]; po.arr[1] = arr[AX1]; po.arr[2] = arr[AX2];
+        po.arr[3] = arr[AI0]; po.arr[4] = arr[AM1]; po.arr[5] = arr[AM2];
+        s1.p[0] = {arr[AX1], arr[AX0], arr[AM1], arr[AA1], dec[0]};
+        s1.p[1] = s1.p[0];
+        pa.A1 = arr[AA1]; pa.X2 = arr[AX2]; pa.out[0] = arr[AI1]; pa.out[1] = arr[AM3];
+        s23.p[0] = {arr[AX2], arr[AI0], arr[AM2], arr[AB1], dec[1]};
+        s23.p[1] = {arr[AX2], arr[AI1], arr[AM3], arr[AB2], dec[2]};
+        va = {arr[AX0], arr[AA1], arr[AB1], arr[AB2]};
+    }
+};
+// trellises per wavefront of the state-parallel trellis kernel: one or two wavefronts per SIMD
+static uint32_t gpw_of(uint32_t n_tr) { return n_tr <= 2048 ? 1u : n_tr <= 4096 ? 2u : n_tr <= 8192 ? 4u : SMALL_G; }
+
 // The five launches of one REF decode over n_cb code blocks of size K.
 template <typename Src, bool GROUP>
 static int turbo_ref_run(mi_lte_ctx *ctx, Src src, uint32_t K, uint32_t n_cb, uint8_t *d_c_bits, GroupDesc gd, uint32_t e_cap = 0)
@@ -1993,57 +2022,39 @@ static int turbo_ref_run(mi_lte_ctx *ctx, Src src, uint32_t K, uint32_t n_cb, ui
         ctx->err = "turbo kernels were built with static LDS: absolute LDS addressing is invalid";
         return MI_LTE_ERR_HIP;
     }
-    const size_t n_tiles = (n_cb + 63) / 64, Kp = kpad64(K), arr_bytes = n_tiles * Kp * 64, dec_bytes = n_tiles * Kp * 32;
+    const size_t n_tiles = (n_cb + 63) / 64, Kp = kpad64(K), arr_bytes = n_tiles * Kp * 64;
     rc = mi_ctx_reserve_scratch(ctx, mi_lte_turbo_scratch_bytes(K, n_cb));
     if (rc != MI_LTE_OK) return rc;
-    uint8_t *base = (uint8_t *)ctx->scratch;
-    uint8_t *arr[N_BYTE_ARRAYS];
-    for (int a = 0; a < N_BYTE_ARRAYS; a++) arr[a] = base + a * arr_bytes;
-    uint32_t *dec[3];
-    for (int p = 0; p < 3; p++) dec[p] = (uint32_t *)(base + N_BYTE_ARRAYS * arr_bytes + p * dec_bytes);
+    const RefScratch sc(ctx->scratch, arr_bytes);
     const bool small = n_cb <= ctx->siso_small_max; // a handful of code blocks (a per-call caller's transport block): k_turbo_siso_small
     if (n_cb % 64 && !small) // lanes past the batch end walk whatever the scratch holds; keep it defined (the state-parallel kernel has no such lanes)
-        MI_HIP_CHECK(ctx, hipMemsetAsync(base, 0, N_BYTE_ARRAYS * arr_bytes, ctx->stream));
+        MI_HIP_CHECK(ctx, hipMemsetAsync(sc.base, 0, N_BYTE_ARRAYS * arr_bytes, ctx->stream));
 
     if constexpr (GROUP) { // the per-block descriptors behind the tile arrays and the traceback words
-        CbDesc *d_desc = (CbDesc *)(base + N_BYTE_ARRAYS * arr_bytes + 3 * dec_bytes);
-        gd.desc = src.g.desc = d_desc;
-        MI_LAUNCH(ctx, "k_cb_desc", k_cb_desc, dim3((n_cb + 255) / 256), dim3(256), 0, gd, n_cb, (const uint32_t *)src.nnn, d_desc);
+        gd.desc = src.g.desc = sc.d_desc;
+        MI_LAUNCH(ctx, "k_cb_desc", k_cb_desc, dim3((n_cb + 255) / 256), dim3(256), 0, gd, n_cb, (const uint32_t *)src.nnn, sc.d_desc);
     }
-    PrepOut po;
-    po.arr[0] = arr[AX0]; po.arr[1] = arr[AX1]; po.arr[2] = arr[AX2];
-    po.arr[3] = arr[AI0]; po.arr[4] = arr[AM1]; po.arr[5] = arr[AM2];
     const uint32_t cb_threads = (uint32_t)(((Kp >> 4) + 63) & ~(size_t)63); // one thread per 16-step unit: 64..384
-    MI_LAUNCH(ctx, "k_turbo_prep", (k_turbo_prep<Src, 1>), dim3(8 * xcd_chunk(n_cb)), dim3(cb_threads), prep_lds_bytes(Kp, e_cap), src, K, n_cb, tb.d_pi, po, MultiArgs{});
+    MI_LAUNCH(ctx, "k_turbo_prep", (k_turbo_prep<Src, 1>), dim3(8 * xcd_chunk(n_cb)), dim3(cb_threads), prep_lds_bytes(Kp, e_cap), src, K, n_cb, tb.d_pi, sc.po, MultiArgs{});
 
-    SisoArgs s1;
-    s1.p[0] = {arr[AX1], arr[AX0], arr[AM1], arr[AA1], dec[0]};
-    s1.p[1] = s1.p[0];
     // a handful of code blocks: states on the lanes instead of code blocks
-    auto gpw_of = [](uint32_t n_tr) { return n_tr <= 2048 ? 1u : n_tr <= 4096 ? 2u : n_tr <= 8192 ? 4u : SMALL_G; }; // one or two wavefronts per SIMD
     auto lds_of = [&](uint32_t gpw) { return sizeof(uint32_t) * gpw * (64 * 4 * 2 + (Kp >> 5) * 4); };
     if (small)
-        MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<false>, dim3((n_cb + gpw_of(n_cb) - 1) / gpw_of(n_cb)), dim3(64), lds_of(gpw_of(n_cb)), s1, K, n_cb, 0u,
+        MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<false>, dim3((n_cb + gpw_of(n_cb) - 1) / gpw_of(n_cb)), dim3(64), lds_of(gpw_of(n_cb)), sc.s1, K, n_cb, 0u,
                   gpw_of(n_cb), MultiArgs{});
     else
-        MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<false>, dim3(((n_tiles + 1) / 2 + 3) / 4), dim3(256), 0, s1, K, (uint32_t)n_tiles, 0u, MultiArgs{}, (const uint32_t *)nullptr); // two tiles per lane
+        MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<false>, dim3(((n_tiles + 1) / 2 + 3) / 4), dim3(256), 0, sc.s1, K, (uint32_t)n_tiles, 0u, MultiArgs{}, (const uint32_t *)nullptr); // two tiles per lane
 
-    PermArgs pa;
-    pa.A1 = arr[AA1]; pa.X2 = arr[AX2]; pa.out[0] = arr[AI1]; pa.out[1] = arr[AM3];
     const uint32_t perm_grid = ((8 * xcd_chunk(n_cb) + PERM_NB - 1) / PERM_NB + 7u) & ~7u; // a multiple of 8: b + i * grid stays on b's XCD
-    MI_LAUNCH(ctx, "k_turbo_perm", k_turbo_perm<1>, dim3(perm_grid), dim3(cb_threads), MTAB_N + Kp + 32, pa, K, n_cb, tb.d_pi, MultiArgs{});
+    MI_LAUNCH(ctx, "k_turbo_perm", k_turbo_perm<1>, dim3(perm_grid), dim3(cb_threads), MTAB_N + Kp + 32, sc.pa, K, n_cb, tb.d_pi, MultiArgs{});
 
-    SisoArgs s23;
-    s23.p[0] = {arr[AX2], arr[AI0], arr[AM2], arr[AB1], dec[1]};
-    s23.p[1] = {arr[AX2], arr[AI1], arr[AM3], arr[AB2], dec[2]};
     if (small)
-        MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<false>, dim3((2 * n_cb + gpw_of(2 * n_cb) - 1) / gpw_of(2 * n_cb)), dim3(64), lds_of(gpw_of(2 * n_cb)), s23, K,
+        MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<false>, dim3((2 * n_cb + gpw_of(2 * n_cb) - 1) / gpw_of(2 * n_cb)), dim3(64), lds_of(gpw_of(2 * n_cb)), sc.s23, K,
                   n_cb, 1u, gpw_of(2 * n_cb), MultiArgs{});
     else
-        MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<false>, dim3((n_tiles + 3) / 4), dim3(256), 0, s23, K, (uint32_t)n_tiles, 1u, MultiArgs{}, (const uint32_t *)nullptr); // passes 2 and 3 of a tile per lane
+        MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<false>, dim3((n_tiles + 3) / 4), dim3(256), 0, sc.s23, K, (uint32_t)n_tiles, 1u, MultiArgs{}, (const uint32_t *)nullptr); // passes 2 and 3 of a tile per lane
 
-    VoteArgs va = {arr[AX0], arr[AA1], arr[AB1], arr[AB2]};
-    MI_LAUNCH(ctx, "k_turbo_vote", (k_turbo_vote<GROUP, 1>), dim3(8 * xcd_chunk(n_cb)), dim3(cb_threads), 3 * Kp + 64, va, K, n_cb, tb.d_inv2, d_c_bits, gd, MultiArgs{});
+    MI_LAUNCH(ctx, "k_turbo_vote", (k_turbo_vote<GROUP, 1>), dim3(8 * xcd_chunk(n_cb)), dim3(cb_threads), 3 * Kp + 64, sc.va, K, n_cb, tb.d_inv2, d_c_bits, gd, MultiArgs{});
     MI_HIP_CHECK(ctx, hipGetLastError());
     ctx->last_kernels = "k_turbo_prep:1,k_turbo_siso:2,k_turbo_perm:1,k_turbo_vote:1";
     return MI_LTE_OK;
@@ -2075,46 +2086,48 @@ static int rm_rank_tables(mi_lte_ctx *ctx, uint32_t K, RmTables *out)
     return MI_LTE_OK;
 }
 
+// the kernels' view of a plan's hand-over; cb_base: the first code-block slot the launch covers
+static GroupDesc group_desc(const mi_lte_ctx *ctx, const MiDecodeIO &io, uint32_t cb_base = 0)
+{
+    return {io.d_allocs, io.d_cb_alloc + cb_base, io.d_e, io.d_e_off, io.d_e_len, io.d_out_bits, io.out_stride, io.d_status, ctx->d_crc_tab, io.ul ? 1u : 0u, io.packed ? 1u : 0u};
+}
+// LDS bytes that stage a group's longest allocation: room for the zero slot behind it
+static uint32_t stage_cap(uint32_t e_max_bytes) { return (e_max_bytes + 16u + 63u) & ~63u; }
+
+// Can the block-size group join a merged decode?  Every stream has at most 31 NULL slots, so a lap of the circular buffer consumes at least
+// 3K - 81 soft bits: while the longest allocation makes no more than 258 laps no sum of int8 values leaves int16, and the kernels may keep the
+// rate un-matching sums in pairs (SrcRateUnmatchPk), as the merged kernels do; a group beyond that takes the per-size path with 32-bit sums.
+static bool mi_turbo_ref_multi_takes(uint32_t K, uint32_t e_max_bytes) { return (e_max_bytes + (3 * K - 81) - 1) / (3 * K - 81) <= 258; }
+
 // the per-size path of mi_turbo_ref_dispatch: decode the code blocks of one size K straight from the demodulator's soft bits
-static int mi_turbo_ref_group(mi_lte_ctx *ctx, uint32_t K, uint32_t n_cb, const mi_lte_pdsch_alloc *d_allocs,
-                              const uint32_t *d_cb_alloc, const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len,
-                              uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, uint32_t e_max_bytes, bool ul, bool packed)
+static int mi_turbo_ref_group(mi_lte_ctx *ctx, const MiKGroup &gr, const MiDecodeIO &io)
 {
     int rc = mi_ctx_crc_table(ctx);
     if (rc != MI_LTE_OK) return rc;
-    GroupDesc gd{d_allocs, d_cb_alloc, d_e, d_e_off, d_e_len, d_out_bits, out_stride, d_status, ctx->d_crc_tab, ul ? 1u : 0u, packed ? 1u : 0u};
+    const GroupDesc gd = group_desc(ctx, io, gr.cb_base);
     RmTables rt;
-    rc = rm_rank_tables(ctx, K, &rt);
+    rc = rm_rank_tables(ctx, gr.K, &rt);
     if (rc != MI_LTE_OK) return rc;
     SrcRateUnmatch src;
     src.g    = gd;
     src.tabs = rt.d_tabs;
     src.nnn  = rt.d_nnn;
     // stage e in LDS when the largest allocation of the group fits next to the block's own arrays
-    const uint32_t cap = (e_max_bytes + 16u + 63u) & ~63u; // room for the zero slot behind the longest allocation
-    src.e_cap          = (prep_lds_bytes(kpad64(K), cap) <= 48 * 1024) ? cap : 0;
-    // every stream has at most 31 NULL slots, so a lap of the circular buffer consumes at least 3K - 81 soft bits: while the longest
-    // allocation makes no more than 258 laps no sum of int8 values leaves int16, and the kernel may keep them in pairs
-    const uint32_t laps = (e_max_bytes + (3 * K - 81) - 1) / (3 * K - 81);
-    if (laps <= 258) {
+    const uint32_t cap = stage_cap(gr.e_max);
+    src.e_cap          = (prep_lds_bytes(kpad64(gr.K), cap) <= 48 * 1024) ? cap : 0;
+    if (mi_turbo_ref_multi_takes(gr.K, gr.e_max)) {
         SrcRateUnmatchPk pk;
         static_cast<SrcRateUnmatch &>(pk) = src;
-        return turbo_ref_run<SrcRateUnmatchPk, true>(ctx, pk, K, n_cb, nullptr, gd, src.e_cap);
+        return turbo_ref_run<SrcRateUnmatchPk, true>(ctx, pk, gr.K, gr.n_cb, nullptr, gd, src.e_cap);
     }
-    return turbo_ref_run<SrcRateUnmatch, true>(ctx, src, K, n_cb, nullptr, gd, src.e_cap);
+    return turbo_ref_run<SrcRateUnmatch, true>(ctx, src, gr.K, gr.n_cb, nullptr, gd, src.e_cap);
 }
-
-// Can the block-size group join a merged decode?  The merged kernels keep the rate un-matching sums as int16 pairs (SrcRateUnmatchPk): a
-// group whose longest allocation makes more than 258 laps of the circular buffer takes the per-size path with 32-bit sums instead.
-static bool mi_turbo_ref_multi_takes(uint32_t K, uint32_t e_max_bytes) { return (e_max_bytes + (3 * K - 81) - 1) / (3 * K - 81) <= 258; }
 
 // A whole PDSCH batch -- the code blocks of MANY sizes -- through the REF decoder with every kernel launched once (the per-code-block
 // kernels once per workgroup width): see KSeg.  `groups` in ascending K, cb_base = the group's first slot in d_cb_alloc.  The tables the
 // kernels read are rebuilt only when the groups differ from the ones `cache` was built for (a static plan: once; a dynamic plan: per
 // assignment).
-static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_groups, const mi_lte_pdsch_alloc *d_allocs, const uint32_t *d_cb_alloc,
-                              const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
-                              bool ul, bool packed, MiMultiCache *cache)
+static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_groups, const MiDecodeIO &io, MiMultiCache *cache)
 {
     if (!groups || n_groups == 0 || n_groups > 0xFFFF || !cache) return MI_LTE_ERR_INVALID_ARG;
     int rc = mi_ctx_crc_table(ctx);
@@ -2141,7 +2154,7 @@ static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t 
             if ((rc = mi_ctx_turbo_tables(ctx, gr.K, 0, &tb)) != MI_LTE_OK || (rc = rm_rank_tables(ctx, gr.K, &rt)) != MI_LTE_OK) return rc;
             KSeg &sg = segs[i];
             memset(&sg, 0, sizeof(sg));
-            const uint32_t Kp = kpad64(gr.K), cap = (gr.e_max + 16u + 63u) & ~63u;
+            const uint32_t Kp = kpad64(gr.K), cap = stage_cap(gr.e_max);
             sg.K = gr.K; sg.n_cb = gr.n_cb; sg.cb_base = gr.cb_base; sg.n_tiles = (gr.n_cb + 63) / 64;
             // LDS for an allocation's soft bits: room for the size's longest allocation, but no more than a lap and a quarter of the circular buffer
             // (3 (K + 4) positions) -- an allocation beyond that is staged lap by lap (gather_windowed_pk), and one repeated allocation of a size
@@ -2236,7 +2249,6 @@ static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t 
         deal(G.n_wv1, &G.ord_wv1, &G.n_ord1);
         deal(G.n_wv23, &G.ord_wv23, &G.n_ord23);
         // ... and of the state-parallel trellis kernel (a handful of code blocks in all): workgroup = wavefront = up to gpw trellises of one size
-        auto gpw_of = [](uint32_t n_tr) { return n_tr <= 2048 ? 1u : n_tr <= 4096 ? 2u : n_tr <= 8192 ? 4u : SMALL_G; };
         uint32_t tot = 0, kp_all = 0;
         for (uint32_t i = 0; i < n_groups; i++) { tot += groups[i].n_cb; kp_all = std::max(kp_all, kpad64(groups[i].K)); }
         G.gpw1 = gpw_of(tot); G.gpw23 = gpw_of(2 * tot); G.kp_all = kp_all;
@@ -2274,26 +2286,18 @@ static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t 
         cache->built_for.assign(groups, groups + n_groups);
     }
     const MiMultiGeom &G = cache->geom;
-    const size_t A = G.arr_bytes, dec_bytes = A / 2;
-    rc = mi_ctx_reserve_scratch(ctx, N_BYTE_ARRAYS * A + 3 * dec_bytes + (size_t)((G.n_slots + 63) & ~63u) * sizeof(CbDesc));
+    const size_t A = G.arr_bytes;
+    rc = mi_ctx_reserve_scratch(ctx, N_BYTE_ARRAYS * A + 3 * (A / 2) + (size_t)((G.n_slots + 63) & ~63u) * sizeof(CbDesc));
     if (rc != MI_LTE_OK) return rc;
-    uint8_t *base = (uint8_t *)ctx->scratch;
-    uint8_t *arr[N_BYTE_ARRAYS];
-    for (int a = 0; a < N_BYTE_ARRAYS; a++) arr[a] = base + a * A;
-    uint32_t *dec[3];
-    for (int p = 0; p < 3; p++) dec[p] = (uint32_t *)(base + N_BYTE_ARRAYS * A + p * dec_bytes);
-    CbDesc *d_desc = (CbDesc *)(base + N_BYTE_ARRAYS * A + 3 * dec_bytes);
+    const RefScratch sc(ctx->scratch, A);
     const KSeg     *d_segs = (const KSeg *)cache->d_tab;
     const uint32_t *d_map  = (const uint32_t *)((const uint8_t *)cache->d_tab + G.map_off);
 
-    GroupDesc gd{d_allocs, d_cb_alloc, d_e, d_e_off, d_e_len, d_out_bits, out_stride, d_status, ctx->d_crc_tab, ul ? 1u : 0u, packed ? 1u : 0u};
-    gd.desc = d_desc;
-    MI_LAUNCH(ctx, "k_cb_desc", k_cb_desc_multi, dim3((G.n_slots + 255) / 256), dim3(256), 0, gd, G.n_slots, d_segs, n_groups, d_desc);
+    GroupDesc gd = group_desc(ctx, io);
+    gd.desc = sc.d_desc;
+    MI_LAUNCH(ctx, "k_cb_desc", k_cb_desc_multi, dim3((G.n_slots + 255) / 256), dim3(256), 0, gd, G.n_slots, d_segs, n_groups, sc.d_desc);
     SrcRateUnmatchPk src;
     src.g = gd; src.tabs = nullptr; src.nnn = nullptr; src.e_cap = 0;
-    PrepOut po;
-    po.arr[0] = arr[AX0]; po.arr[1] = arr[AX1]; po.arr[2] = arr[AX2];
-    po.arr[3] = arr[AI0]; po.arr[4] = arr[AM1]; po.arr[5] = arr[AM2];
     for (int c = 0; c < NCLS; c++)
         if (G.grid_cb[c]) {
             // a width that holds ONE size (W4: each of its two sizes): the per-size kernel with kernel arguments, on the merged layout -- its
@@ -2304,45 +2308,36 @@ static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t 
                 RmTables    rt;
                 if ((rc = mi_ctx_turbo_tables(ctx, gr.K, 0, &tb)) != MI_LTE_OK || (rc = rm_rank_tables(ctx, gr.K, &rt)) != MI_LTE_OK) return rc;
                 SrcRateUnmatchPk s1 = src;
-                s1.tabs = rt.d_tabs; s1.nnn = rt.d_nnn; s1.g.desc = d_desc + gr.cb_base; s1.e_cap = G.e_cap_one[c];
-                PrepOut p1 = po;
+                s1.tabs = rt.d_tabs; s1.nnn = rt.d_nnn; s1.g.desc = sc.d_desc + gr.cb_base; s1.e_cap = G.e_cap_one[c];
+                PrepOut p1 = sc.po;
                 for (int a = 0; a < 6; a++) p1.arr[a] += G.off_one[c];
                 MI_LAUNCH(ctx, "k_turbo_prep", (k_turbo_prep<SrcRateUnmatchPk, 1, false>), dim3(G.grid_cb[c]), dim3(64 * (c + 1)), G.lds_prep[c], s1, gr.K, gr.n_cb, (const uint16_t *)tb.d_pi,
                           p1, MultiArgs{});
                 continue;
             }
-            MI_LAUNCH(ctx, "k_turbo_prep", (k_turbo_prep<SrcRateUnmatchPk, 1, true>), dim3(G.grid_cb[c]), dim3(64 * (c + 1)), G.lds_prep[c], src, 0u, 0u, (const uint16_t *)nullptr, po,
+            MI_LAUNCH(ctx, "k_turbo_prep", (k_turbo_prep<SrcRateUnmatchPk, 1, true>), dim3(G.grid_cb[c]), dim3(64 * (c + 1)), G.lds_prep[c], src, 0u, 0u, (const uint16_t *)nullptr, sc.po,
                       (MultiArgs{d_segs, d_map + G.map_cb[c]}));
         }
-    SisoArgs s1;
-    s1.p[0] = {arr[AX1], arr[AX0], arr[AM1], arr[AA1], dec[0]};
-    s1.p[1] = s1.p[0];
     // a handful of code blocks in all (a per-call caller's subframe): the trellis's states on the lanes instead of code blocks, as in the per-size launches
     const bool small = G.n_slots <= ctx->siso_small_max;
     auto lds_small = [&](uint32_t gpw) { return sizeof(uint32_t) * gpw * (64 * 4 * 2 + (G.kp_all >> 5) * 4); };
     if (small)
-        MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<true>, dim3(G.n_ws1), dim3(64), lds_small(G.gpw1), s1, 0u, 0u, 0u, G.gpw1, (MultiArgs{d_segs, d_map + G.map_ws1}));
+        MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<true>, dim3(G.n_ws1), dim3(64), lds_small(G.gpw1), sc.s1, 0u, 0u, 0u, G.gpw1, (MultiArgs{d_segs, d_map + G.map_ws1}));
     else
-    MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<true>, dim3(G.n_ord1 ? G.n_ord1 / 4 : (G.n_wv1 + 3) / 4), dim3(256), G.siso_pad1, s1, 0u, G.n_wv1, 0u, (MultiArgs{d_segs, d_map + G.map_wv1}),
+    MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<true>, dim3(G.n_ord1 ? G.n_ord1 / 4 : (G.n_wv1 + 3) / 4), dim3(256), G.siso_pad1, sc.s1, 0u, G.n_wv1, 0u, (MultiArgs{d_segs, d_map + G.map_wv1}),
               G.n_ord1 ? d_map + G.ord_wv1 : (const uint32_t *)nullptr);
-    PermArgs pa;
-    pa.A1 = arr[AA1]; pa.X2 = arr[AX2]; pa.out[0] = arr[AI1]; pa.out[1] = arr[AM3];
     for (int c = 0; c < NCLS; c++)
         if (G.grid_perm[c])
-            MI_LAUNCH(ctx, "k_turbo_perm", (k_turbo_perm<1, true>), dim3(G.grid_perm[c]), dim3(64 * (c + 1)), MTAB_N + G.kp_max[c] + 32, pa, 0u, 0u, (const uint16_t *)nullptr,
+            MI_LAUNCH(ctx, "k_turbo_perm", (k_turbo_perm<1, true>), dim3(G.grid_perm[c]), dim3(64 * (c + 1)), MTAB_N + G.kp_max[c] + 32, sc.pa, 0u, 0u, (const uint16_t *)nullptr,
                       (MultiArgs{d_segs, d_map + G.map_perm[c]}));
-    SisoArgs s23;
-    s23.p[0] = {arr[AX2], arr[AI0], arr[AM2], arr[AB1], dec[1]};
-    s23.p[1] = {arr[AX2], arr[AI1], arr[AM3], arr[AB2], dec[2]};
     if (small)
-        MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<true>, dim3(G.n_ws23), dim3(64), lds_small(G.gpw23), s23, 0u, 0u, 1u, G.gpw23, (MultiArgs{d_segs, d_map + G.map_ws23}));
+        MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<true>, dim3(G.n_ws23), dim3(64), lds_small(G.gpw23), sc.s23, 0u, 0u, 1u, G.gpw23, (MultiArgs{d_segs, d_map + G.map_ws23}));
     else
-    MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<true>, dim3(G.n_ord23 ? G.n_ord23 / 4 : (G.n_wv23 + 3) / 4), dim3(256), G.siso_pad23, s23, 0u, G.n_wv23, 1u, (MultiArgs{d_segs, d_map + G.map_wv23}),
+    MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<true>, dim3(G.n_ord23 ? G.n_ord23 / 4 : (G.n_wv23 + 3) / 4), dim3(256), G.siso_pad23, sc.s23, 0u, G.n_wv23, 1u, (MultiArgs{d_segs, d_map + G.map_wv23}),
               G.n_ord23 ? d_map + G.ord_wv23 : (const uint32_t *)nullptr);
-    VoteArgs va = {arr[AX0], arr[AA1], arr[AB1], arr[AB2]};
     for (int c = 0; c < NCLS; c++)
         if (G.grid_cb[c])
-            MI_LAUNCH(ctx, "k_turbo_vote", (k_turbo_vote<true, 1, true>), dim3(G.grid_cb[c]), dim3(64 * (c + 1)), 3 * G.kp_max[c] + 64, va, 0u, 0u, (const uint16_t *)nullptr,
+            MI_LAUNCH(ctx, "k_turbo_vote", (k_turbo_vote<true, 1, true>), dim3(G.grid_cb[c]), dim3(64 * (c + 1)), 3 * G.kp_max[c] + 64, sc.va, 0u, 0u, (const uint16_t *)nullptr,
                       (uint8_t *)nullptr, gd, (MultiArgs{d_segs, d_map + G.map_cb[c]}));
     MI_HIP_CHECK(ctx, hipGetLastError());
     return MI_LTE_OK;
@@ -2354,9 +2349,7 @@ static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t 
 // sliver of the device -- 65 536 mixed subframes took 72.6 ms that way, 48.8 of them in the decoder (profiles/r06_chain_mixed_per_size.json).
 // That needs ctx->merged_decode and two groups the merged kernels take; every other group (more than 258 laps: 32-bit sums), and every group
 // when the merged launches do not run, takes its own launches.  Sets the decoder's part of ctx->last_kernels.
-int mi_turbo_ref_dispatch(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_groups, const mi_lte_pdsch_alloc *d_allocs, const uint32_t *d_cb_alloc,
-                          const int8_t *d_e, const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status,
-                          bool ul, bool packed, MiMultiCache *cache)
+int mi_turbo_ref_dispatch(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_groups, const MiDecodeIO &io, MiMultiCache *cache)
 {
     std::vector<MiKGroup> take;
     if (ctx->merged_decode)
@@ -2364,13 +2357,11 @@ int mi_turbo_ref_dispatch(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_gr
             if (mi_turbo_ref_multi_takes(groups[i].K, groups[i].e_max)) take.push_back(groups[i]);
     const bool merged = take.size() >= 2;
     int        rc;
-    if (merged && (rc = mi_turbo_ref_multi(ctx, take.data(), (uint32_t)take.size(), d_allocs, d_cb_alloc, d_e, d_e_off, d_e_len, d_out_bits, out_stride,
-                                           d_status, ul, packed, cache)) != MI_LTE_OK)
-        return rc;
+    if (merged && (rc = mi_turbo_ref_multi(ctx, take.data(), (uint32_t)take.size(), io, cache)) != MI_LTE_OK) return rc;
     for (uint32_t i = 0; i < n_groups; i++) {
         const MiKGroup &gr = groups[i];
         if (merged && mi_turbo_ref_multi_takes(gr.K, gr.e_max)) continue;
-        rc = mi_turbo_ref_group(ctx, gr.K, gr.n_cb, d_allocs, d_cb_alloc + gr.cb_base, d_e, d_e_off, d_e_len, d_out_bits, out_stride, d_status, gr.e_max, ul, packed);
+        rc = mi_turbo_ref_group(ctx, gr, io);
         if (rc != MI_LTE_OK) return rc;
     }
     ctx->last_kernels = !merged                 ? "k_turbo_prep,k_turbo_siso,k_turbo_perm,k_turbo_vote per block size"
@@ -2385,18 +2376,17 @@ void mi_multi_cache_free(MiMultiCache *cache)
     if (cache) { cache->d_tab = nullptr; cache->cap = 0; cache->built_for.clear(); }
 }
 
-int mi_turbo_bcjr_group(mi_lte_ctx *ctx, uint32_t K, uint32_t n_cb, const mi_lte_pdsch_alloc *d_allocs, const uint32_t *d_cb_alloc, const int8_t *d_e,
-                        const uint32_t *d_e_off, const uint32_t *d_e_len, uint8_t *d_out_bits, uint32_t out_stride, int32_t *d_status, bool ul,
-                        int8_t *d_soft, uint8_t *d_c_bits, uint32_t n_iter, int qpp_spec, bool packed, uint32_t e_max_bytes, bool block_mode, bool early)
+int mi_turbo_bcjr_group(mi_lte_ctx *ctx, const MiKGroup &gr, const MiDecodeIO &io, int8_t *d_soft, uint8_t *d_c_bits, uint32_t mode, uint32_t n_iter, int qpp_spec)
 {
+    const uint32_t K = gr.K, n_cb = gr.n_cb;
     int rc = mi_ctx_crc_table(ctx);
     if (rc != MI_LTE_OK) return rc;
-    GroupDesc gd{d_allocs, d_cb_alloc, d_e, d_e_off, d_e_len, d_out_bits, out_stride, d_status, ctx->d_crc_tab, ul ? 1u : 0u, packed ? 1u : 0u};
+    GroupDesc gd = group_desc(ctx, io, gr.cb_base);
     RmTables  t;
     rc = rm_rank_tables(ctx, K, &t);
     if (rc != MI_LTE_OK) return rc;
-    const uint32_t cap = (e_max_bytes + 16u + 63u) & ~63u, e_cap = cap <= 60 * 1024 ? cap : 0; // stage the allocation in LDS when it fits
-    if (block_mode) { // the one-block-per-wavefront kernel takes the interleaved int8 block
+    const uint32_t cap = stage_cap(gr.e_max), e_cap = cap <= 60 * 1024 ? cap : 0; // stage the allocation in LDS when it fits
+    if (mode == MI_LTE_TURBO_BCJR_BLOCK) { // the one-block-per-wavefront kernel takes the interleaved int8 block
         MI_LAUNCH(ctx, "k_rm_to_i8", k_rm_to_i8, dim3(n_cb), dim3(256), e_cap, gd, K, n_cb, (const uint16_t *)t.d_tabs, (const uint32_t *)t.d_nnn, d_soft, e_cap);
         MI_HIP_CHECK(ctx, hipGetLastError());
         rc = mi_turbo_bcjr_block_batch(ctx, d_soft, K, n_cb, n_iter, qpp_spec, d_c_bits);
@@ -2418,7 +2408,7 @@ int mi_turbo_bcjr_group(mi_lte_ctx *ctx, uint32_t K, uint32_t n_cb, const mi_lte
         src.g = gd; src.tabs = t.d_tabs; src.nnn = t.d_nnn; src.e_cap = e_cap2;
         MI_LAUNCH(ctx, "k_rm_bcjr_prep", k_rm_bcjr_prep, dim3(8 * xcd_chunk(n_cb)), dim3(cb_threads), e_cap2 + Kp, src, K, n_cb, (const uint16_t *)tb.d_pi, mb);
         MI_HIP_CHECK(ctx, hipGetLastError());
-        rc = mi_turbo_bcjr_iterate(ctx, K, n_cb, n_iter, qpp_spec, d_c_bits, early);
+        rc = mi_turbo_bcjr_iterate(ctx, K, n_cb, n_iter, qpp_spec, d_c_bits, mode == MI_LTE_TURBO_BCJR_EARLY);
     }
     if (rc != MI_LTE_OK) return rc;
     MI_LAUNCH(ctx, "k_crc_finish", k_crc_finish, dim3(n_cb), dim3(256), 0, (const uint8_t *)d_c_bits, K, n_cb, gd);

@@ -23,9 +23,8 @@
 #include <type_traits>
 
 #include <cstring>
-#include "ctx.hpp"
+#include "plan_core.hpp"
 #include "phy_dev.hpp"
-#include "lte_tables.h"
 
 namespace {
 
@@ -447,16 +446,11 @@ __global__ __launch_bounds__(64) void k_pucch_decode(const float *__restrict__ s
 
 struct mi_lte_pusch_plan {
     mi_lte_dl_cfg cfg;
-    uint32_t      n_alloc = 0, out_stride = 0, M_max = 0, words_max = 0;
-    size_t        e_bytes = 0;
-    mi_lte_pdsch_alloc *d_allocs = nullptr;
-    PuschDesc          *d_desc   = nullptr;
-    float              *d_dmrs   = nullptr;
-    uint32_t *d_e_off = nullptr, *d_e_len = nullptr, *d_cb_alloc = nullptr;
-    int8_t   *d_e = nullptr;
-    std::vector<MiKGroup> groups;
-    std::vector<uint32_t> h_e_off, h_e_len;
-    MiMultiCache          multi; // the merged decode's device tables for `groups` (turbo.hip: mi_turbo_ref_dispatch)
+    MiPlanCore    core;
+    uint32_t      M_max = 0, words_max = 0;
+    PuschDesc    *d_desc = nullptr;
+    float        *d_dmrs = nullptr;
+    std::vector<uint32_t> h_e_len;
 };
 
 // the float next above or equal to 1 / d (see quot)
@@ -504,13 +498,6 @@ static int pusch_shapes(mi_lte_ctx *ctx)
     return MI_LTE_OK;
 }
 
-static uint32_t ul_qpp_size_at_least(uint32_t B)
-{
-    for (int r = 0; r < LTE_QPP_N_SIZES; r++)
-        if (LTE_QPP_ROWS[r].K >= B) return LTE_QPP_ROWS[r].K;
-    return 0;
-}
-
 // h_dmrs (optional): caller-supplied reference signals, 4 x 12*N_prb floats per allocation back to back -- the
 // per-call host form passes the arrays liblte_phy_ul_init left in the caller's LIBLTE_PHY_STRUCT
 extern "C" void mi_lte_pusch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl);
@@ -524,22 +511,19 @@ int mi_pusch_plan_create_impl(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const m
     auto *pl    = new mi_lte_pusch_plan();
     auto  guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_lte_pusch_plan_destroy(nullptr, pl); });
     pl->cfg     = *cfg;
-    pl->n_alloc = n_alloc;
-    std::map<uint32_t, std::vector<uint32_t>> byK;
-    std::map<uint32_t, uint32_t>              emaxK;
+    pl->core.n_alloc = n_alloc;
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> dmrs_at; // (cell, subframe, N_prb) -> float offset
     std::vector<float>     dmrs;
     std::vector<PuschDesc> desc(n_alloc);
+    std::vector<uint8_t>   row(n_alloc);
     uint32_t max_tbs = 0;
-    size_t   off = 0;
-    pl->h_e_off.resize(n_alloc);
     pl->h_e_len.resize(n_alloc);
     for (uint32_t a = 0; a < n_alloc; a++) {
         const mi_lte_pdsch_alloc &al = h_allocs[a];
-        const uint32_t B = al.tbs + 24, K = (B <= 6144) ? ul_qpp_size_at_least(B) : 0;
+        const int r = mi_qpp_row_at_least(al.tbs + 24);
         // N_prb the reference has a transform pre-decoding plan for (liblte_phy.cc:2360-2377)
         const bool planned = al.N_prb > 0 && al.N_prb < cfg->N_rb_dl && (al.N_prb % 2 == 0 || al.N_prb % 3 == 0 || al.N_prb % 5 == 0);
-        if (K == 0 || !planned || al.mod_type > 3 || al.unit >= n_units) {
+        if (r < 0 || !planned || al.mod_type > 3 || al.unit >= n_units) {
             ctx->err = "PUSCH allocation outside the envelope (one code block; N_prb < N_rb_ul and divisible by 2, 3 or 5) or malformed";
             return MI_LTE_ERR_UNSUPPORTED;
         }
@@ -567,36 +551,26 @@ int mi_pusch_plan_create_impl(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const m
             }
             desc[a] = {sf, cell, it->second};
         }
-        byK[K].push_back(a);
+        row[a] = (uint8_t)r;
         max_tbs = std::max(max_tbs, al.tbs);
         const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : al.mod_type == 1 ? 2 : 1, E = 12 * M * Qm;
         pl->M_max     = std::max(pl->M_max, M);
         pl->words_max = std::max(pl->words_max, (E + 31) / 32 + 1);
-        emaxK[K]       = std::max(emaxK[K], E);
-        pl->h_e_off[a] = (uint32_t)(off >> 6); // in 64-byte units
         pl->h_e_len[a] = E;
-        off += (E + 63) & ~63u;
     }
     if (pl->words_max > 4096) { ctx->err = "allocation larger than the scrambling table"; return MI_LTE_ERR_UNSUPPORTED; }
-    pl->e_bytes    = off;
-    pl->out_stride = (max_tbs + 63) & ~63u;
+    pl->core.e_bytes    = mi_plan_soft_layout(pl->h_e_len.data(), n_alloc, pl->core.h_e_off);
+    pl->core.out_stride = mi_out_stride(max_tbs, false);
     std::vector<uint32_t> cb_alloc;
-    for (auto &kv : byK) {
-        pl->groups.push_back({kv.first, (uint32_t)kv.second.size(), (uint32_t)cb_alloc.size(), emaxK[kv.first]});
-        cb_alloc.insert(cb_alloc.end(), kv.second.begin(), kv.second.end());
-    }
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc));
+    mi_plan_group(row.data(), nullptr, pl->h_e_len.data(), n_alloc, pl->core.groups, cb_alloc);
+    MI_HIP_CHECK(ctx, pl->core.allocate(n_alloc, pl->core.e_bytes));
     MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_desc, sizeof(PuschDesc) * n_alloc));
     MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_dmrs, sizeof(float) * std::max<size_t>(dmrs.size(), 1)));
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_e_off, sizeof(uint32_t) * n_alloc));
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_e_len, sizeof(uint32_t) * n_alloc));
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_cb_alloc, sizeof(uint32_t) * n_alloc));
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_e, pl->e_bytes ? pl->e_bytes : 64));
-    MI_H2D(ctx, pl->d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
+    MI_H2D(ctx, pl->core.d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
     MI_H2D(ctx, pl->d_desc, desc.data(), sizeof(PuschDesc) * n_alloc);
     MI_H2D(ctx, pl->d_dmrs, dmrs.data(), sizeof(float) * dmrs.size());
-    MI_H2D(ctx, pl->d_e_off, pl->h_e_off.data(), sizeof(uint32_t) * n_alloc);
-    MI_H2D(ctx, pl->d_cb_alloc, cb_alloc.data(), sizeof(uint32_t) * n_alloc);
+    MI_H2D(ctx, pl->core.d_e_off, pl->core.h_e_off.data(), sizeof(uint32_t) * n_alloc);
+    MI_H2D(ctx, pl->core.d_cb_alloc, cb_alloc.data(), sizeof(uint32_t) * n_alloc);
     MI_HIP_CHECK(ctx, mi_stream_wait_polling(ctx));
     guard.armed = false;
     *out = pl;
@@ -620,23 +594,18 @@ void mi_lte_pusch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl)
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    (void)hipFree(pl->d_allocs);
+    pl->core.release();
     (void)hipFree(pl->d_desc);
     (void)hipFree(pl->d_dmrs);
-    (void)hipFree(pl->d_e_off);
-    (void)hipFree(pl->d_e_len);
-    (void)hipFree(pl->d_cb_alloc);
-    (void)hipFree(pl->d_e);
-    mi_multi_cache_free(&pl->multi);
     delete pl;
 }
 
-uint32_t mi_lte_pusch_plan_out_stride(const mi_lte_pusch_plan *pl) { return pl ? pl->out_stride : 0; }
+uint32_t mi_lte_pusch_plan_out_stride(const mi_lte_pusch_plan *pl) { return pl ? pl->core.out_stride : 0; }
 
 int mi_lte_pusch_plan_soft_bits(const mi_lte_pusch_plan *pl, uint32_t alloc, const int8_t **d_e, uint32_t *n_bits)
 {
-    if (!pl || alloc >= pl->n_alloc || !d_e || !n_bits) return MI_LTE_ERR_INVALID_ARG;
-    *d_e    = pl->d_e + (size_t)pl->h_e_off[alloc] * 64;
+    if (!pl || alloc >= pl->core.n_alloc || !d_e || !n_bits) return MI_LTE_ERR_INVALID_ARG;
+    *d_e    = pl->core.d_e + (size_t)pl->core.h_e_off[alloc] * 64;
     *n_bits = pl->h_e_len[alloc];
     return MI_LTE_OK;
 }
@@ -663,15 +632,14 @@ int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float 
         const int t = atoi(ev);
         if (t >= 64 && t <= (int)PUSCH_THREADS && t % 64 == 0) threads = (uint32_t)t;
     }
-#define MI_PUSCH_LAUNCH(T) MI_LAUNCH(ctx, "k_pusch_demod", k_pusch_demod<T>, dim3(pl->n_alloc), dim3(T), lds, d_subframes, (uint32_t)mi_lte_ul_subframe_floats(), \
-                                    pl->d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->d_e, pl->d_e_off, pl->d_e_len, pl->M_max, S_par, recip_up(S_par), \
+#define MI_PUSCH_LAUNCH(T) MI_LAUNCH(ctx, "k_pusch_demod", k_pusch_demod<T>, dim3(pl->core.n_alloc), dim3(T), lds, d_subframes, (uint32_t)mi_lte_ul_subframe_floats(), \
+                                    pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->M_max, S_par, recip_up(S_par), \
                                     static_cast<const PuschShape *>(ctx->d_pusch_shapes))
     if (threads == 64) MI_PUSCH_LAUNCH(64); else if (threads == 128) MI_PUSCH_LAUNCH(128); else if (threads == 192) MI_PUSCH_LAUNCH(192); else MI_PUSCH_LAUNCH(256);
 #undef MI_PUSCH_LAUNCH
     MI_HIP_CHECK(ctx, hipGetLastError());
     // several block sizes (the UEs of a subframe rarely share one): one launch set over all of them, as in the PDSCH chain
-    rc = mi_turbo_ref_dispatch(ctx, pl->groups.data(), (uint32_t)pl->groups.size(), pl->d_allocs, pl->d_cb_alloc, pl->d_e, pl->d_e_off, pl->d_e_len,
-                               d_out_bits, pl->out_stride, d_status, /*ul=*/true, false, &pl->multi);
+    rc = mi_turbo_ref_dispatch(ctx, pl->core.groups.data(), (uint32_t)pl->core.groups.size(), pl->core.io(d_out_bits, d_status, /*ul=*/true), &pl->core.multi);
     if (rc != MI_LTE_OK) return rc;
     ctx->last_kernels.insert(0, "k_pusch_demod:1,");
     return MI_LTE_OK;
