@@ -119,25 +119,19 @@ def noisy_batch():
     return [0, 5, 3, 8], [17, 301, 42, 503], per_unit
 
 
-@pytest.mark.parametrize("packed", [False, True])
-def test_rate_unmatch_decode_and_assembly_exact(ctx, port, ref, ref_phy, packed):
-    """Every block's cb_soft equals the reference's rate un-matching (N_codeblocks = C) of the tap's soft bits [off_r, off_r + E_r), mapped
-    by the decoder's rule (NULL -> 0, sums saturated to +-127); the output row, status and cb_ok equal the desegmentation + CRC24B / CRC24A
-    of the plain-C models' decisions on those blocks (BCJR x 8: lo_turbo_decode_bcjr; BCJR_BLOCK x 6: lo_turbo_decode_bcjr_block)."""
+def check_blocks_exact(port, ref, ref_phy, plan, allocs, res, n_soft):
+    """The three stages of every allocation of a plan that ran under BCJR x 8 and BCJR_BLOCK x 6 (res, in that order) against what
+    specifies them: cb_soft against the reference's rate un-matching, the output row / status / cb_ok against the plain-C models' decisions
+    on those blocks + the numpy desegmentation.  Returns ([(C, K, soft buffer limited) per allocation], passes, failures)."""
     import openlte_amd as m
-    n_soft = 125184
-    sfs, cells, per_unit = noisy_batch()
-    allocs, tx, plan, res = run_cells(ctx, 100, sfs, cells, per_unit, n_soft, 2, 11.0, seed=5 + packed,
-                                      decoders=((m.TURBO_BCJR, 8), (m.TURBO_BCJR_BLOCK, 6)), packed=packed)
     n_fail = n_pass = 0
-    seen_c, limited = set(), 0
+    seen = []
     for a, al in enumerate(allocs):
         e = plan.soft_bits(a)
         Qm = {1: 2, 2: 4, 3: 6}[al.mod_type]
         lay = m.dlsch_layout(al.tbs, len(e), Qm, al.tx_mode, al.rv_idx, n_soft, 8)
         nc, K = lay["C"], lay["K"]
-        seen_c.add(nc)
-        limited += lay["N_cb"] < 96 * ((K + 4 + 31) // 32)
+        seen.append((nc, K, lay["N_cb"] < 96 * ((K + 4 + 31) // 32)))
         blocks = plan.cb_soft(a)
         assert blocks.shape == (nc, 3 * (K + 4))
         for r in range(nc):
@@ -155,7 +149,58 @@ def test_rate_unmatch_decode_and_assembly_exact(ctx, port, ref, ref_phy, packed)
             assert (st[a], cb_ok[a]) == (want_st, want_mask), (a, st[a], cb_ok[a], want_st, want_mask)
             n_pass += st[a] == 0
             n_fail += st[a] != 0
+    return seen, n_pass, n_fail
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_rate_unmatch_decode_and_assembly_exact(ctx, port, ref, ref_phy, packed):
+    """Every block's cb_soft equals the reference's rate un-matching (N_codeblocks = C) of the tap's soft bits [off_r, off_r + E_r), mapped
+    by the decoder's rule (NULL -> 0, sums saturated to +-127); the output row, status and cb_ok equal the desegmentation + CRC24B / CRC24A
+    of the plain-C models' decisions on those blocks (BCJR x 8: lo_turbo_decode_bcjr; BCJR_BLOCK x 6: lo_turbo_decode_bcjr_block)."""
+    import openlte_amd as m
+    n_soft = 125184
+    sfs, cells, per_unit = noisy_batch()
+    allocs, tx, plan, res = run_cells(ctx, 100, sfs, cells, per_unit, n_soft, 2, 11.0, seed=5 + packed,
+                                      decoders=((m.TURBO_BCJR, 8), (m.TURBO_BCJR_BLOCK, 6)), packed=packed)
+    seen, n_pass, n_fail = check_blocks_exact(port, ref, ref_phy, plan, allocs, res, n_soft)
+    seen_c, limited = {nc for nc, K, lim in seen}, sum(lim for nc, K, lim in seen)
     assert seen_c >= {1, 2, 3, 6, 13} and limited >= 6
+    assert n_pass > 0 and n_fail > 0, (n_pass, n_fail)
+    plan.close()
+
+
+def segment_class_batch():
+    """100 RB grants whose code blocks fall in the segment classes of k_bcjr_half that noisy_batch (K = 3136, 5824: one segment; 6144:
+    eight) does not reach: n_seg = 2 (9912 -> 2 x 4992, 12576 -> 3 x 4224), n_seg = 4 (10680 -> 2 x 5376, 12960 -> 3 x 4352, 17568 ->
+    3 x 5888), and one-block grants whose K = tbs + 24 is a ragged n_seg = 2 size (992, 1120, 1504, 1888: K < kpad64(K), the last segment
+    ends short) or the ragged n_seg = 4 one (2016).  Code rates from ~0.4 (QPSK: decodes at any SNR the test runs at) to ~1 (64QAM on
+    too few PRBs: cannot decode), the rest in between; rv 0-3."""
+    per_unit = [
+        [alloc(0, 2, 9912, 0, 30, 0x111, rv=1), alloc(0, 3, 12576, 30, 35, 0x112, rv=0), alloc(0, 1, 1096, 65, 10, 0x113, rv=2)],
+        [alloc(1, 3, 10680, 0, 30, 0x114, rv=0), alloc(1, 1, 968, 30, 6, 0x115, rv=2), alloc(1, 3, 9912, 36, 12, 0x116, rv=0)],
+        [alloc(2, 2, 12960, 0, 40, 0x117, rv=3), alloc(2, 3, 17568, 40, 50, 0x118, rv=0), alloc(2, 3, 1480, 90, 2, 0x119, rv=1)],
+        [alloc(3, 2, 1864, 0, 5, 0x11A, rv=1), alloc(3, 3, 1992, 5, 6, 0x11B, rv=0), alloc(3, 1, 10680, 11, 60, 0x11C, rv=3)],
+    ]
+    return [0, 5, 3, 8], [17, 301, 42, 503], per_unit
+
+
+def test_rate_unmatch_decode_and_assembly_exact_at_the_other_segment_classes(ctx, port, ref, ref_phy):
+    """test_rate_unmatch_decode_and_assembly_exact's three checks on a plan whose code blocks the batch kernels cut into 2 and 4 segments
+    (full and ragged), under BCJR x 8 and BCJR_BLOCK x 6, at an SNR where some transport blocks pass and some fail.  N_soft of UE
+    category 1: the three-block sizes' soft buffers are limited, the two-block ones' are not."""
+    import openlte_amd as m
+    port.lo_bcjr_n_seg.restype = C.c_uint32
+    n_soft = 250368
+    sfs, cells, per_unit = segment_class_batch()
+    allocs, tx, plan, res = run_cells(ctx, 100, sfs, cells, per_unit, n_soft, 2, 11.0, seed=23,
+                                      decoders=((m.TURBO_BCJR, 8), (m.TURBO_BCJR_BLOCK, 6)))
+    seen, n_pass, n_fail = check_blocks_exact(port, ref, ref_phy, plan, allocs, res, n_soft)
+    classes = {(int(port.lo_bcjr_n_seg(K)), nc, K % 64 != 0) for nc, K, lim in seen}  # (n_seg, C, ragged last segment)
+    print("3GPP segment classes: (C, K, limited) per grant %s, status per grant %s / %s, cb_ok %s / %s"
+          % (seen, list(res[0][0]), list(res[1][0]), list(res[0][2]), list(res[1][2])))
+    assert classes >= {(2, 2, False), (2, 3, False), (4, 2, False), (4, 3, False), (2, 1, True), (4, 1, True)}, classes
+    assert {K for nc, K, lim in seen} >= {4992, 4224, 5376, 4352, 5888, 992, 1120, 1504, 1888, 2016}
+    assert any(lim for nc, K, lim in seen) and not all(lim for nc, K, lim in seen)
     assert n_pass > 0 and n_fail > 0, (n_pass, n_fail)
     plan.close()
 
