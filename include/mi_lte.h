@@ -438,6 +438,49 @@ int      mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *plan, const
 /* stage tap: device pointer to the de-interleaved, descrambled soft bits (int8, 12*12*N_prb*Q_m of them) */
 int      mi_lte_pusch_plan_soft_bits(const mi_lte_pusch_plan *plan, uint32_t alloc, const int8_t **d_e, uint32_t *n_bits);
 
+/* ---------------------------------------------------------------- PUSCH, 3GPP transport-block mode (opt-in)
+ * The uplink as 36.211 / 36.212 specify it rather than as the reference receives it.  The reference's receiver cannot decode what a UE
+ * sends beyond single-block QPSK: its transform pre-decoder (liblte_phy.cc:6627-6660) multiplies the unnormalised backward DFT by
+ * sqrt(M), M = 12 N_prb, where 36.211 5.3.3 needs 1 / sqrt(M), so the de-mapper sees M times the constellation point -- 16QAM and 64QAM
+ * fail and every QPSK soft bit saturates at +-1 -- and ulsch_channel_decode (:12363-12501) handles one code block.  The plans above
+ * reproduce both; a plan of this mode does neither.
+ *
+ * Demodulator: that of the plans above -- DMRS estimate, equaliser, transform pre-decoding, de-mapping, descrambling, the 12-column
+ *   transpose -- with the pre-decoder's output scaled by r = (float)(1.0 / sqrt((double)M)) (one factor; the same kernel otherwise).
+ *   QPSK, 16QAM and 64QAM; mod_type 0 (BPSK) is MI_LTE_ERR_UNSUPPORTED.  N_prb < N_rb_ul and divisible by 2, 3 or 5, as above.
+ * UL-SCH (36.212 5.2.2.1-5.2.2.5, N_L = 1, no control information): CRC24A, segmentation and CRC24B as in 5.1.2 (the PDSCH 3GPP mode's:
+ *   F = 0, C <= 13, every tbs of 36.213 Table 7.1.7.2.1-1), rate matching with N_cb = K_w -- the uplink has no soft-buffer limit --
+ *   k0 = R (2 ceil(K_w / (8 R)) rv + 2), G = 12 * 12 N_prb * Q_m, G' = G / Q_m and E_r as in mi_lte_dlsch_layout.  Without control
+ *   information the channel interleaver (5.2.2.8) is the transpose the demodulator undoes.
+ * Code blocks: the kernels of the PDSCH 3GPP mode (rate un-matching into the int8 layout of mi_lte_turbo_decode_batch, repeats summed
+ *   and saturated to +-127; the BCJR kernels, one launch set per block size; CRC24B, desegmentation, CRC24A).
+ * Decoder: MI_LTE_TURBO_BCJR (default, 8 iterations), MI_LTE_TURBO_BCJR_EARLY or MI_LTE_TURBO_BCJR_BLOCK with the exact interleaver.
+ *   mi_lte_pusch_plan_set_decoder on such a plan: MI_LTE_ERR_UNSUPPORTED for MI_LTE_TURBO_REF, MI_LTE_ERR_INVALID_ARG for qpp_spec = 0 or
+ *   n_iter outside 1..64; on a plan of mi_lte_pusch_plan_create: MI_LTE_ERR_UNSUPPORTED whatever is asked (it stays the reference's chain).
+ * Verdict: d_status[a] = 0 when every block's CRC24B and the transport block's CRC24A pass, else 2.  The output row holds the decoded
+ *   payload (tbs bits) whatever the verdict, one bit per byte or packed (mi_lte_pusch_plan_set_output; a plan of mi_lte_pusch_plan_create
+ *   has the one-bit-per-byte form only: packed != 0 is MI_LTE_ERR_UNSUPPORTED there).  The output stride covers the plan's largest tbs.
+ * What is exact: everything from the int8 soft bits on (pinned to the reference's liblte_phy_rate_unmatch_turbo with channel type
+ *   ULSCH and N_codeblocks = C, to the plain-C BCJR models and to a desegmentation in numpy); the soft bits' half-plane decisions equal
+ *   those of the plans above byte for byte (a positive factor does not move a sign). */
+/* Host arithmetic only: mi_lte_dlsch_layout with an unlimited soft buffer (N_cb = K_w) and K_MIMO = 1 -- that is, with the soft-buffer
+ * configuration {MI_LTE_ULSCH_N_SOFT, MI_LTE_ULSCH_M_HARQ}, whose N_IR / 13 lies far above the largest K_w (18 528) */
+#define MI_LTE_ULSCH_N_SOFT 0xFFFFFFFFu
+#define MI_LTE_ULSCH_M_HARQ 1u
+int mi_lte_ulsch_layout(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t rv, mi_lte_dlsch_layout_t *out);
+/* A plan in this mode: the arguments of mi_lte_pusch_plan_create.  mi_lte_pusch_decode_run, _out_stride, _soft_bits and _destroy work on it
+ * as on any plan.  MI_LTE_ERR_UNSUPPORTED: BPSK, an N_prb without a transform plan, a tbs the segmentation refuses, a unit index past
+ * n_units; MI_LTE_ERR_INVALID_ARG: a resource block outside the carrier.  Every refusal comes before any launch and leaves the context usable. */
+int mi_lte_pusch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
+                                  const uint32_t *h_unit_n_id_cell, uint32_t n_units, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                  mi_lte_pusch_plan **out);
+int mi_lte_pusch_plan_set_decoder(mi_lte_pusch_plan *plan, uint32_t mode, uint32_t n_iter, int qpp_spec);
+int mi_lte_pusch_plan_set_output(mi_lte_pusch_plan *plan, uint32_t packed);
+/* stage taps of a 3GPP plan, valid after a run, with the meanings of mi_lte_pdsch_plan_cb_soft / _cb_ok; MI_LTE_ERR_INVALID_ARG on a plan of
+ * mi_lte_pusch_plan_create */
+int mi_lte_pusch_plan_cb_soft(const mi_lte_pusch_plan *plan, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K);
+int mi_lte_pusch_plan_cb_ok(const mi_lte_pusch_plan *plan, const uint32_t **d_mask);
+
 /* PRACH detection: replaces liblte_phy_detect_prach() (liblte_phy.h:862-868, implementation liblte_phy.cc:3299-3479)
  * for a batch of PRACH occasions (d_occ_start[o] = sample index of the occasion's first cyclic-prefix sample; an
  * occasion spans mi_lte_prach_occasion_samples() samples), preamble formats 0-4 (format 4, the TDD UpPTS preamble of
@@ -953,6 +996,16 @@ int    mi_lte_synth_ul_units_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *u
                                 const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs,
                                 uint32_t n_alloc, const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits,
                                 uint32_t tbs_stride);
+/* UL-SCH transmit side of the PUSCH 3GPP mode (36.212 5.2.2.1-5.2.2.5, the layout of mi_lte_ulsch_layout): CRC24A, segmentation, CRC24B per
+ * block when C > 1, turbo encoding with the exact QPP interleaver, rate matching with N_cb = K_w, concatenation of the blocks' E_r bits.
+ * bits: tbs payload bits, one per byte; e_out: G bits, one per byte (before the channel interleaver). */
+int    mi_lte_ulsch_encode_3gpp(uint32_t tbs, const uint8_t *bits, uint32_t G, uint32_t Q_m, uint32_t rv, uint8_t *e_out);
+/* mi_lte_synth_ul_units_i8 with that encoder: the input of the PUSCH 3GPP plans.  Same arguments; any tbs mi_lte_ulsch_layout accepts, no
+ * BPSK.  A single-block transport block whose interleaver the reference evaluates without overflow gives mi_lte_synth_ul_units_i8's bytes. */
+int    mi_lte_synth_ul_units_3gpp_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units,
+                                     const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs,
+                                     uint32_t n_alloc, const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits,
+                                     uint32_t tbs_stride);
 
 /* n_occ PRACH occasions (format 0-3 preambles per 36.211 5.7.2-5.7.3): preamble h_preamble_idx[o] of the cell's 64,
  * delayed by h_delay[o] samples, through a flat channel + AWGN; mi_lte_synth_prach_len() complex int8 samples each. */

@@ -24,16 +24,34 @@ size_t mi_lte_synth_ul_unit_len(uint32_t fft_size)
     return (30720 / s + 16 + 15) / 16 * 16; // one subframe plus slack for the channel delay
 }
 
-int mi_lte_synth_ul_units_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units, const uint32_t *h_subfr_num,
-                             const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
-                             const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride)
+// UL-SCH transmit side of the PUSCH plans' 3GPP transport-block mode (36.212 5.2.2.1-5.2.2.5, N_L = 1): the inverse of what the plan decodes
+int mi_lte_ulsch_encode_3gpp(uint32_t tbs, const uint8_t *bits, uint32_t G, uint32_t Q_m, uint32_t rv, uint8_t *e_out)
+{
+    const mi_lte_dlsch_cfg unlimited = {MI_LTE_ULSCH_N_SOFT, MI_LTE_ULSCH_M_HARQ}; // (mi_lte_ulsch_layout's: N_cb = K_w)
+    return mi_lte_dlsch_encode_3gpp(tbs, bits, G, Q_m, 1, rv, &unlimited, e_out);
+}
+
+} // extern "C"
+
+// The uplink generator behind mi_lte_synth_ul_units_i8 (spec = false: one code block, the reference's wrapped interleaver -- what the
+// reference-mode plans and the reference itself decode) and mi_lte_synth_ul_units_3gpp_i8 (mi_lte_ulsch_encode_3gpp)
+static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units, const uint32_t *h_subfr_num,
+                          const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                          const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride, bool spec)
 {
     if (!cfg || !ul || !h_subfr_num || !h_n_id_cell || !h_allocs || !chan || !h_iq) return MI_LTE_ERR_INVALID_ARG;
     if (!synth::valid_grid(cfg->fft_size, cfg->N_rb_dl)) return MI_LTE_ERR_INVALID_ARG;
+    auto valid = [&](const mi_lte_pdsch_alloc &al) {
+        if (!spec) return synth::valid_alloc(al, cfg->N_rb_dl);
+        mi_lte_pdsch_alloc one = al;
+        one.tbs = 16; // the grid conditions; the transport block's are the layout's
+        mi_lte_dlsch_layout_t lay;
+        return synth::valid_alloc(one, cfg->N_rb_dl) && al.mod_type != 0 && mi_lte_ulsch_layout(al.tbs, 0, 2, al.rv_idx, &lay) == MI_LTE_OK;
+    };
     for (uint32_t u = 0; u < n_units; u++) {
         if (h_n_id_cell[u] > 503) return MI_LTE_ERR_INVALID_ARG;
         for (uint32_t a = 0; a < n_alloc; a++)
-            if (!synth::valid_alloc(h_allocs[(size_t)u * n_alloc + a], cfg->N_rb_dl) || (h_tx_bits && h_allocs[(size_t)u * n_alloc + a].tbs > tbs_stride))
+            if (!valid(h_allocs[(size_t)u * n_alloc + a]) || (h_tx_bits && h_allocs[(size_t)u * n_alloc + a].tbs > tbs_stride))
                 return MI_LTE_ERR_INVALID_ARG;
     }
     const uint32_t N = cfg->fft_size, sc = 2048 / N, cp0 = 160 / sc, cpe = 144 / sc, N_rb = cfg->N_rb_dl, half = 6 * N_rb, N_sc = 12 * N_rb;
@@ -53,14 +71,21 @@ int mi_lte_synth_ul_units_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, 
             uint32_t       K = 0, f1, f2;
             for (int r = 0; r < LTE_QPP_N_SIZES; r++)
                 if (LTE_QPP_ROWS[r].K >= B) { K = LTE_QPP_ROWS[r].K; break; }
-            if (al.N_prb == 0 || al.N_prb > N_rb || B > 6144 || K != B || !synth::qpp_params(K, &f1, &f2)) return MI_LTE_ERR_UNSUPPORTED;
+            if (al.N_prb == 0 || al.N_prb > N_rb) return MI_LTE_ERR_UNSUPPORTED;
+            if (!spec && (B > 6144 || K != B || !synth::qpp_params(K, &f1, &f2))) return MI_LTE_ERR_UNSUPPORTED;
             // UL-SCH: CRC24A, turbo code, rate matching with N_cb = K_w (36.212 5.2.2.1-5.2.2.5)
-            std::vector<uint8_t> b(K), d(3 * (K + 4)), g(G), h(G), c(G);
+            std::vector<uint8_t> b(spec ? al.tbs : K), g(G), h(G), c(G);
             for (uint32_t i = 0; i < al.tbs; i++) b[i] = (uint8_t)(rng.next() & 1u);
-            synth::crc24a(b.data(), al.tbs, b.data() + al.tbs);
             if (h_tx_bits) memcpy(h_tx_bits + ((size_t)u * n_alloc + a) * tbs_stride, b.data(), al.tbs);
-            synth::turbo_encode(b.data(), K, true, d.data());
-            synth::rate_match(d.data(), K + 4, 0xFFFFFFFFu, al.rv_idx, G, g.data());
+            if (spec) { // segmentation and CRC24B as well, the exact interleaver
+                const int rc = mi_lte_ulsch_encode_3gpp(al.tbs, b.data(), G, Qm, al.rv_idx, g.data());
+                if (rc != MI_LTE_OK) return rc;
+            } else {
+                std::vector<uint8_t> d(3 * (K + 4));
+                synth::crc24a(b.data(), al.tbs, b.data() + al.tbs);
+                synth::turbo_encode(b.data(), K, true, d.data());
+                synth::rate_match(d.data(), K + 4, 0xFFFFFFFFu, al.rv_idx, G, g.data());
+            }
             // channel interleaver without control information (36.212 5.2.2.8): the R' x 12 matrix of Q_m-bit symbols is
             // written row by row and read column by column -> h[(s*M + k)*Q + q] = g[(k*12 + s)*Q + q]
             for (uint32_t s = 0; s < 12; s++)
@@ -151,6 +176,21 @@ int mi_lte_synth_ul_units_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, 
     return MI_LTE_OK;
 }
 
+extern "C" {
+
+int mi_lte_synth_ul_units_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units, const uint32_t *h_subfr_num,
+                             const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                             const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride)
+{
+    return synth_ul_units(cfg, ul, n_units, h_subfr_num, h_n_id_cell, h_allocs, n_alloc, chan, h_iq, h_tx_bits, tbs_stride, false);
+}
+
+int mi_lte_synth_ul_units_3gpp_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units, const uint32_t *h_subfr_num,
+                                  const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                  const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride)
+{
+    return synth_ul_units(cfg, ul, n_units, h_subfr_num, h_n_id_cell, h_allocs, n_alloc, chan, h_iq, h_tx_bits, tbs_stride, true);
+}
 
 // ---- PRACH (36.211 5.7.2-5.7.3): preamble v of root u is x_u((n + C_v) mod 839); its 839-point DFT sits on the PRACH
 // sub-carriers (1.25 kHz spacing) phi + K(k0 + 1/2) + k in natural order; cyclic prefix + sequence (twice for formats 2, 3)

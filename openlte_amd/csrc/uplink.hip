@@ -14,6 +14,10 @@
 //       mixed-radix Stockham transform through LDS.
 //   then the downlink's turbo stage (turbo.hip) with the UL-SCH rate-matching rule (N_cb = K_w).
 //
+// The 3GPP transport-block mode (mi_lte_pusch_plan_create_3gpp, include/mi_lte.h) is the same chain as 36.211 / 36.212 specify it: the
+// pre-decoder's output times 1 / sqrt(M) (36.211 5.3.3; k_pusch_demod<.., SPEC = true>), so that 16QAM and 64QAM de-map and QPSK keeps its
+// soft information, and transport blocks of 1 .. 13 code blocks through dlsch3gpp.hip's kernels with N_cb = K_w (36.212 5.2.2).
+//
 // The DFT sizes are not powers of two and FFTW's operation order is unspecified, so like the downlink FFT
 // this stage is tolerance-checked; everything from the int8 soft bits on is integer-exact.
 #include <algorithm>
@@ -49,7 +53,8 @@ struct DftPass {
 };
 struct PuschShape {
     float    sqrt_M, r_M;
-    uint32_t n_pass, pad;
+    uint32_t n_pass;
+    float    r_sqrt_M; // (float)(1 / sqrt((double)M)): the 3GPP mode's scale (36.211 5.3.3)
     DftPass  pass[MAX_PASSES];
 };
 static_assert(sizeof(PuschShape) == 160, "one row = 40 words");
@@ -201,7 +206,9 @@ __device__ __forceinline__ void dft_pass(const float2 *__restrict__ in, float2 *
 // THREADS = the workgroup's width as a compile-time constant (64 / 128 / 192 / 256): every phase is a loop `o += THREADS` -- with blockDim.x the
 // stride was re-read from the dispatch packet in every iteration of the de-mapper's loop (a store in the body could alias it as far as the
 // compiler knows) -- and the index products are 24-bit multiplies (v_mul_lo_u32 / v_mad_u64_u32 issue at a quarter of the rate)
-template <uint32_t THREADS>
+// SPEC = the 3GPP mode's demodulator (mi_lte_pusch_plan_create_3gpp): the pre-decoder's output scaled by 1 / sqrt(M) as 36.211 5.3.3 has it,
+// where the reference -- and SPEC = false -- multiplies by sqrt(M).  One factor; everything else is the same code.
+template <uint32_t THREADS, bool SPEC = false>
 __attribute__((amdgpu_waves_per_eu(WPE, 8)))
 __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict__ subframes, uint32_t sf_stride,
                                                      const mi_lte_pdsch_alloc *__restrict__ allocs, const PuschDesc *__restrict__ desc,
@@ -268,7 +275,8 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
     }
     __syncthreads();
 
-    const float sqrt_M = sh.sqrt_M; // liblte_phy.cc:6644 (integer argument -> double sqrt, stored to float: formed on the host)
+    // liblte_phy.cc:6644 (integer argument -> double sqrt, stored to float: formed on the host), or its reciprocal for the 3GPP mode
+    const float scale = SPEC ? sh.r_sqrt_M : sh.sqrt_M;
     int8_t     *e      = e_base + (size_t)e_off[a_idx] * 64; // 64-byte units
 
     for (uint32_t s0 = 0; s0 < 12; s0 += S_par) { // S_par data symbols at a time (all 12 when they fit in LDS)
@@ -330,7 +338,7 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
             const uint32_t k = S == 12 ? __umul24(o, 43691u) >> 19 : quot(o, r_S_par), sy = o - __umul24(k, S), s = s0 + sy; // neighbouring threads write neighbouring bytes of e
             const float2   x = src[__umul24(sy, M_max) + k];
             int8_t         b[6] = {0, 0, 0, 0, 0, 0};
-            demap_symbol(sqrt_M * x.x, sqrt_M * x.y, MOD, b);
+            demap_symbol(scale * x.x, scale * x.y, MOD, b);
             const uint32_t n0 = (__umul24(s, M) + k) * QM, w = n0 >> 5, sh = n0 & 31;
             const uint32_t c  = __builtin_amdgcn_alignbit(cw[w + 1], cw[w], sh);
             int8_t        *ob = e + (__umul24(k, 12u) + s) * QM; // (32-bit offset: an allocation's soft bits are at most 12 * 1320 * 6 bytes)
@@ -451,7 +459,13 @@ struct mi_lte_pusch_plan {
     PuschDesc    *d_desc = nullptr;
     float        *d_dmrs = nullptr;
     std::vector<uint32_t> h_e_len;
+    // 3GPP transport-block mode (mi_lte_pusch_plan_create_3gpp): the spec-normalised demodulator, dlsch3gpp.hip's code blocks and a BCJR decoder
+    MiDlsch3     *g3 = nullptr;
+    uint32_t      decoder = MI_LTE_TURBO_BCJR, n_iter = 8, max_tbs = 0;
 };
+
+// UL-SCH rate matching has no soft-buffer limit (36.212 5.2.2.5: N_cb = K_w).  As a DL-SCH soft-buffer configuration: an N_IR no block reaches
+static const mi_lte_dlsch_cfg ULSCH_AS_DLSCH = {MI_LTE_ULSCH_N_SOFT, MI_LTE_ULSCH_M_HARQ};
 
 // the float next above or equal to 1 / d (see quot)
 static float recip_up(uint32_t d)
@@ -472,6 +486,7 @@ static int pusch_shapes(mi_lte_ctx *ctx)
         PuschShape    &sh = tab[n];
         const uint32_t M  = 12 * n;
         sh.sqrt_M = (float)sqrt((double)M);
+        sh.r_sqrt_M = (float)(1.0 / sqrt((double)M));
         sh.r_M    = recip_up(M);
         uint32_t rem = M, Ns = 1;
         while (rem > 1) {
@@ -499,11 +514,12 @@ static int pusch_shapes(mi_lte_ctx *ctx)
 }
 
 // h_dmrs (optional): caller-supplied reference signals, 4 x 12*N_prb floats per allocation back to back -- the
-// per-call host form passes the arrays liblte_phy_ul_init left in the caller's LIBLTE_PHY_STRUCT
+// per-call host form passes the arrays liblte_phy_ul_init left in the caller's LIBLTE_PHY_STRUCT.
+// spec: a plan in the 3GPP transport-block mode -- the transport block's conditions are mi_lte_ulsch_layout's, its code blocks dlsch3gpp.hip's
 extern "C" void mi_lte_pusch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl);
-int mi_pusch_plan_create_impl(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
-                              const uint32_t *h_unit_n_id_cell, uint32_t n_units, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
-                              const float *h_dmrs, mi_lte_pusch_plan **out)
+static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
+                             const uint32_t *h_unit_n_id_cell, uint32_t n_units, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                             const float *h_dmrs, mi_lte_pusch_plan **out, bool spec)
 {
     if (!ctx || !cfg || (!ul && !h_dmrs) || !h_unit_subfr_num || !h_unit_n_id_cell || !h_allocs || !out || n_alloc == 0 || n_units == 0)
         return MI_LTE_ERR_INVALID_ARG;
@@ -520,12 +536,17 @@ int mi_pusch_plan_create_impl(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const m
     pl->h_e_len.resize(n_alloc);
     for (uint32_t a = 0; a < n_alloc; a++) {
         const mi_lte_pdsch_alloc &al = h_allocs[a];
-        const int r = mi_qpp_row_at_least(al.tbs + 24);
+        const int r = spec ? 0 : mi_qpp_row_at_least(al.tbs + 24);
         // N_prb the reference has a transform pre-decoding plan for (liblte_phy.cc:2360-2377)
         const bool planned = al.N_prb > 0 && al.N_prb < cfg->N_rb_dl && (al.N_prb % 2 == 0 || al.N_prb % 3 == 0 || al.N_prb % 5 == 0);
         if (r < 0 || !planned || al.mod_type > 3 || al.unit >= n_units) {
             ctx->err = "PUSCH allocation outside the envelope (one code block; N_prb < N_rb_ul and divisible by 2, 3 or 5) or malformed";
             return MI_LTE_ERR_UNSUPPORTED;
+        }
+        if (spec) {
+            mi_lte_dlsch_layout_t lay;
+            const int rc = al.mod_type == 0 ? MI_LTE_ERR_UNSUPPORTED : mi_lte_ulsch_layout(al.tbs, 0, 2, al.rv_idx & 3u, &lay);
+            if (rc != MI_LTE_OK) { ctx->err = "PUSCH allocation outside the 3GPP transport-block mode (BPSK, F != 0 or tbs > 75376)"; return rc; }
         }
         for (uint32_t sl = 0; sl < 2; sl++) // a resource block past the carrier would be read out of the neighbouring symbol row
             for (uint32_t i = 0; i < al.N_prb; i++)
@@ -561,9 +582,14 @@ int mi_pusch_plan_create_impl(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const m
     if (pl->words_max > 4096) { ctx->err = "allocation larger than the scrambling table"; return MI_LTE_ERR_UNSUPPORTED; }
     pl->core.e_bytes    = mi_plan_soft_layout(pl->h_e_len.data(), n_alloc, pl->core.h_e_off);
     pl->core.out_stride = mi_out_stride(max_tbs, false);
-    std::vector<uint32_t> cb_alloc;
-    mi_plan_group(row.data(), nullptr, pl->h_e_len.data(), n_alloc, pl->core.groups, cb_alloc);
+    pl->max_tbs         = max_tbs;
+    std::vector<uint32_t> cb_alloc(n_alloc, 0u);
+    if (!spec) mi_plan_group(row.data(), nullptr, pl->h_e_len.data(), n_alloc, pl->core.groups, cb_alloc);
     MI_HIP_CHECK(ctx, pl->core.allocate(n_alloc, pl->core.e_bytes));
+    if (spec) {
+        const int rc = mi_dlsch3_create(ctx, &ULSCH_AS_DLSCH, h_allocs, n_alloc, &pl->g3);
+        if (rc != MI_LTE_OK) return rc;
+    }
     MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_desc, sizeof(PuschDesc) * n_alloc));
     MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_dmrs, sizeof(float) * std::max<size_t>(dmrs.size(), 1)));
     MI_H2D(ctx, pl->core.d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
@@ -577,6 +603,13 @@ int mi_pusch_plan_create_impl(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const m
     return MI_LTE_OK;
 }
 
+int mi_pusch_plan_create_impl(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
+                              const uint32_t *h_unit_n_id_cell, uint32_t n_units, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                              const float *h_dmrs, mi_lte_pusch_plan **out)
+{
+    return pusch_plan_create(ctx, cfg, ul, h_unit_subfr_num, h_unit_n_id_cell, n_units, h_allocs, n_alloc, h_dmrs, out, /*spec=*/false);
+}
+
 extern "C" {
 
 int mi_lte_pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
@@ -585,6 +618,53 @@ int mi_lte_pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
 {
     if (!ul) return MI_LTE_ERR_INVALID_ARG;
     return mi_pusch_plan_create_impl(ctx, cfg, ul, h_unit_subfr_num, h_unit_n_id_cell, n_units, h_allocs, n_alloc, nullptr, out);
+}
+
+int mi_lte_ulsch_layout(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t rv, mi_lte_dlsch_layout_t *out)
+{
+    return mi_lte_dlsch_layout(tbs, G, Q_m, 1, rv, &ULSCH_AS_DLSCH, out);
+}
+
+int mi_lte_pusch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
+                                  const uint32_t *h_unit_n_id_cell, uint32_t n_units, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                  mi_lte_pusch_plan **out)
+{
+    if (!ul) return MI_LTE_ERR_INVALID_ARG;
+    return pusch_plan_create(ctx, cfg, ul, h_unit_subfr_num, h_unit_n_id_cell, n_units, h_allocs, n_alloc, nullptr, out, /*spec=*/true);
+}
+
+int mi_lte_pusch_plan_set_decoder(mi_lte_pusch_plan *pl, uint32_t mode, uint32_t n_iter, int qpp_spec)
+{
+    if (!pl) return MI_LTE_ERR_INVALID_ARG;
+    if (!pl->g3) return MI_LTE_ERR_UNSUPPORTED; // a reference-mode plan stays what it is: the REF decoder
+    const bool bcjr = mi_is_bcjr(mode);
+    if (!(mode == MI_LTE_TURBO_REF || bcjr) || (bcjr && (n_iter == 0 || n_iter > 64))) return MI_LTE_ERR_INVALID_ARG;
+    if (mode == MI_LTE_TURBO_REF) return MI_LTE_ERR_UNSUPPORTED;
+    if (!qpp_spec) return MI_LTE_ERR_INVALID_ARG;
+    pl->decoder = mode; pl->n_iter = n_iter;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_set_output(mi_lte_pusch_plan *pl, uint32_t packed)
+{
+    if (!pl) return MI_LTE_ERR_INVALID_ARG;
+    if (!pl->g3) return packed ? MI_LTE_ERR_UNSUPPORTED : MI_LTE_OK;
+    pl->core.packed     = packed ? 1u : 0u;
+    pl->core.out_stride = mi_out_stride(pl->max_tbs, packed != 0);
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_cb_soft(const mi_lte_pusch_plan *pl, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K)
+{
+    if (!pl || !pl->g3) return MI_LTE_ERR_INVALID_ARG;
+    return mi_dlsch3_cb_soft(pl->g3, alloc, d_blocks, C, K);
+}
+
+int mi_lte_pusch_plan_cb_ok(const mi_lte_pusch_plan *pl, const uint32_t **d_mask)
+{
+    if (!pl || !pl->g3 || !d_mask) return MI_LTE_ERR_INVALID_ARG;
+    *d_mask = mi_dlsch3_cb_ok(pl->g3);
+    return MI_LTE_OK;
 }
 
 void mi_lte_pusch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl)
@@ -597,6 +677,7 @@ void mi_lte_pusch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl)
     pl->core.release();
     (void)hipFree(pl->d_desc);
     (void)hipFree(pl->d_dmrs);
+    mi_dlsch3_free(pl->g3);
     delete pl;
 }
 
@@ -632,12 +713,20 @@ int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float 
         const int t = atoi(ev);
         if (t >= 64 && t <= (int)PUSCH_THREADS && t % 64 == 0) threads = (uint32_t)t;
     }
-#define MI_PUSCH_LAUNCH(T) MI_LAUNCH(ctx, "k_pusch_demod", k_pusch_demod<T>, dim3(pl->core.n_alloc), dim3(T), lds, d_subframes, (uint32_t)mi_lte_ul_subframe_floats(), \
+#define MI_PUSCH_LAUNCH_V(T, SPEC) MI_LAUNCH(ctx, "k_pusch_demod", (k_pusch_demod<T, SPEC>), dim3(pl->core.n_alloc), dim3(T), lds, d_subframes, (uint32_t)mi_lte_ul_subframe_floats(), \
                                     pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->M_max, S_par, recip_up(S_par), \
                                     static_cast<const PuschShape *>(ctx->d_pusch_shapes))
+#define MI_PUSCH_LAUNCH(T) do { if (pl->g3) MI_PUSCH_LAUNCH_V(T, true); else MI_PUSCH_LAUNCH_V(T, false); } while (0)
     if (threads == 64) MI_PUSCH_LAUNCH(64); else if (threads == 128) MI_PUSCH_LAUNCH(128); else if (threads == 192) MI_PUSCH_LAUNCH(192); else MI_PUSCH_LAUNCH(256);
 #undef MI_PUSCH_LAUNCH
+#undef MI_PUSCH_LAUNCH_V
     MI_HIP_CHECK(ctx, hipGetLastError());
+    if (pl->g3) { // 3GPP mode: the code blocks of dlsch3gpp.hip, no HARQ pool bound
+        if ((rc = mi_dlsch3_run(ctx, pl->g3, nullptr, nullptr, pl->core.io(d_out_bits, d_status, /*ul=*/true), pl->decoder, pl->n_iter)) != MI_LTE_OK) return rc;
+        const size_t at = ctx->last_kernels.find(','); // (mi_dlsch3_run lists the downlink's demodulator in front of its own kernels)
+        ctx->last_kernels.replace(0, at == std::string::npos ? 0 : at, "k_pusch_demod:1");
+        return MI_LTE_OK;
+    }
     // several block sizes (the UEs of a subframe rarely share one): one launch set over all of them, as in the PDSCH chain
     rc = mi_turbo_ref_dispatch(ctx, pl->core.groups.data(), (uint32_t)pl->core.groups.size(), pl->core.io(d_out_bits, d_status, /*ul=*/true), &pl->core.multi);
     if (rc != MI_LTE_OK) return rc;

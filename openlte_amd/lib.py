@@ -61,6 +61,15 @@ def dlsch_layout(tbs, G, Q_m, tx_mode=1, rv=0, n_soft=1237248, m_dl_harq=8):
     return {"C": out.C, "K": out.K, "B": out.B, "N_cb": out.N_cb, "k0": out.k0, "E": list(out.E[:out.C]), "off": list(out.off[:out.C])}
 
 
+def ulsch_layout(tbs, G, Q_m, rv=0):
+    """mi_lte_ulsch_layout (host arithmetic): dlsch_layout for the uplink -- no soft-buffer limit (N_cb = K_w).  The same dict."""
+    out = DlschLayout()
+    rc = load_library().mi_lte_ulsch_layout(tbs, G, Q_m, rv, C.byref(out))
+    if rc != 0:
+        raise MiLteError("mi_lte_ulsch_layout(%d, %d, %d) failed: %d" % (tbs, G, Q_m, rc), rc)
+    return {"C": out.C, "K": out.K, "B": out.B, "N_cb": out.N_cb, "k0": out.k0, "E": list(out.E[:out.C]), "off": list(out.off[:out.C])}
+
+
 HARQ_NONE, HARQ_NEW_DATA = 0xFFFFFFFF, 1
 
 
@@ -261,6 +270,12 @@ def load_library():
     L.mi_lte_pusch_plan_out_stride.restype = u32
     L.mi_lte_pusch_decode_run.argtypes = [vp, vp, vp, vp, vp]
     L.mi_lte_pusch_plan_soft_bits.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32)]
+    L.mi_lte_pusch_plan_create_3gpp.argtypes = L.mi_lte_pusch_plan_create.argtypes
+    L.mi_lte_pusch_plan_set_decoder.argtypes = [vp, u32, u32, C.c_int]
+    L.mi_lte_pusch_plan_set_output.argtypes = [vp, u32]
+    L.mi_lte_pusch_plan_cb_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
+    L.mi_lte_pusch_plan_cb_ok.argtypes = [vp, C.POINTER(vp)]
+    L.mi_lte_ulsch_layout.argtypes = [u32, u32, u32, u32, C.POINTER(DlschLayout)]
     L.mi_lte_prach_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), C.POINTER(vp)]
     L.mi_lte_prach_plan_create_roots.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), f32p, f32p, u32, C.POINTER(vp)]
     L.mi_lte_prach_plan_destroy.argtypes = [vp, vp]
@@ -583,15 +598,16 @@ class DlPipeline:
 
 
 class PuschPlan:
-    """mi_lte_pusch_plan: PUSCH allocations (one per scheduled UE) over a batch of uplink subframe units."""
+    """mi_lte_pusch_plan: PUSCH allocations (one per scheduled UE) over a batch of uplink subframe units.  spec: a plan in the 3GPP
+    transport-block mode (mi_lte_pusch_plan_create_3gpp)."""
 
-    def __init__(self, ctx, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs):
-        self.ctx, self.n_alloc = ctx, len(allocs)
+    def __init__(self, ctx, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, spec=False):
+        self.ctx, self.n_alloc, self.packed = ctx, len(allocs), False
         arr = (PdschAlloc * len(allocs))(*allocs)
         h = C.c_void_p()
         sf, cell = np.ascontiguousarray(unit_subfr_num, np.uint32), np.ascontiguousarray(unit_n_id_cell, np.uint32)
-        ctx._check(ctx.L.mi_lte_pusch_plan_create(ctx.h, C.byref(cfg), C.byref(ulcfg), sf, cell, len(sf), C.cast(arr, C.c_void_p),
-                                                  len(allocs), C.byref(h)))
+        create = ctx.L.mi_lte_pusch_plan_create_3gpp if spec else ctx.L.mi_lte_pusch_plan_create
+        ctx._check(create(ctx.h, C.byref(cfg), C.byref(ulcfg), sf, cell, len(sf), C.cast(arr, C.c_void_p), len(allocs), C.byref(h)))
         self.h = h
         self.out_stride = ctx.L.mi_lte_pusch_plan_out_stride(h)
         self.tbs = [a.tbs for a in allocs]
@@ -608,6 +624,8 @@ class PuschPlan:
             self.run_dev(d_subframes, d_out, d_st)
             st = d_st.download(np.int32)
             bits = d_out.download(np.uint8).reshape(self.n_alloc, self.out_stride)
+            if self.packed:  # back to one bit per byte for the caller
+                return st, [np.unpackbits(bits[a, :(self.tbs[a] + 7) // 8])[:self.tbs[a]] for a in range(self.n_alloc)]
             return st, [bits[a, :self.tbs[a]] for a in range(self.n_alloc)]
         finally:
             d_out.free()
@@ -619,6 +637,32 @@ class PuschPlan:
         self.ctx._check(self.ctx.L.mi_lte_pusch_plan_soft_bits(self.h, alloc, C.byref(pe), C.byref(n)))
         out = np.empty(int(n.value), np.int8)
         self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, pe.value, out.nbytes))
+        return out
+
+    def set_decoder(self, mode, n_iter=8, qpp_spec=1):
+        """3GPP mode: TURBO_BCJR (default, 8 iterations), TURBO_BCJR_EARLY or TURBO_BCJR_BLOCK, exact interleaver."""
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_set_decoder(self.h, mode, n_iter, qpp_spec))
+
+    def set_packed(self, packed=True):
+        """3GPP mode: eight bits per byte (first bit in the most significant position) instead of one; changes out_stride."""
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_set_output(self.h, 1 if packed else 0))
+        self.packed = bool(packed)
+        self.out_stride = self.ctx.L.mi_lte_pusch_plan_out_stride(self.h)
+
+    def cb_soft(self, alloc):
+        """3GPP mode, after a run: the C rate-un-matched code blocks of one allocation, int8 [C, 3 (K + 4)] (stage tap)."""
+        p, nc, k = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_cb_soft(self.h, alloc, C.byref(p), C.byref(nc), C.byref(k)))
+        out = np.empty((nc.value, 3 * (k.value + 4)), np.int8)
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
+        return out
+
+    def cb_ok(self):
+        """3GPP mode, after a run: uint32 [n_alloc], bit r set when code block r's CRC24B passed (one block: bit 0 = the CRC24A verdict)."""
+        p = C.c_void_p()
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_cb_ok(self.h, C.byref(p)))
+        out = np.empty(self.n_alloc, np.uint32)
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
         return out
 
     def close(self):
@@ -988,6 +1032,11 @@ class Context:
 
     def pusch_plan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs):
         return PuschPlan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs)
+
+    def pusch_plan_3gpp(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs):
+        """A PUSCH plan in the 3GPP transport-block mode: the spec-normalised demodulator (QPSK / 16QAM / 64QAM), 36.212 segmentation (any tbs
+        of Table 7.1.7.2.1-1), BCJR x 8 with the exact interleaver by default."""
+        return PuschPlan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, spec=True)
 
     # ---- PDSCH ------------------------------------------------------------------------------
     def pdsch_plan(self, cfg, n_pdcch_symbs, allocs):

@@ -38,6 +38,8 @@ def _lib():
         L.mi_lte_synth_ul_unit_len.restype = C.c_size_t
         L.mi_lte_synth_ul_units_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(UlCfg), C.c_uint32, _u32p, _u32p, C.c_void_p, C.c_uint32,
                                                C.POINTER(SynthChannel), _i8p, _u8p, C.c_uint32]
+        L.mi_lte_synth_ul_units_3gpp_i8.argtypes = L.mi_lte_synth_ul_units_i8.argtypes
+        L.mi_lte_ulsch_encode_3gpp.argtypes = [C.c_uint32, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, _u8p]
         L.mi_lte_synth_prach_len.argtypes = [C.c_uint32, C.c_uint32]
         L.mi_lte_synth_prach_len.restype = C.c_size_t
         L.mi_lte_synth_prach_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(PrachCfg), C.c_uint32, _u32p, _u32p, C.POINTER(SynthChannel), _i8p]
@@ -134,9 +136,9 @@ def ul_unit_len(fft_size=2048):
     return int(_lib().mi_lte_synth_ul_unit_len(fft_size))
 
 
-def ul_units(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, gain=(0.5, 1.5), max_delay=4, snr_db=30.0, peak=100.0, seed=1):
+def ul_units(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, gain=(0.5, 1.5), max_delay=4, snr_db=30.0, peak=100.0, seed=1, spec=False):
     """Synthesise len(subfr_num) uplink subframe units, n_alloc PUSCH transmissions each (allocs unit-major).
-    Returns (iq int8 [n, ul_unit_len, 2], tx_bits uint8 [n, n_alloc, max_tbs])."""
+    Returns (iq int8 [n, ul_unit_len, 2], tx_bits uint8 [n, n_alloc, max_tbs]).  spec: ul_units_3gpp."""
     n = len(subfr_num)
     ul = ul_unit_len(cfg.fft_size)
     iq = np.zeros((n, ul, 2), np.int8)
@@ -144,12 +146,27 @@ def ul_units(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, gain=(0.5, 1.5),
     tx = np.zeros((n, max(n_alloc, 1), max_tbs), np.uint8)
     arr = (PdschAlloc * max(len(allocs), 1))(*allocs)
     ch = SynthChannel(gain[0], gain[1], float(max_delay), float(snr_db), float(peak), int(seed))
-    rc = _lib().mi_lte_synth_ul_units_i8(C.byref(cfg), C.byref(ulcfg), n, np.ascontiguousarray(subfr_num, np.uint32),
-                                         np.ascontiguousarray(n_id_cell, np.uint32), C.cast(arr, C.c_void_p), n_alloc,
-                                         C.byref(ch), iq, tx, max_tbs)
+    fn = _lib().mi_lte_synth_ul_units_3gpp_i8 if spec else _lib().mi_lte_synth_ul_units_i8
+    rc = fn(C.byref(cfg), C.byref(ulcfg), n, np.ascontiguousarray(subfr_num, np.uint32), np.ascontiguousarray(n_id_cell, np.uint32),
+            C.cast(arr, C.c_void_p), n_alloc, C.byref(ch), iq, tx, max_tbs)
     if rc != 0:
-        raise MiLteError("mi_lte_synth_ul_units_i8 failed: %d" % rc)
+        raise MiLteError("mi_lte_synth_ul_units%s_i8 failed: %d" % ("_3gpp" if spec else "", rc), rc)
     return iq, tx
+
+
+def ul_units_3gpp(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, **chan):
+    """ul_units with the 3GPP UL-SCH transmitter (mi_lte_synth_ul_units_3gpp_i8): any tbs of Table 7.1.7.2.1-1, the exact interleaver."""
+    return ul_units(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, spec=True, **chan)
+
+
+def ulsch_encode_3gpp(bits, G, Q_m, rv=0):
+    """mi_lte_ulsch_encode_3gpp: the G rate-matched bits (one per byte, before the channel interleaver) of the transport block `bits`."""
+    bits = np.ascontiguousarray(bits, np.uint8)
+    e = np.zeros(max(G, 1), np.uint8)
+    rc = _lib().mi_lte_ulsch_encode_3gpp(len(bits), bits, G, Q_m, rv, e)
+    if rc != 0:
+        raise MiLteError("mi_lte_ulsch_encode_3gpp failed: %d" % rc, rc)
+    return e[:G]
 
 
 def prach_occasions(cfg, prach_cfg, preamble_idx, delay, gain=(0.5, 1.5), snr_db=20.0, peak=100.0, seed=1):

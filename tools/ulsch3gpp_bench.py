@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""The PUSCH plans' 3GPP transport-block mode at full load: 2 048 uplink subframe units of a 20 MHz cell, each with one 99-PRB 64QAM grant of
+TBS 73 712 (13 code blocks of K = 5696: 26 624 blocks), BCJR x 8 with the exact interleaver.  Reports the plan's run (demodulation + rate
+un-matching + decode + finish; the front end runs once before) in ms and information Gbit/s, the per-kernel split, next to it
+mi_lte_turbo_decode_batch BCJR x 8 on the same 26 624 rate-un-matched blocks (the plan's cb_soft tap): the decode alone -- and k_pusch_demod's
+time in both variants from the same process: the 3GPP plan's and a reference-mode plan's over the same grids with one-block QPSK transport
+blocks on the same 99 PRB (the reference-mode envelope; the demodulator's work does not depend on the transport block).
+
+    python tools/ulsch3gpp_bench.py [--units 2048] [--steps 10] [--warmup 2]
+Prints one JSON line last."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import openlte_amd as m  # noqa: E402
+from openlte_amd import synth  # noqa: E402
+
+TBS, N_PRB = 73712, 99
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--units", type=int, default=2048)
+    ap.add_argument("--unique", type=int, default=10, help="distinct synthesised subframes (subframe numbers 0..9), repeated over the units")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    args = ap.parse_args()
+    ctx = m.Context(0)
+    cfg, ul = m.DlCfg(2048, 100, 1, m.IQ_I8), m.UlCfg(3, 0, 0, 2, 1)
+    nu, n, cell = args.unique, args.units, 42
+    prbs = list(range(N_PRB))
+    sfs_u = list(range(nu))
+    iq, tx = synth.ul_units_3gpp(cfg, ul, sfs_u, [cell] * nu, [m.make_alloc(i, 3, TBS, prbs, 0x100 + i) for i in range(nu)], 1, snr_db=30.0,
+                                 max_delay=3, seed=11)
+    ulen = iq.shape[1]
+    sfs = [sfs_u[u % nu] for u in range(n)]
+    d_iq = ctx.to_device(iq.reshape(-1, 2))
+    d_start = ctx.to_device(((np.arange(n) % nu) * ulen).astype(np.uint64))  # unit u reads the capture of distinct subframe u % unique
+    d_sub = ctx.alloc(n * ctx.ul_subframe_floats() * 4)
+    ctx.ul_frontend_dev(cfg, d_iq, None, d_start, n, d_sub)
+    plan = ctx.pusch_plan_3gpp(cfg, ul, sfs, [cell] * n, [m.make_alloc(u, 3, TBS, prbs, 0x100 + u % nu) for u in range(n)])
+    # the same grids, the same 99 PRB and 64QAM de-mapping through the reference-mode demodulator: a one-block transport block (its decode fails, which
+    # is not what is timed)
+    plan_ref = ctx.pusch_plan(cfg, ul, sfs, [cell] * n, [m.make_alloc(u, 3, 6120, prbs, 0x100 + u % nu) for u in range(n)])
+    d_out, d_st = ctx.alloc(n * plan.out_stride), ctx.alloc(4 * n)
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        ctx.sync()
+        ctx.timer_start()
+        for _ in range(args.steps):
+            fn()
+        return ctx.timer_stop() / args.steps
+
+    def profiled(p):
+        ctx.profile(True)
+        p.run_dev(d_sub, d_out, d_st)
+        ctx.sync()
+        rep = {k: round(ms, 4) for k, (nl, ms) in sorted(ctx.profile_report().items(), key=lambda kv: -kv[1][1])}
+        ctx.profile(False)
+        return rep
+
+    ms_plan = timed(lambda: plan.run_dev(d_sub, d_out, d_st))
+    st = d_st.download(np.int32)
+    bits = d_out.download(np.uint8).reshape(n, plan.out_stride)
+    tx_ok = all((bits[u, :TBS] == tx[u % nu, 0, :TBS]).all() for u in range(nu))
+    split = profiled(plan)
+    demod_ms = {"3gpp": [], "reference": []}
+    for _ in range(3):  # alternated
+        demod_ms["3gpp"].append(profiled(plan)["k_pusch_demod"])
+        demod_ms["reference"].append(profiled(plan_ref)["k_pusch_demod"])
+
+    p, nc, K = C.c_void_p(), C.c_uint32(), C.c_uint32()
+    ctx._check(ctx.L.mi_lte_pusch_plan_cb_soft(plan.h, 0, C.byref(p), C.byref(nc), C.byref(K)))
+    n_cb = n * nc.value
+    d_c = ctx.alloc(n_cb * K.value)
+    ms_dec = timed(lambda: ctx._check(ctx.L.mi_lte_turbo_decode_batch(ctx.h, p, m.SOFT_I8, K.value, n_cb, m.TURBO_BCJR, 8, 1, d_c.ptr)))
+    info = n * TBS
+    res = {"workload": "ulsch3gpp", "units": n, "tbs": TBS, "n_prb": N_PRB, "code_blocks": n_cb, "K": K.value, "decoder": "bcjr x8, exact interleaver",
+           "steps": args.steps, "warmup": args.warmup, "plan_ms": round(ms_plan, 3), "plan_info_gbit_per_s": round(info / ms_plan / 1e6, 3),
+           "decode_batch_ms": round(ms_dec, 3), "decode_batch_info_gbit_per_s": round(info / ms_dec / 1e6, 3),
+           "plan_rate_vs_decode_batch": round(ms_dec / ms_plan, 4), "plan_kernel_ms": split, "k_pusch_demod_ms": demod_ms,
+           "status_ok": int((st == 0).sum()), "distinct_units_equal_tx": bool(tx_ok), "device": ctx.device_name}
+    print("3GPP PUSCH plan: %.3f ms per run of %d units (%.2f Gbit/s information), decode_batch alone %.3f ms (%.2f Gbit/s): %.1f %%"
+          % (ms_plan, n, res["plan_info_gbit_per_s"], ms_dec, res["decode_batch_info_gbit_per_s"], 100 * res["plan_rate_vs_decode_batch"]))
+    print("k_pusch_demod, ms per run: 3GPP variant %s, reference variant %s" % (demod_ms["3gpp"], demod_ms["reference"]))
+    print(json.dumps(res))
+    plan.close()
+    plan_ref.close()
+    ctx.close()
+    return 0 if (st == 0).all() and tx_ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
