@@ -447,7 +447,8 @@ int      mi_lte_pusch_plan_soft_bits(const mi_lte_pusch_plan *plan, uint32_t all
  *
  * Demodulator: that of the plans above -- DMRS estimate, equaliser, transform pre-decoding, de-mapping, descrambling, the 12-column
  *   transpose -- with the pre-decoder's output scaled by r = (float)(1.0 / sqrt((double)M)) (one factor; the same kernel otherwise).
- *   QPSK, 16QAM and 64QAM; mod_type 0 (BPSK) is MI_LTE_ERR_UNSUPPORTED.  N_prb < N_rb_ul and divisible by 2, 3 or 5, as above.
+ *   QPSK, 16QAM and 64QAM; mod_type 0 (BPSK) is MI_LTE_ERR_UNSUPPORTED.  N_prb < N_rb_ul and divisible by 2, 3 or 5, as above, or 1
+ *   (M = 12, a size 36.211 5.3.3 allows and the reference has no plan for).
  * UL-SCH (36.212 5.2.2.1-5.2.2.5, N_L = 1, no control information): CRC24A, segmentation and CRC24B as in 5.1.2 (the PDSCH 3GPP mode's:
  *   F = 0, C <= 13, every tbs of 36.213 Table 7.1.7.2.1-1), rate matching with N_cb = K_w -- the uplink has no soft-buffer limit --
  *   k0 = R (2 ceil(K_w / (8 R)) rv + 2), G = 12 * 12 N_prb * Q_m, G' = G / Q_m and E_r as in mi_lte_dlsch_layout.  Without control
@@ -480,6 +481,61 @@ int mi_lte_pusch_plan_set_output(mi_lte_pusch_plan *plan, uint32_t packed);
  * mi_lte_pusch_plan_create */
 int mi_lte_pusch_plan_cb_soft(const mi_lte_pusch_plan *plan, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K);
 int mi_lte_pusch_plan_cb_ok(const mi_lte_pusch_plan *plan, const uint32_t **d_mask);
+
+/* ---------------------------------------------------------------- control information on PUSCH in the 3GPP mode (opt-in)
+ * A UE that holds an uplink grant sends its HARQ-ACK, rank indication and CQI inside that PUSCH (36.212 5.2.2.6-5.2.2.8), which changes
+ * the channel interleaver from a transpose and G from 12 * 12 N_prb * Q_m.  N_L = 1, normal prefix, no SRS (N_symb = 12), FDD (no ACK
+ * bundling).  The interleaver matrix has M = 12 N_prb rows and 12 columns of Q_m-bit cells; cell (r, c) is the demodulator's soft-bit
+ * group at byte (r * 12 + c) * Q_m (mi_lte_pusch_plan_soft_bits, unchanged) and bits (c * M + r) * Q_m .. of the scrambled sequence.
+ *   RI  (5.2.2.8): symbol i = 0 .. Qp_ri - 1 in cell (M - 1 - i / 4, col), col walking 1, 10, 7, 4 (column set {1, 4, 7, 10}).
+ *   CQI then data (5.2.2.7, 5.2.2.8): q_0 .. q_(Q_cqi - 1) | f_0 .. f_(G - 1) written Q_m bits per cell row by row, skipping RI cells:
+ *        G = Q_m (12 M - Qp_ri) - Q_cqi.
+ *   ACK (5.2.2.8): symbol i = 0 .. Qp_ack - 1 in cell (M - 1 - i / 4, col), col walking 2, 9, 8, 3 (column set {2, 3, 8, 9}); it
+ *        overwrites the data or CQI symbol of that cell.
+ *   ACK / RI symbols (5.2.2.6, tables 5.2.2.6-1 .. -4): O = 1: [o0 y x .. x]; O = 2: w = (o0, o1, o0 ^ o1), symbol n carries
+ *        [w[2n mod 3] w[(2n + 1) mod 3] x .. x].
+ *   Scrambling (36.211 5.3.1): x -> 1, y -> the previous scrambled bit, every other bit b ^ c(i).
+ * CQI is an opaque run of Q_cqi coded bits: its block / convolutional code (5.2.2.6.4) is the caller's on both sides. */
+typedef struct {
+    uint8_t  O_ack, O_ri;   /* information bits: 0 (none), 1 or 2 */
+    uint16_t Qp_ack, Qp_ri; /* coded symbols Q' (<= 4 M each) */
+    uint32_t Q_cqi;         /* coded CQI bits, a multiple of Q_m */
+} mi_lte_ulsch_uci;         /* all zero: no control information */
+/* Q' of 36.212 5.2.2.6: min(ceil(O' * M_sc_initial * N_symb_initial * beta / sum_K_r), cap) in 64-bit integers, beta = beta_x8 / 8 (every
+ * offset of 36.213 tables 8.6.3-1 .. -3 is a multiple of 1 / 8).  kind: MI_LTE_UCI_ACK / _RI (cap 4 M) or _CQI (cap 12 M - Qp_ri, and
+ * O' = O + 8, the CRC, above 11 bits); M = 12 N_prb of the present subframe; sum_K_r: C * K of mi_lte_ulsch_layout. */
+enum { MI_LTE_UCI_ACK = 0, MI_LTE_UCI_RI = 1, MI_LTE_UCI_CQI = 2 };
+int mi_lte_ulsch_uci_qprime(uint32_t kind, uint32_t O, uint32_t beta_x8, uint32_t M_sc_initial, uint32_t N_symb_initial, uint32_t sum_K_r,
+                            uint32_t N_prb, uint32_t Qp_ri, uint32_t *Qp);
+/* G of an allocation with control information (5.2.2.7).  MI_LTE_ERR_INVALID_ARG: O > 2, Q' > 4 M, O = 0 with Q' != 0 or the reverse,
+ * Q_cqi not a multiple of Q_m, Q_m not 2 / 4 / 6, N_prb outside 1 .. 110, G <= 0. */
+int mi_lte_ulsch_uci_G(uint32_t N_prb, uint32_t Q_m, const mi_lte_ulsch_uci *uci, uint32_t *G);
+/* The channel interleaver with control information (5.2.2.8) cell by cell: kind[r * 12 + c] is the cell's class, index[2 (r * 12 + c)]
+ * its symbol's number in its own stream (data: f's symbol, CQI: q's symbol, RI / ACK: i), index[2 (r * 12 + c) + 1] for an ACK cell the
+ * data (MI_LTE_UCI_CELL_ACK_DATA) or CQI (_ACK_CQI) symbol it overwrote, 0xFFFFFFFF elsewhere.  The transmitter below is driven by it. */
+enum { MI_LTE_UCI_CELL_DATA = 0, MI_LTE_UCI_CELL_CQI = 1, MI_LTE_UCI_CELL_RI = 2, MI_LTE_UCI_CELL_ACK_DATA = 3, MI_LTE_UCI_CELL_ACK_CQI = 4 };
+int mi_lte_ulsch_uci_map(uint32_t N_prb, uint32_t Q_m, const mi_lte_ulsch_uci *uci, uint8_t *kind /*[12 M]*/, uint32_t *index /*[12 M][2]*/);
+/* A 3GPP plan whose allocation a carries h_uci[a] (h_uci = NULL: mi_lte_pusch_plan_create_3gpp).  After the demodulator
+ *   k_ulsch_uci_gather  undoes the interleaver above (36.212 5.2.2.8): the allocation's G data soft bits in sequence order, followed by
+ *                       its Q_cqi CQI soft bits, 0 where an ACK symbol overwrote one (an erasure); rate un-matching reads the former;
+ *   k_ulsch_uci_decide  sums the ACK and RI symbols' soft bits 0 and 1 (36.212 5.2.2.6; a copied bit y with the descrambling of 36.211
+ *                       5.3.1 undone: negated where c(i0) != c(i0 + 1)) and decides: O = 1: S[0] = sum (u0 + u1'), bit = S[0] < 0;
+ *                       O = 2: u0 into S[2n mod 3], u1 into S[(2n + 1) mod 3], the first maximum of sum_j (1 - 2 w_j) S[j] over
+ *                       (o0, o1) = 00, 01, 10, 11.  Integer sums: exact.  A DTX threshold on |S| is the caller's.
+ * then the code blocks of a plain 3GPP plan.  Refusals on top of mi_lte_pusch_plan_create_3gpp's: whatever mi_lte_ulsch_uci_G refuses,
+ * mi_lte_ulsch_layout(tbs, G, Q_m, rv) failing, and a G of fewer symbols than the transport block has code blocks (MI_LTE_ERR_INVALID_ARG). */
+typedef struct {
+    uint8_t ack[2], ri[2];    /* decided bits (unused ones 0) */
+    int32_t S_ack[3], S_ri[3]; /* the sums behind them (O = 1: S[0] only) */
+} mi_lte_ulsch_uci_result;    /* all zero for an allocation without control information */
+int mi_lte_pusch_plan_create_3gpp_uci(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
+                                      const uint32_t *h_unit_n_id_cell, uint32_t n_units, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                      const mi_lte_ulsch_uci *h_uci /*[n_alloc]*/, mi_lte_pusch_plan **out);
+/* after a run of such a plan (MI_LTE_ERR_INVALID_ARG on any other): the n_alloc result records; an allocation's Q_cqi CQI soft bits
+ * (36.212 5.2.2.6.4's decoder input) and its G data soft bits (5.2.2.5's), device pointers into the plan */
+int mi_lte_pusch_plan_uci_results(const mi_lte_pusch_plan *plan, const mi_lte_ulsch_uci_result **d_records);
+int mi_lte_pusch_plan_cqi_soft(const mi_lte_pusch_plan *plan, uint32_t alloc, const int8_t **d_cqi, uint32_t *Q_cqi);
+int mi_lte_pusch_plan_data_soft(const mi_lte_pusch_plan *plan, uint32_t alloc, const int8_t **d_data, uint32_t *G);
 
 /* PRACH detection: replaces liblte_phy_detect_prach() (liblte_phy.h:862-868, implementation liblte_phy.cc:3299-3479)
  * for a batch of PRACH occasions (d_occ_start[o] = sample index of the occasion's first cyclic-prefix sample; an
@@ -1006,6 +1062,21 @@ int    mi_lte_synth_ul_units_3gpp_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_c
                                      const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs,
                                      uint32_t n_alloc, const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits,
                                      uint32_t tbs_stride);
+/* The UE's multiplexer and scrambler for one allocation (36.212 5.2.2.7-5.2.2.8, 36.211 5.3.1; the rules at mi_lte_ulsch_uci above):
+ * f: the G = mi_lte_ulsch_uci_G coded data bits, h_ack / h_ri: O_ack / O_ri information bits, h_cqi: Q_cqi coded bits, one per byte
+ * (NULL where there are none).  h_mux: the 12 * 12 N_prb * Q_m interleaved values in transmit order before scrambling, 0 / 1 or the
+ * placeholders 2 = x, 3 = y; h_scr (optional): the bits after scrambling with the Gold sequence of c_init. */
+int    mi_lte_ulsch_mux_3gpp(uint32_t N_prb, uint32_t Q_m, const mi_lte_ulsch_uci *uci, const uint8_t *f, const uint8_t *h_ack,
+                             const uint8_t *h_ri, const uint8_t *h_cqi, uint32_t c_init, uint8_t *h_mux, uint8_t *h_scr);
+/* mi_lte_synth_ul_units_3gpp_i8 with control information: per allocation (unit-major, as h_allocs) its descriptor h_uci, 2 bytes of
+ * h_ack and of h_ri (the first O_* are sent) and h_cqi_stride bytes of h_cqi (the first Q_cqi are sent; NULL when no allocation has
+ * CQI).  The control values are the caller's and none is drawn from the generator's random numbers: with all-zero descriptors the
+ * output is mi_lte_synth_ul_units_3gpp_i8's byte for byte. */
+int    mi_lte_synth_ul_units_3gpp_uci_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units,
+                                         const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs,
+                                         uint32_t n_alloc, const mi_lte_synth_channel *chan, const mi_lte_ulsch_uci *h_uci,
+                                         const uint8_t *h_ack, const uint8_t *h_ri, const uint8_t *h_cqi, uint32_t h_cqi_stride,
+                                         int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride);
 
 /* n_occ PRACH occasions (format 0-3 preambles per 36.211 5.7.2-5.7.3): preamble h_preamble_idx[o] of the cell's 64,
  * delayed by h_delay[o] samples, through a flat channel + AWGN; mi_lte_synth_prach_len() complex int8 samples each. */

@@ -33,13 +33,72 @@ int mi_lte_ulsch_encode_3gpp(uint32_t tbs, const uint8_t *bits, uint32_t G, uint
 
 } // extern "C"
 
+// One ACK / RI symbol (36.212 5.2.2.6, tables 5.2.2.6-1 .. -4): O = 1: [o0 y x ..]; O = 2: [w[2n mod 3] w[(2n + 1) mod 3] x ..], w = (o0, o1, o0 ^ o1).
+// Placeholders as values: 2 = x, 3 = y
+static void uci_symbol(uint32_t O, const uint8_t *bits, uint32_t n, uint32_t Qm, uint8_t *o)
+{
+    if (O == 1) { o[0] = bits[0] & 1u; o[1] = 3; }
+    else {
+        const uint8_t w[3] = {(uint8_t)(bits[0] & 1u), (uint8_t)(bits[1] & 1u), (uint8_t)((bits[0] ^ bits[1]) & 1u)};
+        o[0] = w[(2 * n) % 3]; o[1] = w[(2 * n + 1) % 3];
+    }
+    for (uint32_t q = 2; q < Qm; q++) o[q] = 2;
+}
+
+// Data and control multiplexing and the channel interleaver (36.212 5.2.2.7-5.2.2.8) cell by cell from mi_lte_ulsch_uci_map: h[(c*M + r)*Q_m + q], the
+// order the scrambler and the modulator take, holds cell (r, c)
+static int ulsch_mux(uint32_t N_prb, uint32_t Qm, const mi_lte_ulsch_uci *uci, const uint8_t *f, const uint8_t *ack, const uint8_t *ri, const uint8_t *cqi, uint8_t *h)
+{
+    if (!uci || !f || !h || (uci->O_ack && !ack) || (uci->O_ri && !ri) || (uci->Q_cqi && !cqi)) return MI_LTE_ERR_INVALID_ARG;
+    const uint32_t M = 12 * N_prb;
+    std::vector<uint8_t>  kind(12 * (size_t)(M ? M : 1));
+    std::vector<uint32_t> index(24 * (size_t)(M ? M : 1));
+    const int rc = mi_lte_ulsch_uci_map(N_prb, Qm, uci, kind.data(), index.data());
+    if (rc != MI_LTE_OK) return rc;
+    for (uint32_t r = 0; r < M; r++)
+        for (uint32_t c = 0; c < 12; c++) {
+            const uint32_t cell = r * 12 + c, n = index[2 * cell];
+            uint8_t       *o = h + ((size_t)c * M + r) * Qm;
+            switch (kind[cell]) {
+            case MI_LTE_UCI_CELL_DATA: memcpy(o, f + (size_t)n * Qm, Qm); break;
+            case MI_LTE_UCI_CELL_CQI:  memcpy(o, cqi + (size_t)n * Qm, Qm); break;
+            case MI_LTE_UCI_CELL_RI:   uci_symbol(uci->O_ri, ri, n, Qm, o); break;
+            default:                   uci_symbol(uci->O_ack, ack, n, Qm, o); break;
+            }
+        }
+    return MI_LTE_OK;
+}
+
+// Scrambling with placeholders (36.211 5.3.1): x -> 1, y -> the scrambled bit before it, every other bit b ^ c(i)
+static void scramble_ul(uint8_t *h, const uint8_t *c, size_t n)
+{
+    for (size_t i = 0; i < n; i++) h[i] = h[i] == 2 ? 1 : h[i] == 3 ? (i ? h[i - 1] : 1) : (uint8_t)((h[i] ^ c[i]) & 1u);
+}
+
+extern "C" int mi_lte_ulsch_mux_3gpp(uint32_t N_prb, uint32_t Q_m, const mi_lte_ulsch_uci *uci, const uint8_t *f, const uint8_t *h_ack,
+                                     const uint8_t *h_ri, const uint8_t *h_cqi, uint32_t c_init, uint8_t *h_mux, uint8_t *h_scr)
+{
+    const int rc = ulsch_mux(N_prb, Q_m, uci, f, h_ack, h_ri, h_cqi, h_mux);
+    if (rc != MI_LTE_OK || !h_scr) return rc;
+    const size_t n = 12 * 12 * (size_t)N_prb * Q_m;
+    std::vector<uint8_t> c(n);
+    synth::gold(c_init, (uint32_t)n, c.data());
+    memcpy(h_scr, h_mux, n);
+    scramble_ul(h_scr, c.data(), n);
+    return MI_LTE_OK;
+}
+
 // The uplink generator behind mi_lte_synth_ul_units_i8 (spec = false: one code block, the reference's wrapped interleaver -- what the
-// reference-mode plans and the reference itself decode) and mi_lte_synth_ul_units_3gpp_i8 (mi_lte_ulsch_encode_3gpp)
+// reference-mode plans and the reference itself decode) and mi_lte_synth_ul_units_3gpp_i8 (mi_lte_ulsch_encode_3gpp); with h_uci
+// (mi_lte_synth_ul_units_3gpp_uci_i8) the multiplexer above stands in front of the scrambler.  The control values are the caller's: the random
+// numbers go to payload bits and channel draws in the same order whatever the descriptors are
+struct UlUci { const mi_lte_ulsch_uci *uci; const uint8_t *ack, *ri, *cqi; uint32_t cqi_stride; };
 static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units, const uint32_t *h_subfr_num,
                           const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
-                          const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride, bool spec)
+                          const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride, bool spec, const UlUci *uu = nullptr)
 {
     if (!cfg || !ul || !h_subfr_num || !h_n_id_cell || !h_allocs || !chan || !h_iq) return MI_LTE_ERR_INVALID_ARG;
+    if (uu && (!spec || !uu->uci || !uu->ack || !uu->ri)) return MI_LTE_ERR_INVALID_ARG;
     if (!synth::valid_grid(cfg->fft_size, cfg->N_rb_dl)) return MI_LTE_ERR_INVALID_ARG;
     auto valid = [&](const mi_lte_pdsch_alloc &al) {
         if (!spec) return synth::valid_alloc(al, cfg->N_rb_dl);
@@ -54,6 +113,17 @@ static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uin
             if (!valid(h_allocs[(size_t)u * n_alloc + a]) || (h_tx_bits && h_allocs[(size_t)u * n_alloc + a].tbs > tbs_stride))
                 return MI_LTE_ERR_INVALID_ARG;
     }
+    for (size_t k = 0; uu && k < (size_t)n_units * n_alloc; k++) { // the descriptors, and the transport block over the G they leave
+        const mi_lte_pdsch_alloc &al = h_allocs[k];
+        const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : 2;
+        uint32_t       G  = 0;
+        mi_lte_dlsch_layout_t lay;
+        int rc = mi_lte_ulsch_uci_G(al.N_prb, Qm, &uu->uci[k], &G);
+        if (rc == MI_LTE_OK) rc = mi_lte_ulsch_layout(al.tbs, G, Qm, al.rv_idx, &lay);
+        if (rc != MI_LTE_OK) return rc;
+        if (G / Qm < lay.C) return MI_LTE_ERR_INVALID_ARG; // a code block without a symbol
+        if (uu->uci[k].Q_cqi && (!uu->cqi || uu->uci[k].Q_cqi > uu->cqi_stride)) return MI_LTE_ERR_INVALID_ARG;
+    }
     const uint32_t N = cfg->fft_size, sc = 2048 / N, cp0 = 160 / sc, cpe = 144 / sc, N_rb = cfg->N_rb_dl, half = 6 * N_rb, N_sc = 12 * N_rb;
     const size_t unit_len = mi_lte_synth_ul_unit_len(N);
     synth::Rng   rng(chan->seed);
@@ -67,14 +137,17 @@ static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uin
         for (uint32_t a = 0; a < n_alloc; a++) {
             const mi_lte_pdsch_alloc &al = h_allocs[(size_t)u * n_alloc + a];
             const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : al.mod_type == 1 ? 2 : 1;
-            const uint32_t M = 12 * al.N_prb, G = 12 * M * Qm, B = al.tbs + 24;
+            const size_t   k_al = (size_t)u * n_alloc + a;
+            const uint32_t M = 12 * al.N_prb, N_bits = 12 * M * Qm, B = al.tbs + 24;
+            uint32_t       G = N_bits; // the bits left to UL-SCH data (36.212 5.2.2.7)
+            if (uu && mi_lte_ulsch_uci_G(al.N_prb, Qm, &uu->uci[k_al], &G) != MI_LTE_OK) return MI_LTE_ERR_INVALID_ARG;
             uint32_t       K = 0, f1, f2;
             for (int r = 0; r < LTE_QPP_N_SIZES; r++)
                 if (LTE_QPP_ROWS[r].K >= B) { K = LTE_QPP_ROWS[r].K; break; }
             if (al.N_prb == 0 || al.N_prb > N_rb) return MI_LTE_ERR_UNSUPPORTED;
             if (!spec && (B > 6144 || K != B || !synth::qpp_params(K, &f1, &f2))) return MI_LTE_ERR_UNSUPPORTED;
             // UL-SCH: CRC24A, turbo code, rate matching with N_cb = K_w (36.212 5.2.2.1-5.2.2.5)
-            std::vector<uint8_t> b(spec ? al.tbs : K), g(G), h(G), c(G);
+            std::vector<uint8_t> b(spec ? al.tbs : K), g(G), h(N_bits), c(N_bits);
             for (uint32_t i = 0; i < al.tbs; i++) b[i] = (uint8_t)(rng.next() & 1u);
             if (h_tx_bits) memcpy(h_tx_bits + ((size_t)u * n_alloc + a) * tbs_stride, b.data(), al.tbs);
             if (spec) { // segmentation and CRC24B as well, the exact interleaver
@@ -88,11 +161,17 @@ static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uin
             }
             // channel interleaver without control information (36.212 5.2.2.8): the R' x 12 matrix of Q_m-bit symbols is
             // written row by row and read column by column -> h[(s*M + k)*Q + q] = g[(k*12 + s)*Q + q]
-            for (uint32_t s = 0; s < 12; s++)
-                for (uint32_t k = 0; k < M; k++)
-                    for (uint32_t q = 0; q < Qm; q++) h[((size_t)s * M + k) * Qm + q] = g[((size_t)k * 12 + s) * Qm + q];
-            synth::gold((al.rnti << 14) | (sf << 9) | cell, G, c.data());
-            for (uint32_t i = 0; i < G; i++) h[i] ^= c[i];
+            // with control information: ulsch_mux, which places the same cells around and under the control symbols
+            if (uu) {
+                const int rc = ulsch_mux(al.N_prb, Qm, &uu->uci[k_al], g.data(), uu->ack + 2 * k_al, uu->ri + 2 * k_al,
+                                         uu->cqi ? uu->cqi + k_al * uu->cqi_stride : nullptr, h.data());
+                if (rc != MI_LTE_OK) return rc;
+            } else
+                for (uint32_t s = 0; s < 12; s++)
+                    for (uint32_t k = 0; k < M; k++)
+                        for (uint32_t q = 0; q < Qm; q++) h[((size_t)s * M + k) * Qm + q] = g[((size_t)k * 12 + s) * Qm + q];
+            synth::gold((al.rnti << 14) | (sf << 9) | cell, N_bits, c.data());
+            scramble_ul(h.data(), c.data(), N_bits);
             std::vector<float> m_re(12 * (size_t)M), m_im(12 * (size_t)M);
             synth::modulate(h.data(), 12 * M, al.mod_type, m_re.data(), m_im.data());
             // transform precoding (36.211 5.3.3): forward DFT of each symbol's M points scaled by 1/sqrt(M), what a real
@@ -190,6 +269,16 @@ int mi_lte_synth_ul_units_3gpp_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg 
                                   const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride)
 {
     return synth_ul_units(cfg, ul, n_units, h_subfr_num, h_n_id_cell, h_allocs, n_alloc, chan, h_iq, h_tx_bits, tbs_stride, true);
+}
+
+int mi_lte_synth_ul_units_3gpp_uci_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units, const uint32_t *h_subfr_num,
+                                      const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                      const mi_lte_synth_channel *chan, const mi_lte_ulsch_uci *h_uci, const uint8_t *h_ack, const uint8_t *h_ri,
+                                      const uint8_t *h_cqi, uint32_t h_cqi_stride, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride)
+{
+    const UlUci uu = {h_uci, h_ack, h_ri, h_cqi, h_cqi_stride};
+    if (!h_uci) return MI_LTE_ERR_INVALID_ARG;
+    return synth_ul_units(cfg, ul, n_units, h_subfr_num, h_n_id_cell, h_allocs, n_alloc, chan, h_iq, h_tx_bits, tbs_stride, true, &uu);
 }
 
 // ---- PRACH (36.211 5.7.2-5.7.3): preamble v of root u is x_u((n + C_v) mod 839); its 839-point DFT sits on the PRACH

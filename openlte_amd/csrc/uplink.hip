@@ -16,7 +16,8 @@
 //
 // The 3GPP transport-block mode (mi_lte_pusch_plan_create_3gpp, include/mi_lte.h) is the same chain as 36.211 / 36.212 specify it: the
 // pre-decoder's output times 1 / sqrt(M) (36.211 5.3.3; k_pusch_demod<.., SPEC = true>), so that 16QAM and 64QAM de-map and QPSK keeps its
-// soft information, and transport blocks of 1 .. 13 code blocks through dlsch3gpp.hip's kernels with N_cb = K_w (36.212 5.2.2).
+// soft information, and transport blocks of 1 .. 13 code blocks through dlsch3gpp.hip's kernels with N_cb = K_w (36.212 5.2.2).  With control
+// information (mi_lte_pusch_plan_create_3gpp_uci) ulsch_uci.hip's two kernels run between the demodulator, which is the same, and the code blocks.
 //
 // The DFT sizes are not powers of two and FFTW's operation order is unspecified, so like the downlink FFT
 // this stage is tolerance-checked; everything from the int8 soft bits on is integer-exact.
@@ -29,6 +30,7 @@
 #include <cstring>
 #include "plan_core.hpp"
 #include "phy_dev.hpp"
+#include "ulsch_uci.h"
 
 namespace {
 
@@ -462,6 +464,7 @@ struct mi_lte_pusch_plan {
     // 3GPP transport-block mode (mi_lte_pusch_plan_create_3gpp): the spec-normalised demodulator, dlsch3gpp.hip's code blocks and a BCJR decoder
     MiDlsch3     *g3 = nullptr;
     uint32_t      decoder = MI_LTE_TURBO_BCJR, n_iter = 8, max_tbs = 0;
+    MiUlschUci   *uci = nullptr; // control information on the allocations (mi_lte_pusch_plan_create_3gpp_uci): ulsch_uci.hip's part
 };
 
 // UL-SCH rate matching has no soft-buffer limit (36.212 5.2.2.5: N_cb = K_w).  As a DL-SCH soft-buffer configuration: an N_IR no block reaches
@@ -516,13 +519,15 @@ static int pusch_shapes(mi_lte_ctx *ctx)
 // h_dmrs (optional): caller-supplied reference signals, 4 x 12*N_prb floats per allocation back to back -- the
 // per-call host form passes the arrays liblte_phy_ul_init left in the caller's LIBLTE_PHY_STRUCT.
 // spec: a plan in the 3GPP transport-block mode -- the transport block's conditions are mi_lte_ulsch_layout's, its code blocks dlsch3gpp.hip's
+// h_uci (optional, spec only): one control-information descriptor per allocation
 extern "C" void mi_lte_pusch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl);
 static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
                              const uint32_t *h_unit_n_id_cell, uint32_t n_units, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
-                             const float *h_dmrs, mi_lte_pusch_plan **out, bool spec)
+                             const float *h_dmrs, mi_lte_pusch_plan **out, bool spec, const mi_lte_ulsch_uci *h_uci = nullptr)
 {
     if (!ctx || !cfg || (!ul && !h_dmrs) || !h_unit_subfr_num || !h_unit_n_id_cell || !h_allocs || !out || n_alloc == 0 || n_units == 0)
         return MI_LTE_ERR_INVALID_ARG;
+    if (h_uci && !spec) { ctx->err = "control information on PUSCH needs a plan in the 3GPP transport-block mode"; return MI_LTE_ERR_UNSUPPORTED; }
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     auto *pl    = new mi_lte_pusch_plan();
     auto  guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_lte_pusch_plan_destroy(nullptr, pl); });
@@ -532,13 +537,16 @@ static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
     std::vector<float>     dmrs;
     std::vector<PuschDesc> desc(n_alloc);
     std::vector<uint8_t>   row(n_alloc);
+    std::vector<uint32_t>  c_init(n_alloc);
     uint32_t max_tbs = 0;
     pl->h_e_len.resize(n_alloc);
     for (uint32_t a = 0; a < n_alloc; a++) {
         const mi_lte_pdsch_alloc &al = h_allocs[a];
         const int r = spec ? 0 : mi_qpp_row_at_least(al.tbs + 24);
         // N_prb the reference has a transform pre-decoding plan for (liblte_phy.cc:2360-2377)
-        const bool planned = al.N_prb > 0 && al.N_prb < cfg->N_rb_dl && (al.N_prb % 2 == 0 || al.N_prb % 3 == 0 || al.N_prb % 5 == 0);
+        // (the 3GPP mode also takes the single resource block: M = 12 is a size of 36.211 5.3.3, and a grant that small is where control
+        // information fills whole rows; the reference's test leaves it out only because 1 is no multiple of 2, 3 or 5)
+        const bool planned = al.N_prb > 0 && al.N_prb < cfg->N_rb_dl && (al.N_prb % 2 == 0 || al.N_prb % 3 == 0 || al.N_prb % 5 == 0 || (spec && al.N_prb == 1));
         if (r < 0 || !planned || al.mod_type > 3 || al.unit >= n_units) {
             ctx->err = "PUSCH allocation outside the envelope (one code block; N_prb < N_rb_ul and divisible by 2, 3 or 5) or malformed";
             return MI_LTE_ERR_UNSUPPORTED;
@@ -547,6 +555,21 @@ static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
             mi_lte_dlsch_layout_t lay;
             const int rc = al.mod_type == 0 ? MI_LTE_ERR_UNSUPPORTED : mi_lte_ulsch_layout(al.tbs, 0, 2, al.rv_idx & 3u, &lay);
             if (rc != MI_LTE_OK) { ctx->err = "PUSCH allocation outside the 3GPP transport-block mode (BPSK, F != 0 or tbs > 75376)"; return rc; }
+        }
+        if (h_uci) { // the descriptor's own conditions, then the transport block over the G that the control information leaves (36.212 5.2.2.7)
+            const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : 2;
+            uint32_t       G  = 0;
+            int rc = mi_lte_ulsch_uci_G(al.N_prb, Qm, &h_uci[a], &G);
+            if (rc != MI_LTE_OK) {
+                ctx->err = "control information refused: O > 2, Q' > 4 M, O without Q' or Q' without O, Q_cqi not a multiple of Q_m, or no room left for data";
+                return rc;
+            }
+            mi_lte_dlsch_layout_t lay;
+            if ((rc = mi_lte_ulsch_layout(al.tbs, G, Qm, al.rv_idx & 3u, &lay)) != MI_LTE_OK) {
+                ctx->err = "the transport block does not fit the bits that control information leaves (mi_lte_ulsch_layout)";
+                return rc;
+            }
+            if (G / Qm < lay.C) { ctx->err = "control information leaves a code block without a symbol"; return MI_LTE_ERR_INVALID_ARG; }
         }
         for (uint32_t sl = 0; sl < 2; sl++) // a resource block past the carrier would be read out of the neighbouring symbol row
             for (uint32_t i = 0; i < al.N_prb; i++)
@@ -572,6 +595,7 @@ static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
             }
             desc[a] = {sf, cell, it->second};
         }
+        c_init[a] = (al.rnti << 14) | (sf << 9) | cell; // (k_pusch_demod's)
         row[a] = (uint8_t)r;
         max_tbs = std::max(max_tbs, al.tbs);
         const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : al.mod_type == 1 ? 2 : 1, E = 12 * M * Qm;
@@ -588,6 +612,10 @@ static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
     MI_HIP_CHECK(ctx, pl->core.allocate(n_alloc, pl->core.e_bytes));
     if (spec) {
         const int rc = mi_dlsch3_create(ctx, &ULSCH_AS_DLSCH, h_allocs, n_alloc, &pl->g3);
+        if (rc != MI_LTE_OK) return rc;
+    }
+    if (h_uci) {
+        const int rc = mi_ulsch_uci_create(ctx, h_allocs, h_uci, c_init.data(), pl->core.h_e_off.data(), n_alloc, pl->core.e_bytes, &pl->uci);
         if (rc != MI_LTE_OK) return rc;
     }
     MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_desc, sizeof(PuschDesc) * n_alloc));
@@ -631,6 +659,38 @@ int mi_lte_pusch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, con
 {
     if (!ul) return MI_LTE_ERR_INVALID_ARG;
     return pusch_plan_create(ctx, cfg, ul, h_unit_subfr_num, h_unit_n_id_cell, n_units, h_allocs, n_alloc, nullptr, out, /*spec=*/true);
+}
+
+int mi_lte_pusch_plan_create_3gpp_uci(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
+                                      const uint32_t *h_unit_n_id_cell, uint32_t n_units, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                      const mi_lte_ulsch_uci *h_uci, mi_lte_pusch_plan **out)
+{
+    if (!ul) return MI_LTE_ERR_INVALID_ARG;
+    return pusch_plan_create(ctx, cfg, ul, h_unit_subfr_num, h_unit_n_id_cell, n_units, h_allocs, n_alloc, nullptr, out, /*spec=*/true, h_uci);
+}
+
+int mi_lte_pusch_plan_uci_results(const mi_lte_pusch_plan *pl, const mi_lte_ulsch_uci_result **d_records)
+{
+    if (!pl || !pl->uci || !d_records) return MI_LTE_ERR_INVALID_ARG;
+    *d_records = pl->uci->d_res;
+    return MI_LTE_OK;
+}
+
+// the gathered run of an allocation: G data soft bits at the plan's offset, the Q_cqi CQI soft bits behind them
+int mi_lte_pusch_plan_data_soft(const mi_lte_pusch_plan *pl, uint32_t alloc, const int8_t **d_data, uint32_t *G)
+{
+    if (!pl || !pl->uci || alloc >= pl->core.n_alloc || !d_data || !G) return MI_LTE_ERR_INVALID_ARG;
+    *d_data = pl->uci->d_e + (size_t)pl->core.h_e_off[alloc] * 64;
+    *G      = pl->uci->h_G[alloc];
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_cqi_soft(const mi_lte_pusch_plan *pl, uint32_t alloc, const int8_t **d_cqi, uint32_t *Q_cqi)
+{
+    if (!pl || !pl->uci || alloc >= pl->core.n_alloc || !d_cqi || !Q_cqi) return MI_LTE_ERR_INVALID_ARG;
+    *d_cqi = pl->uci->d_e + (size_t)pl->core.h_e_off[alloc] * 64 + pl->uci->h_G[alloc];
+    *Q_cqi = pl->uci->h_Q_cqi[alloc];
+    return MI_LTE_OK;
 }
 
 int mi_lte_pusch_plan_set_decoder(mi_lte_pusch_plan *pl, uint32_t mode, uint32_t n_iter, int qpp_spec)
@@ -678,6 +738,7 @@ void mi_lte_pusch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl)
     (void)hipFree(pl->d_desc);
     (void)hipFree(pl->d_dmrs);
     mi_dlsch3_free(pl->g3);
+    mi_ulsch_uci_free(pl->uci);
     delete pl;
 }
 
@@ -722,9 +783,14 @@ int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float 
 #undef MI_PUSCH_LAUNCH_V
     MI_HIP_CHECK(ctx, hipGetLastError());
     if (pl->g3) { // 3GPP mode: the code blocks of dlsch3gpp.hip, no HARQ pool bound
-        if ((rc = mi_dlsch3_run(ctx, pl->g3, nullptr, nullptr, pl->core.io(d_out_bits, d_status, /*ul=*/true), pl->decoder, pl->n_iter)) != MI_LTE_OK) return rc;
+        MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/true);
+        if (pl->uci) { // control information: rate un-matching reads the gathered data run (G soft bits per allocation, the same offsets)
+            if ((rc = mi_ulsch_uci_run(ctx, pl->uci, pl->core.d_e, pl->core.d_e_off)) != MI_LTE_OK) return rc;
+            io.d_e = pl->uci->d_e; io.d_e_len = pl->uci->d_e_len;
+        }
+        if ((rc = mi_dlsch3_run(ctx, pl->g3, nullptr, nullptr, io, pl->decoder, pl->n_iter)) != MI_LTE_OK) return rc;
         const size_t at = ctx->last_kernels.find(','); // (mi_dlsch3_run lists the downlink's demodulator in front of its own kernels)
-        ctx->last_kernels.replace(0, at == std::string::npos ? 0 : at, "k_pusch_demod:1");
+        ctx->last_kernels.replace(0, at == std::string::npos ? 0 : at, pl->uci ? "k_pusch_demod:1,k_ulsch_uci_gather:1,k_ulsch_uci_decide:1" : "k_pusch_demod:1");
         return MI_LTE_OK;
     }
     // several block sizes (the UEs of a subframe rarely share one): one launch set over all of them, as in the PDSCH chain

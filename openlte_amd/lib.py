@@ -70,6 +70,49 @@ def ulsch_layout(tbs, G, Q_m, rv=0):
     return {"C": out.C, "K": out.K, "B": out.B, "N_cb": out.N_cb, "k0": out.k0, "E": list(out.E[:out.C]), "off": list(out.off[:out.C])}
 
 
+class UlschUci(C.Structure):
+    """mi_lte_ulsch_uci: the control information multiplexed on one PUSCH allocation (36.212 5.2.2.6-5.2.2.8); all zero: none"""
+    _fields_ = [("O_ack", C.c_uint8), ("O_ri", C.c_uint8), ("Qp_ack", C.c_uint16), ("Qp_ri", C.c_uint16), ("Q_cqi", C.c_uint32)]
+
+
+class UlschUciResult(C.Structure):
+    """mi_lte_ulsch_uci_result"""
+    _fields_ = [("ack", C.c_uint8 * 2), ("ri", C.c_uint8 * 2), ("S_ack", C.c_int32 * 3), ("S_ri", C.c_int32 * 3)]
+
+
+UCI_ACK, UCI_RI, UCI_CQI = 0, 1, 2
+UCI_CELL_DATA, UCI_CELL_CQI, UCI_CELL_RI, UCI_CELL_ACK_DATA, UCI_CELL_ACK_CQI = range(5)
+
+
+def ulsch_uci_qprime(kind, O, beta_x8, M_sc_initial, N_symb_initial, sum_K_r, N_prb, Qp_ri=0):
+    """mi_lte_ulsch_uci_qprime (host arithmetic): Q' of 36.212 5.2.2.6 for kind UCI_ACK / UCI_RI / UCI_CQI, beta as eighths."""
+    out = C.c_uint32()
+    rc = load_library().mi_lte_ulsch_uci_qprime(kind, O, beta_x8, M_sc_initial, N_symb_initial, sum_K_r, N_prb, Qp_ri, C.byref(out))
+    if rc != 0:
+        raise MiLteError("mi_lte_ulsch_uci_qprime failed: %d" % rc, rc)
+    return out.value
+
+
+def ulsch_uci_G(N_prb, Q_m, uci):
+    """mi_lte_ulsch_uci_G (host arithmetic): the coded data bits an allocation with control information `uci` leaves, 36.212 5.2.2.7."""
+    out = C.c_uint32()
+    rc = load_library().mi_lte_ulsch_uci_G(N_prb, Q_m, C.byref(uci), C.byref(out))
+    if rc != 0:
+        raise MiLteError("mi_lte_ulsch_uci_G failed: %d" % rc, rc)
+    return out.value
+
+
+def ulsch_uci_map(N_prb, Q_m, uci):
+    """mi_lte_ulsch_uci_map (host arithmetic): (kind uint8 [M, 12], index uint32 [M, 12, 2]) of the interleaver matrix, M = 12 N_prb:
+    a cell's class (UCI_CELL_*), its symbol's number in its own stream, and for an ACK cell the data / CQI symbol it overwrote."""
+    M = 12 * N_prb
+    kind, index = np.zeros(12 * max(M, 1), np.uint8), np.zeros(24 * max(M, 1), np.uint32)
+    rc = load_library().mi_lte_ulsch_uci_map(N_prb, Q_m, C.byref(uci), kind.ctypes.data, index.ctypes.data)
+    if rc != 0:
+        raise MiLteError("mi_lte_ulsch_uci_map failed: %d" % rc, rc)
+    return kind.reshape(M, 12), index.reshape(M, 12, 2)
+
+
 HARQ_NONE, HARQ_NEW_DATA = 0xFFFFFFFF, 1
 
 
@@ -276,6 +319,13 @@ def load_library():
     L.mi_lte_pusch_plan_cb_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
     L.mi_lte_pusch_plan_cb_ok.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_ulsch_layout.argtypes = [u32, u32, u32, u32, C.POINTER(DlschLayout)]
+    L.mi_lte_ulsch_uci_qprime.argtypes = [u32] * 8 + [C.POINTER(u32)]
+    L.mi_lte_ulsch_uci_G.argtypes = [u32, u32, C.POINTER(UlschUci), C.POINTER(u32)]
+    L.mi_lte_ulsch_uci_map.argtypes = [u32, u32, C.POINTER(UlschUci), vp, vp]
+    L.mi_lte_pusch_plan_create_3gpp_uci.argtypes = L.mi_lte_pusch_plan_create.argtypes[:-1] + [vp, C.POINTER(vp)]
+    L.mi_lte_pusch_plan_uci_results.argtypes = [vp, C.POINTER(vp)]
+    L.mi_lte_pusch_plan_cqi_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32)]
+    L.mi_lte_pusch_plan_data_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32)]
     L.mi_lte_prach_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), C.POINTER(vp)]
     L.mi_lte_prach_plan_create_roots.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), f32p, f32p, u32, C.POINTER(vp)]
     L.mi_lte_prach_plan_destroy.argtypes = [vp, vp]
@@ -599,15 +649,26 @@ class DlPipeline:
 
 class PuschPlan:
     """mi_lte_pusch_plan: PUSCH allocations (one per scheduled UE) over a batch of uplink subframe units.  spec: a plan in the 3GPP
-    transport-block mode (mi_lte_pusch_plan_create_3gpp)."""
+    transport-block mode (mi_lte_pusch_plan_create_3gpp); uci: one UlschUci per allocation (mi_lte_pusch_plan_create_3gpp_uci)."""
 
-    def __init__(self, ctx, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, spec=False):
+    def __init__(self, ctx, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, spec=False, uci=None):
         self.ctx, self.n_alloc, self.packed = ctx, len(allocs), False
         arr = (PdschAlloc * len(allocs))(*allocs)
         h = C.c_void_p()
         sf, cell = np.ascontiguousarray(unit_subfr_num, np.uint32), np.ascontiguousarray(unit_n_id_cell, np.uint32)
-        create = ctx.L.mi_lte_pusch_plan_create_3gpp if spec else ctx.L.mi_lte_pusch_plan_create
-        ctx._check(create(ctx.h, C.byref(cfg), C.byref(ulcfg), sf, cell, len(sf), C.cast(arr, C.c_void_p), len(allocs), C.byref(h)))
+        if uci is not None:
+            if not spec:
+                raise MiLteError("control information on PUSCH needs a plan in the 3GPP transport-block mode (pusch_plan_3gpp)", -4)
+            if len(uci) != len(allocs):
+                raise ValueError("uci: one UlschUci per allocation")
+            u_arr = (UlschUci * len(allocs))(*uci)
+            rc = ctx.L.mi_lte_pusch_plan_create_3gpp_uci(ctx.h, C.byref(cfg), C.byref(ulcfg), sf, cell, len(sf), C.cast(arr, C.c_void_p), len(allocs),
+                                                         C.cast(u_arr, C.c_void_p), C.byref(h))
+            if rc != 0:
+                raise MiLteError("libmi_lte error %d: %s" % (rc, ctx.L.mi_lte_last_error(ctx.h).decode()), rc)
+        else:
+            create = ctx.L.mi_lte_pusch_plan_create_3gpp if spec else ctx.L.mi_lte_pusch_plan_create
+            ctx._check(create(ctx.h, C.byref(cfg), C.byref(ulcfg), sf, cell, len(sf), C.cast(arr, C.c_void_p), len(allocs), C.byref(h)))
         self.h = h
         self.out_stride = ctx.L.mi_lte_pusch_plan_out_stride(h)
         self.tbs = [a.tbs for a in allocs]
@@ -664,6 +725,32 @@ class PuschPlan:
         out = np.empty(self.n_alloc, np.uint32)
         self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
         return out
+
+    def _tap(self, fn, alloc):
+        p, n = C.c_void_p(), C.c_uint32()
+        self.ctx._check(fn(self.h, alloc, C.byref(p), C.byref(n)))
+        out = np.empty(int(n.value), np.int8)
+        if out.nbytes:
+            self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
+        return out
+
+    def data_soft(self, alloc):
+        """Plan with control information, after a run: the allocation's G data soft bits in sequence order (what rate un-matching reads),
+        0 where an ACK symbol overwrote one."""
+        return self._tap(self.ctx.L.mi_lte_pusch_plan_data_soft, alloc)
+
+    def cqi_soft(self, alloc):
+        """Plan with control information, after a run: the allocation's Q_cqi CQI soft bits, 0 where an ACK symbol overwrote one."""
+        return self._tap(self.ctx.L.mi_lte_pusch_plan_cqi_soft, alloc)
+
+    def uci_results(self):
+        """Plan with control information, after a run: one dict per allocation {ack: [2], ri: [2], S_ack: [3], S_ri: [3]} -- the decided
+        HARQ-ACK and RI bits and the soft-bit sums behind them (all zero where the allocation has none)."""
+        p = C.c_void_p()
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_uci_results(self.h, C.byref(p)))
+        rec = (UlschUciResult * self.n_alloc)()
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, C.addressof(rec), p.value, C.sizeof(rec)))
+        return [{"ack": list(r.ack), "ri": list(r.ri), "S_ack": list(r.S_ack), "S_ri": list(r.S_ri)} for r in rec]
 
     def close(self):
         if self.h:
@@ -1030,13 +1117,15 @@ class Context:
     def pdcch_plan(self, cfg, cells, phich_res=1.0, per_port_estimates=False):
         return PdcchPlan(self, cfg, cells, phich_res, 0, per_port_estimates)
 
-    def pusch_plan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs):
-        return PuschPlan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs)
+    def pusch_plan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, uci=None):
+        """A reference-mode PUSCH plan.  It has no control information: a `uci` is refused (MiLteError, -4)."""
+        return PuschPlan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, uci=uci)
 
-    def pusch_plan_3gpp(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs):
+    def pusch_plan_3gpp(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, uci=None):
         """A PUSCH plan in the 3GPP transport-block mode: the spec-normalised demodulator (QPSK / 16QAM / 64QAM), 36.212 segmentation (any tbs
-        of Table 7.1.7.2.1-1), BCJR x 8 with the exact interleaver by default."""
-        return PuschPlan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, spec=True)
+        of Table 7.1.7.2.1-1), BCJR x 8 with the exact interleaver by default.  uci: one UlschUci per allocation -- HARQ-ACK, RI and CQI
+        multiplexed on the PUSCH (36.212 5.2.2.6-5.2.2.8); see PuschPlan.uci_results / cqi_soft / data_soft."""
+        return PuschPlan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, spec=True, uci=uci)
 
     # ---- PDSCH ------------------------------------------------------------------------------
     def pdsch_plan(self, cfg, n_pdcch_symbs, allocs):

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .lib import load_library, MiLteError, DlCfg, UlCfg, PrachCfg, PdschAlloc, DlschCfg
+from .lib import load_library, MiLteError, DlCfg, UlCfg, PrachCfg, PdschAlloc, DlschCfg, UlschUci
 
 _i8p = np.ctypeslib.ndpointer(np.int8, flags="C_CONTIGUOUS")
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
@@ -40,6 +40,9 @@ def _lib():
                                                C.POINTER(SynthChannel), _i8p, _u8p, C.c_uint32]
         L.mi_lte_synth_ul_units_3gpp_i8.argtypes = L.mi_lte_synth_ul_units_i8.argtypes
         L.mi_lte_ulsch_encode_3gpp.argtypes = [C.c_uint32, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, _u8p]
+        L.mi_lte_synth_ul_units_3gpp_uci_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(UlCfg), C.c_uint32, _u32p, _u32p, C.c_void_p, C.c_uint32,
+                                                        C.POINTER(SynthChannel), C.c_void_p, _u8p, _u8p, _u8p, C.c_uint32, _i8p, _u8p, C.c_uint32]
+        L.mi_lte_ulsch_mux_3gpp.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(UlschUci), _u8p, _u8p, _u8p, _u8p, C.c_uint32, _u8p, _u8p]
         L.mi_lte_synth_prach_len.argtypes = [C.c_uint32, C.c_uint32]
         L.mi_lte_synth_prach_len.restype = C.c_size_t
         L.mi_lte_synth_prach_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(PrachCfg), C.c_uint32, _u32p, _u32p, C.POINTER(SynthChannel), _i8p]
@@ -154,9 +157,47 @@ def ul_units(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, gain=(0.5, 1.5),
     return iq, tx
 
 
-def ul_units_3gpp(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, **chan):
-    """ul_units with the 3GPP UL-SCH transmitter (mi_lte_synth_ul_units_3gpp_i8): any tbs of Table 7.1.7.2.1-1, the exact interleaver."""
-    return ul_units(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, spec=True, **chan)
+def ul_units_3gpp(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, uci=None, ack=None, ri=None, cqi=None, gain=(0.5, 1.5), max_delay=4,
+                  snr_db=30.0, peak=100.0, seed=1):
+    """ul_units with the 3GPP UL-SCH transmitter (mi_lte_synth_ul_units_3gpp_i8): any tbs of Table 7.1.7.2.1-1, the exact interleaver.
+    uci: one UlschUci per allocation (unit-major, as allocs) -- mi_lte_synth_ul_units_3gpp_uci_i8, with the control values the caller's:
+    ack[k], ri[k] the allocation's information bits (sequences of O_ack / O_ri bits) and cqi[k] its Q_cqi coded CQI bits."""
+    if uci is None:
+        return ul_units(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, gain=gain, max_delay=max_delay, snr_db=snr_db, peak=peak, seed=seed, spec=True)
+    n, na = len(subfr_num), len(allocs)
+    if len(uci) != na:
+        raise ValueError("uci: one UlschUci per allocation")
+    iq = np.zeros((n, ul_unit_len(cfg.fft_size), 2), np.int8)
+    max_tbs = max([a.tbs for a in allocs], default=8)
+    tx = np.zeros((n, max(n_alloc, 1), max_tbs), np.uint8)
+    stride = max([u.Q_cqi for u in uci] + [1])
+    h_ack, h_ri, h_cqi = np.zeros((max(na, 1), 2), np.uint8), np.zeros((max(na, 1), 2), np.uint8), np.zeros((max(na, 1), stride), np.uint8)
+    for k, u in enumerate(uci):
+        for dst, src, cnt, what in ((h_ack, ack, u.O_ack, "ack"), (h_ri, ri, u.O_ri, "ri"), (h_cqi, cqi, u.Q_cqi, "cqi")):
+            if cnt:
+                if src is None or len(src[k]) != cnt:
+                    raise ValueError("%s[%d]: %d bits" % (what, k, cnt))
+                dst[k, :min(cnt, dst.shape[1])] = np.asarray(src[k], np.uint8)[:dst.shape[1]]  # (O > 2 is the library's to refuse)
+    arr, u_arr = (PdschAlloc * max(na, 1))(*allocs), (UlschUci * max(na, 1))(*uci)
+    ch = SynthChannel(gain[0], gain[1], float(max_delay), float(snr_db), float(peak), int(seed))
+    rc = _lib().mi_lte_synth_ul_units_3gpp_uci_i8(C.byref(cfg), C.byref(ulcfg), n, np.ascontiguousarray(subfr_num, np.uint32),
+                                                  np.ascontiguousarray(n_id_cell, np.uint32), C.cast(arr, C.c_void_p), n_alloc, C.byref(ch),
+                                                  C.cast(u_arr, C.c_void_p), h_ack, h_ri, h_cqi, stride, iq, tx, max_tbs)
+    if rc != 0:
+        raise MiLteError("mi_lte_synth_ul_units_3gpp_uci_i8 failed: %d" % rc, rc)
+    return iq, tx
+
+
+def ulsch_mux_3gpp(N_prb, Q_m, uci, f, ack=(), ri=(), cqi=(), c_init=0):
+    """mi_lte_ulsch_mux_3gpp: (values before scrambling, 0 / 1 / 2 = x / 3 = y; bits after scrambling), each uint8 [12 * 12 N_prb * Q_m] in
+    transmit order, of one allocation whose G coded data bits are f."""
+    n = 12 * 12 * N_prb * Q_m
+    pad = lambda v, m: np.concatenate([np.asarray(v, np.uint8).reshape(-1), np.zeros(m, np.uint8)])
+    mux, scr = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+    rc = _lib().mi_lte_ulsch_mux_3gpp(N_prb, Q_m, C.byref(uci), np.ascontiguousarray(f, np.uint8), pad(ack, 2), pad(ri, 2), pad(cqi, 1), c_init, mux, scr)
+    if rc != 0:
+        raise MiLteError("mi_lte_ulsch_mux_3gpp failed: %d" % rc, rc)
+    return mux[:n], scr[:n]
 
 
 def ulsch_encode_3gpp(bits, G, Q_m, rv=0):

@@ -6,7 +6,11 @@ mi_lte_turbo_decode_batch BCJR x 8 on the same 26 624 rate-un-matched blocks (th
 time in both variants from the same process: the 3GPP plan's and a reference-mode plan's over the same grids with one-block QPSK transport
 blocks on the same 99 PRB (the reference-mode envelope; the demodulator's work does not depend on the transport block).
 
-    python tools/ulsch3gpp_bench.py [--units 2048] [--steps 10] [--warmup 2]
+    python tools/ulsch3gpp_bench.py [--units 2048] [--steps 10] [--warmup 2] [--uci]
+--uci: the same grants with control information multiplexed on them (HARQ-ACK O = 1, Q' = 48; RI O = 2, Q' = 24; 600 coded CQI bits): the run of a
+plan of mi_lte_pusch_plan_create_3gpp_uci against a plain 3GPP plan of the same build on the same subframes (alternated; the plain plan rate
+un-matches over the wrong G and fails its CRCs there, which costs it nothing: the decoders run a fixed eight iterations), the per-kernel split with
+k_ulsch_uci_gather and k_ulsch_uci_decide next to k_dl3_rm_i8, and the gather's bytes per second (every soft byte once in and once out).
 Prints one JSON line last."""
 import argparse
 import ctypes as C
@@ -29,14 +33,18 @@ def main():
     ap.add_argument("--unique", type=int, default=10, help="distinct synthesised subframes (subframe numbers 0..9), repeated over the units")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--uci", action="store_true", help="the control-information leg (see above)")
     args = ap.parse_args()
     ctx = m.Context(0)
     cfg, ul = m.DlCfg(2048, 100, 1, m.IQ_I8), m.UlCfg(3, 0, 0, 2, 1)
     nu, n, cell = args.unique, args.units, 42
     prbs = list(range(N_PRB))
     sfs_u = list(range(nu))
+    ctl = m.UlschUci(1, 2, 48, 24, 600) if args.uci else None
+    ack, ri = [[u & 1] for u in range(nu)], [[(u >> 1) & 1, u & 1] for u in range(nu)]
+    cqi = np.random.default_rng(5).integers(0, 2, (nu, 600)).astype(np.uint8)
     iq, tx = synth.ul_units_3gpp(cfg, ul, sfs_u, [cell] * nu, [m.make_alloc(i, 3, TBS, prbs, 0x100 + i) for i in range(nu)], 1, snr_db=30.0,
-                                 max_delay=3, seed=11)
+                                 max_delay=3, seed=11, **(dict(uci=[ctl] * nu, ack=ack, ri=ri, cqi=cqi) if args.uci else {}))
     ulen = iq.shape[1]
     sfs = [sfs_u[u % nu] for u in range(n)]
     d_iq = ctx.to_device(iq.reshape(-1, 2))
@@ -57,6 +65,10 @@ def main():
         for _ in range(args.steps):
             fn()
         return ctx.timer_stop() / args.steps
+
+    if args.uci:
+        plan_ref.close()
+        return uci_leg(ctx, args, cfg, ul, sfs, cell, prbs, ctl, ack, ri, cqi, tx, d_sub, plan, timed, d_out, d_st)
 
     def profiled(p):
         ctx.profile(True)
@@ -95,6 +107,43 @@ def main():
     plan_ref.close()
     ctx.close()
     return 0 if (st == 0).all() and tx_ok else 1
+
+
+def uci_leg(ctx, args, cfg, ul, sfs, cell, prbs, ctl, ack, ri, cqi, tx, d_sub, plan, timed, d_out, d_st):
+    n, nu = args.units, args.unique
+    plan_uci = ctx.pusch_plan_3gpp(cfg, ul, sfs, [cell] * n, [m.make_alloc(u, 3, TBS, prbs, 0x100 + u % nu) for u in range(n)], uci=[ctl] * n)
+    ms = {"uci": [], "plain": []}
+    for _ in range(3):  # alternated
+        ms["uci"].append(round(timed(lambda: plan_uci.run_dev(d_sub, d_out, d_st)), 3))
+        ms["plain"].append(round(timed(lambda: plan.run_dev(d_sub, d_out, d_st)), 3))
+    plan_uci.run_dev(d_sub, d_out, d_st)
+    st = d_st.download(np.int32)
+    bits = d_out.download(np.uint8).reshape(n, plan.out_stride)
+    rec = plan_uci.uci_results()
+    tx_ok = all((bits[u, :TBS] == tx[u % nu, 0, :TBS]).all() for u in range(nu))
+    ctl_ok = all(rec[u]["ack"][:1] == ack[u % nu] and rec[u]["ri"] == ri[u % nu] for u in range(n))
+    cq = plan_uci.cqi_soft(0)
+    cqi_ok = bool((((cq < 0) == (cqi[0] == 1)) | (cq == 0)).all())
+    ctx.profile(True)
+    plan_uci.run_dev(d_sub, d_out, d_st)
+    ctx.sync()
+    split = {k: round(v[1], 4) for k, v in sorted(ctx.profile_report().items(), key=lambda kv: -kv[1][1])}
+    ctx.profile(False)
+    run_bytes = m.ulsch_uci_G(N_PRB, 6, ctl) + ctl.Q_cqi
+    gather_tb_s = 2.0 * n * run_bytes / (split["k_ulsch_uci_gather"] * 1e-3) / 1e12
+    res = {"workload": "ulsch3gpp_uci", "units": n, "tbs": TBS, "n_prb": N_PRB, "uci": {"O_ack": 1, "Qp_ack": 48, "O_ri": 2, "Qp_ri": 24, "Q_cqi": 600},
+           "steps": args.steps, "warmup": args.warmup, "plan_uci_ms": ms["uci"], "plan_plain_ms": ms["plain"],
+           "uci_over_plain": round(min(ms["uci"]) / min(ms["plain"]), 4), "plan_kernel_ms": split, "gather_bytes_in_plus_out": 2 * n * run_bytes,
+           "gather_tb_per_s": round(gather_tb_s, 3), "status_ok": int((st == 0).sum()), "distinct_units_equal_tx": bool(tx_ok),
+           "control_bits_equal_tx": bool(ctl_ok), "cqi_signs_equal_tx": cqi_ok, "device": ctx.device_name}
+    print("3GPP PUSCH plan with control information: %s ms per run of %d units, plain plan on the same subframes %s ms" % (ms["uci"], n, ms["plain"]))
+    print("k_ulsch_uci_gather %.4f ms (%.2f TB/s in + out), k_ulsch_uci_decide %.4f ms, k_dl3_rm_i8 %.4f ms"
+          % (split["k_ulsch_uci_gather"], gather_tb_s, split["k_ulsch_uci_decide"], split["k_dl3_rm_i8"]))
+    print(json.dumps(res))
+    plan_uci.close()
+    plan.close()
+    ctx.close()
+    return 0 if (st == 0).all() and tx_ok and ctl_ok and cqi_ok else 1
 
 
 if __name__ == "__main__":
