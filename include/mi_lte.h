@@ -495,7 +495,8 @@ int mi_lte_pusch_plan_cb_ok(const mi_lte_pusch_plan *plan, const uint32_t **d_ma
  *   ACK / RI symbols (5.2.2.6, tables 5.2.2.6-1 .. -4): O = 1: [o0 y x .. x]; O = 2: w = (o0, o1, o0 ^ o1), symbol n carries
  *        [w[2n mod 3] w[(2n + 1) mod 3] x .. x].
  *   Scrambling (36.211 5.3.1): x -> 1, y -> the previous scrambled bit, every other bit b ^ c(i).
- * CQI is an opaque run of Q_cqi coded bits: its block / convolutional code (5.2.2.6.4) is the caller's on both sides. */
+ * CQI is a run of Q_cqi coded bits.  Its block / convolutional code (5.2.2.6.4) is mi_lte_cqi_encode on the transmitting side and, opt-in
+ * per plan, k_ulsch_cqi_decode on the receiving one (the CQI section below); without the opt-in the run stays opaque. */
 typedef struct {
     uint8_t  O_ack, O_ri;   /* information bits: 0 (none), 1 or 2 */
     uint16_t Qp_ack, Qp_ri; /* coded symbols Q' (<= 4 M each) */
@@ -536,6 +537,43 @@ int mi_lte_pusch_plan_create_3gpp_uci(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg,
 int mi_lte_pusch_plan_uci_results(const mi_lte_pusch_plan *plan, const mi_lte_ulsch_uci_result **d_records);
 int mi_lte_pusch_plan_cqi_soft(const mi_lte_pusch_plan *plan, uint32_t alloc, const int8_t **d_cqi, uint32_t *Q_cqi);
 int mi_lte_pusch_plan_data_soft(const mi_lte_pusch_plan *plan, uint32_t alloc, const int8_t **d_data, uint32_t *G);
+
+/* ---------------------------------------------------------------- CQI channel coding on PUSCH (36.212 5.2.2.6.4)
+ * O <= 11 information bits: the (32, O) block code of table 5.2.2.6.4-1, b_i = sum_n o_n M_i,n mod 2, repeated: q_i = b_(i mod 32).
+ * O > 11 (up to MI_LTE_CQI_MAX_BITS): CRC8 (gCRC8 = D^8 + D^7 + D^4 + D^3 + D + 1, register 0) appended, L = O + 8 bits through the
+ * tail-biting convolutional code (5.1.3.1) and its rate matching (5.1.4.2) to Q_cqi bits.  A positive soft bit means bit 0.
+ * mi_lte_cqi_encode (host arithmetic, one bit per byte): MI_LTE_ERR_INVALID_ARG for O = 0, O > MI_LTE_CQI_MAX_BITS, Q_cqi = 0,
+ * Q_cqi > 6 * 12 * 1320 (the soft bits of the largest allocation) and null pointers.
+ * The decoder, k_ulsch_cqi_decode, one wavefront per run, integers throughout (every result is exact):
+ *   1. repeats add up in int32: r_i = sum of e_k over k = i mod 32 (block code); rate matching undone into d[3 L], received bit k where
+ *      transmitted bit k came from, positions never sent 0 (convolutional code).  A 0 soft bit (an ACK-overwritten cell) adds nothing.
+ *   2a. block code: the maximum of sum_i (1 - 2 b_i(o)) r_i over all 2^O words, ties to the smallest w = sum_n o_n 2^n.
+ *   2b. convolutional code: maximum-correlation Viterbi, states (c_k-1 .. c_k-6) (newest bit the most significant), all 64 metrics 0 at
+ *       the start, 3 L steps, step t on d[3 (t mod L) ..]; state n's survivor is the larger of its predecessors 2 (n & 31) and
+ *       2 (n & 31) + 1 by metric + sum_x (1 - 2 label_x) d_x, the even one on a tie; end state: the first maximum in state order;
+ *       traceback over all 3 L steps, the bits of steps L .. 2 L - 1 are c_0 .. c_(L-1); CRC8 is checked over them.
+ * A DTX decision is the caller's: metric against energy. */
+#define MI_LTE_CQI_MAX_BITS 128
+enum { MI_LTE_CQI_NONE = 0, MI_LTE_CQI_NO_CRC = 1 /* block code */, MI_LTE_CQI_CRC_OK = 2, MI_LTE_CQI_CRC_FAIL = 3 };
+typedef struct {
+    uint32_t O;        /* 0: nothing decoded for this run */
+    uint32_t crc;      /* MI_LTE_CQI_* */
+    int32_t  metric;   /* correlation of the decided code word (convolutional: the decided L bits re-encoded) with r / d */
+    int32_t  energy;   /* sum |r_i| or sum |d_k|: what a caller normalises a DTX threshold by */
+    uint32_t bits[4];  /* information bit n at bit (n & 31) of word n >> 5; unused bits 0 */
+} mi_lte_cqi_result;
+typedef struct { uint32_t off /* bytes from d_soft, even */, Q_cqi, O, pad; } mi_lte_cqi_desc;
+int mi_lte_cqi_encode(uint32_t O, const uint8_t *o_bits, uint32_t Q_cqi, uint8_t *q_bits /*[Q_cqi]*/);
+/* n runs of int8 soft bits, everything device-resident, one launch on the context's stream (no wait).  d_soft is 2-byte aligned and run i
+ * spans d_soft + off .. + Q_cqi.  The kernel checks the descriptors itself: O = 0, O > MI_LTE_CQI_MAX_BITS, Q_cqi = 0,
+ * Q_cqi > 6 * 12 * 1320 or an odd off yield the all-zero record and read nothing. */
+int mi_lte_cqi_decode_batch(mi_lte_ctx *ctx, const int8_t *d_soft, const mi_lte_cqi_desc *d_desc, uint32_t n, mi_lte_cqi_result *d_out);
+/* A plan of mi_lte_pusch_plan_create_3gpp_uci decodes the CQI of allocation a as h_O_cqi[a] information bits (0: left opaque) from its next
+ * run on: k_ulsch_cqi_decode once, behind k_ulsch_uci_decide, over the runs mi_lte_pusch_plan_cqi_soft hands out.  h_O_cqi = NULL turns
+ * decoding off again.  MI_LTE_ERR_INVALID_ARG, the plan left as it was: any other plan, O > MI_LTE_CQI_MAX_BITS, O > 0 where Q_cqi = 0. */
+int mi_lte_pusch_plan_set_cqi_decode(mi_lte_pusch_plan *plan, const uint32_t *h_O_cqi /*[n_alloc]*/);
+/* the n_alloc records (device pointer into the plan): all zero before a first run with decoding on and for allocations left opaque */
+int mi_lte_pusch_plan_cqi_results(const mi_lte_pusch_plan *plan, const mi_lte_cqi_result **d_records);
 
 /* PRACH detection: replaces liblte_phy_detect_prach() (liblte_phy.h:862-868, implementation liblte_phy.cc:3299-3479)
  * for a batch of PRACH occasions (d_occ_start[o] = sample index of the occasion's first cyclic-prefix sample; an

@@ -198,8 +198,12 @@ int mi_ulsch_uci_create(mi_lte_ctx *ctx, const mi_lte_pdsch_alloc *h_allocs, con
     MI_HIP_CHECK(ctx, hipMalloc((void **)&u->d_e, std::max<size_t>(e_bytes, 64)));
     MI_HIP_CHECK(ctx, hipMalloc((void **)&u->d_e_len, sizeof(uint32_t) * n_alloc));
     MI_HIP_CHECK(ctx, hipMalloc((void **)&u->d_res, sizeof(mi_lte_ulsch_uci_result) * n_alloc));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&u->d_cqi_desc, sizeof(mi_lte_cqi_desc) * n_alloc));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&u->d_cqi_res, sizeof(mi_lte_cqi_result) * n_alloc));
     MI_HIP_CHECK(ctx, hipMemsetAsync(u->d_e, 0, std::max<size_t>(e_bytes, 64), ctx->stream)); // (the taps read defined bytes before a first run)
     MI_HIP_CHECK(ctx, hipMemsetAsync(u->d_res, 0, sizeof(mi_lte_ulsch_uci_result) * n_alloc, ctx->stream));
+    MI_HIP_CHECK(ctx, hipMemsetAsync(u->d_cqi_desc, 0, sizeof(mi_lte_cqi_desc) * n_alloc, ctx->stream));
+    MI_HIP_CHECK(ctx, hipMemsetAsync(u->d_cqi_res, 0, sizeof(mi_lte_cqi_result) * n_alloc, ctx->stream));
     MI_H2D(ctx, u->d_desc, desc.data(), sizeof(UciDesc) * n_alloc);
     MI_H2D(ctx, u->d_e_len, u->h_G.data(), sizeof(uint32_t) * n_alloc);
     MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -215,6 +219,8 @@ void mi_ulsch_uci_free(MiUlschUci *u)
     (void)hipFree(u->d_e);
     (void)hipFree(u->d_e_len);
     (void)hipFree(u->d_res);
+    (void)hipFree(u->d_cqi_desc);
+    (void)hipFree(u->d_cqi_res);
     delete u;
 }
 

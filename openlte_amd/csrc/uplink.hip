@@ -17,7 +17,8 @@
 // The 3GPP transport-block mode (mi_lte_pusch_plan_create_3gpp, include/mi_lte.h) is the same chain as 36.211 / 36.212 specify it: the
 // pre-decoder's output times 1 / sqrt(M) (36.211 5.3.3; k_pusch_demod<.., SPEC = true>), so that 16QAM and 64QAM de-map and QPSK keeps its
 // soft information, and transport blocks of 1 .. 13 code blocks through dlsch3gpp.hip's kernels with N_cb = K_w (36.212 5.2.2).  With control
-// information (mi_lte_pusch_plan_create_3gpp_uci) ulsch_uci.hip's two kernels run between the demodulator, which is the same, and the code blocks.
+// information (mi_lte_pusch_plan_create_3gpp_uci) ulsch_uci.hip's two kernels run between the demodulator, which is the same, and the code blocks,
+// and behind them, opt-in (mi_lte_pusch_plan_set_cqi_decode), ulsch_cqi.hip's CQI decoder.
 //
 // The DFT sizes are not powers of two and FFTW's operation order is unspecified, so like the downlink FFT
 // this stage is tolerance-checked; everything from the int8 soft bits on is integer-exact.
@@ -693,6 +694,19 @@ int mi_lte_pusch_plan_cqi_soft(const mi_lte_pusch_plan *pl, uint32_t alloc, cons
     return MI_LTE_OK;
 }
 
+int mi_lte_pusch_plan_set_cqi_decode(mi_lte_pusch_plan *pl, const uint32_t *h_O_cqi)
+{
+    if (!pl || !pl->uci) return MI_LTE_ERR_INVALID_ARG;
+    return mi_ulsch_cqi_set(pl->uci, pl->core.h_e_off.data(), pl->core.e_bytes, h_O_cqi);
+}
+
+int mi_lte_pusch_plan_cqi_results(const mi_lte_pusch_plan *pl, const mi_lte_cqi_result **d_records)
+{
+    if (!pl || !pl->uci || !d_records) return MI_LTE_ERR_INVALID_ARG;
+    *d_records = pl->uci->d_cqi_res;
+    return MI_LTE_OK;
+}
+
 int mi_lte_pusch_plan_set_decoder(mi_lte_pusch_plan *pl, uint32_t mode, uint32_t n_iter, int qpp_spec)
 {
     if (!pl) return MI_LTE_ERR_INVALID_ARG;
@@ -786,11 +800,15 @@ int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float 
         MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/true);
         if (pl->uci) { // control information: rate un-matching reads the gathered data run (G soft bits per allocation, the same offsets)
             if ((rc = mi_ulsch_uci_run(ctx, pl->uci, pl->core.d_e, pl->core.d_e_off)) != MI_LTE_OK) return rc;
+            if (pl->uci->cqi_on && (rc = mi_ulsch_cqi_run(ctx, pl->uci)) != MI_LTE_OK) return rc; // (opt-in: mi_lte_pusch_plan_set_cqi_decode)
             io.d_e = pl->uci->d_e; io.d_e_len = pl->uci->d_e_len;
         }
         if ((rc = mi_dlsch3_run(ctx, pl->g3, nullptr, nullptr, io, pl->decoder, pl->n_iter)) != MI_LTE_OK) return rc;
         const size_t at = ctx->last_kernels.find(','); // (mi_dlsch3_run lists the downlink's demodulator in front of its own kernels)
-        ctx->last_kernels.replace(0, at == std::string::npos ? 0 : at, pl->uci ? "k_pusch_demod:1,k_ulsch_uci_gather:1,k_ulsch_uci_decide:1" : "k_pusch_demod:1");
+        ctx->last_kernels.replace(0, at == std::string::npos ? 0 : at,
+                                  !pl->uci        ? "k_pusch_demod:1"
+                                  : pl->uci->cqi_on ? "k_pusch_demod:1,k_ulsch_uci_gather:1,k_ulsch_uci_decide:1,k_ulsch_cqi_decode:1"
+                                                    : "k_pusch_demod:1,k_ulsch_uci_gather:1,k_ulsch_uci_decide:1");
         return MI_LTE_OK;
     }
     // several block sizes (the UEs of a subframe rarely share one): one launch set over all of them, as in the PDSCH chain

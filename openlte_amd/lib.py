@@ -113,6 +113,38 @@ def ulsch_uci_map(N_prb, Q_m, uci):
     return kind.reshape(M, 12), index.reshape(M, 12, 2)
 
 
+class CqiResult(C.Structure):
+    """mi_lte_cqi_result: one decoded CQI run.  O = 0: nothing decoded; crc: CQI_NONE / CQI_NO_CRC (block code) / CQI_CRC_OK / CQI_CRC_FAIL;
+    metric: the decided code word's correlation with the combined soft bits, energy: the sum of their magnitudes; bits: information bit n
+    at bit n & 31 of word n >> 5."""
+    _fields_ = [("O", C.c_uint32), ("crc", C.c_uint32), ("metric", C.c_int32), ("energy", C.c_int32), ("bits", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {"O": self.O, "crc": self.crc, "metric": self.metric, "energy": self.energy, "bits": list(self.bits)}
+
+
+class CqiDesc(C.Structure):
+    """mi_lte_cqi_desc: a run of Q_cqi soft bits at byte `off` (even) of the batch's soft bits, O information bits"""
+    _fields_ = [("off", C.c_uint32), ("Q_cqi", C.c_uint32), ("O", C.c_uint32), ("pad", C.c_uint32)]
+
+
+CQI_NONE, CQI_NO_CRC, CQI_CRC_OK, CQI_CRC_FAIL = range(4)
+CQI_MAX_BITS, CQI_MAX_Q = 128, 6 * 12 * 1320
+
+
+def cqi_encode(O, bits, Q_cqi):
+    """mi_lte_cqi_encode (host arithmetic): the Q_cqi coded bits of O CQI information bits (36.212 5.2.2.6.4), one per byte -- what
+    synth.ul_units_3gpp takes as `cqi`."""
+    bits = np.ascontiguousarray(bits, np.uint8)
+    if len(bits) < O:
+        raise ValueError("cqi_encode: %d information bits given, O = %d" % (len(bits), O))
+    out = np.zeros(Q_cqi if 0 < Q_cqi <= CQI_MAX_Q else 1, np.uint8)  # (a refused size is not allocated)
+    rc = load_library().mi_lte_cqi_encode(O, bits.ctypes.data, Q_cqi, out.ctypes.data)
+    if rc != 0:
+        raise MiLteError("mi_lte_cqi_encode(%d, %d) failed: %d" % (O, Q_cqi, rc), rc)
+    return out
+
+
 HARQ_NONE, HARQ_NEW_DATA = 0xFFFFFFFF, 1
 
 
@@ -326,6 +358,10 @@ def load_library():
     L.mi_lte_pusch_plan_uci_results.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_pusch_plan_cqi_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32)]
     L.mi_lte_pusch_plan_data_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32)]
+    L.mi_lte_cqi_encode.argtypes = [u32, vp, u32, vp]
+    L.mi_lte_cqi_decode_batch.argtypes = [vp, vp, vp, u32, vp]
+    L.mi_lte_pusch_plan_set_cqi_decode.argtypes = [vp, vp]
+    L.mi_lte_pusch_plan_cqi_results.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_prach_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), C.POINTER(vp)]
     L.mi_lte_prach_plan_create_roots.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), f32p, f32p, u32, C.POINTER(vp)]
     L.mi_lte_prach_plan_destroy.argtypes = [vp, vp]
@@ -752,6 +788,31 @@ class PuschPlan:
         self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, C.addressof(rec), p.value, C.sizeof(rec)))
         return [{"ack": list(r.ack), "ri": list(r.ri), "S_ack": list(r.S_ack), "S_ri": list(r.S_ri)} for r in rec]
 
+    def set_cqi_decode(self, O_list):
+        """Plan with control information: decode the CQI of allocation a as O_list[a] information bits (0: left opaque) from the next run
+        on (k_ulsch_cqi_decode behind k_ulsch_uci_decide); None turns decoding off again.  A refusal (MiLteError, -1) leaves the plan as
+        it was: a plan without control information, O > CQI_MAX_BITS, O > 0 on an allocation without CQI."""
+        if O_list is None:
+            arr = None
+        else:
+            if len(O_list) != self.n_alloc:
+                raise ValueError("set_cqi_decode: one O per allocation")
+            arr = np.ascontiguousarray(O_list, np.uint32)
+        rc = self.ctx.L.mi_lte_pusch_plan_set_cqi_decode(self.h, None if arr is None else arr.ctypes.data)
+        if rc != 0:
+            raise MiLteError("mi_lte_pusch_plan_set_cqi_decode failed: %d" % rc, rc)
+
+    def cqi_results(self):
+        """Plan with control information: one CqiResult.as_dict() per allocation -- all zero before a first run with decoding on and
+        for allocations left opaque."""
+        p = C.c_void_p()
+        rc = self.ctx.L.mi_lte_pusch_plan_cqi_results(self.h, C.byref(p))
+        if rc != 0:
+            raise MiLteError("mi_lte_pusch_plan_cqi_results failed: %d" % rc, rc)
+        rec = (CqiResult * self.n_alloc)()
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, C.addressof(rec), p.value, C.sizeof(rec)))
+        return [r.as_dict() for r in rec]
+
     def close(self):
         if self.h:
             self.ctx.L.mi_lte_pusch_plan_destroy(self.ctx.h, self.h)
@@ -1128,6 +1189,29 @@ class Context:
         return PuschPlan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, spec=True, uci=uci)
 
     # ---- PDSCH ------------------------------------------------------------------------------
+    def cqi_decode_batch(self, soft, descs):
+        """mi_lte_cqi_decode_batch on host data: soft int8 [n], descs a list of (off, Q_cqi, O); one CqiResult.as_dict() per descriptor.
+        A descriptor the kernel cannot serve (O of 0 or > CQI_MAX_BITS, Q_cqi of 0 or > CQI_MAX_Q, odd off) gives the all-zero record;
+        one it would serve must lie inside soft."""
+        soft = np.ascontiguousarray(soft, np.int8)
+        arr = (CqiDesc * len(descs))(*[CqiDesc(off, q, o, 0) for off, q, o in descs])
+        for d in arr:
+            if 1 <= d.O <= CQI_MAX_BITS and 1 <= d.Q_cqi <= CQI_MAX_Q and d.off % 2 == 0 and d.off + d.Q_cqi > len(soft):
+                raise ValueError("cqi_decode_batch: run at %d + %d past the %d soft bits" % (d.off, d.Q_cqi, len(soft)))
+        d_soft, d_desc, d_out = self.alloc(max(soft.nbytes, 2)), self.alloc(C.sizeof(arr)), self.alloc(C.sizeof(CqiResult) * len(descs))
+        try:
+            if soft.nbytes:
+                d_soft.upload(soft)
+            self._check(self.L.mi_lte_memcpy_h2d(self.h, d_desc.ptr, C.addressof(arr), C.sizeof(arr)))
+            self._check(self.L.mi_lte_cqi_decode_batch(self.h, d_soft.ptr, d_desc.ptr, len(descs), d_out.ptr))
+            rec = (CqiResult * len(descs))()
+            self._check(self.L.mi_lte_memcpy_d2h(self.h, C.addressof(rec), d_out.ptr, C.sizeof(rec)))
+            return [r.as_dict() for r in rec]
+        finally:
+            d_soft.free()
+            d_desc.free()
+            d_out.free()
+
     def pdsch_plan(self, cfg, n_pdcch_symbs, allocs):
         return PdschPlan(self, cfg, n_pdcch_symbs, allocs)
 

@@ -6,11 +6,15 @@ mi_lte_turbo_decode_batch BCJR x 8 on the same 26 624 rate-un-matched blocks (th
 time in both variants from the same process: the 3GPP plan's and a reference-mode plan's over the same grids with one-block QPSK transport
 blocks on the same 99 PRB (the reference-mode envelope; the demodulator's work does not depend on the transport block).
 
-    python tools/ulsch3gpp_bench.py [--units 2048] [--steps 10] [--warmup 2] [--uci]
+    python tools/ulsch3gpp_bench.py [--units 2048] [--steps 10] [--warmup 2] [--uci | --cqi]
 --uci: the same grants with control information multiplexed on them (HARQ-ACK O = 1, Q' = 48; RI O = 2, Q' = 24; 600 coded CQI bits): the run of a
 plan of mi_lte_pusch_plan_create_3gpp_uci against a plain 3GPP plan of the same build on the same subframes (alternated; the plain plan rate
 un-matches over the wrong G and fails its CRCs there, which costs it nothing: the decoders run a fixed eight iterations), the per-kernel split with
 k_ulsch_uci_gather and k_ulsch_uci_decide next to k_dl3_rm_i8, and the gather's bytes per second (every soft byte once in and once out).
+--cqi: the --uci grants with real CQI reports in the 600 coded bits (mi_lte_cqi_encode: O = 11, the block code, on the even subframes, O = 64,
+CRC8 and the convolutional code, on the odd ones) and the plan decoding them (mi_lte_pusch_plan_set_cqi_decode): the run with decoding off,
+with every allocation decoded as O = 11 and with every allocation as O = 64, alternated (the kernel's work does not depend on what was sent),
+k_ulsch_cqi_decode's own time in both, and the records of a run with each allocation's own O against the sent reports.
 Prints one JSON line last."""
 import argparse
 import ctypes as C
@@ -34,7 +38,9 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--uci", action="store_true", help="the control-information leg (see above)")
+    ap.add_argument("--cqi", action="store_true", help="the CQI decoding leg (see above)")
     args = ap.parse_args()
+    cqi_leg_on, args.uci = args.cqi, args.uci or args.cqi
     ctx = m.Context(0)
     cfg, ul = m.DlCfg(2048, 100, 1, m.IQ_I8), m.UlCfg(3, 0, 0, 2, 1)
     nu, n, cell = args.unique, args.units, 42
@@ -43,6 +49,10 @@ def main():
     ctl = m.UlschUci(1, 2, 48, 24, 600) if args.uci else None
     ack, ri = [[u & 1] for u in range(nu)], [[(u >> 1) & 1, u & 1] for u in range(nu)]
     cqi = np.random.default_rng(5).integers(0, 2, (nu, 600)).astype(np.uint8)
+    cqi_O = [11 if u % 2 == 0 else 64 for u in range(nu)]
+    cqi_o = [np.random.default_rng(50 + u).integers(0, 2, cqi_O[u]).astype(np.uint8) for u in range(nu)]
+    if cqi_leg_on:
+        cqi = np.stack([m.cqi_encode(cqi_O[u], cqi_o[u], 600) for u in range(nu)])
     iq, tx = synth.ul_units_3gpp(cfg, ul, sfs_u, [cell] * nu, [m.make_alloc(i, 3, TBS, prbs, 0x100 + i) for i in range(nu)], 1, snr_db=30.0,
                                  max_delay=3, seed=11, **(dict(uci=[ctl] * nu, ack=ack, ri=ri, cqi=cqi) if args.uci else {}))
     ulen = iq.shape[1]
@@ -66,6 +76,10 @@ def main():
             fn()
         return ctx.timer_stop() / args.steps
 
+    if cqi_leg_on:
+        plan_ref.close()
+        plan.close()
+        return cqi_leg(ctx, args, cfg, ul, sfs, cell, prbs, ctl, cqi_O, cqi_o, tx, d_sub, timed, d_out, d_st)
     if args.uci:
         plan_ref.close()
         return uci_leg(ctx, args, cfg, ul, sfs, cell, prbs, ctl, ack, ri, cqi, tx, d_sub, plan, timed, d_out, d_st)
@@ -144,6 +158,51 @@ def uci_leg(ctx, args, cfg, ul, sfs, cell, prbs, ctl, ack, ri, cqi, tx, d_sub, p
     plan.close()
     ctx.close()
     return 0 if (st == 0).all() and tx_ok and ctl_ok and cqi_ok else 1
+
+
+def cqi_leg(ctx, args, cfg, ul, sfs, cell, prbs, ctl, cqi_O, cqi_o, tx, d_sub, timed, d_out, d_st):
+    n, nu = args.units, args.unique
+    plan = ctx.pusch_plan_3gpp(cfg, ul, sfs, [cell] * n, [m.make_alloc(u, 3, TBS, prbs, 0x100 + u % nu) for u in range(n)], uci=[ctl] * n)
+    legs = {"off": None, "O11": [11] * n, "O64": [64] * n}
+    ms, kernel_ms = {k: [] for k in legs}, {}
+    for _ in range(3):  # alternated
+        for k, O_list in legs.items():
+            plan.set_cqi_decode(O_list)
+            ms[k].append(round(timed(lambda: plan.run_dev(d_sub, d_out, d_st)), 3))
+    for k, O_list in legs.items():
+        plan.set_cqi_decode(O_list)
+        plan.run_dev(d_sub, d_out, d_st)
+        ctx.profile(True)
+        plan.run_dev(d_sub, d_out, d_st)
+        ctx.sync()
+        rep = ctx.profile_report()
+        ctx.profile(False)
+        kernel_ms[k] = {name: round(rep[name][1], 4) for name in ("k_ulsch_uci_gather", "k_ulsch_uci_decide", "k_ulsch_cqi_decode") if name in rep}
+    plan.set_cqi_decode([cqi_O[u % nu] for u in range(n)])
+    plan.run_dev(d_sub, d_out, d_st)
+    st = d_st.download(np.int32)
+    bits = d_out.download(np.uint8).reshape(n, plan.out_stride)
+    rec = plan.cqi_results()
+    tx_ok = all((bits[u, :TBS] == tx[u % nu, 0, :TBS]).all() for u in range(nu))
+
+    def sent(u):
+        O, words = cqi_O[u % nu], [0, 0, 0, 0]
+        for i, b in enumerate(cqi_o[u % nu]):
+            words[i >> 5] |= int(b) << (i & 31)
+        return (O, m.CQI_NO_CRC if O <= 11 else m.CQI_CRC_OK, words)
+
+    cqi_ok = all((rec[u]["O"], rec[u]["crc"], rec[u]["bits"]) == sent(u) for u in range(n))
+    res = {"workload": "ulsch3gpp_cqi", "units": n, "tbs": TBS, "n_prb": N_PRB, "uci": {"O_ack": 1, "Qp_ack": 48, "O_ri": 2, "Qp_ri": 24, "Q_cqi": 600},
+           "steps": args.steps, "warmup": args.warmup, "plan_ms": ms, "on_minus_off_ms": {k: round(min(ms[k]) - min(ms["off"]), 3) for k in ("O11", "O64")},
+           "kernel_ms": kernel_ms, "status_ok": int((st == 0).sum()), "distinct_units_equal_tx": bool(tx_ok), "cqi_reports_equal_tx": bool(cqi_ok),
+           "record_0": rec[0], "record_1": rec[1], "device": ctx.device_name}
+    print("3GPP PUSCH plan with control information, ms per run of %d units: CQI decoding off %s, O = 11 %s, O = 64 %s" % (n, ms["off"], ms["O11"], ms["O64"]))
+    print("k_ulsch_cqi_decode: O = 11 %.4f ms, O = 64 %.4f ms; k_ulsch_uci_gather %.4f ms"
+          % (kernel_ms["O11"]["k_ulsch_cqi_decode"], kernel_ms["O64"]["k_ulsch_cqi_decode"], kernel_ms["off"]["k_ulsch_uci_gather"]))
+    print(json.dumps(res))
+    plan.close()
+    ctx.close()
+    return 0 if (st == 0).all() and tx_ok and cqi_ok else 1
 
 
 if __name__ == "__main__":
