@@ -25,17 +25,15 @@
 // metric g(u,z) = [u==0](Ls+La) + [z==0]Lp, positive LLR = bit 0.
 #include "ctx.hpp"
 
+using namespace turbo_geom;
+
 namespace {
 
 constexpr int BCJR_NEG = -6000, BCJR_X_MAX = 340, BCJR_LE_MAX = 254;
 
-__host__ __device__ inline uint32_t kpad64(uint32_t K) { return (K + 63u) & ~63u; }
 __device__ __forceinline__ int sb(uint32_t w, int k) { return (int)__builtin_amdgcn_sbfe(w, 8 * k, 8); }
 
 __device__ __forceinline__ size_t g8(uint32_t tile, uint32_t Kp, uint32_t lane, uint32_t gran) { return (size_t)tile * Kp * 64 + (size_t)gran * 1024 + lane * 16; }   // byte offset, int8 granule arrays
-// XCD-aware block -> code block mapping of the per-code-block kernels (see turbo.hip)
-__host__ __device__ inline uint32_t xcd_chunk(uint32_t n_cb) { return ((((n_cb + 63u) >> 6) + 7u) >> 3) << 6; }
-__device__ __forceinline__ uint32_t xcd_cb(uint32_t b, uint32_t n_cb) { return (b & 7u) * xcd_chunk(n_cb) + (b >> 3); }
 
 __host__ __device__ inline uint32_t bcjr_n_seg(uint32_t K)
 {
@@ -827,9 +825,9 @@ int mi_turbo_bcjr_batch(mi_lte_ctx *ctx, const int8_t *d_soft, uint32_t K, uint3
     if (rc != MI_LTE_OK) return rc;
     BcjrBufs B{mb.S1, mb.P1, mb.S2, mb.P2, mb.tail};
     const size_t   Kp = kpad64(K);
-    const uint32_t cb_threads = (uint32_t)(((Kp >> 4) + 63) & ~(size_t)63);
+    const uint32_t cb_threads = cb_width(K);
     static const bool one_per_wg = [] { const char *e = getenv("MI_LTE_BCJR_PREP1"); return e && atoi(e) != 0; }(); // (A/B: the one-block-per-workgroup kernel)
-    if (one_per_wg || 8 * Kp > 64 * 1024) MI_LAUNCH(ctx, "k_bcjr_prep", k_bcjr_prep, dim3(8 * xcd_chunk(n_cb)), dim3(cb_threads), Kp, d_soft, K, n_cb, tb.d_pi, B);
+    if (one_per_wg || 8 * Kp > 64 * 1024) MI_LAUNCH(ctx, "k_bcjr_prep", k_bcjr_prep, dim3(cb_grid(n_cb)), dim3(cb_threads), Kp, d_soft, K, n_cb, tb.d_pi, B);
     else MI_LAUNCH(ctx, "k_bcjr_prep", k_bcjr_prep8, dim3(xcd_chunk(n_cb)), dim3(512), 8 * Kp, d_soft, K, n_cb, tb.d_pi, B);
     (void)cb_threads;
     return mi_turbo_bcjr_iterate(ctx, K, n_cb, n_iter, qpp_spec, d_c_bits, early);

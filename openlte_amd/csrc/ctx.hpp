@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mi_lte.h"
+#include "turbo_plan.hpp"
 
 struct TurboTables {       // device-resident per-K tables
     uint16_t *d_pi  = nullptr; // interleaver index pi[i]
@@ -131,20 +132,7 @@ hipError_t mi_stream_wait_polling(mi_lte_ctx *ctx); // the per-call forms' wait:
 int   mi_ctx_gold_tables(mi_lte_ctx *ctx);
 int   mi_ctx_crc_table(mi_lte_ctx *ctx);
 int   mi_ctx_fft_twiddles(mi_lte_ctx *ctx);
-// the REF decode of a plan's block-size groups: many sizes in one launch set (turbo.hip: KSeg, mi_turbo_ref_multi) or size by size
-struct MiKGroup { uint32_t K, n_cb, cb_base, e_max; }; // a block size's code blocks: slots cb_base .. cb_base + n_cb of the batch's code-block order; e_max: its longest allocation's soft bits
-struct MiMultiGeom { // launch geometry derived from the groups; classes = workgroup widths 64 (c + 1)
-    uint64_t arr_bytes = 0;                           // bytes of one scratch array over all sizes
-    uint32_t n_slots = 0, n_wv1 = 0, n_wv23 = 0;
-    uint32_t grid_cb[6] = {0}, grid_perm[6] = {0}, lds_prep[6] = {0}, kp_max[6] = {0};
-    uint32_t map_cb[6] = {0}, map_perm[6] = {0}, map_wv1 = 0, map_wv23 = 0; // where each launch's map starts (entries)
-    uint32_t ord_wv1 = 0, ord_wv23 = 0, n_ord1 = 0, n_ord23 = 0;             // the trellis kernel's launch order: launched wavefront -> wavefront of the map (entries; 0 = none)
-    uint32_t siso_pad1 = 0, siso_pad23 = 0;                                  // dynamic LDS the trellis kernel is launched with: it holds nothing, it limits the resident workgroups per compute unit
-    int      one_size[6] = {-1, -1, -1, -1, -1, -1};   // the index of a width's ONLY size (its prep launch then takes the per-size kernel), -1 otherwise
-    uint64_t off_one[6] = {0}; uint32_t e_cap_one[6] = {0};
-    uint32_t map_ws1 = 0, map_ws23 = 0, n_ws1 = 0, n_ws23 = 0, gpw1 = 1, gpw23 = 1, kp_all = 0; // the state-parallel trellis kernel's launches (a handful of blocks)
-    size_t   map_off = 0;                             // bytes from the table's start to the maps
-};
+// the merged REF decode's device tables for the groups they were built for (turbo_plan.hpp; turbo.hip: mi_turbo_ref_multi)
 struct MiMultiCache { void *d_tab = nullptr; size_t cap = 0; std::vector<MiKGroup> built_for; MiMultiGeom geom; };
 void  mi_multi_cache_free(MiMultiCache *cache);
 int   mi_ctx_turbo_tables(mi_lte_ctx *ctx, uint32_t K, int spec, TurboTables *out);

@@ -20,16 +20,17 @@
 // Kernel sequence per batch:  prep -> siso(pass 1) -> perm -> siso(pass 2 | pass 3) -> vote
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
 #include <vector>
 
 #include "plan_core.hpp"
 
+using namespace turbo_geom;
+
 namespace {
 
 constexpr uint32_t RX_NULL_AS_INT = 10000; // RX_NULL_BIT, liblte_phy.cc:1620
-
-__host__ __device__ inline uint32_t kpad64(uint32_t K) { return (K + 63u) & ~63u; }
 
 // ------------------------------------------------------------------------------------------------
 // small device helpers
@@ -138,13 +139,6 @@ __device__ __forceinline__ void block_max_i2(int &a, int &b, int *red)
 
 struct PrepOut { uint8_t *arr[6]; }; // X0 X1 X2 I0 M1 M2
 
-// XCD-aware block -> code block mapping for the one-workgroup-per-code-block kernels.  Workgroup b runs
-// on XCD b % 8 (observed dispatch order; used for speed only), and a tile line is 64 bytes per code
-// block inside a 4 KiB burst shared by 64 code blocks: giving each XCD a contiguous range of tiles keeps
-// all writers (readers) of a burst behind one L2, so lines leave for HBM whole instead of in halves.
-__host__ __device__ inline uint32_t xcd_chunk(uint32_t n_cb) { return ((((n_cb + 63u) >> 6) + 7u) >> 3) << 6; } // code blocks per XCD
-__device__ __forceinline__ uint32_t xcd_cb(uint32_t b, uint32_t n_cb) { return (b & 7u) * xcd_chunk(n_cb) + (b >> 3); }
-
 // ------------------------------------------------------------------------------------------------
 // prep: Step 0 (NULL -> 0), Step 1 scaling to int8, Step 4 (interleave d0), SISO output magnitudes
 // for passes 1 and 2.  One workgroup per code block.
@@ -201,7 +195,6 @@ __device__ __forceinline__ void unpack_idx16(const IdxRaw &r, uint32_t (&idx)[16
     for (int k = 0; k < 16; k++) idx[k] = (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
 }
 
-struct KSeg; // (a block size's row of a merged decode's table, below)
 typedef __attribute__((address_space(4))) const KSeg const_seg_fwd_t;
 // ---- where the soft values of a code block come from
 // (a) directly from the caller, in the reference's interleaved d[i*3+x] layout
@@ -346,29 +339,7 @@ struct GroupDesc {                 // one launch = the code blocks of one size K
     const CbDesc   *desc;          // [n_cb] filled by k_cb_desc before the first kernel of the group (REF decoder)
 };
 
-// One block size of a MERGED decode (mi_turbo_ref_multi: a PDSCH batch whose allocations have many code-block sizes -- a cell's TTIs
-// have dozens of the 188).  Launched size by size such a batch is ~7 launches per size in series, each far too small for the device (a
-// trellis walk is as long for one tile as for a thousand); merged, every kernel below is launched ONCE over the tiles / code blocks of
-// all sizes (the per-code-block kernels once per workgroup width, 64 .. 384 threads), and what the per-size launches pass as kernel
-// arguments -- K, the block count, the interleaver and rank tables, where the size's tiles lie in the scratch arrays -- is read from
-// this table by the workgroup (wavefront) at its start: one scalar load of its index in `map`, then scalar loads of the row.
-struct KSeg {
-    uint32_t        K, n_cb, cb_base, n_tiles; // cb_base: the size's first slot in the batch's code-block order (cb_alloc, desc)
-    uint32_t        wg_cb;                     // first workgroup of the size in its prep / vote launch (a multiple of 8: blockIdx % 8 = XCD)
-    uint32_t        wg_perm, perm_grid;        // the same for perm, and the size's own grid there (a workgroup takes PERM_NB blocks grid apart)
-    uint32_t        e_cap;                     // LDS bytes prep stages an allocation's soft bits in (0: gathers from global memory)
-    uint32_t        wv1, wv23;                 // first wavefront of the size in SISO pass 1 / passes 2 + 3
-    uint64_t        arr_off;                   // where the size's tiles start in each of the eleven byte arrays (traceback words: half of it)
-    // mi_ctx_turbo_tables / rm_rank_tables of K.  Typed as GLOBAL pointers: a pointer that comes out of memory is otherwise of unknown address
-    // space and every load through it a flat_load, which counts against the LDS counter too -- k_turbo_prep's LDS gathers then waited for its
-    // table loads (W4 as a merged decode: 4.88 ms, 4.53 without them)
-    __attribute__((address_space(1))) const uint16_t *pi, *inv2, *tabs;
-    __attribute__((address_space(1))) const uint32_t *nnn;
-    uint32_t        ws1, ws23;                 // first workgroup of the size in the state-parallel trellis kernel's launches (a handful of blocks: k_turbo_siso_small)
-    uint64_t        pad;
-};
-static_assert(sizeof(KSeg) == 96, "KSeg is read with scalar loads: keep it a multiple of 16 bytes");
-struct MultiArgs { const KSeg *segs; const uint32_t *map; }; // map: per 512 workgroups (prep, vote: a size's grid is a multiple of that), per 128 (perm), per wavefront (siso) the index of its size
+// A merged decode's table (turbo_plan.hpp: KSeg, MultiArgs) as the kernels read it.
 // Both reads go through the CONSTANT address space: only then are they scalar loads (the kernels store to global memory, and a plain pointer
 // carries no promise that the table is not what they store to); the scalar cache serves the row every workgroup of a CU reads.
 // What remains: on W4 (two sizes of 8192 and 1024 tiles, each filling the device by itself) the merged k_turbo_prep takes 4.3-4.5 ms
@@ -606,19 +577,6 @@ __device__ __forceinline__ void SrcRateUnmatch::seg(const_seg_fwd_t &sg)
     tabs = (const uint16_t *)sg.tabs; nnn = (const uint32_t *)sg.nnn; g.desc += sg.cb_base;
 }
 struct SrcRateUnmatchPk : SrcRateUnmatch { static constexpr bool kPacked = true; };
-
-// LDS tables that replace the per-element IEEE divisions: the quantiser and the SISO output magnitude
-// are functions of one small integer and a per-block constant, so each distinct value is divided once
-// (with exactly the reference's float expression) and every element looks its result up.
-constexpr uint32_t QTAB_N = 4096; // q(x) for |x| <= 2047 (signed index x + max on the integer path); larger maxima divide per element
-constexpr uint32_t QTAB_HALF = 2048;
-constexpr uint32_t MTAB_N = 256;  // w = |a|+|b| <= 254
-// k_turbo_prep's LDS: mtab1 | mtab2 | reduction scratch (64 B) | { staged e [e_cap]  OVER  qtab [QTAB_N] | q(d0) [Kp] }.  The soft bits are dead once
-// every wavefront has summed its own (the first block-wide maximum is the fence), the quantiser table and q(d0) are written after it: they
-// share the bytes.  Before round 6 the four lay side by side -- 9.7 KB for a 64-thread workgroup, 16.7 for a 128-thread one, which held those
-// widths at 4 and 4.5 wavefronts per SIMD where the registers allow 6.
-constexpr uint32_t PREP_RED_AT = 2 * MTAB_N, PREP_E_AT = PREP_RED_AT + 64, PREP_QTAB_AT = PREP_E_AT, PREP_Q0_AT = PREP_QTAB_AT + QTAB_N;
-__host__ __device__ constexpr uint32_t prep_lds_bytes(uint32_t Kp, uint32_t e_cap) { return PREP_E_AT + (e_cap > QTAB_N + Kp ? e_cap : QTAB_N + Kp); }
 
 // byte-parallel helpers for the per-code-block kernels.  Soft values travel as four int8 per register; |a| of one of them is
 // the masked byte SAD of the biased word (x + 128 per byte, i.e. word ^ 0x80808080) against 0x80 in that byte alone
@@ -1184,7 +1142,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
 // bits only (state s came from 2(s&3) + bit[s&3]); maps compose associatively, so a suffix scan over the 64 steps of a chunk (lanes as
 // steps again, a map = 8 x 3 bits in a register) gives every step's state at once, and with it the sign of every output.
 // Same arithmetic as k_turbo_siso, same arrays in and out.
-constexpr uint32_t SMALL_G = 8; // trellises per wavefront at most (4 lanes each)
 // sel(n - c, b + u, a - u) for the lane's lower state, the upper state takes (-c, -u): both at once on int16 pairs, cw = (c, -c), uw = (u, -u)
 struct SmallPar { uint32_t cw, uw; };
 
@@ -1424,7 +1381,7 @@ struct PermArgs { const uint8_t *A1; const uint8_t *X2; uint8_t *out[2]; /* I1, 
 #ifndef PERM_NB
 #define PERM_NB 4
 #endif
-static_assert(PERM_NB == 4, "a size's perm grid is a multiple of 128 workgroups (the merged decode's map granularity) only for four blocks per workgroup");
+static_assert(PERM_NB == PERM_BLOCKS, "a size's perm grid is a multiple of 128 workgroups (the merged decode's map granularity) only for four blocks per workgroup");
 template <int NSLOT, bool MULTI = false>
 __global__ __launch_bounds__(384) void k_turbo_perm(PermArgs a, uint32_t K_arg, uint32_t n_cb_arg, const uint16_t *__restrict__ pi_arg, MultiArgs ma)
 {
@@ -1963,20 +1920,23 @@ __global__ __launch_bounds__(256) void k_crc_finish(const uint8_t *__restrict__ 
 // host side
 
 namespace {
-constexpr int N_BYTE_ARRAYS = 11; // X0 X1 X2 I0 M1 M2 A1 I1 M3 B1 B2
-enum { AX0, AX1, AX2, AI0, AM1, AM2, AA1, AI1, AM3, AB1, AB2 };
+enum { AX0, AX1, AX2, AI0, AM1, AM2, AA1, AI1, AM3, AB1, AB2 }; // the N_BYTE_ARRAYS
+static_assert(sizeof(CbDesc) == CB_DESC_BYTES, "ref_scratch_bytes counts a descriptor per slot");
 } // namespace
 
 extern "C" size_t mi_lte_turbo_scratch_bytes(uint32_t K, uint32_t n_cb)
 {
-    const size_t n_tiles = (n_cb + 63) / 64, Kp = kpad64(K);
-    return n_tiles * Kp * 64 * N_BYTE_ARRAYS + 3 * n_tiles * Kp * 32 + n_tiles * 64 * sizeof(CbDesc);
+    const size_t n_tiles = (n_cb + 63) / 64;
+    return ref_scratch_bytes(n_tiles * kpad64(K) * 64, n_tiles * 64);
 }
 
-static bool no_static_lds(const void *kernel)
+// The per-code-block kernels address their dynamic LDS block from 0 (lds_u8 and friends): that holds while they own no static LDS.
+static bool no_static_lds(std::initializer_list<const void *> kernels)
 {
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, kernel) == hipSuccess && a.sharedSizeBytes == 0;
+    for (const void *k : kernels)
+        if (hipFuncGetAttributes(&a, k) != hipSuccess || a.sharedSizeBytes != 0) return false;
+    return true;
 }
 
 // The scratch of one REF decode carved up -- eleven byte arrays of arr_bytes each, three arrays of traceback words of half that, the
@@ -2005,8 +1965,6 @@ struct RefScratch {
         va = {arr[AX0], arr[AA1], arr[AB1], arr[AB2]};
     }
 };
-// trellises per wavefront of the state-parallel trellis kernel: one or two wavefronts per SIMD
-static uint32_t gpw_of(uint32_t n_tr) { return n_tr <= 2048 ? 1u : n_tr <= 4096 ? 2u : n_tr <= 8192 ? 4u : SMALL_G; }
 
 // The five launches of one REF decode over n_cb code blocks of size K.
 template <typename Src, bool GROUP>
@@ -2015,15 +1973,10 @@ static int turbo_ref_run(mi_lte_ctx *ctx, Src src, uint32_t K, uint32_t n_cb, ui
     TurboTables tb;
     int         rc = mi_ctx_turbo_tables(ctx, K, 0, &tb);
     if (rc != MI_LTE_OK) return rc;
-    // the per-code-block kernels address their dynamic LDS block from 0 (lds_u8 and friends): that holds while they own no static LDS
-    static const bool lds_ok = no_static_lds((const void *)k_turbo_prep<Src, 1>) && no_static_lds((const void *)k_turbo_perm<1>) &&
-                               no_static_lds((const void *)k_turbo_vote<GROUP, 1>);
-    if (!lds_ok) {
-        ctx->err = "turbo kernels were built with static LDS: absolute LDS addressing is invalid";
-        return MI_LTE_ERR_HIP;
-    }
+    static const bool lds_ok = no_static_lds({(const void *)k_turbo_prep<Src, 1>, (const void *)k_turbo_perm<1>, (const void *)k_turbo_vote<GROUP, 1>});
+    if (!lds_ok) { ctx->err = "turbo kernels were built with static LDS: absolute LDS addressing is invalid"; return MI_LTE_ERR_HIP; }
     const size_t n_tiles = (n_cb + 63) / 64, Kp = kpad64(K), arr_bytes = n_tiles * Kp * 64;
-    rc = mi_ctx_reserve_scratch(ctx, mi_lte_turbo_scratch_bytes(K, n_cb));
+    rc = mi_ctx_reserve_scratch(ctx, ref_scratch_bytes(arr_bytes, n_tiles * 64));
     if (rc != MI_LTE_OK) return rc;
     const RefScratch sc(ctx->scratch, arr_bytes);
     const bool small = n_cb <= ctx->siso_small_max; // a handful of code blocks (a per-call caller's transport block): k_turbo_siso_small
@@ -2034,19 +1987,18 @@ static int turbo_ref_run(mi_lte_ctx *ctx, Src src, uint32_t K, uint32_t n_cb, ui
         gd.desc = src.g.desc = sc.d_desc;
         MI_LAUNCH(ctx, "k_cb_desc", k_cb_desc, dim3((n_cb + 255) / 256), dim3(256), 0, gd, n_cb, (const uint32_t *)src.nnn, sc.d_desc);
     }
-    const uint32_t cb_threads = (uint32_t)(((Kp >> 4) + 63) & ~(size_t)63); // one thread per 16-step unit: 64..384
-    MI_LAUNCH(ctx, "k_turbo_prep", (k_turbo_prep<Src, 1>), dim3(8 * xcd_chunk(n_cb)), dim3(cb_threads), prep_lds_bytes(Kp, e_cap), src, K, n_cb, tb.d_pi, sc.po, MultiArgs{});
+    const uint32_t cb_threads = cb_width(K);
+    MI_LAUNCH(ctx, "k_turbo_prep", (k_turbo_prep<Src, 1>), dim3(cb_grid(n_cb)), dim3(cb_threads), prep_lds_bytes(Kp, e_cap), src, K, n_cb, tb.d_pi, sc.po, MultiArgs{});
 
     // a handful of code blocks: states on the lanes instead of code blocks
-    auto lds_of = [&](uint32_t gpw) { return sizeof(uint32_t) * gpw * (64 * 4 * 2 + (Kp >> 5) * 4); };
+    auto lds_of = [&](uint32_t gpw) { return siso_small_lds_bytes(gpw, Kp); };
     if (small)
         MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<false>, dim3((n_cb + gpw_of(n_cb) - 1) / gpw_of(n_cb)), dim3(64), lds_of(gpw_of(n_cb)), sc.s1, K, n_cb, 0u,
                   gpw_of(n_cb), MultiArgs{});
     else
         MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<false>, dim3(((n_tiles + 1) / 2 + 3) / 4), dim3(256), 0, sc.s1, K, (uint32_t)n_tiles, 0u, MultiArgs{}, (const uint32_t *)nullptr); // two tiles per lane
 
-    const uint32_t perm_grid = ((8 * xcd_chunk(n_cb) + PERM_NB - 1) / PERM_NB + 7u) & ~7u; // a multiple of 8: b + i * grid stays on b's XCD
-    MI_LAUNCH(ctx, "k_turbo_perm", k_turbo_perm<1>, dim3(perm_grid), dim3(cb_threads), MTAB_N + Kp + 32, sc.pa, K, n_cb, tb.d_pi, MultiArgs{});
+    MI_LAUNCH(ctx, "k_turbo_perm", k_turbo_perm<1>, dim3(perm_grid_of(n_cb)), dim3(cb_threads), MTAB_N + Kp + 32, sc.pa, K, n_cb, tb.d_pi, MultiArgs{});
 
     if (small)
         MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<false>, dim3((2 * n_cb + gpw_of(2 * n_cb) - 1) / gpw_of(2 * n_cb)), dim3(64), lds_of(gpw_of(2 * n_cb)), sc.s23, K,
@@ -2054,7 +2006,7 @@ static int turbo_ref_run(mi_lte_ctx *ctx, Src src, uint32_t K, uint32_t n_cb, ui
     else
         MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<false>, dim3((n_tiles + 3) / 4), dim3(256), 0, sc.s23, K, (uint32_t)n_tiles, 1u, MultiArgs{}, (const uint32_t *)nullptr); // passes 2 and 3 of a tile per lane
 
-    MI_LAUNCH(ctx, "k_turbo_vote", (k_turbo_vote<GROUP, 1>), dim3(8 * xcd_chunk(n_cb)), dim3(cb_threads), 3 * Kp + 64, sc.va, K, n_cb, tb.d_inv2, d_c_bits, gd, MultiArgs{});
+    MI_LAUNCH(ctx, "k_turbo_vote", (k_turbo_vote<GROUP, 1>), dim3(cb_grid(n_cb)), dim3(cb_threads), 3 * Kp + 64, sc.va, K, n_cb, tb.d_inv2, d_c_bits, gd, MultiArgs{});
     MI_HIP_CHECK(ctx, hipGetLastError());
     ctx->last_kernels = "k_turbo_prep:1,k_turbo_siso:2,k_turbo_perm:1,k_turbo_vote:1";
     return MI_LTE_OK;
@@ -2091,13 +2043,6 @@ static GroupDesc group_desc(const mi_lte_ctx *ctx, const MiDecodeIO &io, uint32_
 {
     return {io.d_allocs, io.d_cb_alloc + cb_base, io.d_e, io.d_e_off, io.d_e_len, io.d_out_bits, io.out_stride, io.d_status, ctx->d_crc_tab, io.ul ? 1u : 0u, io.packed ? 1u : 0u};
 }
-// LDS bytes that stage a group's longest allocation: room for the zero slot behind it
-static uint32_t stage_cap(uint32_t e_max_bytes) { return (e_max_bytes + 16u + 63u) & ~63u; }
-
-// Can the block-size group join a merged decode?  Every stream has at most 31 NULL slots, so a lap of the circular buffer consumes at least
-// 3K - 81 soft bits: while the longest allocation makes no more than 258 laps no sum of int8 values leaves int16, and the kernels may keep the
-// rate un-matching sums in pairs (SrcRateUnmatchPk), as the merged kernels do; a group beyond that takes the per-size path with 32-bit sums.
-static bool mi_turbo_ref_multi_takes(uint32_t K, uint32_t e_max_bytes) { return (e_max_bytes + (3 * K - 81) - 1) / (3 * K - 81) <= 258; }
 
 // the per-size path of mi_turbo_ref_dispatch: decode the code blocks of one size K straight from the demodulator's soft bits
 static int mi_turbo_ref_group(mi_lte_ctx *ctx, const MiKGroup &gr, const MiDecodeIO &io)
@@ -2112,9 +2057,8 @@ static int mi_turbo_ref_group(mi_lte_ctx *ctx, const MiKGroup &gr, const MiDecod
     src.g    = gd;
     src.tabs = rt.d_tabs;
     src.nnn  = rt.d_nnn;
-    // stage e in LDS when the largest allocation of the group fits next to the block's own arrays
     const uint32_t cap = stage_cap(gr.e_max);
-    src.e_cap          = (prep_lds_bytes(kpad64(gr.K), cap) <= 48 * 1024) ? cap : 0;
+    src.e_cap          = prep_stages(gr.K, cap) ? cap : 0;
     if (mi_turbo_ref_multi_takes(gr.K, gr.e_max)) {
         SrcRateUnmatchPk pk;
         static_cast<SrcRateUnmatch &>(pk) = src;
@@ -2132,145 +2076,27 @@ static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t 
     if (!groups || n_groups == 0 || n_groups > 0xFFFF || !cache) return MI_LTE_ERR_INVALID_ARG;
     int rc = mi_ctx_crc_table(ctx);
     if (rc != MI_LTE_OK) return rc;
-    static const bool lds_ok = no_static_lds((const void *)k_turbo_prep<SrcRateUnmatchPk, 1, true>) && no_static_lds((const void *)k_turbo_perm<1, true>) &&
-                               no_static_lds((const void *)k_turbo_vote<true, 1, true>);
+    static const bool lds_ok = no_static_lds({(const void *)k_turbo_prep<SrcRateUnmatchPk, 1, true>, (const void *)k_turbo_perm<1, true>, (const void *)k_turbo_vote<true, 1, true>});
     if (!lds_ok) { ctx->err = "turbo kernels were built with static LDS: absolute LDS addressing is invalid"; return MI_LTE_ERR_HIP; }
-    constexpr int NCLS = 6; // workgroup widths 64 .. 384: one thread per 16-step unit
-    auto cls_of = [](uint32_t K) { return (int)((((kpad64(K) >> 4) + 63) >> 6) - 1); };
     const bool same = cache->built_for.size() == n_groups && memcmp(cache->built_for.data(), groups, sizeof(MiKGroup) * n_groups) == 0;
     if (!same) {
         cache->built_for.clear(); // (until the upload below has succeeded: a rebuild that fails part-way leaves no key next to its tables)
-        std::vector<KSeg>     segs(n_groups);
-        std::vector<uint32_t> map;
-        MiMultiGeom          &G = cache->geom;
-        G = MiMultiGeom{};
-        uint64_t arr = 0;
-        uint32_t cbs = 0;
+        cache->geom = MiMultiGeom{};
+        std::vector<std::pair<TurboTables, RmTables>> tabs(n_groups); // the tables of every size, built on first use
+        for (uint32_t i = 0; i < n_groups; i++)
+            if ((rc = mi_ctx_turbo_tables(ctx, groups[i].K, 0, &tabs[i].first)) != MI_LTE_OK || (rc = rm_rank_tables(ctx, groups[i].K, &tabs[i].second)) != MI_LTE_OK) return rc;
+        MiMultiPlan plan;
+        const char *why = nullptr;
+        if ((rc = mi_turbo_multi_plan(groups, n_groups, &plan, &why)) != MI_LTE_OK) {
+            if (why) ctx->err = why;
+            return rc;
+        }
         for (uint32_t i = 0; i < n_groups; i++) {
-            const MiKGroup &gr = groups[i];
-            if ((i && gr.K <= groups[i - 1].K) || gr.n_cb == 0) { ctx->err = "merged decode: groups must be non-empty and in ascending block size"; return MI_LTE_ERR_INVALID_ARG; }
-            TurboTables tb;
-            RmTables    rt;
-            if ((rc = mi_ctx_turbo_tables(ctx, gr.K, 0, &tb)) != MI_LTE_OK || (rc = rm_rank_tables(ctx, gr.K, &rt)) != MI_LTE_OK) return rc;
-            KSeg &sg = segs[i];
-            memset(&sg, 0, sizeof(sg));
-            const uint32_t Kp = kpad64(gr.K), cap = stage_cap(gr.e_max);
-            sg.K = gr.K; sg.n_cb = gr.n_cb; sg.cb_base = gr.cb_base; sg.n_tiles = (gr.n_cb + 63) / 64;
-            // LDS for an allocation's soft bits: room for the size's longest allocation, but no more than a lap and a quarter of the circular buffer
-            // (3 (K + 4) positions) -- an allocation beyond that is staged lap by lap (gather_windowed_pk), and one repeated allocation of a size
-            // no longer sets the occupancy of every workgroup of its width (width 64 of the mixed batch: 16 KB -> 9.7 KB per workgroup).
-            // Only where the LDS is what limits the occupancy -- the 64-thread width, K <= 1024, one wavefront per workgroup: 1.02 -> 0.80 ms of the mixed
-            // batch's prep; applied to every width it cost the 128- and 192-thread ones 0.05 and 0.11 ms (their blocks beyond a lap and a quarter pay
-            // two barriers per lap and their occupancy is bound by registers anyway), gpurun_out/windowed.log
-            const uint32_t cap_w = (uint32_t)((15 * (size_t)(gr.K + 4) / 4 + 64 + 63) & ~(size_t)63);
-            sg.e_cap = (prep_lds_bytes(Kp, cap) <= 48 * 1024) ? (Kp <= 1024 ? std::min(cap, cap_w) : cap) : cap_w;
-            sg.arr_off = arr;
-            typedef __attribute__((address_space(1))) const uint16_t gl16_t;
-            typedef __attribute__((address_space(1))) const uint32_t gl32_t;
-            sg.pi = (gl16_t *)tb.d_pi; sg.inv2 = (gl16_t *)tb.d_inv2; sg.tabs = (gl16_t *)rt.d_tabs; sg.nnn = (gl32_t *)rt.d_nnn;
-            arr += (uint64_t)sg.n_tiles * Kp * 64;
-            cbs = std::max(cbs, gr.cb_base + gr.n_cb);
-            const int c = cls_of(gr.K);
-            // (a size whose last tile is partly filled stays with the table kernel: it zeroes the idle lanes the trellis kernel will walk)
-            G.one_size[c] = (G.lds_prep[c] == 0 && gr.n_cb % 64 == 0) ? (int)i : -1; // the width's only size so far, or not the only one
-            G.off_one[c] = sg.arr_off; G.e_cap_one[c] = sg.e_cap;
-            G.lds_prep[c] = std::max(G.lds_prep[c], prep_lds_bytes(Kp, sg.e_cap));
-            G.kp_max[c]   = std::max(G.kp_max[c], Kp);
+            KSeg &sg = plan.segs[i];
+            sg.pi = (decltype(sg.pi))tabs[i].first.d_pi; sg.inv2 = (decltype(sg.inv2))tabs[i].first.d_inv2;
+            sg.tabs = (decltype(sg.tabs))tabs[i].second.d_tabs; sg.nnn = (decltype(sg.nnn))tabs[i].second.d_nnn;
         }
-        G.arr_bytes = arr;
-        G.n_slots   = cbs;
-        // workgroup -> size maps of the per-code-block kernels, one entry per 512 (prep, vote) / 128 (perm) workgroups -- a few KB: they stay in the scalar cache --, class after class
-        for (int c = 0; c < NCLS; c++) {
-            G.map_cb[c] = (uint32_t)map.size();
-            uint32_t wg = 0;
-            for (uint32_t i = 0; i < n_groups; i++)
-                if (cls_of(groups[i].K) == c) {
-                    segs[i].wg_cb = wg;
-                    const uint32_t g = 8 * xcd_chunk(groups[i].n_cb);
-                    map.insert(map.end(), g / 512, i);
-                    wg += g;
-                }
-            G.grid_cb[c] = wg;
-        }
-        for (int c = 0; c < NCLS; c++) {
-            G.map_perm[c] = (uint32_t)map.size();
-            uint32_t wg = 0;
-            for (uint32_t i = 0; i < n_groups; i++)
-                if (cls_of(groups[i].K) == c) {
-                    segs[i].wg_perm   = wg;
-                    segs[i].perm_grid = ((8 * xcd_chunk(groups[i].n_cb) + PERM_NB - 1) / PERM_NB + 7u) & ~7u; // a multiple of 8: b + i * grid stays on b's XCD
-                    map.insert(map.end(), segs[i].perm_grid / 128, i);
-                    wg += segs[i].perm_grid;
-                }
-            G.grid_perm[c] = wg;
-        }
-        // wavefront -> size maps of the trellis kernel, the largest sizes first (their walks are the longest: started first, the short ones fill in behind them)
-        G.map_wv1 = (uint32_t)map.size();
-        uint32_t wv = 0;
-        for (uint32_t i = n_groups; i-- > 0;) {
-            segs[i].wv1 = wv;
-            map.insert(map.end(), (segs[i].n_tiles + 1) / 2, i);
-            wv += (segs[i].n_tiles + 1) / 2;
-        }
-        G.n_wv1   = wv;
-        G.map_wv23 = (uint32_t)map.size();
-        wv = 0;
-        for (uint32_t i = n_groups; i-- > 0;) {
-            segs[i].wv23 = wv;
-            map.insert(map.end(), segs[i].n_tiles, i);
-            wv += segs[i].n_tiles;
-        }
-        G.n_wv23 = wv;
-        // The order the trellis kernel's workgroups are LAUNCHED in.  A walk is as long as its block size, the device holds 1024 workgroups of four
-        // walks at a time, and a mixed batch has little more than that (pass 1) or twice that (passes 2 + 3): with the longest walks simply first,
-        // a compute unit's four resident workgroups are neighbours in the sorted order and the unit that got the four longest decides when the
-        // launch ends.  Dealt out in rounds of 256 (one workgroup per compute unit and round), every other round backwards, each unit gets the
-        // r-th longest of one round with the r-th shortest of the next: equal sums (0.07 ms of the mixed batch's 3.6; a scatter that gives up
-        // "longest first" costs 1.3).  Batches of a few sizes (W4) keep the sorted order.
-        // And how many of them a compute unit holds at a time.  The registers allow four (16 walks per unit, 4096 in all): right for W4, whose
-        // walks are equally long and come in more than two rounds of that.  A mixed batch of this size has 1.2 rounds (pass 1) and 2.3 (passes
-        // 2 + 3) of walks between 44 and 4612 steps: the units that drew short ones run dry and nothing is left to hand them.  Half as many
-        // resident workgroups are twice as many rounds -- the queue stays non-empty until close to the end -- at the price of fewer wavefronts to
-        // hide latency behind; measured on the mixed batch (gpurun_out/occ*.log): 2 per unit for pass 1 and 3 for passes 2 + 3 take 0.12-0.15 ms
-        // off the trellis kernel's 3.6, one per unit costs 0.15.  The limit is set with dynamic LDS that the kernel never touches.
-        const bool many_sizes = n_groups >= 8;
-        if (many_sizes) { G.siso_pad1 = 60000; G.siso_pad23 = 45000; } // (+ the kernel's own 8 KB: two / three of them in a unit's 160 KB)
-        auto deal = [&](uint32_t n_wv, uint32_t *at, uint32_t *n_out) {
-            const uint32_t n_wg = (n_wv + 3) / 4;
-            if (!many_sizes || n_wg < 512) return; // (*n_out stays 0: the sorted order)
-            *at = (uint32_t)map.size();
-            for (uint32_t j = 0; j < n_wg; j++) {
-                const uint32_t round = j / 256, c = j % 256, in_round = std::min(256u, n_wg - 256 * round);
-                const uint32_t src = (round & 1u) ? 256 * round + (in_round - 1 - std::min(c, in_round - 1)) : j;
-                for (uint32_t t = 0; t < 4; t++) map.push_back(4 * src + t < n_wv ? 4 * src + t : 0xFFFFFFFFu);
-            }
-            *n_out = 4 * n_wg;
-        };
-        deal(G.n_wv1, &G.ord_wv1, &G.n_ord1);
-        deal(G.n_wv23, &G.ord_wv23, &G.n_ord23);
-        // ... and of the state-parallel trellis kernel (a handful of code blocks in all): workgroup = wavefront = up to gpw trellises of one size
-        uint32_t tot = 0, kp_all = 0;
-        for (uint32_t i = 0; i < n_groups; i++) { tot += groups[i].n_cb; kp_all = std::max(kp_all, kpad64(groups[i].K)); }
-        G.gpw1 = gpw_of(tot); G.gpw23 = gpw_of(2 * tot); G.kp_all = kp_all;
-        G.map_ws1 = (uint32_t)map.size();
-        uint32_t wg = 0;
-        for (uint32_t i = 0; i < n_groups; i++) {
-            const uint32_t n = (groups[i].n_cb + G.gpw1 - 1) / G.gpw1;
-            segs[i].ws1 = wg;
-            map.insert(map.end(), n, i);
-            wg += n;
-        }
-        G.n_ws1   = wg;
-        G.map_ws23 = (uint32_t)map.size();
-        wg = 0;
-        for (uint32_t i = 0; i < n_groups; i++) {
-            const uint32_t n = (2 * groups[i].n_cb + G.gpw23 - 1) / G.gpw23;
-            segs[i].ws23 = wg;
-            map.insert(map.end(), n, i);
-            wg += n;
-        }
-        G.n_ws23 = wg;
-        const size_t seg_bytes = sizeof(KSeg) * n_groups, map_bytes = (sizeof(uint32_t) * map.size() + 15) & ~(size_t)15, need = seg_bytes + map_bytes;
+        const size_t seg_bytes = plan.geom.map_off, map_bytes = (sizeof(uint32_t) * plan.map.size() + 15) & ~(size_t)15, need = seg_bytes + map_bytes;
         if (need > cache->cap) {
             MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
             if (cache->d_tab) (void)hipFree(cache->d_tab);
@@ -2279,15 +2105,15 @@ static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t 
             cache->cap = need + need / 4;
         }
         std::vector<uint8_t> blob(need, 0);
-        memcpy(blob.data(), segs.data(), seg_bytes);
-        memcpy(blob.data() + seg_bytes, map.data(), sizeof(uint32_t) * map.size());
+        memcpy(blob.data(), plan.segs.data(), seg_bytes);
+        memcpy(blob.data() + seg_bytes, plan.map.data(), sizeof(uint32_t) * plan.map.size());
         MI_H2D(ctx, cache->d_tab, blob.data(), need); // (waits: the kernels of an earlier run that read the old tables are behind it on the stream)
-        G.map_off = seg_bytes;
+        cache->geom = plan.geom;
         cache->built_for.assign(groups, groups + n_groups);
     }
     const MiMultiGeom &G = cache->geom;
     const size_t A = G.arr_bytes;
-    rc = mi_ctx_reserve_scratch(ctx, N_BYTE_ARRAYS * A + 3 * (A / 2) + (size_t)((G.n_slots + 63) & ~63u) * sizeof(CbDesc));
+    rc = mi_ctx_reserve_scratch(ctx, ref_scratch_bytes(A, G.n_slots));
     if (rc != MI_LTE_OK) return rc;
     const RefScratch sc(ctx->scratch, A);
     const KSeg     *d_segs = (const KSeg *)cache->d_tab;
@@ -2320,7 +2146,7 @@ static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t 
         }
     // a handful of code blocks in all (a per-call caller's subframe): the trellis's states on the lanes instead of code blocks, as in the per-size launches
     const bool small = G.n_slots <= ctx->siso_small_max;
-    auto lds_small = [&](uint32_t gpw) { return sizeof(uint32_t) * gpw * (64 * 4 * 2 + (G.kp_all >> 5) * 4); };
+    auto lds_small = [&](uint32_t gpw) { return siso_small_lds_bytes(gpw, G.kp_all); };
     if (small)
         MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<true>, dim3(G.n_ws1), dim3(64), lds_small(G.gpw1), sc.s1, 0u, 0u, 0u, G.gpw1, (MultiArgs{d_segs, d_map + G.map_ws1}));
     else
@@ -2391,7 +2217,7 @@ int mi_turbo_bcjr_group(mi_lte_ctx *ctx, const MiKGroup &gr, const MiDecodeIO &i
         MI_HIP_CHECK(ctx, hipGetLastError());
         rc = mi_turbo_bcjr_block_batch(ctx, d_soft, K, n_cb, n_iter, qpp_spec, d_c_bits);
     } else { // the batch kernels: rate un-matching writes their granule arrays itself (k_rm_bcjr_prep)
-        static const bool lds_ok = no_static_lds((const void *)k_rm_bcjr_prep);
+        static const bool lds_ok = no_static_lds({(const void *)k_rm_bcjr_prep});
         if (!lds_ok) { ctx->err = "k_rm_bcjr_prep was built with static LDS"; return MI_LTE_ERR_HIP; }
         TurboTables tb;
         rc = mi_ctx_turbo_tables(ctx, K, qpp_spec ? 1 : 0, &tb);
@@ -2400,13 +2226,13 @@ int mi_turbo_bcjr_group(mi_lte_ctx *ctx, const MiKGroup &gr, const MiDecodeIO &i
         rc = mi_turbo_bcjr_begin(ctx, K, n_cb, &mb);
         if (rc != MI_LTE_OK) return rc;
         const size_t   Kp = kpad64(K);
-        const uint32_t cb_threads = (uint32_t)(((Kp >> 4) + 63) & ~(size_t)63), e_cap2 = (Kp + cap <= 60 * 1024) ? cap : 0;
+        const uint32_t cb_threads = cb_width(K), e_cap2 = (Kp + cap <= 60 * 1024) ? cap : 0;
         CbDesc *d_desc = (CbDesc *)mb.aux; // the per-block descriptors k_cb_desc writes
         gd.desc = d_desc;
         MI_LAUNCH(ctx, "k_cb_desc", k_cb_desc, dim3((n_cb + 255) / 256), dim3(256), 0, gd, n_cb, (const uint32_t *)t.d_nnn, d_desc);
         SrcRateUnmatch src;
         src.g = gd; src.tabs = t.d_tabs; src.nnn = t.d_nnn; src.e_cap = e_cap2;
-        MI_LAUNCH(ctx, "k_rm_bcjr_prep", k_rm_bcjr_prep, dim3(8 * xcd_chunk(n_cb)), dim3(cb_threads), e_cap2 + Kp, src, K, n_cb, (const uint16_t *)tb.d_pi, mb);
+        MI_LAUNCH(ctx, "k_rm_bcjr_prep", k_rm_bcjr_prep, dim3(cb_grid(n_cb)), dim3(cb_threads), e_cap2 + Kp, src, K, n_cb, (const uint16_t *)tb.d_pi, mb);
         MI_HIP_CHECK(ctx, hipGetLastError());
         rc = mi_turbo_bcjr_iterate(ctx, K, n_cb, n_iter, qpp_spec, d_c_bits, mode == MI_LTE_TURBO_BCJR_EARLY);
     }

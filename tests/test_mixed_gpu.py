@@ -48,12 +48,12 @@ def _ref_decode_all(ref, po, lists, iq):
     return grids, res
 
 
-def _synth(m, cfg, lists, seed):
+def _synth(m, cfg, lists, seed, snr_db=None):
     from openlte_amd import synth
     iq, tx, allocs = [], [], []
     for u, (sf, cell, cfi, lst) in enumerate(lists):
         al = _allocs(m, u, lst, cfi)
-        q, t = synth.dl_units(cfg, [sf], [cell], al, len(al), n_pdcch_symbs=cfi, snr_db=(30.0, 27.0, 24.0)[u % 3], max_delay=8, seed=seed + u)
+        q, t = synth.dl_units(cfg, [sf], [cell], al, len(al), n_pdcch_symbs=cfi, snr_db=snr_db or (30.0, 27.0, 24.0)[u % 3], max_delay=8, seed=seed + u)
         iq.append(q[0])
         tx += [t[0, a, :al[a].tbs].copy() for a in range(len(al))]
         allocs += al
@@ -158,3 +158,45 @@ def test_merged_decode_after_reassignment_of_a_dynamic_plan(ctx):
         plan.close()
     finally:
         ctx.set_turbo_small_batch(4096)
+
+
+def test_merged_decode_of_widths_that_hold_a_single_size(ctx):
+    """Two block sizes in two workgroup widths -- K = 40 (tbs 16: 1 PRB QPSK, 64 threads) and K = 1120 (tbs 1096: 4 PRB 16QAM, 128 threads) --
+    with exactly 64 code blocks each (four subframes, 30 dB): every width holds ONE size of whole tiles, so both prep launches take the
+    per-size kernel on the merged layout (MiMultiGeom::one_size).  Then one more K = 40 allocation (65 and 64): the first width falls back
+    to the table-driven kernel with a partly filled last tile while the second keeps the shortcut.  Either way verdicts and bits are those of
+    the per-size launches, and every allocation that passes its CRC carries the transmitted bits."""
+    import openlte_amd as m
+    cfg = m.DlCfg(2048, 100, 1, m.IQ_I8 | m.CE_COMPACT)
+    for extra in (0, 1):
+        lists = []
+        for u in range(4):
+            n_small = 16 + (extra if u == 0 else 0)
+            lst = [(1, 16, a, 1, 0x100 + a, 0) for a in range(n_small)] + [(2, 1096, n_small + 4 * a, 4, 0x200 + a, 0) for a in range(16)]
+            lists.append(((1, 2, 3, 4)[u], 40 + u, 2, lst))
+        iq, tx, allocs = _synth(m, cfg, lists, 9400 + extra, snr_db=30.0)
+        assert [sum(a.tbs == t for a in allocs) for t in (16, 1096)] == [64 + extra, 64]
+        n = len(lists)
+        sfs, cells = np.array([l[0] for l in lists], np.uint32), np.array([l[1] for l in lists], np.uint32)
+        d_iq, d_start = ctx.to_device(iq.reshape(-1, 2)), ctx.to_device((np.arange(n) * iq.shape[1]).astype(np.uint64))
+        d_sf, d_cell = ctx.to_device(sfs), ctx.to_device(cells)
+        d_sub = ctx.alloc(n * ctx.subframe_floats(1) * 4)
+        ctx.dl_frontend_dev(cfg, d_iq, None, d_start, d_sf, d_cell, n, d_sub)
+        plan = ctx.pdsch_plan(cfg, 2, allocs)
+        got = {}
+        ctx.set_turbo_small_batch(0)
+        try:
+            for merged in (True, False):
+                ctx.set_turbo_merged(merged)
+                got[merged] = plan.run(d_sub, sfs, cells)
+                assert ("over all block sizes" in ctx.last_kernels()) == merged, (extra, merged, ctx.last_kernels())
+        finally:
+            ctx.set_turbo_small_batch(4096)
+            ctx.set_turbo_merged(True)
+        (st_a, bits_a), (st_b, bits_b) = got[True], got[False]
+        assert (st_a == st_b).all(), extra
+        assert all((x == y).all() for x, y in zip(bits_a, bits_b)), extra
+        assert all((bits_a[a] == tx[a]).all() for a in range(len(allocs)) if st_a[a] == 0), extra
+        plan.close()
+        for b in (d_iq, d_start, d_sf, d_cell, d_sub):
+            b.free()
