@@ -704,6 +704,92 @@ int  mi_lte_model_atan2f(const float *h_y, const float *h_x, float *h_out, size_
 int  mi_lte_dci_1a_unpack(uint32_t payload, uint32_t n_bits, uint32_t rnti, uint32_t N_rb_dl, uint32_t N_ant, mi_lte_pdcch_dci *out);
 int  mi_lte_dci_1c_unpack(uint32_t payload, uint32_t n_bits, uint32_t rnti, uint32_t N_rb_dl, uint32_t N_ant, mi_lte_pdcch_dci *out);
 
+/* ---------------------------------------------------------------- PDCCH, 3GPP mode: blind search over the whole control region (opt-in)
+ * mi_lte_pdcch_search_* find every DCI of a set of RNTIs anywhere in the control region: the UE-specific search space of 36.213 9.1.1 at
+ * aggregation levels 1, 2, 4, 8 next to the common one, any DCI size, with a tail-biting decoder.  The calls above keep the reference's
+ * behaviour; this path shares their PCFICH decoder, their de-mapper and their tables and nothing of the reference's candidate handling.
+ *
+ * Search spaces (mi_lte_pdcch_search_space, host arithmetic).  Y_(-1) = rnti, Y_k = (39827 Y_(k-1)) mod 65537 for k = subfr_num = 0 .. 9;
+ * candidate m = 0 .. M(L) - 1 of aggregation level L starts at CCE L ((Y_k + m) mod floor(N_cce / L)), M = 6, 6, 2, 2 for L = 1, 2, 4, 8.
+ * floor(N_cce / L) = 0 gives *n = 0 (no modulus is taken).  Duplicates stay as the formula yields them.  MI_LTE_ERR_INVALID_ARG: rnti = 0
+ * or > 0xFFFF, L not in {1, 2, 4, 8}, subfr_num > 9, null pointers.  The common search space is L = 4 at CCEs 0, 4, 8, 12 and L = 8 at
+ * CCEs 0, 8, wherever those CCEs exist, for any RNTI.
+ *
+ * The plan holds, per listed cell and N_symbs = 1 .. 4, the resource elements of EVERY CCE in order and N_cce; per listed DCI size the
+ * rate-matching map of 36.212 5.1.4.2 (576 entries: received bit k of a candidate of any L came from d[map[k]], k < 72 L -- the map of
+ * level L is the first 72 L entries of the map of level 8); and the RNTI set as a 65 536-bit device bitmap.  The set is exactly what the
+ * caller lists (SI-, P- and RA-RNTIs included only when listed); mi_lte_pdcch_search_plan_set_rntis replaces it, n_rnti = 0 empties it.
+ * Refused like mi_lte_pdcch_plan_create (MI_LTE_ERR_UNSUPPORTED): a non-standard bandwidth, a port count other than 1 / 2 / 4, N_g outside
+ * (0, 2], the extended PHICH duration.  MI_LTE_ERR_INVALID_ARG: n_sizes = 0 or > MI_LTE_PDCCH_SEARCH_MAX_SIZES, a size outside 8 .. 64, a
+ * size listed twice, a cell past 503, an RNTI of 0 or above 0xFFFF.  Every refusal comes before any launch.
+ *
+ * mi_lte_pdcch_search_run, everything queued on the context's stream, one wait (before the compacted results are read), no allocation
+ * after the first run at a given n_units:
+ *   1. k_pdcch_search_demod, one workgroup per subframe.  CFI from the PCFICH as k_pdcch_decode finds it; N_symbs = cfi + (N_rb_dl <= 10).
+ *      Every CCE's 36 resource elements through the transmit-diversity combiner with each port's own estimate (the arithmetic of
+ *      MI_LTE_PDCCH_PER_PORT_ESTIMATES), the QPSK de-mapper and the descrambler (c_init = (subfr_num << 9) + cell, CCE c at bit 72 c):
+ *      int8 soft bits soft[unit][72 cce + k], positive = bit 0.  A cell the plan was not built for, a subframe number past 9, cfi = 0 or
+ *      N_symbs > 4: h_cfi = 0, h_n_cce = 0, no hit.
+ *   2. k_pdcch_search_decode, one wavefront per (unit, candidate, size).  Candidates: every L in {8, 4, 2, 1} and every first CCE with
+ *      cce mod L = 0 and cce + L <= N_cce.  With N = n_bits + 16, a pair with N >= 72 L is skipped (no redundancy left).  Per pair:
+ *      a. rate un-matching in int32: d[map[r]] = sum over j of soft[r + 3 N j] (r < 3 N, r + 3 N j < 72 L); positions never sent are 0.
+ *      b. energy = sum |d|; energy = 0 is no hit whatever the CRC says.  (Step 1's de-mapper never yields a 0: its smallest magnitude is 1, so
+ *         a noiseless empty region reads +-1 in the scrambler's pattern and is turned away by the CRC and the RNTI set like any noise.)
+ *      c. the tail-biting decoder of the CQI section, step 2b (the same device code), over the N steps: maximum-correlation Viterbi, all
+ *         64 metrics 0 at the start, three laps, the even predecessor on a tie, end state the first maximum in state order, traceback
+ *         over all 3 N steps, the bits of the middle lap; metric = the decided word re-encoded and correlated with d.
+ *      d. x = CRC16 remainder (0x11021, register 0) of the n_bits information bits XOR the 16 received parity bits: the RNTI when the
+ *         CRC matches (antenna-selection mask 0).  A hit needs x != 0, x in the RNTI set, and either MI_LTE_PDCCH_SEARCH_ANY_CCE, or the
+ *         candidate in the common search space, or the candidate among x's own UE-specific candidates of this subframe (the arithmetic
+ *         of mi_lte_pdcch_search_space, on the device).
+ *   3. k_pdcch_search_compact, one wavefront per unit: the hits ordered by (L descending, first CCE ascending, position of the size in
+ *      the plan's list ascending); the first MI_LTE_PDCCH_SEARCH_MAX_FOUND are written, h_n_found[u] is the total and may exceed the cap
+ *      (slots past the total are zero).  Only these lists, h_cfi, h_n_cce and h_n_found cross the link.
+ * What the search does not resolve: a DCI sent at L = 4 is also found at L = 2 and L = 1 from the same first CCE (a prefix of its
+ * rate-matched bits still decodes) and by the L = 8 candidate that holds it plus empty CCEs.  Each is reported with its metric and
+ * energy; choosing among them is the caller's, like a DTX threshold elsewhere in this header.
+ * mi_lte_pdcch_search_soft: the soft bits of the last run (device pointer into the plan, unit u at u * *unit_stride, 72 h_n_cce[u] valid). */
+#define MI_LTE_PDCCH_SEARCH_MAX_SIZES 4
+#define MI_LTE_PDCCH_SEARCH_MAX_FOUND 16
+#define MI_LTE_PDCCH_SEARCH_ANY_CCE   1u   /* report a hit wherever it lies, not only inside its RNTI's search spaces */
+typedef struct {
+    uint32_t rnti, L, cce, n_bits;   /* cce = first CCE */
+    uint64_t payload;                /* first DCI bit in bit n_bits-1 */
+    int32_t  metric, energy;         /* as mi_lte_cqi_result: decided word re-encoded against d; sum |d| */
+} mi_lte_pdcch_found;
+typedef struct mi_lte_pdcch_search_plan mi_lte_pdcch_search_plan;
+int  mi_lte_pdcch_search_space(uint32_t rnti, uint32_t subfr_num, uint32_t N_cce, uint32_t L, uint32_t *first_cce /* [6] */, uint32_t *n);
+int  mi_lte_pdcch_search_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, float phich_res, uint32_t phich_dur_extended, uint32_t flags,
+                                     const uint32_t *h_cells, uint32_t n_cells, const uint32_t *h_n_bits, uint32_t n_sizes,
+                                     mi_lte_pdcch_search_plan **out);
+int  mi_lte_pdcch_search_plan_set_rntis(mi_lte_ctx *ctx, mi_lte_pdcch_search_plan *plan, const uint32_t *h_rnti, uint32_t n_rnti);
+void mi_lte_pdcch_search_plan_destroy(mi_lte_ctx *ctx, mi_lte_pdcch_search_plan *plan);
+int  mi_lte_pdcch_search_run(mi_lte_ctx *ctx, mi_lte_pdcch_search_plan *plan, const float *d_subframes, const uint32_t *d_subfr_num,
+                             const uint32_t *d_n_id_cell, uint32_t n_units, uint32_t *h_cfi, uint32_t *h_n_cce, uint32_t *h_n_found,
+                             mi_lte_pdcch_found *h_found /* [n_units][MI_LTE_PDCCH_SEARCH_MAX_FOUND] */);
+int  mi_lte_pdcch_search_soft(const mi_lte_pdcch_search_plan *plan, const int8_t **d_soft, uint32_t *unit_stride); /* valid after a run */
+/* A C-RNTI's DCI format 0 / 1A as this library's transmitter packs them (tx_ctrl.cc, pinned to the reference's dci_0_pack / dci_1a_pack),
+ * host arithmetic.  Both: the flag bit (1 = format 1A, 0 = format 0), then one more flag, then the resource indication value in
+ * ceil(log2(N_rb (N_rb + 1) / 2)) bits, decoded over its WHOLE range (36.213 7.1.6.3 / 8.1): with q = floor(RIV / N_rb), r = RIV mod N_rb,
+ * length = q + 1 and start = r when q + r < N_rb, otherwise length = N_rb - q + 1 and start = N_rb - 1 - r.
+ * Format 1A: localized (0) / distributed (1), RIV, MCS 5 bits, HARQ process 3, NDI 1, RV 2, TPC 2.  MCS 0-9 QPSK, 10-16 16QAM, 17-28 64QAM
+ * with I_TBS = MCS, MCS - 1, MCS - 2; tbs = 8 x (36.213 table 7.1.7.2.1-1)[I_TBS][N_prb - 1].  alloc is filled (mod_type, tbs, rv_idx,
+ * tx_mode = 1 or 2 by N_ant, rnti, N_prb, prb[2][N_prb]; unit and n_pdcch_symbs left 0) for the 3GPP PDSCH plans.
+ * Format 0: hopping flag, RIV over N_rb (= N_rb_ul), MCS / RV 5 bits, NDI 1, TPC 2, DMRS cyclic shift 3, CQI request 1, padding.  alloc carries
+ * rnti, N_prb and prb only (the uplink transport block is the PUSCH plan's business).
+ * Returns 0; 4 for what has no transport block of its own here -- MCS 29-31 (either format), a distributed assignment, a RIV past
+ * N_rb (N_rb + 1) / 2 - 1 -- with every field read so far filled in; MI_LTE_ERR_INVALID_ARG: a null pointer, n_bits > 64 or too small for the
+ * fields, rnti = 0 or > 0xFFFF, N_rb = 0 or > 110, N_ant not 1 / 2 / 4. */
+typedef struct {
+    uint32_t format;        /* 0 = DCI format 0, 1 = DCI format 1A                                   */
+    uint32_t flag;          /* format 1A: 1 = distributed VRBs; format 0: the hopping flag           */
+    uint32_t riv, rb_start, N_prb;
+    uint32_t mcs, harq, ndi, rv, tpc;   /* harq, rv: format 1A only                                  */
+    uint32_t cyclic_shift, cqi_request; /* format 0 only                                             */
+    mi_lte_pdsch_alloc alloc;
+} mi_lte_dci_crnti;
+int  mi_lte_dci_0_1a_unpack_crnti(uint64_t payload, uint32_t n_bits, uint32_t rnti, uint32_t N_rb, uint32_t N_ant, mi_lte_dci_crnti *out);
+
 /* ---------------------------------------------------------------- PBCH
  * mi_lte_pbch_decode_run replaces liblte_phy_bch_channel_decode() (liblte/hdr/liblte_phy.h:947-953, implementation
  * liblte/src/liblte_phy.cc:3968-4105 with bch_channel_decode :12581-12650) for a batch of device subframes holding subframe 0
@@ -1075,6 +1161,20 @@ typedef struct {
 int mi_lte_synth_ctrl_grids(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t n_units, const uint32_t *h_subfr_num,
                             const uint32_t *h_n_id_cell, const uint32_t *h_cfi, const mi_lte_synth_dci *h_dci, uint32_t n_dci,
                             const mi_lte_synth_channel *chan, float *h_grids);
+
+/* mi_lte_synth_ctrl_grids with any DCI anywhere: per unit n_rec (at most MI_LTE_SYNTH_MAX_REC) records, rnti = 0 marks an unused slot;
+ * n_bits (1 .. 64) payload bits, first bit in bit n_bits - 1, on the L (1, 2, 4, 8) CCEs from cce (a multiple of L).  The processing is the
+ * one function the two generators share: CRC16 masked with the RNTI, the tail-biting encoder, rate matching to 72 L bits, scrambling at
+ * bit 72 cce, transmit diversity onto that CCE range -- a format-1A DCI given as an L = 4 record at CCE 4 a yields mi_lte_synth_ctrl_grids'
+ * grid for the same seed byte for byte.  MI_LTE_ERR_INVALID_ARG: records that overlap, a record reaching past the unit's N_cce. */
+#define MI_LTE_SYNTH_MAX_REC 8
+typedef struct {
+    uint32_t rnti, L, cce, n_bits;
+    uint64_t payload;
+} mi_lte_synth_dci_rec;
+int mi_lte_synth_ctrl_grids_dci(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t n_units, const uint32_t *h_subfr_num,
+                                const uint32_t *h_n_id_cell, const uint32_t *h_cfi, const mi_lte_synth_dci_rec *h_rec, uint32_t n_rec,
+                                const mi_lte_synth_channel *chan, float *h_grids);
 
 /* n_units uplink subframes for tests / benchmarks: every unit carries n_alloc PUSCH transmissions
  * (allocs[u*n_alloc + a], .unit ignored) with random transport blocks, through one flat channel per unit.

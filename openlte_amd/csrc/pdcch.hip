@@ -17,6 +17,10 @@
 //       traceback by re-comparing stored metrics) with ONE TRELLIS STATE PER LANE (64 states = one wavefront; the two
 //       predecessor metrics arrive by lane shuffle, the traceback compares are one ballot per step), CRC16 and the RNTI
 //       test for SI-, P- and RA-RNTI (dci_channel_decode :12952-13040).
+//   k_pdcch_search_demod / _decode / _compact : the PDCCH's own 3GPP mode (include/mi_lte.h), a blind search over the whole control region that
+//       shares the PCFICH decoder, the de-mapper and the tables above and none of the reference's candidate handling: every CCE to int8 soft
+//       bits with each port's own estimate; one wavefront per (unit, candidate at L = 8, 4, 2, 1, DCI size) with the tail-biting decoder of
+//       tbcc_dev.h, CRC16, the RNTI bitmap and the search spaces of 36.213 9.1.1; the hits ordered and capped per unit.
 // The soft values are integers from the de-mapper on, so the decoder is exact; the de-mapper itself (atan2f / sqrtf) is
 // float.  Candidate CCEs past the last CCE of the subframe read stale scratch in the reference; here they count as erasures
 // (what a fresh LIBLTE_PHY_STRUCT gives).
@@ -30,6 +34,7 @@
 #include "phy_dev.hpp"
 #include "lte_tables.h"
 #include "synth.hpp"
+#include "tbcc_dev.h"
 
 namespace {
 
@@ -93,14 +98,15 @@ __device__ __forceinline__ void combine(const float (&yr)[4], const float (&yi)[
 // receiver).  With two ports row 2 is never written: port 1's estimate is 0 and the second antenna goes unsuppressed; with
 // four ports nothing decodes.  per_port = 0 reproduces exactly that (rows never written read as the zeros a fresh
 // LIBLTE_PHY_STRUCT holds); per_port = 1 is the decoder the reference meant.
-// (n_planes = number of channel-estimate planes the device subframe was laid out with; N_ant = ports the combiner assumes)
+// (n_planes = number of channel-estimate planes the device subframe was laid out with; N_ant = ports the combiner assumes;
+// ln, stride: this thread's first group and the number of threads that share the list -- a wavefront's lane and 64 unless given)
 template <uint32_t N_ant>
 __device__ __forceinline__ void demod_res_n(const float *__restrict__ base, uint32_t n_planes, uint32_t per_port, const uint32_t *__restrict__ re,
-                                            uint32_t n_re, const GoldTables &gt, uint32_t c_init, uint32_t c_off, int *soft, uint32_t ln)
+                                            uint32_t n_re, const GoldTables &gt, uint32_t c_init, uint32_t c_off, int *soft, uint32_t ln, uint32_t stride)
 {
     const float *y_re_p = base, *y_im_p = base + 16 * N_SC_MAX, *h_re_p = base + 2 * 16 * N_SC_MAX;
     const float *h_im_p = h_re_p + (size_t)n_planes * 16 * N_SC_MAX;
-    for (uint32_t g = ln; g < n_re / N_ant; g += 64) {
+    for (uint32_t g = ln; g < n_re / N_ant; g += stride) {
         float yr[4], yi[4], hr[4][4], hi[4][4], xr[4], xi[4];
         const bool absent = re[g * N_ant] == NO_RE;
         for (uint32_t e = 0; e < N_ant; e++) {
@@ -133,12 +139,12 @@ __device__ __forceinline__ void demod_res_n(const float *__restrict__ base, uint
 
 __device__ __forceinline__ void demod_res(const float *__restrict__ base, uint32_t n_planes, uint32_t N_ant, uint32_t per_port,
                                           const uint32_t *__restrict__ re, uint32_t n_re, const GoldTables &gt, uint32_t c_init, uint32_t c_off,
-                                          int *soft, uint32_t ln)
+                                          int *soft, uint32_t ln, uint32_t stride = 64)
 {
     // the port count is a template parameter so that the small per-group arrays stay in registers
-    if (N_ant == 1) demod_res_n<1>(base, n_planes, per_port, re, n_re, gt, c_init, c_off, soft, ln);
-    else if (N_ant == 2) demod_res_n<2>(base, n_planes, per_port, re, n_re, gt, c_init, c_off, soft, ln);
-    else demod_res_n<4>(base, n_planes, per_port, re, n_re, gt, c_init, c_off, soft, ln);
+    if (N_ant == 1) demod_res_n<1>(base, n_planes, per_port, re, n_re, gt, c_init, c_off, soft, ln, stride);
+    else if (N_ant == 2) demod_res_n<2>(base, n_planes, per_port, re, n_re, gt, c_init, c_off, soft, ln, stride);
+    else demod_res_n<4>(base, n_planes, per_port, re, n_re, gt, c_init, c_off, soft, ln, stride);
 }
 
 // The reference's K = 7, rate-1/3 Viterbi decoder (viterbi_decode, liblte_phy.cc:10161-10332) over N trellis steps, one state per
@@ -206,6 +212,28 @@ __device__ __forceinline__ uint32_t crc16_syndrome(uint32_t bits_lo, uint32_t bi
     return (par ^ rem) & 0xFFFFu;
 }
 
+// PCFICH (pcfich_channel_demap + cfi_channel_decode) by one wavefront: gather / combine / de-map / descramble the 16 resource elements
+// listed in re[] into pc_soft[32] (LDS), then the CFI by minimum distance; 0: no code word within CFI_N_ACCEPTABLE_BERS.  The same value on every lane.
+__device__ __forceinline__ uint32_t pcfich_cfi(const float *__restrict__ base, uint32_t N_ant, uint32_t per_port, const uint32_t *__restrict__ re,
+                                               const GoldTables &gt, uint32_t sf, uint32_t cell, int *pc_soft, uint32_t ln)
+{
+    demod_res(base, N_ant, N_ant, per_port, re, 16, gt, (((sf + 1) * (2 * cell + 1)) << 9) + cell, 0, pc_soft, ln);
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    uint32_t bit = 0, m[4] = {0, 0, 0, 0};
+    if (ln < 32) {
+        bit = pc_soft[ln] >= 0 ? 0u : 1u;
+        const uint32_t r = ln % 3; // CFI code words (36.212 table 5.3.4-1): 011 011.. | 101 101.. | 110 110.. | all zero
+        m[0] = ((r == 0 ? 0u : 1u) != bit); m[1] = ((r == 1 ? 0u : 1u) != bit); m[2] = ((r == 2 ? 0u : 1u) != bit); m[3] = (0u != bit);
+    }
+    uint32_t ber[4];
+    for (int k = 0; k < 4; k++) ber[k] = (uint32_t)__popcll(__ballot(ln < 32 && m[k]));
+    uint32_t min_ber = 32, cfi = 0;
+    for (uint32_t k = 0; k < 4; k++)
+        if (ber[k] < min_ber) { min_ber = ber[k]; cfi = k + 1; }
+    return (min_ber < 4) ? cfi : 0u; // CFI_N_ACCEPTABLE_BERS (:2092)
+}
+
 __global__ __launch_bounds__(384) void k_pdcch_decode(const float *__restrict__ subframes, uint32_t sf_stride,
                                                       const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell,
                                                       PdcchDev P, GoldTables gt, PdcchResult *__restrict__ out)
@@ -236,23 +264,8 @@ __global__ __launch_bounds__(384) void k_pdcch_decode(const float *__restrict__ 
     }
     // ---- PCFICH (pcfich_channel_demap + cfi_channel_decode)
     if (wave == 0) {
-        demod_res(base, P.N_ant, P.N_ant, P.per_port, P.pcfich + (size_t)ci * 16, 16, gt, (((sf + 1) * (2 * cell + 1)) << 9) + cell, 0, pc_soft, ln);
-        __builtin_amdgcn_s_waitcnt(0);
-        __builtin_amdgcn_wave_barrier();
-        uint32_t bit = 0, m[4] = {0, 0, 0, 0};
-        if (ln < 32) {
-            bit = pc_soft[ln] >= 0 ? 0u : 1u;
-            const uint32_t r = ln % 3; // CFI code words (36.212 table 5.3.4-1): 011 011.. | 101 101.. | 110 110.. | all zero
-            m[0] = ((r == 0 ? 0u : 1u) != bit); m[1] = ((r == 1 ? 0u : 1u) != bit); m[2] = ((r == 2 ? 0u : 1u) != bit); m[3] = (0u != bit);
-        }
-        uint32_t ber[4];
-        for (int k = 0; k < 4; k++) ber[k] = (uint32_t)__popcll(__ballot(ln < 32 && m[k]));
-        if (ln == 0) {
-            uint32_t min_ber = 32, cfi = 0;
-            for (uint32_t k = 0; k < 4; k++)
-                if (ber[k] < min_ber) { min_ber = ber[k]; cfi = k + 1; }
-            s_cfi = (min_ber < 4) ? cfi : 0u; // CFI_N_ACCEPTABLE_BERS (:2092)
-        }
+        const uint32_t cfi = pcfich_cfi(base, P.N_ant, P.per_port, P.pcfich + (size_t)ci * 16, gt, sf, cell, pc_soft, ln);
+        if (ln == 0) s_cfi = cfi;
     }
     __syncthreads();
     const uint32_t cfi = s_cfi, n_symbs = cfi + (P.N_rb_dl <= 10 ? 1u : 0u);
@@ -289,6 +302,179 @@ __global__ __launch_bounds__(384) void k_pdcch_decode(const float *__restrict__ 
         }
         __builtin_amdgcn_wave_barrier();
     }
+}
+
+// ---- blind search over the whole control region (include/mi_lte.h: "PDCCH, 3GPP mode") -------------------------------------
+constexpr uint32_t SEARCH_N_MAX = 64 + 16, SEARCH_WAVES = 4, SEARCH_CHUNK_CCE = 16, SEARCH_MAP = 576, NO_CELL = 0xFFFFFFFFu;
+
+struct PdcchSearchDev {
+    uint32_t N_rb_dl, N_ant, n_cells, n_sizes, n_bits[MI_LTE_PDCCH_SEARCH_MAX_SIZES], flags;
+    uint32_t max_cce, max_waves;  // the largest N_cce of the tables and the (candidate, size) pairs it has
+    uint32_t unit_stride;         // soft bits per unit: 72 max_cce
+    const uint32_t *cells;        // [n_cells]
+    const uint32_t *pcfich;       // [n_cells][16]
+    const uint32_t *n_cce;        // [n_cells][4 (N_symbs - 1)]
+    const uint32_t *cce_re;       // [n_cells][4][36 max_cce] RE index of every CCE's elements in order
+    const uint16_t *rm_map;       // [n_sizes][SEARCH_MAP] position in d[3 N] of received bit k (of a candidate of any L)
+    const uint32_t *rnti_bits;    // [2048] the RNTI set
+};
+struct SearchUnit { uint32_t cfi, n_cce; };
+struct SearchHit { uint64_t payload; int32_t metric, energy; };
+struct SearchOut { uint32_t cfi, n_cce, n_found, pad; mi_lte_pdcch_found found[MI_LTE_PDCCH_SEARCH_MAX_FOUND]; };
+
+// 36.213 9.1.1: Y_k for k = sf, from Y_(-1) = rnti; and the number of candidates of an aggregation level
+__host__ __device__ inline uint32_t search_space_y(uint32_t rnti, uint32_t sf)
+{
+    uint32_t y = rnti;
+    for (uint32_t k = 0; k <= sf; k++) y = (39827u * y) % 65537u; // (y <= 65536: the product stays below 2^32)
+    return y;
+}
+__host__ __device__ inline uint32_t search_space_m(uint32_t L) { return L <= 2 ? 6u : 2u; }
+
+// the candidates of n_cce CCEs in reporting order: every L = 8, 4, 2, 1 in turn, first CCEs ascending
+__host__ __device__ inline uint32_t search_n_cand(uint32_t n_cce) { return (n_cce >> 3) + (n_cce >> 2) + (n_cce >> 1) + n_cce; }
+__host__ __device__ inline void search_cand(uint32_t n_cce, uint32_t cand, uint32_t &L, uint32_t &cce)
+{
+    const uint32_t n8 = n_cce >> 3, n4 = n_cce >> 2, n2 = n_cce >> 1;
+    if (cand < n8) { L = 8; cce = 8 * cand; }
+    else if (cand < n8 + n4) { L = 4; cce = 4 * (cand - n8); }
+    else if (cand < n8 + n4 + n2) { L = 2; cce = 2 * (cand - n8 - n4); }
+    else { L = 1; cce = cand - n8 - n4 - n2; }
+}
+
+// one workgroup per subframe: CFI, then every CCE de-mapped to int8 soft bits, SEARCH_CHUNK_CCE CCEs at a time through LDS
+__global__ __launch_bounds__(256) void k_pdcch_search_demod(const float *__restrict__ subframes, uint32_t sf_stride, const uint32_t *__restrict__ subfr_num,
+                                                            const uint32_t *__restrict__ n_id_cell, PdcchSearchDev P, GoldTables gt,
+                                                            SearchUnit *__restrict__ units, int8_t *__restrict__ soft_out)
+{
+    __shared__ int      soft[72 * SEARCH_CHUNK_CCE];
+    __shared__ int      pc_soft[32];
+    __shared__ uint32_t s_cfi, s_cell_idx;
+    const uint32_t unit = blockIdx.x, wave = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    const uint32_t sf = subfr_num[unit], cell = n_id_cell[unit];
+    const float   *base = subframes + (size_t)unit * sf_stride;
+    if (threadIdx.x == 0) {
+        uint32_t ci = NO_CELL;
+        for (uint32_t k = 0; k < P.n_cells; k++)
+            if (P.cells[k] == cell) { ci = k; break; }
+        s_cell_idx = sf <= 9 ? ci : NO_CELL; // (a subframe number the scrambler and the search spaces have no meaning for)
+        s_cfi      = 0;
+    }
+    __syncthreads();
+    const uint32_t ci = s_cell_idx;
+    if (ci != NO_CELL && wave == 0) {
+        const uint32_t cfi = pcfich_cfi(base, P.N_ant, 1, P.pcfich + (size_t)ci * 16, gt, sf, cell, pc_soft, ln);
+        if (ln == 0) s_cfi = cfi;
+    }
+    __syncthreads();
+    const uint32_t n_symbs = s_cfi + (P.N_rb_dl <= 10 ? 1u : 0u);
+    const bool     ok = ci != NO_CELL && s_cfi != 0 && n_symbs <= 4;
+    const uint32_t cfi = ok ? s_cfi : 0u, n_cce = ok ? min(P.n_cce[(size_t)ci * 4 + n_symbs - 1], P.max_cce) : 0u;
+    if (threadIdx.x == 0) units[unit] = SearchUnit{cfi, n_cce};
+    if (n_cce == 0) return; // (uniform)
+    const uint32_t *re  = P.cce_re + ((size_t)ci * 4 + n_symbs - 1) * 36 * P.max_cce;
+    int8_t         *out = soft_out + (size_t)unit * P.unit_stride;
+    for (uint32_t c0 = 0; c0 < n_cce; c0 += SEARCH_CHUNK_CCE) { // (uniform)
+        const uint32_t nc = min(SEARCH_CHUNK_CCE, n_cce - c0);
+        demod_res(base, P.N_ant, P.N_ant, 1, re + 36 * c0, 36 * nc, gt, (sf << 9) + cell, 72 * c0, soft, threadIdx.x, 256);
+        __syncthreads();
+        for (uint32_t k = threadIdx.x; k < 72 * nc; k += 256) out[72 * c0 + k] = (int8_t)soft[k];
+        __syncthreads();
+    }
+}
+
+// one wavefront per (unit, candidate, size); nothing in here waits for another wavefront
+__global__ __launch_bounds__(64 * SEARCH_WAVES) void k_pdcch_search_decode(const int8_t *__restrict__ soft, const SearchUnit *__restrict__ units,
+                                                                           const uint32_t *__restrict__ subfr_num, PdcchSearchDev P, uint32_t blocks_per_unit,
+                                                                           uint16_t *__restrict__ hit_rnti, SearchHit *__restrict__ hit_rec)
+{
+    __shared__ int32_t  d_all[SEARCH_WAVES][3 * SEARCH_N_MAX];
+    __shared__ uint64_t surv_all[SEARCH_WAVES][3 * SEARCH_N_MAX];
+    __shared__ uint8_t  cb_all[SEARCH_WAVES][SEARCH_N_MAX];
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), ln = threadIdx.x & 63;
+    const uint32_t unit = blockIdx.x / blocks_per_unit, w = (blockIdx.x - unit * blocks_per_unit) * SEARCH_WAVES + wv;
+    const uint32_t n_cce = units[unit].n_cce, cand = w / P.n_sizes, si = w - cand * P.n_sizes;
+    if (cand >= search_n_cand(n_cce)) return; // (uniform per wavefront, like everything up to the CRC)
+    uint32_t L, cce;
+    search_cand(n_cce, cand, L, cce);
+    const uint32_t n_bits = si == 0 ? P.n_bits[0] : si == 1 ? P.n_bits[1] : si == 2 ? P.n_bits[2] : P.n_bits[3];
+    const uint32_t N = n_bits + 16, E = 72 * L, P3 = 3 * N;
+    uint16_t      *hit = hit_rnti + (size_t)unit * P.max_waves + w;
+    if (N >= E || N > SEARCH_N_MAX) { // no redundancy left
+        if (ln == 0) *hit = 0;
+        return;
+    }
+    int32_t  *d    = d_all[wv];
+    uint64_t *surv = surv_all[wv];
+    uint8_t  *cb   = cb_all[wv];
+    auto      wave_sync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); };
+    // a. rate un-matching: the circular buffer without its dummies has period 3 N, so every d position gathers its own repeats
+    const int8_t   *e   = soft + (size_t)unit * P.unit_stride + 72 * cce;
+    const uint16_t *map = P.rm_map + (size_t)si * SEARCH_MAP;
+    int32_t         energy = 0;
+    for (uint32_t r = ln; r < P3; r += 64) {
+        int32_t s = 0;
+        for (uint32_t k = r; k < E; k += P3) s += e[k];
+        d[map[r]] = s;
+        energy += abs(s);
+    }
+    energy = wave_sum(energy);
+    wave_sync();
+    if (energy == 0) { // b. an empty region
+        if (ln == 0) *hit = 0;
+        return;
+    }
+    int32_t metric;
+    tbcc_decode(d, N, surv, cb, ln, wave_sync, metric); // c.
+    if (ln == 0) { // d. CRC16 and acceptance
+        uint32_t rem = 0, par = 0;
+        uint64_t payload = 0;
+        for (uint32_t i = 0; i < N; i++) {
+            rem = (rem << 1) | (i < n_bits ? cb[i] : 0u);
+            if (rem & 0x10000u) rem ^= 0x11021u;
+            if (i < n_bits) payload = (payload << 1) | cb[i];
+            else par = (par << 1) | cb[i];
+        }
+        const uint32_t x = (rem ^ par) & 0xFFFFu;
+        bool ok = x != 0 && ((P.rnti_bits[x >> 5] >> (x & 31u)) & 1u);
+        if (ok && !(P.flags & MI_LTE_PDCCH_SEARCH_ANY_CCE) && !(L >= 4 && cce < 16)) { // not in the common search space: x's own candidates
+            const uint32_t y = search_space_y(x, subfr_num[unit]), nl = n_cce / L; // (nl >= 1: the candidate exists)
+            ok = false;
+            for (uint32_t m = 0; m < search_space_m(L); m++) ok = ok || L * ((y + m) % nl) == cce;
+        }
+        *hit = ok ? (uint16_t)x : (uint16_t)0;
+        if (ok) hit_rec[(size_t)unit * P.max_waves + w] = SearchHit{payload, metric, energy};
+    }
+}
+
+// one wavefront per unit: the hits in wave order (= L descending, first CCE ascending, size position ascending), the first MAX_FOUND kept
+__global__ __launch_bounds__(64) void k_pdcch_search_compact(const SearchUnit *__restrict__ units, PdcchSearchDev P, const uint16_t *__restrict__ hit_rnti,
+                                                             const SearchHit *__restrict__ hit_rec, SearchOut *__restrict__ out)
+{
+    const uint32_t   unit = blockIdx.x, ln = threadIdx.x;
+    const SearchUnit u = units[unit];
+    const uint32_t   n_w = search_n_cand(u.n_cce) * P.n_sizes;
+    SearchOut       *o = out + unit;
+    uint32_t         total = 0;
+    for (uint32_t w0 = 0; w0 < n_w; w0 += 64) { // (uniform)
+        const uint32_t w = w0 + ln, x = w < n_w ? hit_rnti[(size_t)unit * P.max_waves + w] : 0u;
+        const uint64_t m = __ballot(x != 0);
+        const uint32_t rank = total + (uint32_t)__popcll(m & ((1ull << ln) - 1));
+        if (x != 0 && rank < MI_LTE_PDCCH_SEARCH_MAX_FOUND) {
+            const uint32_t  cand = w / P.n_sizes, si = w - cand * P.n_sizes;
+            const SearchHit h = hit_rec[(size_t)unit * P.max_waves + w];
+            uint32_t        L, cce;
+            search_cand(u.n_cce, cand, L, cce);
+            mi_lte_pdcch_found f;
+            f.rnti = x; f.L = L; f.cce = cce;
+            f.n_bits = si == 0 ? P.n_bits[0] : si == 1 ? P.n_bits[1] : si == 2 ? P.n_bits[2] : P.n_bits[3];
+            f.payload = h.payload; f.metric = h.metric; f.energy = h.energy;
+            o->found[rank] = f;
+        }
+        total += (uint32_t)__popcll(m);
+    }
+    if (ln < MI_LTE_PDCCH_SEARCH_MAX_FOUND && ln >= total) o->found[ln] = mi_lte_pdcch_found{0, 0, 0, 0, 0, 0, 0};
+    if (ln == 0) { o->cfi = u.cfi; o->n_cce = u.n_cce; o->n_found = total; o->pad = 0; }
 }
 
 // ---- PBCH (liblte_phy_bch_channel_decode, liblte_phy.cc:3968-4105; bch_channel_decode :12581-12650) ----------------------
@@ -395,14 +581,15 @@ std::vector<uint32_t> cc_interleaver_rank(uint32_t n)
     return out;
 }
 
-// RE lists of the six common-search-space candidates for one (cell, N_symbs)
-void candidate_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_res, uint32_t N_symbs, uint32_t *out /*[N_CAND][RE_MAX]*/)
+// the resource elements of every CCE of one (cell, N_symbs) in order, 36 per CCE: perm[36 N_cce ..] (plus the REGs behind the last whole CCE);
+// returns N_cce
+uint32_t cce_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_res, uint32_t N_symbs, std::vector<uint32_t> &perm)
 {
-    std::fill(out, out + N_CAND * RE_MAX, NO_RE);
+    perm.clear();
     const CtrlRegs cr = ctrl_regs(N_rb_dl, cell, phich_res);
     int64_t n_reg = (int64_t)N_symbs * (N_rb_dl * 3) - N_rb_dl - 4 - (int64_t)cr.phich_k.size();
     if (N_ant == 4) n_reg -= N_rb_dl;
-    if (n_reg <= 0) return;
+    if (n_reg <= 0) return 0;
     const uint32_t N_reg = (uint32_t)n_reg, N_cce = N_reg / 9;
     std::vector<uint32_t> reg(4 * (size_t)N_reg, NO_RE); // REG m: its 4 RE indices (l*1200 + k)
     uint32_t m = 0;
@@ -426,10 +613,20 @@ void candidate_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_
             }
         }
     // undo the cell-specific cyclic shift, then the sub-block interleaver
-    std::vector<uint32_t> shifted(4 * (size_t)N_reg), perm(4 * (size_t)N_reg);
+    std::vector<uint32_t> shifted(4 * (size_t)N_reg);
+    perm.resize(4 * (size_t)N_reg);
     for (uint32_t i = 0; i < N_reg; i++) std::copy(&reg[4 * i], &reg[4 * i] + 4, &shifted[4 * ((i + cell) % N_reg)]);
     const std::vector<uint32_t> rank = cc_interleaver_rank(N_reg);
     for (uint32_t i = 0; i < N_reg; i++) std::copy(&shifted[4 * rank[i]], &shifted[4 * rank[i]] + 4, &perm[4 * i]);
+    return N_cce;
+}
+
+// RE lists of the six common-search-space candidates for one (cell, N_symbs)
+void candidate_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_res, uint32_t N_symbs, uint32_t *out /*[N_CAND][RE_MAX]*/)
+{
+    std::fill(out, out + N_CAND * RE_MAX, NO_RE);
+    std::vector<uint32_t> perm;
+    const uint32_t N_cce = cce_res(N_rb_dl, N_ant, cell, phich_res, N_symbs, perm);
     for (uint32_t c = 0; c < N_CAND; c++) {
         // the reference always tries all six candidates; CCEs past the last one hold whatever its scratch held before --
         // zeros on a fresh LIBLTE_PHY_STRUCT, which de-map to soft value 0.  Here those elements are marked absent and
@@ -472,6 +669,22 @@ struct mi_lte_pdcch_plan {
     mi_lte_dl_cfg cfg;
     PdcchDev      dev{};
     std::vector<void *> owned;
+};
+
+struct mi_lte_pdcch_search_plan {
+    mi_lte_dl_cfg  cfg;
+    PdcchSearchDev dev{};
+    uint32_t      *d_rnti_bits = nullptr;
+    std::vector<void *> owned; // the tables
+    // what a run fills, sized for the largest batch seen (cap_units)
+    uint32_t    cap_units = 0;
+    bool        ran = false;
+    int8_t     *d_soft = nullptr;
+    SearchUnit *d_units = nullptr;
+    uint16_t   *d_hit = nullptr;  // [unit][max_waves] the RNTI found by that (candidate, size) pair, 0 = none
+    SearchHit  *d_rec = nullptr;  // [unit][max_waves] written where d_hit is not 0
+    SearchOut  *d_out = nullptr;
+    std::vector<SearchOut> h_out;
 };
 
 extern "C" {
@@ -751,29 +964,234 @@ int mi_lte_pbch_decode_run(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const floa
 // PCFICH + up to four format-1A DCIs at aggregation level 4 in the common search space (what the reference's own
 // transmitter sends, liblte_phy.cc:4113-4330), through a smooth random channel per port + AWGN, directly as device-subframe
 // grids with noisy channel estimates.  Transmit diversity follows 36.211 6.3.4.3 on all ports.
-int mi_lte_synth_ctrl_grids(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
-                            const uint32_t *h_cfi, const mi_lte_synth_dci *h_dci /*[n_units][n_dci]*/, uint32_t n_dci,
-                            const mi_lte_synth_channel *chan, float *h_grids)
+// ---- the blind search's plan and run (include/mi_lte.h: "PDCCH, 3GPP mode") ----------------------------------------------------
+
+int mi_lte_pdcch_search_space(uint32_t rnti, uint32_t subfr_num, uint32_t N_cce, uint32_t L, uint32_t *first_cce /*[6]*/, uint32_t *n)
 {
-    if (!cfg || !h_subfr_num || !h_n_id_cell || !h_cfi || (n_dci && !h_dci) || n_dci > 4 || !chan || !h_grids) return MI_LTE_ERR_INVALID_ARG;
+    if (!first_cce || !n || rnti == 0 || rnti > 0xFFFFu || subfr_num > 9 || !(L == 1 || L == 2 || L == 4 || L == 8)) return MI_LTE_ERR_INVALID_ARG;
+    const uint32_t nl = N_cce / L;
+    *n = 0;
+    if (nl == 0) return MI_LTE_OK; // no candidate fits: no modulus to take
+    const uint32_t y = search_space_y(rnti, subfr_num);
+    for (uint32_t m = 0; m < search_space_m(L); m++) first_cce[(*n)++] = L * ((y + m) % nl);
+    return MI_LTE_OK;
+}
+
+int mi_lte_pdcch_search_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, float phich_res, uint32_t phich_dur_extended, uint32_t flags,
+                                    const uint32_t *h_cells, uint32_t n_cells, const uint32_t *h_n_bits, uint32_t n_sizes, mi_lte_pdcch_search_plan **out)
+{
+    if (!ctx || !cfg || !h_cells || n_cells == 0 || !h_n_bits || !out) return MI_LTE_ERR_INVALID_ARG;
+    const uint32_t nrb = cfg->N_rb_dl;
+    if (!standard_ctrl_cfg(nrb, phich_res) || !(cfg->N_ant == 1 || cfg->N_ant == 2 || cfg->N_ant == 4) || phich_dur_extended) {
+        ctx->err = "PDCCH search plan: standard bandwidths, 1/2/4 ports, PHICH resource in (0, 2], normal PHICH duration";
+        return MI_LTE_ERR_UNSUPPORTED;
+    }
+    if (n_sizes == 0 || n_sizes > MI_LTE_PDCCH_SEARCH_MAX_SIZES || (flags & ~MI_LTE_PDCCH_SEARCH_ANY_CCE)) return MI_LTE_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n_sizes; i++) {
+        if (h_n_bits[i] < 8 || h_n_bits[i] > 64) return MI_LTE_ERR_INVALID_ARG;
+        for (uint32_t j = 0; j < i; j++)
+            if (h_n_bits[j] == h_n_bits[i]) return MI_LTE_ERR_INVALID_ARG;
+    }
+    for (uint32_t c = 0; c < n_cells; c++)
+        if (h_cells[c] > 503) return MI_LTE_ERR_INVALID_ARG;
+    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    auto *pl = new mi_lte_pdcch_search_plan();
+    auto  guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_lte_pdcch_search_plan_destroy(nullptr, pl); });
+    pl->cfg = *cfg;
+    // every CCE's resource elements, per cell and region size; the tables' extent is the largest N_cce among them
+    std::vector<std::vector<uint32_t>> perm((size_t)n_cells * 4);
+    std::vector<uint32_t> cells(h_cells, h_cells + n_cells), pcf((size_t)n_cells * 16), ncce((size_t)n_cells * 4), cand(N_CAND * RE_MAX);
+    uint32_t max_cce = 0;
+    for (uint32_t c = 0; c < n_cells; c++) {
+        const int rc = mi_lte_pdcch_re_tables(nrb, cfg->N_ant, cells[c], phich_res, 1, &pcf[(size_t)c * 16], cand.data());
+        if (rc != MI_LTE_OK) return rc;
+        for (uint32_t ns = 1; ns <= 4; ns++) {
+            ncce[(size_t)c * 4 + ns - 1] = cce_res(nrb, cfg->N_ant, cells[c], phich_res, ns, perm[(size_t)c * 4 + ns - 1]);
+            max_cce = std::max(max_cce, ncce[(size_t)c * 4 + ns - 1]);
+        }
+    }
+    std::vector<uint32_t> res((size_t)n_cells * 4 * 36 * max_cce, NO_RE);
+    for (size_t t = 0; t < perm.size(); t++) std::copy(perm[t].begin(), perm[t].begin() + 36 * (size_t)ncce[t], res.begin() + t * 36 * max_cce);
+    std::vector<uint16_t> rm((size_t)n_sizes * SEARCH_MAP, 0);
+    for (uint32_t i = 0; i < n_sizes; i++) conv_rm_map(h_n_bits[i] + 16, SEARCH_MAP, &rm[(size_t)i * SEARCH_MAP]);
+    const std::vector<uint32_t> no_rnti(2048, 0);
+    auto up = [&](const void *h, size_t bytes, void **d) -> int {
+        if (hipMalloc(d, bytes ? bytes : 4) != hipSuccess) return -1;
+        pl->owned.push_back(*d);
+        return mi_lte_memcpy_h2d(ctx, *d, h, bytes) == MI_LTE_OK ? 0 : -1;
+    };
+    void *d_cells, *d_pcf, *d_ncce, *d_res, *d_rm, *d_bits;
+    if (up(cells.data(), cells.size() * 4, &d_cells) || up(pcf.data(), pcf.size() * 4, &d_pcf) || up(ncce.data(), ncce.size() * 4, &d_ncce) ||
+        up(res.data(), res.size() * 4, &d_res) || up(rm.data(), rm.size() * 2, &d_rm) || up(no_rnti.data(), no_rnti.size() * 4, &d_bits)) {
+        ctx->err = "PDCCH search plan: device allocation failed";
+        return MI_LTE_ERR_NOMEM;
+    }
+    MI_HIP_CHECK(ctx, mi_stream_wait_polling(ctx));
+    PdcchSearchDev &D = pl->dev;
+    D = PdcchSearchDev{};
+    D.N_rb_dl = nrb; D.N_ant = cfg->N_ant; D.n_cells = n_cells; D.n_sizes = n_sizes; D.flags = flags;
+    for (uint32_t i = 0; i < n_sizes; i++) D.n_bits[i] = h_n_bits[i];
+    D.max_cce = max_cce; D.max_waves = search_n_cand(max_cce) * n_sizes; D.unit_stride = 72 * max_cce;
+    D.cells = (const uint32_t *)d_cells; D.pcfich = (const uint32_t *)d_pcf; D.n_cce = (const uint32_t *)d_ncce; D.cce_re = (const uint32_t *)d_res;
+    D.rm_map = (const uint16_t *)d_rm; D.rnti_bits = (const uint32_t *)d_bits;
+    pl->d_rnti_bits = (uint32_t *)d_bits;
+    guard.armed = false;
+    *out = pl;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pdcch_search_plan_set_rntis(mi_lte_ctx *ctx, mi_lte_pdcch_search_plan *pl, const uint32_t *h_rnti, uint32_t n_rnti)
+{
+    if (!ctx || !pl || (n_rnti && !h_rnti)) return MI_LTE_ERR_INVALID_ARG;
+    std::vector<uint32_t> bits(2048, 0);
+    for (uint32_t i = 0; i < n_rnti; i++) {
+        if (h_rnti[i] == 0 || h_rnti[i] > 0xFFFFu) return MI_LTE_ERR_INVALID_ARG; // (the set stays as it was)
+        bits[h_rnti[i] >> 5] |= 1u << (h_rnti[i] & 31u);
+    }
+    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    MI_H2D(ctx, pl->d_rnti_bits, bits.data(), bits.size() * 4); // (behind whatever run is still queued on the stream)
+    return MI_LTE_OK;
+}
+
+static void search_free_run_buffers(mi_lte_pdcch_search_plan *pl)
+{
+    for (void *p : {(void *)pl->d_soft, (void *)pl->d_units, (void *)pl->d_hit, (void *)pl->d_rec, (void *)pl->d_out})
+        if (p) (void)hipFree(p);
+    pl->d_soft = nullptr; pl->d_units = nullptr; pl->d_hit = nullptr; pl->d_rec = nullptr; pl->d_out = nullptr;
+    pl->cap_units = 0;
+}
+
+void mi_lte_pdcch_search_plan_destroy(mi_lte_ctx *ctx, mi_lte_pdcch_search_plan *pl)
+{
+    if (!pl) return;
+    if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
+    search_free_run_buffers(pl);
+    for (void *p : pl->owned) (void)hipFree(p);
+    delete pl;
+}
+
+int mi_lte_pdcch_search_run(mi_lte_ctx *ctx, mi_lte_pdcch_search_plan *pl, const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell,
+                            uint32_t n_units, uint32_t *h_cfi, uint32_t *h_n_cce, uint32_t *h_n_found, mi_lte_pdcch_found *h_found)
+{
+    if (!ctx || !pl || !d_subframes || !d_subfr_num || !d_n_id_cell || n_units == 0 || !h_cfi || !h_n_cce || !h_n_found || !h_found) return MI_LTE_ERR_INVALID_ARG;
+    const PdcchSearchDev &D = pl->dev;
+    const uint32_t blocks_per_unit = (D.max_waves + SEARCH_WAVES - 1) / SEARCH_WAVES;
+    if ((uint64_t)n_units * std::max(blocks_per_unit, 1u) > 0x7FFFFFFFull) {
+        ctx->err = "PDCCH search: too many units for one launch";
+        return MI_LTE_ERR_UNSUPPORTED;
+    }
+    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    int rc = mi_ctx_gold_tables(ctx);
+    if (rc != MI_LTE_OK) return rc;
+    if (n_units > pl->cap_units) { // the plan's own buffers grow to the largest batch seen; a run at that size or below allocates nothing
+        MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        search_free_run_buffers(pl);
+        pl->ran = false;
+        const size_t nu = n_units, nw = std::max(D.max_waves, 1u);
+        if (hipMalloc((void **)&pl->d_soft, std::max<size_t>(nu * D.unit_stride, 4)) != hipSuccess || hipMalloc((void **)&pl->d_units, nu * sizeof(SearchUnit)) != hipSuccess ||
+            hipMalloc((void **)&pl->d_hit, nu * nw * sizeof(uint16_t)) != hipSuccess || hipMalloc((void **)&pl->d_rec, nu * nw * sizeof(SearchHit)) != hipSuccess ||
+            hipMalloc((void **)&pl->d_out, nu * sizeof(SearchOut)) != hipSuccess) {
+            search_free_run_buffers(pl);
+            ctx->err = "PDCCH search: device allocation failed";
+            return MI_LTE_ERR_NOMEM;
+        }
+        pl->cap_units = n_units;
+        pl->h_out.resize(n_units);
+    }
+    GoldTables gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
+    MI_LAUNCH(ctx, "k_pdcch_search_demod", k_pdcch_search_demod, dim3(n_units), dim3(256), 0, d_subframes, (uint32_t)mi_lte_subframe_floats(pl->cfg.N_ant), d_subfr_num,
+              d_n_id_cell, D, gt, pl->d_units, pl->d_soft);
+    MI_HIP_CHECK(ctx, hipGetLastError());
+    if (blocks_per_unit) {
+        MI_LAUNCH(ctx, "k_pdcch_search_decode", k_pdcch_search_decode, dim3(n_units * blocks_per_unit), dim3(64 * SEARCH_WAVES), 0, pl->d_soft, pl->d_units, d_subfr_num, D,
+                  blocks_per_unit, pl->d_hit, pl->d_rec);
+        MI_HIP_CHECK(ctx, hipGetLastError());
+    }
+    MI_LAUNCH(ctx, "k_pdcch_search_compact", k_pdcch_search_compact, dim3(n_units), dim3(64), 0, pl->d_units, D, pl->d_hit, pl->d_rec, pl->d_out);
+    MI_HIP_CHECK(ctx, hipGetLastError());
+    pl->ran = true;
+    MI_D2H(ctx, pl->h_out.data(), pl->d_out, sizeof(SearchOut) * (size_t)n_units); // the run's one wait
+    for (uint32_t u = 0; u < n_units; u++) {
+        const SearchOut &o = pl->h_out[u];
+        h_cfi[u] = o.cfi; h_n_cce[u] = o.n_cce; h_n_found[u] = o.n_found;
+        memcpy(h_found + (size_t)u * MI_LTE_PDCCH_SEARCH_MAX_FOUND, o.found, sizeof(o.found));
+    }
+    ctx->last_kernels = "k_pdcch_search_demod:1,k_pdcch_search_decode:1,k_pdcch_search_compact:1";
+    return MI_LTE_OK;
+}
+
+int mi_lte_pdcch_search_soft(const mi_lte_pdcch_search_plan *pl, const int8_t **d_soft, uint32_t *unit_stride)
+{
+    if (!pl || !d_soft || !unit_stride || !pl->ran) return MI_LTE_ERR_INVALID_ARG;
+    *d_soft = pl->d_soft;
+    *unit_stride = pl->dev.unit_stride;
+    return MI_LTE_OK;
+}
+
+// A C-RNTI's DCI format 0 / 1A as tx_ctrl.cc packs them (pack_0, pack_1a); the field list is in include/mi_lte.h
+int mi_lte_dci_0_1a_unpack_crnti(uint64_t payload, uint32_t n_bits, uint32_t rnti, uint32_t N_rb, uint32_t N_ant, mi_lte_dci_crnti *o)
+{
+    if (!o || n_bits > 64 || rnti == 0 || rnti > 0xFFFFu || N_rb == 0 || N_rb > 110 || !(N_ant == 1 || N_ant == 2 || N_ant == 4)) return MI_LTE_ERR_INVALID_ARG;
+    const uint32_t riv_len = (uint32_t)ceilf(logf(N_rb * (N_rb + 1) / 2) / logf(2)); // (the float logarithms of the packers)
+    uint32_t pos = n_bits;
+    auto take = [&](uint32_t n) { pos -= n; return (uint32_t)((payload >> pos) & ((1ull << n) - 1ull)); };
+    if (n_bits < 1) return MI_LTE_ERR_INVALID_ARG;
+    memset(o, 0, sizeof(*o));
+    o->format = take(1);
+    if (n_bits < 2 + riv_len + (o->format ? 13u : 12u)) return MI_LTE_ERR_INVALID_ARG;
+    o->flag = take(1);
+    o->riv  = take(riv_len);
+    const uint32_t q = o->riv / N_rb, r = o->riv % N_rb;
+    const bool     riv_ok = o->riv < N_rb * (N_rb + 1) / 2; // (inside that range the two branches below are one-to-one)
+    if (q + r < N_rb) { o->N_prb = q + 1; o->rb_start = r; }
+    else if (riv_ok) { o->N_prb = N_rb - q + 1; o->rb_start = N_rb - 1 - r; }
+    o->mcs = take(5);
+    if (o->format) { o->harq = take(3); o->ndi = take(1); o->rv = take(2); o->tpc = take(2); }
+    else { o->ndi = take(1); o->tpc = take(2); o->cyclic_shift = take(3); o->cqi_request = take(1); }
+    o->alloc.rnti = rnti;
+    if (!riv_ok || o->N_prb == 0 || o->N_prb > N_rb) { o->N_prb = 0; return 4; }
+    if (o->format && o->flag) return 4; // distributed VRBs: no PRB list here
+    o->alloc.N_prb = o->N_prb;
+    for (uint32_t i = 0; i < o->N_prb; i++) o->alloc.prb[0][i] = o->alloc.prb[1][i] = (uint8_t)(o->rb_start + i);
+    if (o->mcs > 28) return 4; // no transport block of its own
+    if (o->format) {
+        const uint32_t i_tbs = o->mcs <= 9 ? o->mcs : o->mcs <= 16 ? o->mcs - 1 : o->mcs - 2;
+        o->alloc.mod_type = o->mcs <= 9 ? 1 : o->mcs <= 16 ? 2 : 3;
+        o->alloc.tbs      = 8u * LTE_TBS_DIV8[i_tbs][o->N_prb - 1];
+        o->alloc.rv_idx   = o->rv;
+        o->alloc.tx_mode  = N_ant == 1 ? 1 : 2;
+    }
+    return 0;
+}
+
+} // extern "C"
+
+// one DCI of a synthetic control region: n_bits payload bits (first bit in bit n_bits - 1) for rnti on CCEs cce .. cce + L - 1
+struct CtrlRec { uint32_t rnti, L, cce, n_bits; uint64_t payload; };
+
+// The body both generators share.  records(u, N_cce, out) lists unit u's DCIs (every one inside the N_cce CCEs, none overlapping) or returns
+// an error; per DCI: CRC16 masked with the RNTI (36.212 5.3.3.2), the tail-biting convolutional code (5.1.3.1), rate matching to 72 L bits
+// (5.1.4.2), scrambling at bit 72 cce of the subframe's sequence, QPSK and transmit diversity onto the CCEs' resource elements.
+template <typename Records>
+static int synth_ctrl_grids(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
+                            const uint32_t *h_cfi, const mi_lte_synth_channel *chan, float *h_grids, Records records)
+{
     const uint32_t nrb = cfg->N_rb_dl, n_ant = cfg->N_ant;
     if (!(n_ant == 1 || n_ant == 2 || n_ant == 4)) return MI_LTE_ERR_INVALID_ARG;
-    uint32_t sz[2];
-    dci_sizes(nrb, &sz[0], &sz[1]);
-    const uint32_t K = sz[0] + 16;
-    std::vector<uint16_t> map(576);
-    conv_rm_map(K, 288, map.data());
     const size_t plane = 16 * (size_t)N_SC_MAX, nf = (2 + 2 * (size_t)n_ant) * plane;
     const double r2 = 1.0 / std::sqrt(2.0);
     synth::Rng   rng(chan->seed);
     std::vector<double> tr(n_ant * plane), ti(n_ant * plane);
-    std::vector<uint32_t> cand(N_CAND * RE_MAX);
+    std::vector<uint32_t> cand(N_CAND * RE_MAX), perm;
+    std::vector<CtrlRec>  recs;
+    std::vector<uint16_t> map(576);
     uint32_t pcf[16];
     for (uint32_t u = 0; u < n_units; u++) {
         const uint32_t sf = h_subfr_num[u], cell = h_n_id_cell[u], cfi = h_cfi[u], n_symbs = cfi + (nrb <= 10 ? 1 : 0);
         if (cfi < 1 || cfi > 4 || n_symbs > 4 || cell > 503 || sf > 9) return MI_LTE_ERR_INVALID_ARG;
         int rc = mi_lte_pdcch_re_tables(nrb, n_ant, cell, phich_res, n_symbs, pcf, cand.data());
         if (rc != MI_LTE_OK) return rc;
+        const uint32_t N_cce = cce_res(nrb, n_ant, cell, phich_res, n_symbs, perm);
         std::fill(tr.begin(), tr.end(), 0.0);
         std::fill(ti.begin(), ti.end(), 0.0);
         // d[0..n): QPSK symbols of scrambled bits b -> transmit-diversity pre-coding onto the elements pos[]
@@ -799,27 +1217,23 @@ int mi_lte_synth_ctrl_grids(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t 
             for (uint32_t i = 0; i < 32; i++) b[i] = (uint8_t)((cfi == 4 ? 0u : ((i % 3) == cfi - 1 ? 0u : 1u)) ^ c[i]);
             place(pcf, b, 16);
         }
-        std::vector<uint8_t> c(4 * 288);
-        synth::gold((sf << 9) + cell, 4 * 288, c.data());
-        for (uint32_t a = 0; a < n_dci; a++) {
-            const mi_lte_synth_dci &d = h_dci[(size_t)u * n_dci + a];
-            if (d.rnti == 0) continue; // unused slot
-            if (cand[a * RE_MAX + 143] == NO_RE) continue; // this candidate's CCEs do not all exist: nothing is sent (as the reference)
-            // DCI format 1A for SI-/P-/RA-RNTI (36.212 5.3.3.1.3; the reference's dci_1a_pack :13138-13215)
+        recs.clear();
+        rc = records(u, N_cce, recs);
+        if (rc != MI_LTE_OK) return rc;
+        std::vector<uint8_t> c(72 * (size_t)N_cce + 1);
+        synth::gold((sf << 9) + cell, 72 * N_cce, c.data());
+        for (const CtrlRec &d : recs) {
+            const uint32_t K = d.n_bits + 16, E = 72 * d.L;
             std::vector<uint8_t> bits(K, 0);
-            uint32_t             pos = 0;
-            auto push = [&](uint32_t v, uint32_t n) { for (uint32_t i = 0; i < n; i++) bits[pos++] = (uint8_t)((v >> (n - 1 - i)) & 1u); };
-            const uint32_t riv_len = (uint32_t)ceilf(logf(nrb * (nrb + 1) / 2) / logf(2));
-            if (d.N_prb == 0 || d.N_prb - 1 > nrb / 2 || d.rb_start + d.N_prb > nrb || d.mcs > 26) return MI_LTE_ERR_INVALID_ARG;
-            push(1, 1); push(0, 1); push(nrb * (d.N_prb - 1) + d.rb_start, riv_len); push(d.mcs, 5); push(0, 3); push(0, 1); push(d.rv_idx, 2); push(1, 2);
+            for (uint32_t i = 0; i < d.n_bits; i++) bits[i] = (uint8_t)((d.payload >> (d.n_bits - 1 - i)) & 1u);
             // CRC16 masked with the RNTI (36.212 5.3.3.2)
             uint32_t rem = 0;
-            for (uint32_t t = 0; t < sz[0] + 16; t++) {
-                rem = (rem << 1) | (t < sz[0] ? bits[t] : 0u);
+            for (uint32_t t = 0; t < K; t++) {
+                rem = (rem << 1) | (t < d.n_bits ? bits[t] : 0u);
                 if (rem & 0x10000u) rem ^= 0x11021u;
             }
             rem ^= d.rnti & 0xFFFFu;
-            for (uint32_t i = 0; i < 16; i++) bits[sz[0] + i] = (uint8_t)((rem >> (15 - i)) & 1u);
+            for (uint32_t i = 0; i < 16; i++) bits[d.n_bits + i] = (uint8_t)((rem >> (15 - i)) & 1u);
             // tail-biting convolutional code, K = 7, rate 1/3 (36.212 5.1.3.1)
             std::vector<uint8_t> dd(3 * K);
             uint32_t             state = 0;
@@ -830,10 +1244,11 @@ int mi_lte_synth_ctrl_grids(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t 
                 for (uint32_t o = 0; o < 3; o++) dd[3 * t + o] = (uint8_t)(__builtin_popcount(reg & G[o]) & 1);
                 state = reg >> 1;
             }
-            // rate matching to E = 288 (aggregation level 4) and scrambling at the candidate's offset
-            uint8_t e[288];
-            for (uint32_t k = 0; k < 288; k++) e[k] = dd[map[k]] ^ c[a * 288 + k];
-            place(&cand[a * RE_MAX], e, 144);
+            // rate matching to E = 72 L and scrambling at the first CCE's offset
+            uint8_t e[576];
+            conv_rm_map(K, E, map.data());
+            for (uint32_t k = 0; k < E; k++) e[k] = dd[map[k]] ^ c[72 * (size_t)d.cce + k];
+            place(&perm[36 * (size_t)d.cce], e, E / 2);
         }
         // channel + noise -> rx grid and estimates (symbols 0..3 only: the control region)
         float *g = h_grids + (size_t)u * nf;
@@ -861,6 +1276,58 @@ int mi_lte_synth_ctrl_grids(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t 
             }
     }
     return MI_LTE_OK;
+}
+
+extern "C" {
+
+int mi_lte_synth_ctrl_grids(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
+                            const uint32_t *h_cfi, const mi_lte_synth_dci *h_dci /*[n_units][n_dci]*/, uint32_t n_dci,
+                            const mi_lte_synth_channel *chan, float *h_grids)
+{
+    if (!cfg || !h_subfr_num || !h_n_id_cell || !h_cfi || (n_dci && !h_dci) || n_dci > 4 || !chan || !h_grids) return MI_LTE_ERR_INVALID_ARG;
+    const uint32_t nrb = cfg->N_rb_dl;
+    uint32_t sz[2];
+    dci_sizes(nrb, &sz[0], &sz[1]);
+    return synth_ctrl_grids(cfg, phich_res, n_units, h_subfr_num, h_n_id_cell, h_cfi, chan, h_grids, [&](uint32_t u, uint32_t N_cce, std::vector<CtrlRec> &out) {
+        for (uint32_t a = 0; a < n_dci; a++) {
+            const mi_lte_synth_dci &d = h_dci[(size_t)u * n_dci + a];
+            if (d.rnti == 0) continue; // unused slot
+            if (4 * a + 4 > N_cce) continue; // this candidate's CCEs do not all exist: nothing is sent (as the reference)
+            // DCI format 1A for SI-/P-/RA-RNTI (36.212 5.3.3.1.3; the reference's dci_1a_pack :13138-13215)
+            uint64_t payload = 0;
+            uint32_t pos = 0;
+            auto push = [&](uint32_t v, uint32_t n) { payload = (payload << n) | (v & ((1u << n) - 1u)); pos += n; };
+            const uint32_t riv_len = (uint32_t)ceilf(logf(nrb * (nrb + 1) / 2) / logf(2));
+            if (d.N_prb == 0 || d.N_prb - 1 > nrb / 2 || d.rb_start + d.N_prb > nrb || d.mcs > 26) return (int)MI_LTE_ERR_INVALID_ARG;
+            push(1, 1); push(0, 1); push(nrb * (d.N_prb - 1) + d.rb_start, riv_len); push(d.mcs, 5); push(0, 3); push(0, 1); push(d.rv_idx, 2); push(1, 2);
+            if (pos > sz[0]) return (int)MI_LTE_ERR_INVALID_ARG;
+            out.push_back(CtrlRec{d.rnti, 4, 4 * a, sz[0], payload << (sz[0] - pos)});
+        }
+        return (int)MI_LTE_OK;
+    });
+}
+
+// any DCI anywhere (include/mi_lte.h): up to MI_LTE_SYNTH_MAX_REC records per unit, rnti = 0 marks an unused slot
+int mi_lte_synth_ctrl_grids_dci(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
+                                const uint32_t *h_cfi, const mi_lte_synth_dci_rec *h_rec /*[n_units][n_rec]*/, uint32_t n_rec,
+                                const mi_lte_synth_channel *chan, float *h_grids)
+{
+    if (!cfg || !h_subfr_num || !h_n_id_cell || !h_cfi || (n_rec && !h_rec) || n_rec > MI_LTE_SYNTH_MAX_REC || !chan || !h_grids) return MI_LTE_ERR_INVALID_ARG;
+    return synth_ctrl_grids(cfg, phich_res, n_units, h_subfr_num, h_n_id_cell, h_cfi, chan, h_grids, [&](uint32_t u, uint32_t N_cce, std::vector<CtrlRec> &out) {
+        uint8_t used[128] = {0}; // (N_cce <= 121: 100 RB, four symbols)
+        for (uint32_t a = 0; a < n_rec; a++) {
+            const mi_lte_synth_dci_rec &d = h_rec[(size_t)u * n_rec + a];
+            if (d.rnti == 0) continue; // unused slot
+            if (d.rnti > 0xFFFFu || !(d.L == 1 || d.L == 2 || d.L == 4 || d.L == 8) || d.cce % d.L || d.n_bits < 1 || d.n_bits > 64) return (int)MI_LTE_ERR_INVALID_ARG;
+            if (d.cce >= N_cce || d.cce + d.L > N_cce || N_cce > 128) return (int)MI_LTE_ERR_INVALID_ARG; // reaches past the last CCE
+            for (uint32_t i = 0; i < d.L; i++) {
+                if (used[d.cce + i]) return (int)MI_LTE_ERR_INVALID_ARG; // overlaps an earlier record
+                used[d.cce + i] = 1;
+            }
+            out.push_back(CtrlRec{d.rnti, d.L, d.cce, d.n_bits, d.n_bits == 64 ? d.payload : d.payload & ((1ull << d.n_bits) - 1ull)});
+        }
+        return (int)MI_LTE_OK;
+    });
 }
 
 } // extern "C"

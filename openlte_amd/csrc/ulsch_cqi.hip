@@ -10,7 +10,7 @@
 //        Q_cqi <= 95 040 soft bits of magnitude <= 127: sum |r| and sum |d| <= 1.21e7, a path metric over three laps <= 3.63e7 < 2^31.
 //     2a. block code: every one of the 2^O words is correlated with r.  A lane owns o_0 .. o_5, the wavefront walks the up to 32 cosets
 //        of o_6 .. o_10 in ascending order; ties go to the smallest w = sum o_n 2^n (strict > inside a lane, (metric, -w) across lanes).
-//     2b. convolutional code: maximum-correlation Viterbi over three laps of the L-step ring, one of the 64 states (c_k-1 .. c_k-6),
+//     2b. convolutional code (tbcc_dev.h, the copy k_pdcch_search_decode runs too): maximum-correlation Viterbi over three laps of the L-step ring, one of the 64 states (c_k-1 .. c_k-6),
 //        newest bit on top) per lane, all metrics starting at 0.  Lane n's predecessors are 2 (n & 31) and 2 (n & 31) + 1; the odd one
 //        survives only when strictly larger; one ballot of survivors per step goes to LDS.  End state: the first maximum in state order.
 //        Lane 0 traces back all 3L steps and keeps the middle lap's bits, then CRC8 is checked over them.
@@ -23,6 +23,7 @@
 
 #include "ctx.hpp"
 #include "cqi_code.h"
+#include "tbcc_dev.h"
 #include "tx_host.h"
 #include "ulsch_uci.h"
 
@@ -33,29 +34,12 @@ constexpr uint32_t CRC8_POLY = 0x19Bu;              // gCRC8 = D^8 + D^7 + D^4 +
 
 __device__ __forceinline__ uint32_t bitrev5(uint32_t j) { return ((j & 1) << 4) | ((j & 2) << 2) | (j & 4) | ((j & 8) >> 2) | ((j & 16) >> 4); }
 
-__device__ __forceinline__ int32_t wave_sum(int32_t v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // the sum of e_k over k = n mod period, k < Q
 __device__ __forceinline__ int32_t combine(const int8_t *__restrict__ e, uint32_t Q, uint32_t n, uint32_t period)
 {
     int32_t s = 0;
     for (uint32_t k = n; k < Q; k += period) s += e[k];
     return s;
-}
-
-// the three output bits (bit x: generator x) of the register reg = (c_k, c_k-1 .. c_k-6), c_k at bit 6
-__device__ __forceinline__ uint32_t conv_label(uint32_t reg)
-{
-    return ((uint32_t)__popc(reg & 0133u) & 1u) | (((uint32_t)__popc(reg & 0171u) & 1u) << 1) | (((uint32_t)__popc(reg & 0165u) & 1u) << 2);
-}
-
-__device__ __forceinline__ int32_t correlate3(uint32_t lab, int32_t d0, int32_t d1, int32_t d2)
-{
-    return ((lab & 1u) ? -d0 : d0) + ((lab & 2u) ? -d1 : d1) + ((lab & 4u) ? -d2 : d2);
 }
 
 __device__ __forceinline__ void block_decode(const int8_t *__restrict__ e, uint32_t Q, uint32_t O, int32_t *d, uint32_t ln, mi_lte_cqi_result &res)
@@ -111,45 +95,10 @@ __device__ __forceinline__ void conv_decode(const int8_t *__restrict__ e, uint32
     }
     energy = wave_sum(energy);
     __syncthreads();
-    // 2. three laps; lane = the state after the step, its input bit is ln >> 5
-    const uint32_t lab0 = conv_label(((ln >> 5) << 6) | ((2 * ln) & 63u)), lab1 = conv_label(((ln >> 5) << 6) | ((2 * ln + 1) & 63u));
-    int32_t        pm = 0;
-    for (uint32_t t = 0, i = 0; t < 3 * L; t++) {
-        const int32_t d0 = d[3 * i], d1 = d[3 * i + 1], d2 = d[3 * i + 2];
-        const int32_t c0 = __shfl(pm, (2 * ln) & 63, 64) + correlate3(lab0, d0, d1, d2);
-        const int32_t c1 = __shfl(pm, (2 * ln + 1) & 63, 64) + correlate3(lab1, d0, d1, d2);
-        const bool    odd = c1 > c0; // (a tie keeps the even predecessor)
-        const uint64_t m  = __ballot(odd);
-        if (ln == 0) surv[t] = m;
-        pm = odd ? c1 : c0;
-        i  = i + 1 == L ? 0 : i + 1;
-    }
-    int32_t  best = pm;
-    uint32_t st   = ln;
-    for (int o = 32; o > 0; o >>= 1) {
-        const int32_t  ob = __shfl_xor(best, o, 64);
-        const uint32_t os = __shfl_xor(st, o, 64);
-        if (ob > best || (ob == best && os < st)) { best = ob; st = os; }
-    }
-    __syncthreads();
-    if (ln == 0) { // (the survivor words do not depend on the state walked: their loads run ahead of the chain)
-        uint32_t cur = st;
-#pragma unroll 8
-        for (int t = (int)(3 * L) - 1; t >= 0; t--) {
-            if ((uint32_t)t >= L && (uint32_t)t < 2 * L) cb[(uint32_t)t - L] = (uint8_t)(cur >> 5);
-            cur = 2 * (cur & 31u) + (uint32_t)((surv[t] >> cur) & 1ull);
-        }
-    }
-    __syncthreads();
-    // 3. the decided bits re-encoded against d, CRC8 over them, the information bits packed
-    int32_t metric = 0;
-    for (uint32_t i = ln; i < L; i += 64) {
-        uint32_t reg = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 7; j++) reg |= (uint32_t)cb[i >= j ? i - j : i + L - j] << (6 - j);
-        metric += correlate3(conv_label(reg), d[3 * i], d[3 * i + 1], d[3 * i + 2]);
-    }
-    metric = wave_sum(metric);
+    // 2. the shared decoder (tbcc_dev.h): three laps, traceback, the decided bits re-encoded against d
+    int32_t metric;
+    tbcc_decode(d, L, surv, cb, ln, [] { __syncthreads(); }, metric);
+    // 3. CRC8 over the decided bits, the information bits packed
     uint32_t rem = 0, par = 0;
     if (ln == 0) {
         for (uint32_t i = 0; i < L; i++) {

@@ -214,6 +214,23 @@ class PdcchDci(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("rnti", "format", "candidate", "n_bits", "payload", "mcs", "alloc_valid", "reserved")] + [("alloc", PdschAlloc)]
 
 
+class PdcchFound(C.Structure):
+    """mi_lte_pdcch_found: one hit of the blind PDCCH search"""
+    _fields_ = [(n, C.c_uint32) for n in ("rnti", "L", "cce", "n_bits")] + [("payload", C.c_uint64), ("metric", C.c_int32), ("energy", C.c_int32)]
+
+    def as_tuple(self):
+        return (self.rnti, self.L, self.cce, self.n_bits, self.payload, self.metric, self.energy)
+
+
+class DciCrnti(C.Structure):
+    """mi_lte_dci_crnti: a C-RNTI's DCI format 0 / 1A, unpacked"""
+    _fields_ = [(n, C.c_uint32) for n in ("format", "flag", "riv", "rb_start", "N_prb", "mcs", "harq", "ndi", "rv", "tpc", "cyclic_shift", "cqi_request")] + \
+               [("alloc", PdschAlloc)]
+
+
+PDCCH_SEARCH_MAX_SIZES, PDCCH_SEARCH_MAX_FOUND, PDCCH_SEARCH_ANY_CCE = 4, 16, 1
+
+
 class CoarseTiming(C.Structure):
     """mi_lte_coarse_timing = LIBLTE_PHY_COARSE_TIMING_STRUCT"""
     _fields_ = [("freq_offset", C.c_float * 5), ("symb_starts", (C.c_uint32 * 7) * 5), ("n_corr_peaks", C.c_uint32)]
@@ -387,6 +404,13 @@ def load_library():
     L.mi_lte_pdcch_re_tables.argtypes = [u32, u32, u32, C.c_float, u32, u32p, u32p]
     L.mi_lte_dci_1a_unpack.argtypes = [u32, u32, u32, u32, u32, C.POINTER(PdcchDci)]
     L.mi_lte_dci_1c_unpack.argtypes = [u32, u32, u32, u32, u32, C.POINTER(PdcchDci)]
+    L.mi_lte_pdcch_search_space.argtypes = [u32, u32, u32, u32, u32p, C.POINTER(u32)]
+    L.mi_lte_pdcch_search_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.c_float, u32, u32, u32p, u32, u32p, u32, C.POINTER(vp)]
+    L.mi_lte_pdcch_search_plan_set_rntis.argtypes = [vp, vp, u32p, u32]
+    L.mi_lte_pdcch_search_plan_destroy.argtypes = [vp, vp]
+    L.mi_lte_pdcch_search_run.argtypes = [vp, vp, vp, vp, vp, u32, u32p, u32p, u32p, C.POINTER(PdcchFound)]
+    L.mi_lte_pdcch_search_soft.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
+    L.mi_lte_dci_0_1a_unpack_crnti.argtypes = [C.c_uint64, u32, u32, u32, u32, C.POINTER(DciCrnti)]
     L.mi_lte_turbo_decode_batch.argtypes = [vp, vp, C.c_int, u32, u32, C.c_int, u32, C.c_int, vp]
     L.mi_lte_set_turbo_small_batch.argtypes = [vp, u32]
     L.mi_lte_turbo_early_exit_iterations.argtypes = [vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
@@ -901,6 +925,63 @@ class PdcchPlan:
             self.h = None
 
 
+class PdcchSearchPlan:
+    """mi_lte_pdcch_search_plan: the blind search over the whole control region (include/mi_lte.h: "PDCCH, 3GPP mode") for the listed cells
+    and DCI sizes; the RNTI set is exactly what set_rntis was given last (empty at first)."""
+
+    def __init__(self, ctx, cfg, cells, sizes, rntis=(), phich_res=1.0, any_cce=False, phich_dur_extended=0):
+        self.ctx, self.cfg = ctx, cfg
+        h = C.c_void_p()
+        cells, sizes = np.ascontiguousarray(cells, np.uint32), np.ascontiguousarray(sizes, np.uint32)
+        ctx._check(ctx.L.mi_lte_pdcch_search_plan_create(ctx.h, C.byref(cfg), float(phich_res), int(phich_dur_extended),
+                                                         PDCCH_SEARCH_ANY_CCE if any_cce else 0, cells, len(cells), sizes, len(sizes), C.byref(h)))
+        self.h = h
+        if len(rntis):
+            try:
+                self.set_rntis(rntis)
+            except Exception:
+                self.close()
+                raise
+
+    def set_rntis(self, rntis):
+        """Replace the RNTI set (an empty list empties it); a value of 0 or above 0xFFFF is refused and the set stays as it was."""
+        r = np.ascontiguousarray(rntis, np.int64).reshape(-1)
+        if len(r) and (r.min() < 0 or r.max() > 0xFFFFFFFF):
+            raise MiLteError("mi_lte_pdcch_search_plan_set_rntis: RNTI out of range", -1)
+        self.ctx._check(self.ctx.L.mi_lte_pdcch_search_plan_set_rntis(self.ctx.h, self.h, np.ascontiguousarray(r, np.uint32), len(r)))
+
+    def search_raw(self, d_subframes, d_sf, d_cell, n_units):
+        """(cfi[n], n_cce[n], n_found[n], ctypes array PdcchFound[n * 16]); the buffers are the plan's and are reused by the next call."""
+        if getattr(self, "_n", None) != n_units:
+            self._n = n_units
+            self._out = [np.zeros(n_units, np.uint32) for _ in range(3)]
+            self._found = (PdcchFound * (PDCCH_SEARCH_MAX_FOUND * n_units))()
+        cfi, ncce, nf = self._out
+        self.ctx._check(self.ctx.L.mi_lte_pdcch_search_run(self.ctx.h, self.h, d_subframes.ptr, d_sf.ptr, d_cell.ptr, n_units, cfi, ncce, nf, self._found))
+        return cfi, ncce, nf, self._found
+
+    def search_dev(self, d_subframes, d_sf, d_cell, n_units):
+        """(cfi[n], n_cce[n], n_found[n] -- the total, which may exceed the 16 kept --, per unit the list of PdcchFound.as_tuple() =
+        (rnti, L, first CCE, n_bits, payload, metric, energy) in the order (L descending, CCE ascending, size position ascending))"""
+        cfi, ncce, nf, found = self.search_raw(d_subframes, d_sf, d_cell, n_units)
+        M = PDCCH_SEARCH_MAX_FOUND
+        return cfi.copy(), ncce.copy(), nf.copy(), [[found[M * u + k].as_tuple() for k in range(min(int(nf[u]), M))] for u in range(n_units)]
+
+    def soft(self, n_units):
+        """The int8 soft bits of the last run, [n_units, 72 * the tables' largest N_cce] (positive = bit 0; 72 n_cce[u] valid per unit)."""
+        p, stride = C.c_void_p(), C.c_uint32()
+        self.ctx._check(self.ctx.L.mi_lte_pdcch_search_soft(self.h, C.byref(p), C.byref(stride)))
+        out = np.zeros((n_units, stride.value), np.int8)
+        if out.size:
+            self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p, out.nbytes))
+        return out
+
+    def close(self):
+        if self.h:
+            self.ctx.L.mi_lte_pdcch_search_plan_destroy(self.ctx.h, self.h)
+            self.h = None
+
+
 class Transmitter:
     """The host-side transmit functions of one cell (mi_lte_tx): the reference's liblte_phy_map_crs / _pss / _sss, _bch_channel_encode,
     _pdsch_channel_encode and _create_dl_subframe on a grid of the reference's layout (tx_symb_re / _im: [4][16][1200]).  Host code, no GPU."""
@@ -984,6 +1065,24 @@ def dci_unpack(fmt, payload, n_bits, rnti, n_rb_dl, n_ant):
     L = load_library()
     f = L.mi_lte_dci_1a_unpack if fmt == 0 else L.mi_lte_dci_1c_unpack
     return f(int(payload), int(n_bits), int(rnti), int(n_rb_dl), int(n_ant), C.byref(d)), d
+
+
+def pdcch_search_space(rnti, subfr_num, n_cce, L):
+    """mi_lte_pdcch_search_space: the first CCEs of the RNTI's UE-specific candidates at aggregation level L (36.213 9.1.1), duplicates kept."""
+    out, n = np.zeros(6, np.uint32), C.c_uint32()
+    rc = load_library().mi_lte_pdcch_search_space(int(rnti), int(subfr_num), int(n_cce), int(L), out, C.byref(n))
+    if rc != 0:
+        raise MiLteError("mi_lte_pdcch_search_space failed: %d" % rc, rc)
+    return [int(x) for x in out[:n.value]]
+
+
+def dci_0_1a_unpack_crnti(payload, n_bits, rnti, n_rb, n_ant=1):
+    """(rc, DciCrnti): a C-RNTI's DCI format 0 / 1A (mi_lte_dci_0_1a_unpack_crnti, host arithmetic); rc 0, or 4 = no transport block of its own."""
+    d = DciCrnti()
+    rc = load_library().mi_lte_dci_0_1a_unpack_crnti(int(payload), int(n_bits), int(rnti), int(n_rb), int(n_ant), C.byref(d))
+    if rc < 0:
+        raise MiLteError("mi_lte_dci_0_1a_unpack_crnti failed: %d" % rc, rc)
+    return rc, d
 
 
 def ul_dmrs_pusch(ulcfg, n_id_cell, n_subfr, n_prb):
@@ -1177,6 +1276,11 @@ class Context:
 
     def pdcch_plan(self, cfg, cells, phich_res=1.0, per_port_estimates=False):
         return PdcchPlan(self, cfg, cells, phich_res, 0, per_port_estimates)
+
+    def pdcch_search_plan(self, cfg, cells, sizes, rntis=(), phich_res=1.0, any_cce=False):
+        """The blind PDCCH search: every CCE-aligned candidate at L = 8, 4, 2, 1 against each of the DCI `sizes` (bits), hits reported for the
+        RNTIs listed -- inside their own or the common search space, or anywhere with any_cce."""
+        return PdcchSearchPlan(self, cfg, cells, sizes, rntis, phich_res, any_cce)
 
     def pusch_plan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, uci=None):
         """A reference-mode PUSCH plan.  It has no control information: a `uci` is refused (MiLteError, -4)."""

@@ -48,8 +48,15 @@ def _lib():
         L.mi_lte_synth_prach_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(PrachCfg), C.c_uint32, _u32p, _u32p, C.POINTER(SynthChannel), _i8p]
         L.mi_lte_synth_ctrl_grids.argtypes = [C.POINTER(DlCfg), C.c_float, C.c_uint32, _u32p, _u32p, _u32p, _u32p, C.c_uint32,
                                               C.POINTER(SynthChannel), _f32p]
+        L.mi_lte_synth_ctrl_grids_dci.argtypes = [C.POINTER(DlCfg), C.c_float, C.c_uint32, _u32p, _u32p, _u32p, C.c_void_p, C.c_uint32,
+                                                  C.POINTER(SynthChannel), _f32p]
         L._synth_bound = True
     return L
+
+
+class SynthDciRec(C.Structure):
+    """mi_lte_synth_dci_rec"""
+    _fields_ = [("rnti", C.c_uint32), ("L", C.c_uint32), ("cce", C.c_uint32), ("n_bits", C.c_uint32), ("payload", C.c_uint64)]
 
 
 def turbo_soft_blocks(K, n, flip=0.02, amp=127, seed=1, ref_wrap=True):
@@ -240,4 +247,23 @@ def ctrl_grids(cfg, subfr_num, n_id_cell, cfi, dcis, phich_res=1.0, gain=(0.6, 1
                                         C.byref(ch), g.reshape(-1))
     if rc != 0:
         raise MiLteError("mi_lte_synth_ctrl_grids failed: %d" % rc)
+    return g
+
+
+def ctrl_grids_dci(cfg, subfr_num, n_id_cell, cfi, recs, phich_res=1.0, gain=(0.6, 1.4), snr_db=10.0, seed=1):
+    """ctrl_grids with any DCI anywhere (mi_lte_synth_ctrl_grids_dci): recs[u] = [(rnti, L, first CCE, n_bits, payload), ...], at most 8 per unit,
+    the payload's first bit in bit n_bits - 1.  Records that overlap or reach past the unit's last CCE are refused (MiLteError, -1)."""
+    n = len(subfr_num)
+    n_rec = max([len(r) for r in recs] + [1])
+    arr = (SynthDciRec * (n * n_rec))()
+    for u, lst in enumerate(recs):
+        for a, (rnti, L, cce, n_bits, payload) in enumerate(lst):
+            arr[u * n_rec + a] = SynthDciRec(int(rnti), int(L), int(cce), int(n_bits), int(payload))
+    g = np.zeros((n, 2 + 2 * cfg.N_ant, 16, 1200), np.float32)
+    ch = SynthChannel(gain[0], gain[1], 0.0, float(snr_db), 0.0, int(seed))
+    rc = _lib().mi_lte_synth_ctrl_grids_dci(C.byref(cfg), float(phich_res), n, np.ascontiguousarray(subfr_num, np.uint32),
+                                            np.ascontiguousarray(n_id_cell, np.uint32), np.ascontiguousarray(cfi, np.uint32), C.cast(arr, C.c_void_p), n_rec,
+                                            C.byref(ch), g.reshape(-1))
+    if rc != 0:
+        raise MiLteError("mi_lte_synth_ctrl_grids_dci failed: %d" % rc, rc)
     return g
