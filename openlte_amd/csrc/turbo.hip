@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "plan_core.hpp"
+#include "turbo_swar.h"
 
 using namespace turbo_geom;
 
@@ -52,10 +53,6 @@ __device__ __forceinline__ uint32_t lds_u16(uint32_t addr) { return *(lds_u16_t 
 typedef short v2s __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2s      as_v2s(uint32_t w) { return __builtin_bit_cast(v2s, w); }
 __device__ __forceinline__ uint32_t as_u32(v2s v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ v2s      even2(uint32_t w) { return (as_v2s(w) << 8) >> 8; }
-__device__ __forceinline__ v2s      odd2(uint32_t w) { return as_v2s(w) >> 8; }
-__device__ __forceinline__ uint32_t merge_bytes(v2s e, v2s o) { return __builtin_amdgcn_perm(as_u32(o), as_u32(e), 0x06020400u); } // low bytes of (e.lo, o.lo, e.hi, o.hi)
-__device__ __forceinline__ v2s      abs2(v2s a) { return __builtin_elementwise_max(a, (v2s)(0) - a); }
 // 0xFFFF per negative half.  Opaque on purpose: from a visible "x >> 15" feeding an and/or select the compiler rebuilds per-half
 // compares and selects, which costs twice the instructions of the mask + one bit-select it replaces.
 __device__ __forceinline__ uint32_t neg_mask(v2s d)
@@ -65,16 +62,6 @@ __device__ __forceinline__ uint32_t neg_mask(v2s d)
     return m;
 }
 __device__ __forceinline__ v2s bit_select(uint32_t m, v2s yes, v2s no) { return as_v2s((as_u32(yes) & m) | (as_u32(no) & ~m)); }
-// (a + b) >> 1 per half, for sums that fit their 16 bits (magnitudes <= 127 here).  The sum is made opaque: the compiler otherwise
-// recognises the "average" idiom and, having no such instruction, expands it into the overflow-safe (a & b) + ((a ^ b) >> 1) -- four
-// instructions (some of them split per half) where these two do.
-__device__ __forceinline__ v2s half_sum(v2s a, v2s b)
-{
-    uint32_t t = as_u32(a + b);
-    asm("" : "+v"(t));
-    return as_v2s(t) >> 1;
-}
-
 // sign * ((|a|+|b|) >> 1), sign negative iff exactly one operand is negative (0 counts as positive).
 // This one form covers the four branches of Step 3 (liblte_phy.cc:10688-10707) and the g=03 soft
 // re-encoder conv_encode_soft (liblte_phy.cc:10123-10147).
@@ -869,7 +856,7 @@ struct SisoPass {
     const uint8_t *in_a; // first soft value of each pair  (in[2t])
     const uint8_t *in_b; // second soft value of each pair (in[2t+1])
     const uint8_t *mag;  // |output| per step
-    uint8_t       *out;  // signed SISO output
+    uint8_t       *out;  // signed SISO output as sign-magnitude bytes (sign in bit 7, clear where the magnitude is 0): the form perm and vote compute in (turbo_swar.h)
     uint32_t      *dec;  // traceback bits: [tile][blk][lane][8 words]
 };
 struct SisoArgs { SisoPass p[2]; };
@@ -939,11 +926,6 @@ __device__ __forceinline__ uint32_t traceback_entry(uint32_t byte, uint32_t cur)
         cur = st;
     }
     return cur | mask << 8;
-}
-__device__ __forceinline__ uint32_t negate_bytes(uint32_t w, uint32_t m) // -b in the bytes where m is 0xFF, b elsewhere
-{
-    const uint32_t x = w ^ m, y = m & 0x01010101u;
-    return ((x & 0x7F7F7F7Fu) + y) ^ (x & 0x80808080u);
 }
 
 // Workgroups of four independent wavefronts (they only share the traceback table).  mode 0: trellis h of wavefront b is tile 2b + h of
@@ -1109,8 +1091,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
                     }
 #pragma unroll
                     for (int h = 0; h < 2; h++) { // steps 7..4 -> bytes 3..0 of o_hi, steps 3..0 -> o_lo
-                        o_hi[h] = negate_bytes(mhi[h], msk[h][0] << 16 | msk[h][1]);
-                        o_lo[h] = negate_bytes(mlo[h], msk[h][2] << 16 | msk[h][3]);
+                        o_hi[h] = turbo_swar::joined_from(mhi[h], msk[h][0] << 16 | msk[h][1]);
+                        o_lo[h] = turbo_swar::joined_from(mlo[h], msk[h][2] << 16 | msk[h][3]);
                     }
                 }
 #pragma unroll
@@ -1314,23 +1296,17 @@ __global__ __launch_bounds__(64) void k_turbo_siso_small(SisoArgs args, uint32_t
             const uint32_t st  = map_at(G, end);                      // state at t
             if (t < K) {
                 const bool    pos = (nxt < st) || (nxt == st && nxt == 0); // "+" when the step moved to a lower state, or stayed in state 0
-                out[(size_t)ch * 4096 + lane] = pos ? m : (uint8_t)(0u - m);
+                out[(size_t)ch * 4096 + lane] = (pos || m == 0) ? m : (uint8_t)(m | 0x80u); // sign-magnitude, no "-0" (see k_turbo_siso)
             }
             end = (uint32_t)__builtin_amdgcn_readlane((int)st, 0);
         }
     }
 }
 
-// A unit of 16 values x[0..15] plus its three-value halo x[-3..-1], as pairs: E[j] = (x[4j-4], x[4j-2]), O[j] = (x[4j-3], x[4j-1]),
-// j = 0 (halo word) .. 4, each pair split into magnitudes and sign masks (0 / 0xFFFF): soft_xor of two such values is
-// ((m_a + m_b) >> 1, s_a ^ s_b), three instructions per pair.  The delayed sequences the soft re-encoder needs are
-//   x[k-2]: even pairs (E[j].hi, E[j+1].lo), odd pairs (O[j].hi, O[j+1].lo)  -- one v_alignbit per component
-//   x[k-3]: even pairs O[j], odd pairs = the even pairs of x[k-2]              -- free
-// with x[<0] = +127 in the first unit (conv_encode_soft register preset, liblte_phy.cc:10097-10100).
-struct SM { v2s m; uint32_t s; }; // |x| and the sign mask of a pair
-__device__ __forceinline__ SM   to_sm(v2s x) { return SM{abs2(x), neg_mask(x)}; }
-__device__ __forceinline__ v2s  to_tc(const SM &a) { return as_v2s(as_u32(a.m) ^ a.s) - as_v2s(a.s); } // back to two's complement
-__device__ __forceinline__ SM   sxor_sm(const SM &a, const SM &b) { return SM{half_sum(a.m, b.m), a.s ^ b.s}; }
+// A unit of 16 values x[0..15] and the word before it (x[-4..-1], of which the re-encoder needs the last three): the soft re-encoder and
+// Steps 3, 10 and 11 run on sign-magnitude bytes, four positions per 32-bit instruction (turbo_swar.h).  x[<0] = +127 in the first unit
+// (conv_encode_soft's register preset, liblte_phy.cc:10097-10100).
+namespace sw = turbo_swar;
 struct UnitWords { uint32_t w[5]; }; // halo word, then the unit's four words
 __device__ __forceinline__ UnitWords load_unit_words(const uint8_t *arr, size_t tile_off, uint32_t lane, uint32_t u)
 {
@@ -1339,37 +1315,6 @@ __device__ __forceinline__ UnitWords load_unit_words(const uint8_t *arr, size_t 
     if (u > 0) prev = *reinterpret_cast<const uint32_t *>(arr + unit_off(tile_off, lane, u - 1) + 12);
     return UnitWords{{prev, c.x, c.y, c.z, c.w}};
 }
-// the pairs of one word, and of the word before it: converted as the walk over the unit reaches them, so that only two words of
-// an array are live in sign-magnitude form at a time
-struct WordPairs { v2s et, ot; SM e, o; }; // two's complement and sign-magnitude
-__device__ __forceinline__ WordPairs word_pairs(uint32_t w)
-{
-    const v2s e = even2(w), o = odd2(w);
-    return WordPairs{e, o, to_sm(e), to_sm(o)};
-}
-__device__ __forceinline__ SM delay_sm(const SM &cur, const SM &prev) // (prev.hi, cur.lo)
-{
-    return SM{as_v2s(__builtin_amdgcn_alignbit(as_u32(cur.m), as_u32(prev.m), 16)), __builtin_amdgcn_alignbit(cur.s, prev.s, 16)};
-}
-// a soft_xor result in all three forms its consumers want: two's complement, magnitude, and the sign mask OF THE VALUE -- a result
-// of magnitude 0 is +0 to whatever reads it next (soft_xor counts 0 as positive), whatever the signs of its operands were
-struct SX { v2s tc, m; uint32_t s; };
-__device__ __forceinline__ SX sxor_full(const SM &a, const SM &b)
-{
-    const SM  r  = sxor_sm(a, b);
-    const v2s tc = to_tc(r);
-    return SX{tc, r.m, neg_mask(tc)};
-}
-// fb = soft_xor(x[k-2], x[k-3]) for the values of word `cur`, `prev` being the word before it: even and odd pairs
-__device__ __forceinline__ void feedback_sm(const WordPairs &cur, const WordPairs &prev, SX &fe, SX &fo)
-{
-    const SM d2e = delay_sm(cur.e, prev.e), d2o = delay_sm(cur.o, prev.o);
-    fe = sxor_full(d2e, prev.o);
-    fo = sxor_full(d2o, d2e);
-}
-// soft_xor(a, f) in two's complement
-__device__ __forceinline__ v2s sxor_tc(const SM &a, const SX &f) { return to_tc(SM{half_sum(a.m, f.m), a.s ^ f.s}); }
-
 // ------------------------------------------------------------------------------------------------
 // perm: Steps 2, 3, 5 and the pass-3 output magnitudes.  One workgroup per code block.
 //   C1 = soft_xor(A1, fb(A1)); I1[i] = C1[pi[i]]; M3 from pairs (q(d2), I1)
@@ -1425,16 +1370,15 @@ __global__ __launch_bounds__(384) void k_turbo_perm(PermArgs a, uint32_t K_arg, 
         uint4          X2 = make_uint4(0, 0, 0, 0);
         if (nv >= 0) {
             const UnitWords wa = load_unit_words(a.A1, tile_off, lane, u);
-            WordPairs       pa = word_pairs(wa.w[0]);
+            uint32_t        pa = wa.w[0];
             X2 = *reinterpret_cast<const uint4 *>(a.X2 + unit_off(tile_off, lane, u));
             uint32_t c1[4];
 #pragma unroll
-            for (int j = 0; j < 4; j++) { // Steps 2-3; 0 past the block end
-                const WordPairs ca = word_pairs(wa.w[j + 1]);
-                SX              fe, fo;
-                feedback_sm(ca, pa, fe, fo);
-                c1[j] = (4 * j < nv) ? merge_bytes(sxor_tc(ca.e, fe), sxor_tc(ca.o, fo)) : 0u;
-                pa    = ca;
+            for (int j = 0; j < 4; j++) { // Steps 2-3, four positions per instruction; 0 past the block end
+                const uint32_t ja = wa.w[j + 1];
+                const sw::SM4  A  = sw::unjoin(ja);
+                c1[j] = (4 * j < nv) ? sw::to_tc(sw::step3(A, sw::feedback(ja, pa))) : 0u; // two's complement again: pass 3 reads it
+                pa    = ja;
             }
             *reinterpret_cast<uint4 *>(sm + 16 * u) = make_uint4(c1[0], c1[1], c1[2], c1[3]);
         }
@@ -1513,37 +1457,30 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     if (nv >= 0) {
         const UnitWords wa = load_unit_words(a.A1, tile_off, lane, u), wb = load_unit_words(a.B1, tile_off, lane, u),
                         wc = load_unit_words(a.B2, tile_off, lane, u);
-        WordPairs       pa = word_pairs(wa.w[0]), pb = word_pairs(wb.w[0]), pc = word_pairs(wc.w[0]);
+        uint32_t        pa = wa.w[0], pb = wb.w[0], pc = wc.w[0];
         const uint4    x0 = *reinterpret_cast<const uint4 *>(a.X0 + unit_off(tile_off, lane, u));
         const uint32_t x0w[4] = {x0.x, x0.y, x0.z, x0.w};
         uint32_t       dn[8]; // D1 + D2 of the unit in natural order, two int16 per word
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const WordPairs ca = word_pairs(wa.w[j + 1]), cb1 = word_pairs(wb.w[j + 1]), cb2 = word_pairs(wc.w[j + 1]);
-            SX              fe, fo, ge, go, he, ho;
-            feedback_sm(ca, pa, fe, fo);
-            feedback_sm(cb1, pb, ge, go); // G  = soft_xor(B1[k-2], B1[k-3])
-            feedback_sm(cb2, pc, he, ho); // G' = soft_xor(B2[k-2], B2[k-3])
-            v2s d[2];
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const SM  &A = h ? ca.o : ca.e, &B = h ? cb1.o : cb1.e, &B_ = h ? cb2.o : cb2.e;
-                const SX  &G = h ? go : ge, &G_ = h ? ho : he;
-                const v2s  At = h ? ca.ot : ca.et;
-                // Step 10 (liblte_phy.cc:10778-10797), as selects: equal signs -> (|B|+|G|)>>1; B >= 0 > G -> -((A - G) >> 1);
-                // B < 0 <= G -> -((-A + G) >> 1) -- the mixed-sign branches read in_act_1 (A), not int_act_1
-                const v2s dAG = At - G.tc, t = as_v2s(as_u32(dAG) ^ B.s) - as_v2s(B.s); // (B >= 0) ? A - G : G - A
-                const v2s v1  = bit_select(B.s ^ G.s, (v2s)(0) - (t >> 1), half_sum(B.m, G.m));
-                // Step 11 (liblte_phy.cc:10800-10819): mixed signs -> -((B - G) >> 1) resp. -((-B - G) >> 1), i.e. -((|B| - G) >> 1)
-                const v2s v2  = bit_select(B_.s ^ G_.s, (v2s)(0) - ((B_.m - G_.tc) >> 1), half_sum(B_.m, G_.m));
-                d[h] = v1 + v2;
-                const v2s c1 = sxor_tc(A, h ? fo : fe); // Steps 2-3
-                (h ? s0o[j] : s0e[j]) = (h ? odd2(x0w[j]) : even2(x0w[j])) + c1;
-            }
-            pa = ca; pb = cb1; pc = cb2;
+            // sign-magnitude bytes, four positions per instruction (turbo_swar.h); only the two nine-bit sums are formed in int16 pairs,
+            // from biased bytes: even pairs (positions 0, 2), odd pairs (1, 3)
+            const uint32_t ja = wa.w[j + 1], jb = wb.w[j + 1], jc = wc.w[j + 1];
+            const sw::SM4  A = sw::unjoin(ja), B = sw::unjoin(jb), B_ = sw::unjoin(jc);
+            const sw::SM4  F  = sw::feedback(ja, pa);
+            const sw::SM4  G  = sw::feedback(jb, pb); // G  = soft_xor(B1[k-2], B1[k-3])
+            const sw::SM4  G_ = sw::feedback(jc, pc); // G' = soft_xor(B2[k-2], B2[k-3])
+            pa = ja; pb = jb; pc = jc;
+            // Steps 10 and 11 (liblte_phy.cc:10778-10819); Step 10's mixed-sign branches read in_act_1 (A), not int_act_1
+            const uint32_t u1 = sw::step10_biased(A, B, G), n2 = sw::step11_neg_biased(B_, G_); // 128 + D1, 128 - D2
+            const uint32_t de = sw::sub_halves(sw::even_halves(u1), sw::even_halves(n2)), dd = sw::sub_halves(sw::odd_halves(u1), sw::odd_halves(n2));
+            // Steps 2-3 and s0 = q(d0) + C1 = (128 + q(d0)) - (128 - C1)
+            const uint32_t x0b = x0w[j] ^ sw::HI, nc = sw::step3_neg_biased(A, F);
+            s0e[j] = as_v2s(sw::sub_halves(sw::even_halves(x0b), sw::even_halves(nc)));
+            s0o[j] = as_v2s(sw::sub_halves(sw::odd_halves(x0b), sw::odd_halves(nc)));
             const bool in = 4 * j < nv; // 0 past the block end (nv is 16, 8 or 0)
-            dn[2 * j]     = in ? __builtin_amdgcn_perm(as_u32(d[1]), as_u32(d[0]), 0x05040100u) : 0u; // (e.lo, o.lo)
-            dn[2 * j + 1] = in ? __builtin_amdgcn_perm(as_u32(d[1]), as_u32(d[0]), 0x07060302u) : 0u; // (e.hi, o.hi)
+            dn[2 * j]     = in ? __builtin_amdgcn_perm(dd, de, 0x05040100u) : 0u; // (e.lo, o.lo)
+            dn[2 * j + 1] = in ? __builtin_amdgcn_perm(dd, de, 0x07060302u) : 0u; // (e.hi, o.hi)
         }
         uint4 *dst = reinterpret_cast<uint4 *>(d12 + 32 * u);
         dst[0] = make_uint4(dn[0], dn[1], dn[2], dn[3]);
