@@ -855,8 +855,9 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(Src::kPacke
 struct SisoPass {
     const uint8_t *in_a; // first soft value of each pair  (in[2t])
     const uint8_t *in_b; // second soft value of each pair (in[2t+1])
-    const uint8_t *mag;  // |output| per step
-    uint8_t       *out;  // signed SISO output as sign-magnitude bytes (sign in bit 7, clear where the magnitude is 0): the form perm and vote compute in (turbo_swar.h)
+    uint32_t      *sgn;  // the SISO output's signs, one bit per step (set: the path's output is negative, whatever its magnitude): [tile][blk][lane][2 words],
+                         // step t of the 64-step block in bit t % 32 of word t / 32.  The magnitude does not depend on the path (k_turbo_prep, k_turbo_perm
+                         // have it), so the sign is all the trellis adds: perm and vote join the two (turbo_swar.h: joined_from_bits)
     uint32_t      *dec;  // traceback bits: [tile][blk][lane][8 words]
 };
 struct SisoArgs { SisoPass p[2]; };
@@ -913,20 +914,8 @@ template <int R> __device__ __forceinline__ v2s byte_pair2(uint32_t w0, uint32_t
 
 // Traceback two steps at a time.  One step of the reference's traceback (liblte_phy.cc:10483-10527) maps (state at t+1, the four stored
 // compare bits of time t) to (state at t, sign of the output); two of them are a function of 3 + 8 bits, kept as a 2048-entry LDS
-// table per workgroup: entry = state after both steps | byte masks (0xFF = negative) of the two outputs in bits 8-23, the first
-// step's in the upper byte.  The outputs are then the magnitude words with the masked bytes negated (carry-free byte arithmetic).
-__device__ __forceinline__ uint32_t traceback_entry(uint32_t byte, uint32_t cur)
-{
-    uint32_t mask = 0;
-    for (int k = 0; k < 2; k++) {
-        const uint32_t nib = k ? byte >> 4 : byte & 15u; // the step processed first sits in the low nibble
-        const uint32_t j = cur & 3u, bit = (nib >> (3 - j)) & 1u, st = 2 * j + bit; // pair j is bit (3-j) of the nibble
-        const bool     pos = (cur < st) || (cur == st && cur == 0); // "+" when the step moved to a lower state, or stayed in state 0
-        if (!pos) mask |= k ? 0x00FFu : 0xFF00u;
-        cur = st;
-    }
-    return cur | mask << 8;
-}
+// table per workgroup (turbo_swar.h: traceback_entry): the state after both steps in bits 0-2, the two outputs' sign bits on top, where
+// one v_alignbit moves them into the block's sign word.
 
 // Workgroups of four independent wavefronts (they only share the traceback table).  mode 0: trellis h of wavefront b is tile 2b + h of
 // pass p[0] (first pass, two tiles per lane); mode 1: trellis h is tile b of pass p[h] (passes 2 and 3 of one tile)
@@ -935,12 +924,16 @@ __device__ __forceinline__ uint32_t traceback_entry(uint32_t byte, uint32_t cur)
 #endif
 // MULTI: a merged launch over the tiles of many block sizes (KSeg): n_tiles_arg is then the launch's wavefront count and K, the tile range and
 // the arrays' offsets come from the wavefront's row of the table (the wavefronts are ordered by falling K: the long walks start first)
-template <bool MULTI>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8))) void k_turbo_siso(SisoArgs args, uint32_t K_arg, uint32_t n_tiles_arg, uint32_t mode, MultiArgs ma,
+// MODE (the `mode` above) is a template parameter for the registers' sake: passes 2 and 3 of a tile have the same first input (p[0].in_a ==
+// p[1].in_a, q(d2): RefScratch), so with MODE = 1 its line is loaded and held once and feeds both halves of byte_pair2
+template <bool MULTI, int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8))) void k_turbo_siso(SisoArgs args, uint32_t K_arg, uint32_t n_tiles_arg, MultiArgs ma,
                                                                                                          const uint32_t *__restrict__ order)
 {
+    constexpr uint32_t mode = MODE;
+    constexpr int      NA = MODE ? 1 : 2; // lines of the first input held per lane
     __shared__ uint32_t tb_lut[2048];
-    for (uint32_t i = threadIdx.x; i < 2048; i += blockDim.x) tb_lut[i] = traceback_entry(i >> 3, i & 7u);
+    for (uint32_t i = threadIdx.x; i < 2048; i += blockDim.x) tb_lut[i] = turbo_swar::traceback_entry(i >> 3, i & 7u);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t       K = K_arg, n_tiles = n_tiles_arg, wv = blockIdx.x * 4 + (threadIdx.x >> 6), n_wv = mode ? n_tiles : (n_tiles + 1) / 2;
@@ -956,16 +949,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
     }
     const uint32_t Kp = kpad64(K), nblk = Kp >> 6;
     if (wv >= n_wv) return; // wavefront-uniform
-    const uint8_t *pa[2], *pb[2], *pmag[2];
-    uint8_t       *pout[2];
-    uint32_t      *dec[2];
+    const uint8_t *pa[2], *pb[2];
+    uint32_t      *dec[2], *sgn[2];
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const SisoPass &ps   = args.p[mode ? h : 0];
         const uint32_t  tile = mode ? wv : min(2 * wv + h, n_tiles - 1); // an odd tile count: the last one twice
         const size_t    off  = seg_off + (size_t)tile * Kp * 64 + lane * 64;
-        pa[h] = ps.in_a + off; pb[h] = ps.in_b + off; pmag[h] = ps.mag + off; pout[h] = ps.out + off;
+        pa[h] = ps.in_a + off; pb[h] = ps.in_b + off;
         dec[h] = ps.dec + (seg_off >> 3) + ((size_t)tile * nblk * 64 + lane) * 8; // (traceback: 32 bytes per step and tile = half an array's 64)
+        sgn[h] = ps.sgn + (seg_off >> 5) + ((size_t)tile * nblk * 64 + lane) * 2; // (signs: 8 bytes per step and tile = an eighth)
     }
 
     v2s pm[8];
@@ -974,12 +967,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
 
     // ---- forward add-compare-select.  A block is 64 steps = one 64-byte line per input and trellis, held as four quarters whose
     // registers are refilled with the next block's data while the current block's last quarter(s) are walked
-    uint4 A[2][4], B[2][4];
+    uint4 A[NA][4], B[2][4];
 #pragma unroll
     for (int h = 0; h < 2; h++)
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            A[h][q] = reinterpret_cast<const uint4 *>(pa[h])[q];
+            if (h < NA) A[h][q] = reinterpret_cast<const uint4 *>(pa[h])[q];
             B[h][q] = reinterpret_cast<const uint4 *>(pb[h])[q];
         }
     for (uint32_t blk = 0; blk < nblk; blk++) {
@@ -993,7 +986,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
                 uint32_t  acc_lo = 0, acc_hi = 0; // steps 0-3 / 4-7 of the group, 16 bits per trellis
                 if (blk * 64 + g * 8 < K) {       // uniform: K is a multiple of 8
                     const uint32_t a0l = g2 ? A[0][q].z : A[0][q].x, a0h = g2 ? A[0][q].w : A[0][q].y;
-                    const uint32_t a1l = g2 ? A[1][q].z : A[1][q].x, a1h = g2 ? A[1][q].w : A[1][q].y;
+                    const uint32_t a1l = g2 ? A[NA - 1][q].z : A[NA - 1][q].x, a1h = g2 ? A[NA - 1][q].w : A[NA - 1][q].y;
                     const uint32_t b0l = g2 ? B[0][q].z : B[0][q].x, b0h = g2 ? B[0][q].w : B[0][q].y;
                     const uint32_t b1l = g2 ? B[1][q].z : B[1][q].x, b1h = g2 ? B[1][q].w : B[1][q].y;
                     acs_step2<0>(pm, byte_pair2<0>(a0l, a1l), byte_pair2<0>(b0l, b1l), acc_lo);
@@ -1016,7 +1009,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
                 for (int qq = (q == 2 ? 0 : 3); qq <= (q == 2 ? 2 : 3); qq++)
 #pragma unroll
                     for (int h = 0; h < 2; h++) {
-                        A[h][qq] = reinterpret_cast<const uint4 *>(pa[h] + (size_t)nxt * 4096)[qq];
+                        if (h < NA) A[h][qq] = reinterpret_cast<const uint4 *>(pa[h] + (size_t)nxt * 4096)[qq];
                         B[h][qq] = reinterpret_cast<const uint4 *>(pb[h] + (size_t)nxt * 4096)[qq];
                     }
             }
@@ -1043,15 +1036,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
         }
     }
 
-    // ---- traceback + signed soft output (liblte_phy.cc:10483-10527), the two trellises interleaved
-    uint4 M[2][4], Mn[2][4], D[2][2], Dn[2][2];
+    // ---- traceback (liblte_phy.cc:10483-10527), the two trellises interleaved: only the decision words are in flight, and what is stored
+    // is the output's sign bit per step, a block's 64 as two words per trellis (a wavefront's store: 512 contiguous bytes)
+    uint4 D[2][2], Dn[2][2];
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const uint4 *dp = reinterpret_cast<const uint4 *>(dec[h] + (size_t)(nblk - 1) * 64 * 8);
         D[h][0] = dp[0];
         D[h][1] = dp[1];
-#pragma unroll
-        for (int q = 0; q < 4; q++) M[h][q] = reinterpret_cast<const uint4 *>(pmag[h] + (size_t)(nblk - 1) * 4096)[q];
     }
     for (int blk = (int)nblk - 1; blk >= 0; blk--) {
         const int prv = blk > 0 ? blk - 1 : 0; // prefetch the block below while this one is traced back
@@ -1060,54 +1052,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
             const uint4 *dpn = reinterpret_cast<const uint4 *>(dec[h] + (size_t)prv * 64 * 8);
             Dn[h][0] = dpn[0];
             Dn[h][1] = dpn[1];
-#pragma unroll
-            for (int q = 0; q < 4; q++) Mn[h][q] = reinterpret_cast<const uint4 *>(pmag[h] + (size_t)prv * 4096)[q];
         }
+        uint32_t sbits[2][2]; // [trellis][word]: steps 32-63, then steps 0-31; a step past the block end leaves a 0 (the groups skipped are the first)
 #pragma unroll
-        for (int q = 3; q >= 0; q--) {
-            uint32_t ow[2][4];
+        for (int g = 7; g >= 0; g--) {
+            if ((g & 3) == 3) sbits[0][g >> 2] = sbits[1][g >> 2] = 0;
+            if ((uint32_t)blk * 64 + g * 8 < K) {
+                uint32_t word[2];
 #pragma unroll
-            for (int g2 = 1; g2 >= 0; g2--) {
-                const int g = 2 * q + g2;
-                uint32_t  o_hi[2] = {0, 0}, o_lo[2] = {0, 0};
-                if ((uint32_t)blk * 64 + g * 8 < K) {
-                    uint32_t word[2], mlo[2], mhi[2], msk[2][4];
+                for (int h = 0; h < 2; h++) {
+                    const uint4 dq = D[h][g >> 2];
+                    word[h] = (g & 3) == 0 ? dq.x : (g & 3) == 1 ? dq.y : (g & 3) == 2 ? dq.z : dq.w;
+                }
+                // the compare bits of step r sit in nibble (7-r) of the word: byte b holds steps 7-2b (low nibble, traced first) and 6-2b
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
 #pragma unroll
                     for (int h = 0; h < 2; h++) {
-                        const uint4 dq = D[h][g >> 2];
-                        word[h] = (g & 3) == 0 ? dq.x : (g & 3) == 1 ? dq.y : (g & 3) == 2 ? dq.z : dq.w;
-                        mlo[h]  = g2 ? M[h][q].z : M[h][q].x;
-                        mhi[h]  = g2 ? M[h][q].w : M[h][q].y;
-                    }
-                    // the compare bits of step r sit in nibble (7-r) of the word: byte b holds steps 7-2b (low nibble, traced first) and 6-2b
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-#pragma unroll
-                        for (int h = 0; h < 2; h++) {
-                            const uint32_t e = tb_lut[((word[h] >> (8 * b)) & 0xFFu) << 3 | (uint32_t)cur[h]];
-                            cur[h]    = (int)(e & 7u);
-                            msk[h][b] = e >> 8;
-                        }
-                    }
-#pragma unroll
-                    for (int h = 0; h < 2; h++) { // steps 7..4 -> bytes 3..0 of o_hi, steps 3..0 -> o_lo
-                        o_hi[h] = turbo_swar::joined_from(mhi[h], msk[h][0] << 16 | msk[h][1]);
-                        o_lo[h] = turbo_swar::joined_from(mlo[h], msk[h][2] << 16 | msk[h][3]);
+                        const uint32_t e = tb_lut[((word[h] >> (8 * b)) & 0xFFu) << 3 | (uint32_t)cur[h]];
+                        cur[h]           = (int)(e & 7u);
+                        sbits[h][g >> 2]   = __builtin_amdgcn_alignbit(sbits[h][g >> 2], e, 30); // << 2 | the two signs, the later step's on top
                     }
                 }
-#pragma unroll
-                for (int h = 0; h < 2; h++) { ow[h][2 * g2] = o_lo[h]; ow[h][2 * g2 + 1] = o_hi[h]; }
             }
-#pragma unroll
-            for (int h = 0; h < 2; h++)
-                reinterpret_cast<uint4 *>(pout[h] + (size_t)blk * 4096)[q] = make_uint4(ow[h][0], ow[h][1], ow[h][2], ow[h][3]);
         }
 #pragma unroll
         for (int h = 0; h < 2; h++) {
+            *reinterpret_cast<uint2 *>(sgn[h] + (size_t)blk * 64 * 2) = make_uint2(sbits[h][0], sbits[h][1]);
             D[h][0] = Dn[h][0];
             D[h][1] = Dn[h][1];
-#pragma unroll
-            for (int q = 0; q < 4; q++) M[h][q] = Mn[h][q];
         }
     }
 }
@@ -1261,17 +1234,15 @@ __global__ __launch_bounds__(64) void k_turbo_siso_small(SisoArgs args, uint32_t
         }
     }
 
-    // ---- traceback + signed soft output (liblte_phy.cc:10483-10527) by function composition, one trellis after the other, lanes = steps
+    // ---- traceback (liblte_phy.cc:10483-10527) by function composition, one trellis after the other, lanes = steps: a chunk's 64 signs are one
+    // ballot, which is the block's two sign words as k_turbo_siso writes them
     const uint2 MAP_ID = make_uint2(0x03020100u, 0x07060504u);
     for (uint32_t g = 0; g < n_g; g++) {
         uint32_t       end = (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)(g * 4)); // state after the last step
-        const uint8_t *mag = pass_of(g).mag + off_of(g);
-        uint8_t       *out = pass_of(g).out + off_of(g);
-        uint8_t m_nxt = mag[(size_t)(n_chunk - 1) * 4096 + lane]; // the magnitudes too are requested a chunk ahead
+        const uint32_t cb  = mode ? (T0 + g) >> 1 : T0 + g;
+        uint32_t      *sgn = pass_of(g).sgn + (seg_off >> 5) + ((size_t)(cb >> 6) * n_chunk * 64 + (cb & 63u)) * 2;
         for (int ch = (int)n_chunk - 1; ch >= 0; ch--) {
             const uint32_t t = (uint32_t)ch * 64 + lane;
-            const uint8_t  m = m_nxt;
-            if (ch > 0) m_nxt = mag[(size_t)(ch - 1) * 4096 + lane];
             const uint4    w = *reinterpret_cast<const uint4 *>(&decw[(g * n_w32 + (t >> 5)) * 4]);
             const uint32_t sh = 31u - (t & 31u);
             uint2          G = MAP_ID; // a step past the block end changes nothing
@@ -1294,10 +1265,9 @@ __global__ __launch_bounds__(64) void k_turbo_siso_small(SisoArgs args, uint32_t
             const uint2    Gn  = make_uint2((uint32_t)__shfl_down((int)G.x, 1u), (uint32_t)__shfl_down((int)G.y, 1u));
             const uint32_t nxt = lane == 63 ? end : map_at(Gn, end); // state at t + 1
             const uint32_t st  = map_at(G, end);                      // state at t
-            if (t < K) {
-                const bool    pos = (nxt < st) || (nxt == st && nxt == 0); // "+" when the step moved to a lower state, or stayed in state 0
-                out[(size_t)ch * 4096 + lane] = (pos || m == 0) ? m : (uint8_t)(m | 0x80u); // sign-magnitude, no "-0" (see k_turbo_siso)
-            }
+            const bool     pos = (nxt < st) || (nxt == st && nxt == 0); // "+" when the step moved to a lower state, or stayed in state 0
+            const uint64_t neg = __ballot(t < K && !pos);
+            if (lane == 0) *reinterpret_cast<uint2 *>(sgn + (size_t)ch * 64 * 2) = make_uint2((uint32_t)neg, (uint32_t)(neg >> 32));
             end = (uint32_t)__builtin_amdgcn_readlane((int)st, 0);
         }
     }
@@ -1315,10 +1285,24 @@ __device__ __forceinline__ UnitWords load_unit_words(const uint8_t *arr, size_t 
     if (u > 0) prev = *reinterpret_cast<const uint32_t *>(arr + unit_off(tile_off, lane, u - 1) + 12);
     return UnitWords{{prev, c.x, c.y, c.z, c.w}};
 }
+// the same for a trellis pass's signed output: the magnitudes (M1 / M2 / M3) joined with the pass's sign bits (SisoPass::sgn)
+__device__ __forceinline__ UnitWords load_unit_joined(const uint8_t *mag, const uint32_t *sgn, size_t tile_off, uint32_t lane, uint32_t u)
+{
+    UnitWords      w = load_unit_words(mag, tile_off, lane, u);
+    const uint32_t *sp = sgn + (tile_off >> 5) + ((size_t)(u >> 2) * 64 + lane) * 2; // [tile][blk][lane][2 words]
+    const uint2    c = *reinterpret_cast<const uint2 *>(sp);
+    uint32_t       ph = 0;
+    if ((u & 3u) == 0 && u > 0) ph = sp[1 - 128]; // the halo's signs: the last four steps of the block before
+    const uint32_t b = sw::unit_sign_bits(c.x, c.y, ph, u);
+    if (u > 0) w.w[0] = sw::joined_from_bits(w.w[0], b & 15u);
+#pragma unroll
+    for (int j = 0; j < 4; j++) w.w[j + 1] = sw::joined_from_bits(w.w[j + 1], (b >> (4 * j + 4)) & 15u);
+    return w;
+}
 // ------------------------------------------------------------------------------------------------
 // perm: Steps 2, 3, 5 and the pass-3 output magnitudes.  One workgroup per code block.
 //   C1 = soft_xor(A1, fb(A1)); I1[i] = C1[pi[i]]; M3 from pairs (q(d2), I1)
-struct PermArgs { const uint8_t *A1; const uint8_t *X2; uint8_t *out[2]; /* I1, M3 */ };
+struct PermArgs { const uint8_t *M1; const uint32_t *S1; /* pass 1's output: magnitudes, signs */ const uint8_t *X2; uint8_t *out[2]; /* I1, M3 */ };
 
 // A workgroup handles PERM_NB code blocks one after the other (workgroup b + i * gridDim.x, i.e. the same XCD's chunk each time): thread u's
 // sixteen interleaver indices are the same for every block, so they are read once and stay in registers -- read per block, the table (the
@@ -1369,7 +1353,7 @@ __global__ __launch_bounds__(384) void k_turbo_perm(PermArgs a, uint32_t K_arg, 
         asm volatile("" : "+v"(u), "+v"(praw.lo.x), "+v"(praw.lo.y), "+v"(praw.lo.z), "+v"(praw.lo.w), "+v"(praw.hi.x), "+v"(praw.hi.y), "+v"(praw.hi.z), "+v"(praw.hi.w));
         uint4          X2 = make_uint4(0, 0, 0, 0);
         if (nv >= 0) {
-            const UnitWords wa = load_unit_words(a.A1, tile_off, lane, u);
+            const UnitWords wa = load_unit_joined(a.M1, a.S1, tile_off, lane, u);
             uint32_t        pa = wa.w[0];
             X2 = *reinterpret_cast<const uint4 *>(a.X2 + unit_off(tile_off, lane, u));
             uint32_t c1[4];
@@ -1414,7 +1398,7 @@ __global__ __launch_bounds__(384) void k_turbo_perm(PermArgs a, uint32_t K_arg, 
 
 // ------------------------------------------------------------------------------------------------
 // vote: Steps 2-3 (again, C1 is cheap to recompute), 8-14.  One workgroup per code block.
-struct VoteArgs { const uint8_t *X0, *A1, *B1, *B2; };
+struct VoteArgs { const uint8_t *X0, *M1, *M2, *M3; const uint32_t *S1, *S2, *S3; }; // the three passes' outputs: magnitudes, signs
 
 // GROUP = false: write the K hard bits of block cb to c_bits (turbo_decode's own output).
 // GROUP = true : finish dlsch_channel_decode (liblte_phy.cc:12840-12869): drop the F filler positions
@@ -1455,8 +1439,8 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     v2s            s0e[4], s0o[4]; // s0 = q(d0) + C1, the part of the vote that is not de-interleaved
     if (threadIdx.x == 0) *reinterpret_cast<uint32_t *>(d12 + 2 * Kp) = 0u; // what a hole of the de-interleaver reads
     if (nv >= 0) {
-        const UnitWords wa = load_unit_words(a.A1, tile_off, lane, u), wb = load_unit_words(a.B1, tile_off, lane, u),
-                        wc = load_unit_words(a.B2, tile_off, lane, u);
+        const UnitWords wa = load_unit_joined(a.M1, a.S1, tile_off, lane, u), wb = load_unit_joined(a.M2, a.S2, tile_off, lane, u),
+                        wc = load_unit_joined(a.M3, a.S3, tile_off, lane, u);
         uint32_t        pa = wa.w[0], pb = wb.w[0], pc = wc.w[0];
         const uint4    x0 = *reinterpret_cast<const uint4 *>(a.X0 + unit_off(tile_off, lane, u));
         const uint32_t x0w[4] = {x0.x, x0.y, x0.z, x0.w};
@@ -1857,7 +1841,7 @@ __global__ __launch_bounds__(256) void k_crc_finish(const uint8_t *__restrict__ 
 // host side
 
 namespace {
-enum { AX0, AX1, AX2, AI0, AM1, AM2, AA1, AI1, AM3, AB1, AB2 }; // the N_BYTE_ARRAYS
+enum { AX0, AX1, AX2, AI0, AM1, AM2, AI1, AM3 }; // the N_BYTE_ARRAYS
 static_assert(sizeof(CbDesc) == CB_DESC_BYTES, "ref_scratch_bytes counts a descriptor per slot");
 } // namespace
 
@@ -1876,8 +1860,8 @@ static bool no_static_lds(std::initializer_list<const void *> kernels)
     return true;
 }
 
-// The scratch of one REF decode carved up -- eleven byte arrays of arr_bytes each, three arrays of traceback words of half that, the
-// per-block descriptors -- and the kernels' arguments wired from it
+// The scratch of one REF decode carved up -- eight byte arrays of arr_bytes each, three arrays of traceback words of half that, three of
+// sign words of an eighth, the per-block descriptors -- and the kernels' arguments wired from it
 struct RefScratch {
     uint8_t *base;
     CbDesc  *d_desc;
@@ -1891,15 +1875,17 @@ struct RefScratch {
         for (int a = 0; a < N_BYTE_ARRAYS; a++) arr[a] = base + a * arr_bytes;
         uint32_t *dec[3];
         for (int p = 0; p < 3; p++) dec[p] = (uint32_t *)(base + N_BYTE_ARRAYS * arr_bytes + p * (arr_bytes / 2));
-        d_desc = (CbDesc *)(base + N_BYTE_ARRAYS * arr_bytes + 3 * (arr_bytes / 2));
+        uint32_t *sgn[3];
+        for (int p = 0; p < 3; p++) sgn[p] = (uint32_t *)(base + N_BYTE_ARRAYS * arr_bytes + 3 * (arr_bytes / 2) + p * (arr_bytes / 8));
+        d_desc = (CbDesc *)(base + N_BYTE_ARRAYS * arr_bytes + 3 * (arr_bytes / 2) + 3 * (arr_bytes / 8));
         po.arr[0] = arr[AX0]; po.arr[1] = arr[AX1]; po.arr[2] = arr[AX2];
         po.arr[3] = arr[AI0]; po.arr[4] = arr[AM1]; po.arr[5] = arr[AM2];
-        s1.p[0] = {arr[AX1], arr[AX0], arr[AM1], arr[AA1], dec[0]};
+        s1.p[0] = {arr[AX1], arr[AX0], sgn[0], dec[0]};
         s1.p[1] = s1.p[0];
-        pa.A1 = arr[AA1]; pa.X2 = arr[AX2]; pa.out[0] = arr[AI1]; pa.out[1] = arr[AM3];
-        s23.p[0] = {arr[AX2], arr[AI0], arr[AM2], arr[AB1], dec[1]};
-        s23.p[1] = {arr[AX2], arr[AI1], arr[AM3], arr[AB2], dec[2]};
-        va = {arr[AX0], arr[AA1], arr[AB1], arr[AB2]};
+        pa.M1 = arr[AM1]; pa.S1 = sgn[0]; pa.X2 = arr[AX2]; pa.out[0] = arr[AI1]; pa.out[1] = arr[AM3];
+        s23.p[0] = {arr[AX2], arr[AI0], sgn[1], dec[1]}; // (k_turbo_siso<.., 1> relies on the two passes sharing in_a)
+        s23.p[1] = {arr[AX2], arr[AI1], sgn[2], dec[2]};
+        va = {arr[AX0], arr[AM1], arr[AM2], arr[AM3], sgn[0], sgn[1], sgn[2]};
     }
 };
 
@@ -1933,7 +1919,7 @@ static int turbo_ref_run(mi_lte_ctx *ctx, Src src, uint32_t K, uint32_t n_cb, ui
         MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<false>, dim3((n_cb + gpw_of(n_cb) - 1) / gpw_of(n_cb)), dim3(64), lds_of(gpw_of(n_cb)), sc.s1, K, n_cb, 0u,
                   gpw_of(n_cb), MultiArgs{});
     else
-        MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<false>, dim3(((n_tiles + 1) / 2 + 3) / 4), dim3(256), 0, sc.s1, K, (uint32_t)n_tiles, 0u, MultiArgs{}, (const uint32_t *)nullptr); // two tiles per lane
+        MI_LAUNCH(ctx, "k_turbo_siso", (k_turbo_siso<false, 0>), dim3(((n_tiles + 1) / 2 + 3) / 4), dim3(256), 0, sc.s1, K, (uint32_t)n_tiles, MultiArgs{}, (const uint32_t *)nullptr); // two tiles per lane
 
     MI_LAUNCH(ctx, "k_turbo_perm", k_turbo_perm<1>, dim3(perm_grid_of(n_cb)), dim3(cb_threads), MTAB_N + Kp + 32, sc.pa, K, n_cb, tb.d_pi, MultiArgs{});
 
@@ -1941,7 +1927,7 @@ static int turbo_ref_run(mi_lte_ctx *ctx, Src src, uint32_t K, uint32_t n_cb, ui
         MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<false>, dim3((2 * n_cb + gpw_of(2 * n_cb) - 1) / gpw_of(2 * n_cb)), dim3(64), lds_of(gpw_of(2 * n_cb)), sc.s23, K,
                   n_cb, 1u, gpw_of(2 * n_cb), MultiArgs{});
     else
-        MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<false>, dim3((n_tiles + 3) / 4), dim3(256), 0, sc.s23, K, (uint32_t)n_tiles, 1u, MultiArgs{}, (const uint32_t *)nullptr); // passes 2 and 3 of a tile per lane
+        MI_LAUNCH(ctx, "k_turbo_siso", (k_turbo_siso<false, 1>), dim3((n_tiles + 3) / 4), dim3(256), 0, sc.s23, K, (uint32_t)n_tiles, MultiArgs{}, (const uint32_t *)nullptr); // passes 2 and 3 of a tile per lane
 
     MI_LAUNCH(ctx, "k_turbo_vote", (k_turbo_vote<GROUP, 1>), dim3(cb_grid(n_cb)), dim3(cb_threads), 3 * Kp + 64, sc.va, K, n_cb, tb.d_inv2, d_c_bits, gd, MultiArgs{});
     MI_HIP_CHECK(ctx, hipGetLastError());
@@ -2087,7 +2073,7 @@ static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t 
     if (small)
         MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<true>, dim3(G.n_ws1), dim3(64), lds_small(G.gpw1), sc.s1, 0u, 0u, 0u, G.gpw1, (MultiArgs{d_segs, d_map + G.map_ws1}));
     else
-    MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<true>, dim3(G.n_ord1 ? G.n_ord1 / 4 : (G.n_wv1 + 3) / 4), dim3(256), G.siso_pad1, sc.s1, 0u, G.n_wv1, 0u, (MultiArgs{d_segs, d_map + G.map_wv1}),
+    MI_LAUNCH(ctx, "k_turbo_siso", (k_turbo_siso<true, 0>), dim3(G.n_ord1 ? G.n_ord1 / 4 : (G.n_wv1 + 3) / 4), dim3(256), G.siso_pad1, sc.s1, 0u, G.n_wv1, (MultiArgs{d_segs, d_map + G.map_wv1}),
               G.n_ord1 ? d_map + G.ord_wv1 : (const uint32_t *)nullptr);
     for (int c = 0; c < NCLS; c++)
         if (G.grid_perm[c])
@@ -2096,7 +2082,7 @@ static int mi_turbo_ref_multi(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t 
     if (small)
         MI_LAUNCH(ctx, "k_turbo_siso_small", k_turbo_siso_small<true>, dim3(G.n_ws23), dim3(64), lds_small(G.gpw23), sc.s23, 0u, 0u, 1u, G.gpw23, (MultiArgs{d_segs, d_map + G.map_ws23}));
     else
-    MI_LAUNCH(ctx, "k_turbo_siso", k_turbo_siso<true>, dim3(G.n_ord23 ? G.n_ord23 / 4 : (G.n_wv23 + 3) / 4), dim3(256), G.siso_pad23, sc.s23, 0u, G.n_wv23, 1u, (MultiArgs{d_segs, d_map + G.map_wv23}),
+    MI_LAUNCH(ctx, "k_turbo_siso", (k_turbo_siso<true, 1>), dim3(G.n_ord23 ? G.n_ord23 / 4 : (G.n_wv23 + 3) / 4), dim3(256), G.siso_pad23, sc.s23, 0u, G.n_wv23, (MultiArgs{d_segs, d_map + G.map_wv23}),
               G.n_ord23 ? d_map + G.ord_wv23 : (const uint32_t *)nullptr);
     for (int c = 0; c < NCLS; c++)
         if (G.grid_cb[c])

@@ -79,11 +79,12 @@ inline uint32_t merged_e_cap(uint32_t K, uint32_t e_max_bytes)
 // rate un-matching sums in pairs (SrcRateUnmatchPk), as the merged kernels do; a group beyond that takes the per-size path with 32-bit sums.
 inline bool mi_turbo_ref_multi_takes(uint32_t K, uint32_t e_max_bytes) { return (e_max_bytes + (3 * K - 81) - 1) / (3 * K - 81) <= 258; }
 
-// The scratch of one REF decode: eleven byte arrays of arr_bytes each (every size's tiles of 64 code blocks x kpad64(K) steps), three
-// arrays of traceback words of half that, and a 32-byte descriptor (CbDesc) per code-block slot, the slots rounded up to whole tiles
-constexpr int    N_BYTE_ARRAYS = 11; // X0 X1 X2 I0 M1 M2 A1 I1 M3 B1 B2
+// The scratch of one REF decode: eight byte arrays of arr_bytes each (every size's tiles of 64 code blocks x kpad64(K) steps), three
+// arrays of traceback words of half that, three of the trellis passes' sign words of an eighth (a bit per step; arr_bytes is a multiple of
+// 4096), and a 32-byte descriptor (CbDesc) per code-block slot, the slots rounded up to whole tiles
+constexpr int    N_BYTE_ARRAYS = 8; // X0 X1 X2 I0 M1 M2 I1 M3
 constexpr size_t CB_DESC_BYTES = 32;
-inline size_t ref_scratch_bytes(size_t arr_bytes, size_t n_slots) { return N_BYTE_ARRAYS * arr_bytes + 3 * (arr_bytes / 2) + ((n_slots + 63) & ~(size_t)63) * CB_DESC_BYTES; }
+inline size_t ref_scratch_bytes(size_t arr_bytes, size_t n_slots) { return N_BYTE_ARRAYS * arr_bytes + 3 * (arr_bytes / 2) + 3 * (arr_bytes / 8) + ((n_slots + 63) & ~(size_t)63) * CB_DESC_BYTES; }
 
 } // namespace turbo_geom
 
@@ -102,7 +103,7 @@ struct KSeg {
     uint32_t        wg_perm, perm_grid;        // the same for perm, and the size's own grid there (a workgroup takes PERM_NB blocks grid apart)
     uint32_t        e_cap;                     // LDS bytes prep stages an allocation's soft bits in (0: gathers from global memory)
     uint32_t        wv1, wv23;                 // first wavefront of the size in SISO pass 1 / passes 2 + 3
-    uint64_t        arr_off;                   // where the size's tiles start in each of the eleven byte arrays (traceback words: half of it)
+    uint64_t        arr_off;                   // where the size's tiles start in each of the eight byte arrays (traceback words: half of it, sign words: an eighth)
     // mi_ctx_turbo_tables / rm_rank_tables of K.  Typed as GLOBAL pointers: a pointer that comes out of memory is otherwise of unknown address
     // space and every load through it a flat_load, which counts against the LDS counter too -- k_turbo_prep's LDS gathers then waited for its
     // table loads (W4 as a merged decode: 4.88 ms, 4.53 without them)

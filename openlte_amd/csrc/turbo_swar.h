@@ -59,6 +59,19 @@ SWAR_FN uint32_t to_joined(uint32_t w)
 // magnitudes (<= 127) and a mask with 0xFF in the negative bytes -> joined bytes, the sign bit cleared where the magnitude is 0: what
 // the trellis kernels' traceback writes
 SWAR_FN uint32_t joined_from(uint32_t m, uint32_t neg_mask) { return m | (neg_mask & (m + LO7) & HI); }
+// the same from four sign BITS (bit i set: byte i is negative; bits 4 and up clear): what the trellis kernels' traceback writes now, one bit
+// per step, and perm and vote expand.  The product puts bit i at bit 8i + 7; its other fifteen partial products land on distinct bits below
+// bit 7 of some byte (14 21 28 | 8 22 29 | 9 16 30 | 10 17 24), so nothing carries and the mask removes them
+SWAR_FN uint32_t joined_from_bits(uint32_t m, uint32_t nib) { return m | ((nib * 0x10204080u) & (m + LO7) & HI); }
+// The sixteen sign bits of unit u (steps 16u .. 16u + 15, bit k = step 16u + k) behind the four of the steps before it (bits 0-3: the halo,
+// whose joined form the re-encoder's delays need) out of the trellis kernels' sign words: c = the two words of the unit's 64-step block,
+// prev_hi = the second word of the block before (read only where u % 4 == 0; the first unit's halo is the preset, not a sign)
+SWAR_FN uint32_t unit_sign_bits(uint32_t c_lo, uint32_t c_hi, uint32_t prev_hi, uint32_t u)
+{
+    const uint32_t q = u & 3u;
+    const uint64_t c = ((uint64_t)c_hi << 32) | c_lo;
+    return q ? (uint32_t)(c >> (16u * q - 4u)) & 0xFFFFFu : (c_lo & 0xFFFFu) << 4 | prev_hi >> 28;
+}
 SWAR_FN SM4 unjoin(uint32_t j) { return SM4{j & LO7, j & HI}; }
 SWAR_FN SM4 split(uint32_t w) { return unjoin(to_joined(w)); }
 SWAR_FN uint32_t join(const SM4 &a) { return a.m | a.s; }
@@ -132,6 +145,23 @@ SWAR_FN uint32_t step11_neg_biased(const SM4 &B, const SM4 &G)
     const uint32_t mx = B.s ^ G.s, tm = mx >> 7, m7 = mx - tm;
     const uint32_t w  = avg_biased(B.m | HI, biased(G.m, mx & B.s)); // 128 + floor((|B| +- |G|) / 2)
     return (w ^ ~(m7 | mx)) + (tm ^ ONES);                           // equal signs: 256 - w
+}
+
+// One entry of the trellis kernels' traceback table: two steps of the reference's traceback (liblte_phy.cc:10483-10527) from state `cur`,
+// `byte` = the stored compare bits of the two steps, the step traced first (the later one) in the low nibble.  Bits 0-2: the state after
+// both; bit 31: the first-traced step's output is negative, bit 30: the second's -- alignbit(acc, entry, 30) appends them to a sign word
+// in step order.
+SWAR_FN uint32_t traceback_entry(uint32_t byte, uint32_t cur)
+{
+    uint32_t sgn = 0;
+    for (int k = 0; k < 2; k++) {
+        const uint32_t nib = k ? byte >> 4 : byte & 15u;
+        const uint32_t j = cur & 3u, bit = (nib >> (3 - j)) & 1u, st = 2 * j + bit; // pair j is bit (3-j) of the nibble
+        const bool     pos = (cur < st) || (cur == st && cur == 0); // "+" when the step moved to a lower state, or stayed in state 0
+        if (!pos) sgn |= k ? 1u << 30 : 1u << 31;
+        cur = st;
+    }
+    return cur | sgn;
 }
 
 } // namespace turbo_swar
