@@ -645,6 +645,70 @@ int mi_lte_ul_pucch_tables(const mi_lte_ul_cfg *ul, uint32_t N_id_cell, uint32_t
 int mi_lte_pucch_decode_run(mi_lte_ctx *ctx, uint32_t N_rb_ul, uint32_t N_ant, const float *d_subframes, const mi_lte_pucch_res *h_res,
                             const float *h_tables, uint32_t n_res, uint8_t *h_bits, uint32_t *h_n_bits, uint32_t *h_rc);
 
+/* ---------------------------------------------------------------- PUCCH formats 2 / 2a / 2b (periodic CQI reports)
+ * Stands for liblte_phy_pucch_format_2_2a_2b_channel_encode / _decode, which the reference declares (liblte/hdr/liblte_phy.h:785-816) and
+ * leaves empty (liblte/src/liblte_phy.cc:3150-3173, both bodies a FIXME).  So the specification is the authority: 36.211 5.4.2, 5.4.3 and
+ * 5.5.2.2, 36.212 5.2.3.3; normal cyclic prefix, one receive antenna, FDD.
+ *
+ * The (20, A) code, 1 <= A <= 13 (36.212 table 5.2.3.3-1): b_i = sum_n a_n M_i,n mod 2.  Its columns 0 .. 10 are the first 20 rows of
+ * the (32, O) code's table 5.2.2.6.4-1.  mi_lte_pucch2_encode: one bit per byte; MI_LTE_ERR_INVALID_ARG for A = 0, A > 13, null pointers.
+ *
+ * mi_lte_ul_pucch2_table (host arithmetic) fills what one (cell, subframe, resource n2 = n_PUCCH^(2), RNTI) needs on both sides:
+ *   r[7 s + l][k] = r_u,v^(alpha(n_s, l))(k) of slot n_s = 2 N_subfr + s, symbol l, sub-carrier k (the base sequences of
+ *     mi_lte_ul_pucch_tables), alpha = 2 pi n_cs / 12, n_cs(n_s, l) = (n_cs^cell(n_s, l) + n'(n_s)) mod 12;
+ *   n' (5.4.2, every modulo the mathematical one): even slot n' = n2 mod 12 if n2 < 12 N_rb_2, else (n2 + N_cs_1 + 1) mod 12;
+ *     odd slot n' = [12 (n'(n_s - 1) + 1)] mod 13 - 1 if n2 < 12 N_rb_2, else (12 - 2 - n2) mod 12;
+ *   prb[s] (5.4.3): m = floor(n2 / 12); floor(m / 2) when (m + s) mod 2 = 0, else N_rb_ul - 1 - floor(m / 2);
+ *   c_scr: bit i = c(i), i < 20, of the Gold sequence with c_init = (N_subfr + 1) (2 N_id_cell + 1) 2^16 + rnti.
+ * MI_LTE_ERR_INVALID_ARG: N_subfr > 9, N_id_cell > 503, N_cs_1 > 7, rnti > 65535, N_rb_ul outside 6 .. 100, N_rb_2 > 110, n2 outside [0, 12 N_rb_2) and
+ * (only when N_cs_1 > 0) [12 N_rb_2, 12 N_rb_2 + 10 - N_cs_1), 2 floor(m / 2) >= N_rb_ul, null pointers.
+ *
+ * mi_lte_pucch2_modulate writes one UE's 2 x 7 x 12 elements into a grid pair re[14][1200], im[14][1200] (the UL subframe layout):
+ * b scrambled with c_scr, QPSK d(n) = ((1 - 2 b(2n)) + j (1 - 2 b(2n+1))) / sqrt 2 (36.211 table 7.1.2-1), d(n) r on data symbol
+ * l = {0, 2, 3, 4, 6}[n mod 5] of slot floor(n / 5), r on symbol 1 and z r on symbol 5 of each slot; z = 1 for format 0 (format 2),
+ * format 1 (2a): ack 0 -> 1, 1 -> -1; format 2 (2b): ack 00 -> 1, 01 -> -j, 10 -> j, 11 -> -1 (table 5.4.2-1).  MI_LTE_ERR_INVALID_ARG:
+ * format > 2, a table whose prb >= 100, null pointers (ack may be NULL for format 0).
+ *
+ * The decoder, k_pucch2_decode, one wavefront per resource.  y(L, k) is the unit's element on symbol L, sub-carrier k, in the UL subframe
+ * layout of mi_lte_ul_frontend_batch:
+ *   1. Correlations.  c[L] = sum_{k<12} y(L, 12 prb[s] + k) conj(r[L][k]), L = 7 s + l, all 14 symbols, float32.  Correlating over the
+ *      12 sub-carriers is what separates UEs on other cyclic shifts of the same resource block; there are no per-sub-carrier estimates.
+ *   2. HARQ-ACK.  D = sum_s c[7s+5] conj(c[7s+1]).  Format 2: z = 1, no ACK bits.  2a: ack = (Re D < 0), z = +-1.  2b: the first maximum
+ *      of (Re D, -Im D, Im D, -Re D) over (b20, b21) = 00, 01, 10, 11, z as in the modulator.
+ *   3. Channel estimates.  h_s = (c[7s+1] + conj(z) c[7s+5]) / 24.  P = (|h_0|^2 + |h_1|^2) / 2.
+ *   4. Soft bits.  v_n = (c[L_n] / 12) conj(h_s), L_n the data symbol of d(n).  g = 32 sqrt 2 / P.  e(2n) = clamp(rintf(g Re v_n), +-127)
+ *      and e(2n+1) likewise from Im, each negated where c_scr's bit is 1.  Positive = bit 0.  Both slots share one g, so the slots combine
+ *      with their own weights.  P = 0 or not finite (or a g that is not finite): all 20 are 0.
+ *   5. Decision.  metric(w) = sum_i (1 - 2 b_i(w)) e_i in int32 over all 2^A words, the first maximum (smallest w = sum a_n 2^n).
+ *   6. Record.  One 64-byte mi_lte_pucch2_result.  The soft bits inside the record are the stage tap.  A DTX threshold (metric against
+ *      energy, P) is the caller's.
+ * mi_lte_pucch2_decode_run: resource r reads unit h_res[r].unit of d_subframes with table h_tabs[h_res[r].tab] -- resources with the same
+ * (subframe number, n2, rnti) share a table -- and writes d_out[r] (device memory).  Descriptors and tables go up in one staging copy;
+ * the call does not wait for the kernel.  Refused before any launch (MI_LTE_ERR_INVALID_ARG): format > 2, A = 0, A > 13, unit >= n_units,
+ * tab >= n_tab, a table whose prb >= N_rb_ul, n_res = 0, n_tab = 0, N_rb_ul outside 6 .. 100, null pointers. */
+typedef struct {
+    float    r_re[14][12], r_im[14][12];
+    uint32_t prb[2];
+    uint32_t c_scr;
+} mi_lte_pucch2_tab;
+typedef struct { uint32_t unit, format /* 0 = format 2, 1 = 2a, 2 = 2b */, tab /* index into h_tabs */, A; } mi_lte_pucch2_res;
+typedef struct {
+    uint32_t A;
+    uint32_t bits;        /* a_n at bit n */
+    int32_t  metric;      /* of the decided word */
+    int32_t  energy;      /* sum |e_i| */
+    uint8_t  ack[2], n_ack /* 0, 1, 2 */, pad0;
+    float    D_re, D_im, P;
+    int8_t   e[20];
+    uint8_t  pad[12];
+} mi_lte_pucch2_result;   /* 64 bytes */
+int mi_lte_ul_pucch2_table(const mi_lte_ul_cfg *ul, uint32_t N_id_cell, uint32_t N_subfr, uint32_t N_rb_ul, uint32_t n_2_pucch, uint32_t N_rb_2,
+                           uint32_t N_cs_1, uint32_t rnti, mi_lte_pucch2_tab *out);
+int mi_lte_pucch2_encode(uint32_t A, const uint8_t *a_bits, uint8_t *b /*[20]*/);
+int mi_lte_pucch2_modulate(const mi_lte_pucch2_tab *tab, uint32_t format, const uint8_t *b /*[20]*/, const uint8_t *ack /*[2]*/, float *re, float *im);
+int mi_lte_pucch2_decode_run(mi_lte_ctx *ctx, uint32_t N_rb_ul, const float *d_subframes, uint32_t n_units, const mi_lte_pucch2_res *h_res,
+                             uint32_t n_res, const mi_lte_pucch2_tab *h_tabs, uint32_t n_tab, mi_lte_pucch2_result *d_out);
+
 /* ---------------------------------------------------------------- PCFICH + PDCCH (common search space)
  * mi_lte_pdcch_plan_* / mi_lte_pdcch_decode_run replace liblte_phy_pdcch_channel_decode()
  * (liblte/hdr/liblte_phy.h:1012-1020, implementation liblte/src/liblte_phy.cc:4519-5135) for a batch of device

@@ -175,3 +175,43 @@ extern "C" int mi_lte_ul_pucch_tables(const mi_lte_ul_cfg *ul, uint32_t N_id_cel
     }
     return MI_LTE_OK;
 }
+
+// PUCCH formats 2 / 2a / 2b: the cyclically shifted sequences of all 14 symbols, the resource-block pair and the scrambling bits of one
+// (cell, subframe, resource n2, RNTI) -- 36.211 5.4.2 (n', the scrambling), 5.4.3 (the blocks) and 5.5.2.2 (the reference symbols use the same
+// shifts).  The reference leaves these formats empty, so the text in mi_lte.h is the contract; n_cs^cell and the base sequences are those of
+// mi_lte_ul_pucch_tables above.
+extern "C" int mi_lte_ul_pucch2_table(const mi_lte_ul_cfg *ul, uint32_t N_id_cell, uint32_t N_subfr, uint32_t N_rb_ul, uint32_t n_2_pucch, uint32_t N_rb_2,
+                                      uint32_t N_cs_1, uint32_t rnti, mi_lte_pucch2_tab *out)
+{
+    if (!ul || !out || N_subfr > 9 || N_id_cell > 503 || N_cs_1 > 7 || rnti > 65535 || N_rb_ul < 6 || N_rb_ul > 100 || N_rb_2 > 110) return MI_LTE_ERR_INVALID_ARG;
+    const uint32_t n2 = n_2_pucch, edge = 12 * N_rb_2;
+    const bool     mixed = n2 >= edge; // a resource in the mixed resource block
+    if (mixed && (N_cs_1 == 0 || n2 >= edge + 10 - N_cs_1)) return MI_LTE_ERR_INVALID_ARG;
+    const uint32_t m = n2 / 12;
+    if (2 * (m / 2) >= N_rb_ul) return MI_LTE_ERR_INVALID_ARG;
+    const uint32_t N_slot = 2 * N_subfr;
+    uint32_t       n_prime[2];
+    if (!mixed) {
+        n_prime[0] = n2 % 12;
+        n_prime[1] = (12 * (n_prime[0] + 1)) % 13 - 1; // (13 is prime and n' + 1 <= 12: the remainder is never 0)
+    } else {
+        n_prime[0] = (n2 + N_cs_1 + 1) % 12;
+        n_prime[1] = (uint32_t)((((int32_t)12 - 2 - (int32_t)n2) % 12 + 12) % 12);
+    }
+    std::vector<uint8_t> c(8 * 7 * 20);
+    synth::gold(N_id_cell, 8 * 7 * 20, c.data());
+    for (uint32_t s = 0; s < 2; s++) {
+        for (uint32_t l = 0; l < 7; l++) {
+            const uint32_t n_cs_cell = bits_to_u8(c.data() + 8 * 7 * (N_slot + s) + 8 * l);
+            const uint32_t n_cs      = (n_cs_cell + n_prime[s]) % 12;
+            const float    alpha     = 2 * M_PI * n_cs / 12; // as in mi_lte_ul_pucch_tables
+            ul_rs_slot(*ul, N_slot + s, N_id_cell, 1, alpha, out->r_re[7 * s + l], out->r_im[7 * s + l], true);
+        }
+        out->prb[s] = (m + s) % 2 == 0 ? m / 2 : N_rb_ul - 1 - m / 2;
+    }
+    uint8_t cs[20];
+    synth::gold((N_subfr + 1) * (2 * N_id_cell + 1) * 65536u + rnti, 20, cs);
+    out->c_scr = 0;
+    for (uint32_t i = 0; i < 20; i++) out->c_scr |= (uint32_t)(cs[i] & 1u) << i;
+    return MI_LTE_OK;
+}

@@ -145,6 +145,70 @@ def cqi_encode(O, bits, Q_cqi):
     return out
 
 
+class Pucch2Tab(C.Structure):
+    """mi_lte_pucch2_tab: the sequences r[7 s + l][k] of all 14 symbols, the resource-block pair and the 20 scrambling bits of one
+    (cell, subframe, n2, RNTI)"""
+    _fields_ = [("r_re", (C.c_float * 12) * 14), ("r_im", (C.c_float * 12) * 14), ("prb", C.c_uint32 * 2), ("c_scr", C.c_uint32)]
+
+    @property
+    def r(self):
+        """complex64 [14, 12]"""
+        return (np.ctypeslib.as_array(self.r_re) + 1j * np.ctypeslib.as_array(self.r_im)).astype(np.complex64)
+
+
+class Pucch2Res(C.Structure):
+    """mi_lte_pucch2_res: format 0 / 1 / 2 = PUCCH format 2 / 2a / 2b, tab the index into the call's tables, A information bits"""
+    _fields_ = [("unit", C.c_uint32), ("format", C.c_uint32), ("tab", C.c_uint32), ("A", C.c_uint32)]
+
+
+class Pucch2Result(C.Structure):
+    """mi_lte_pucch2_result (64 bytes): bits = a_n at bit n; metric of the decided word, energy = sum |e|; D, P and the 20 soft bits e are
+    the decoder's stage taps (mi_lte.h)"""
+    _fields_ = [("A", C.c_uint32), ("bits", C.c_uint32), ("metric", C.c_int32), ("energy", C.c_int32), ("ack", C.c_uint8 * 2), ("n_ack", C.c_uint8),
+                ("pad0", C.c_uint8), ("D_re", C.c_float), ("D_im", C.c_float), ("P", C.c_float), ("e", C.c_int8 * 20), ("pad", C.c_uint8 * 12)]
+
+
+PUCCH2_MAX_BITS, UL_GRID_SC = 13, 1200
+
+
+def pucch2_table(ulcfg, n_id_cell, n_subfr, n_rb_ul, n_2_pucch, n_rb_2, n_cs_1, rnti):
+    """mi_lte_ul_pucch2_table (host arithmetic): the Pucch2Tab of one (cell, subframe, resource n2, RNTI); 36.211 5.4.2, 5.4.3."""
+    out = Pucch2Tab()
+    rc = load_library().mi_lte_ul_pucch2_table(C.byref(ulcfg), n_id_cell, n_subfr, n_rb_ul, n_2_pucch, n_rb_2, n_cs_1, rnti, C.byref(out))
+    if rc != 0:
+        raise MiLteError("mi_lte_ul_pucch2_table(n2 = %d) failed: %d" % (n_2_pucch, rc), rc)
+    return out
+
+
+def pucch2_encode(A, bits):
+    """mi_lte_pucch2_encode (host arithmetic): the 20 coded bits of A <= 13 CQI information bits (36.212 5.2.3.3), one per byte."""
+    bits = np.ascontiguousarray(bits, np.uint8)
+    if len(bits) < A:
+        raise ValueError("pucch2_encode: %d information bits given, A = %d" % (len(bits), A))
+    out = np.zeros(20, np.uint8)
+    rc = load_library().mi_lte_pucch2_encode(A, bits.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise MiLteError("mi_lte_pucch2_encode(%d) failed: %d" % (A, rc), rc)
+    return out
+
+
+def pucch2_modulate(tab, fmt, b, ack=None, grid=None):
+    """mi_lte_pucch2_modulate (host arithmetic): one UE's elements written into `grid` (float32 [2, 14, 1200], real and imaginary halves; a
+    zeroed one is made when None), which is returned.  fmt 0 / 1 / 2 = format 2 / 2a / 2b, ack the one or two HARQ-ACK bits."""
+    b = np.ascontiguousarray(b, np.uint8)
+    if len(b) != 20:
+        raise ValueError("pucch2_modulate: 20 coded bits, not %d" % len(b))
+    if grid is None:
+        grid = np.zeros((2, 14, UL_GRID_SC), np.float32)
+    if grid.shape != (2, 14, UL_GRID_SC) or grid.dtype != np.float32 or not grid.flags.c_contiguous:
+        raise ValueError("pucch2_modulate: grid must be contiguous float32 [2, 14, %d]" % UL_GRID_SC)
+    a = None if ack is None else np.ascontiguousarray(list(ack) + [0, 0], np.uint8)[:2].copy()
+    rc = load_library().mi_lte_pucch2_modulate(C.byref(tab), fmt, b.ctypes.data, None if a is None else a.ctypes.data, grid[0].ctypes.data, grid[1].ctypes.data)
+    if rc != 0:
+        raise MiLteError("mi_lte_pucch2_modulate failed: %d" % rc, rc)
+    return grid
+
+
 HARQ_NONE, HARQ_NEW_DATA = 0xFFFFFFFF, 1
 
 
@@ -395,6 +459,10 @@ def load_library():
     L.mi_lte_pdcch_plan_destroy.argtypes = [vp, vp]
     L.mi_lte_pdcch_decode_run.argtypes = [vp, vp, vp, vp, vp, u32, u32p, u32p, u32p, u32p, C.POINTER(PdcchDci)]
     L.mi_lte_pucch_decode_run.argtypes = [vp, u32, u32, vp, C.POINTER(PucchRes), f32p, u32, u8p, u32p, u32p]
+    L.mi_lte_ul_pucch2_table.argtypes = [C.POINTER(UlCfg)] + [u32] * 7 + [C.POINTER(Pucch2Tab)]
+    L.mi_lte_pucch2_encode.argtypes = [u32, vp, vp]
+    L.mi_lte_pucch2_modulate.argtypes = [C.POINTER(Pucch2Tab), u32, vp, vp, vp, vp]
+    L.mi_lte_pucch2_decode_run.argtypes = [vp, u32, vp, u32, C.POINTER(Pucch2Res), u32, C.POINTER(Pucch2Tab), u32, vp]
     L.mi_lte_coarse_timing_samples.argtypes = [u32, u32]
     L.mi_lte_coarse_timing_samples.restype = C.c_size_t
     L.mi_lte_coarse_timing_run.argtypes = [vp, C.POINTER(DlCfg), vp, vp, C.c_uint64, u32, C.POINTER(CoarseTiming)]
@@ -1245,6 +1313,25 @@ class Context:
         self._check(self.L.mi_lte_pucch_decode_run(self.h, n_rb_ul, 1, d_subframes.ptr, arr, np.ascontiguousarray(tables, np.float32).reshape(-1), n,
                                                    bits.reshape(-1), nb, rc))
         return bits, nb, rc
+
+    def pucch2_decode_dev(self, n_rb_ul, d_subframes, n_units, res, tabs, d_out=None):
+        """mi_lte_pucch2_decode_run: PUCCH formats 2 / 2a / 2b over n_units UL device subframes.  res: list of (unit, format 0/1/2, tab, A),
+        tabs: list of Pucch2Tab (pucch2_table) that the resources index.  With d_out (device memory, 64 bytes per resource) the call
+        queues the kernel and returns None; without, it returns the records as a numpy record array with Pucch2Result's fields."""
+        n, nt = len(res), len(tabs)
+        arr = (Pucch2Res * max(n, 1))(*[Pucch2Res(*r) for r in res])
+        tarr = (Pucch2Tab * max(nt, 1))(*tabs)
+        own = d_out is None
+        if own:
+            d_out = self.alloc(C.sizeof(Pucch2Result) * max(n, 1))
+        try:
+            self._check(self.L.mi_lte_pucch2_decode_run(self.h, n_rb_ul, d_subframes.ptr, n_units, arr, n, tarr, nt, d_out.ptr))
+            if not own:
+                return None
+            return d_out.download(np.uint8, C.sizeof(Pucch2Result) * n).view(np.dtype(Pucch2Result))
+        finally:
+            if own:
+                d_out.free()
 
     def coarse_timing_dev(self, cfg, d_a, d_b, n_slots, start=0):
         """CoarseTiming for samples resident in HBM (d_b None for int8 interleaved)."""
