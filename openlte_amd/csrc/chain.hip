@@ -749,7 +749,9 @@ static int pdsch_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *p
         rc = mi_turbo_bcjr_group(ctx, gr, io, pl->d_bcjr_soft, pl->d_bcjr_bits, pl->decoder, pl->n_iter, pl->qpp_spec);
         if (rc != MI_LTE_OK) return rc;
     }
-    ctx->last_kernels = "k_pdsch_demod:1,k_rm_to_i8,k_bcjr_*,k_crc_finish per block size";
+    // (what mi_turbo_bcjr_group launched: the one-block-per-wavefront decoder takes the interleaved int8 block, the batch kernels their granule arrays)
+    ctx->last_kernels = pl->decoder == MI_LTE_TURBO_BCJR_BLOCK ? "k_pdsch_demod:1,k_rm_to_i8,k_bcjr_block,k_crc_finish per block size"
+                                                               : "k_pdsch_demod:1,k_cb_desc,k_rm_bcjr_prep,k_bcjr_half,k_bcjr_final,k_crc_finish per block size";
     return MI_LTE_OK;
 }
 
