@@ -230,7 +230,9 @@ int      mi_lte_pdsch_plan_soft_bits(const mi_lte_pdsch_plan *plan, uint32_t all
  *   interleaver; mi_lte_pdsch_plan_set_decoder returns MI_LTE_ERR_UNSUPPORTED for MI_LTE_TURBO_REF and MI_LTE_ERR_INVALID_ARG for
  *   qpp_spec = 0 on such a plan.  The blocks are decoded by the kernels of mi_lte_turbo_decode_batch, one launch set per block size.
  * Verdict: d_status[a] = 0 when every block's CRC24B and the transport block's CRC24A pass, else 2.  The output row holds the decoded
- *   payload (tbs bits) whatever the verdict, one bit per byte or packed (mi_lte_pdsch_plan_set_output). */
+ *   payload (tbs bits) whatever the verdict, one bit per byte or packed (mi_lte_pdsch_plan_set_output).  A code block whose channel values
+ *   are all 0 -- no information reached the decoder, e.g. an all-zero grid under MI_LTE_DEMAP_MAXLOG below -- is an erasure: its decisions
+ *   are all 0, which both CRCs accept, so its _cb_ok bit is 0 and the status 2 whatever the CRCs say. */
 typedef struct {
     uint32_t N_soft;    /* total soft channel bits of the UE category (36.306 Table 4.1-1), e.g. 250368, 1237248, 1827072 */
     uint32_t M_dl_harq; /* maximum number of DL HARQ processes (8 for FDD) */
@@ -264,6 +266,41 @@ int mi_lte_pdsch_alloc_decodable_3gpp(const mi_lte_dl_cfg *cfg, const mi_lte_dls
  * _cb_ok:   one uint32 per allocation; bit r set when block r's CRC24B passed (C = 1: bit 0 = the CRC24A verdict). */
 int mi_lte_pdsch_plan_cb_soft(const mi_lte_pdsch_plan *plan, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K);
 int mi_lte_pdsch_plan_cb_ok(const mi_lte_pdsch_plan *plan, const uint32_t **d_mask);
+
+/* ---------------------------------------------------------------- PDSCH, 3GPP mode: max-log soft-decision demapping (opt-in per plan)
+ * By default a 3GPP plan demaps as every plan does, with the reference's modulation_demapper (MI_LTE_DEMAP_REF): +-127 for every 16QAM /
+ * 64QAM bit, a distance grade that ignores the channel gain for QPSK.  MI_LTE_DEMAP_MAXLOG replaces it by log-likelihood ratios; everything
+ * after the soft-bit buffer (rate un-matching, HARQ combining, the decoders) is unchanged and sums and saturates the graded bytes.
+ *
+ * Per resource element (single-port cell: one resource element is one symbol), with y and h from the subframe planes:
+ *   w = |h|^2, z = y conj(h), x = z / w.
+ * Constellations (36.211 7.1.2-7.1.4), per axis: QPSK A = 1/sqrt(2), levels +-A, b0 / b1 = sign of I / Q (0: positive); 16QAM A = 1/sqrt(10),
+ *   levels {+-1, +-3} A, b0 / b1 sign, b2 / b3 0: the inner level; 64QAM A = 1/sqrt(42), levels {+-1, +-3, +-5, +-7} A, b0 / b1 sign,
+ *   b2 / b3 0: levels {1, 3}, b4 / b5 0: levels {3, 5}.
+ * Log-likelihood ratio of bit k, which sits on the axis u = Re x (even k) or Im x (odd k), S0 / S1 the axis levels whose label has bit k = 0 / 1:
+ *   L_k = w (min_{s in S1} (u - s)^2 - min_{s in S0} (u - s)^2), positive: bit 0 (the library's sign convention).  This is the exact max-log
+ *   LLR of the Gray-mapped square constellation up to the common factor 1 / sigma^2; the kernel evaluates its piecewise-linear closed form
+ *   from z and w, without dividing.
+ * Soft bit: v_k = clamp(rint(g_a L_k), -127, 127), rounding to nearest, ties to even; then descrambled with the sequence of the default
+ *   demapper and written to the same buffer at the same offsets with the same e_len (mi_lte_pdsch_plan_soft_bits).
+ * Gain g_a of allocation a: gain > 0: g_a = gain for every allocation -- for a caller who knows sigma^2 and wants properly weighted combining
+ *   across transmissions.  gain == 0, automatic, per allocation and per run: g_a = T / (4 A^2 wbar), wbar the mean of w over the allocation's
+ *   M_symb resource elements and T = MI_LTE_DEMAP_AUTO_T: a noiseless symbol at the mean channel power has its least reliable bit at +-T.
+ *   g_a is rounded to float before use; mi_lte_pdsch_plan_llr_gain reports it.  Under the automatic gain, retransmissions with different
+ *   modulations (or channel powers) combine on this convention and not on 1 / sigma^2.
+ * Degenerate input, no NaN and no trap: a wbar that is 0 or not finite (or a g_a past the float range) gives g_a = 0 and 0 for every soft bit
+ *   of the allocation; w = 0 on a resource element gives 0 for its Q_m soft bits; a non-finite g_a L_k gives 0 for that bit.  An allocation
+ *   whose soft bits are all 0 decodes to status 2 (the erasure rule of the mode's verdict, above).
+ * Refusals (nothing is launched, the plan stays usable and keeps its demapper): MI_LTE_ERR_INVALID_ARG for a NULL plan, an unknown mode, a
+ *   negative or non-finite gain; MI_LTE_ERR_UNSUPPORTED for MAXLOG on a plan that is not in the 3GPP mode or whose sample format has
+ *   MI_LTE_CE_COMPACT (left open).  mode = MI_LTE_DEMAP_REF ignores gain and restores the default path. */
+#define MI_LTE_DEMAP_REF    0u /* the reference's demapper: the default */
+#define MI_LTE_DEMAP_MAXLOG 1u
+#define MI_LTE_DEMAP_AUTO_T 16 /* automatic gain: the least reliable bit of a noiseless symbol at the mean channel power (profiles/demap_llr_sweep.txt) */
+int mi_lte_pdsch_plan_set_demapper(mi_lte_pdsch_plan *plan, uint32_t mode, float gain);
+/* tap, valid after a run: one float per allocation, the gain that run used (0 before a MAXLOG run); device pointer owned by the plan.
+ * MI_LTE_ERR_INVALID_ARG on a plan that is not in the 3GPP mode. */
+int mi_lte_pdsch_plan_llr_gain(const mi_lte_pdsch_plan *plan, const float **d_gain);
 
 /* ---------------------------------------------------------------- PDSCH, 3GPP mode: HARQ soft combining
  * Incremental-redundancy combining of the retransmissions of a transport block in device-resident soft buffers (36.212 5.1.4.1.2: the

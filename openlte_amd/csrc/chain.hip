@@ -50,6 +50,38 @@ __device__ __forceinline__ uint32_t pdsch_mask(uint32_t N_ant, uint32_t cell, ui
     return ~skip & 0xFFFu;
 }
 
+// Wave 0 of the demodulators: the pair table of one allocation -- per (symbol, PRB) pair, for ALL 14 symbols, tab[q].y = a 12-bit RE mask (0 in the
+// control region) under the pair's position L * 1200 + first sub-carrier, tab[q].x = the running count of REs before the pair (a scan inside
+// the wave), tab[n_pairs].x = the total.
+__device__ __forceinline__ void pair_table_scan(uint2 *tab, const mi_lte_pdsch_alloc &al, uint32_t N_ant, uint32_t cell, uint32_t sf, uint32_t cfi,
+                                                uint32_t n_pairs, uint32_t first_sc, uint32_t last_sc)
+{
+    const uint32_t N_prb = al.N_prb;
+    const uint32_t ln = threadIdx.x, per = (n_pairs + 63) / 64, q0 = ln * per, q1 = min(q0 + per, n_pairs);
+    // q / N_prb as a truncated float product (q < 1540): the hardware reciprocal is within 1 ulp of 1 / N_prb, three ulp on top make it an
+    // upper bound, and the excess -- under 5 * 2^-23 of q / N_prb -- stays far below the 1 / N_prb that separates a quotient from the next
+    // integer.  The exact magic number (0xFFFFFFFF / N_prb + 1) was a 32-bit division of a workgroup-uniform value on the vector unit.
+    const float r_prb = __builtin_amdgcn_rcpf((float)N_prb) * (1.0f + 0x1.8p-22f);
+    uint32_t local = 0;
+    for (uint32_t q = q0; q < q1; q++) {
+        const uint32_t L = (uint32_t)((float)q * r_prb), prb = al.prb[L >= 7 ? 1 : 0][q - __umul24(L, N_prb)];
+        const uint32_t m = L < cfi ? 0u : pdsch_mask(N_ant, cell, sf, L, prb, first_sc, last_sc);
+        tab[q].y = m | ((L * N_SC_MAX + prb * 12) << 12); // low 12 bits: RE mask, high 20 bits: L*1200 + first sub-carrier
+        local += __popc(m);
+    }
+    uint32_t incl = local;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t n = __shfl_up(incl, o);
+        if ((int)ln >= o) incl += n;
+    }
+    uint32_t run = incl - local;
+    for (uint32_t q = q0; q < q1; q++) {
+        tab[q].x = run;
+        run += __popc(tab[q].y & 0xFFFu);
+    }
+    if (ln == 63) tab[n_pairs] = make_uint2(incl, 0u); // total
+}
+
 // The kernel is latency-bound (a chain of dependent table reads, then scattered plane reads per resource element), so it lives on
 // occupancy: 8 waves per SIMD with a few spilled registers beat 4 without (2.80 -> 2.18 ms per 32k subframes); the single-port
 // case is its own instantiation so that the 2/4-port combiners do not set its register count.
@@ -86,31 +118,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
     const uint32_t cfi = al.n_pdcch_symbs ? al.n_pdcch_symbs : g.cfi; // the allocation's own control-region size, or the plan's
     const uint32_t n_pairs = 14 * N_prb, pair0 = cfi * N_prb;          // pairs [0, pair0) are the control region: empty masks
     const uint32_t c_init = ((al.rnti << 14) | (0u << 13) | (sf << 9) | cell) & 0x7FFFFFFFu; // 31 bits: the Gold basis has 31 rows
-    if (threadIdx.x < 64) {
-        const uint32_t ln = threadIdx.x, per = (n_pairs + 63) / 64, q0 = ln * per, q1 = min(q0 + per, n_pairs);
-        // q / N_prb as a truncated float product (q < 1540): the hardware reciprocal is within 1 ulp of 1 / N_prb, three ulp on top make it an
-        // upper bound, and the excess -- under 5 * 2^-23 of q / N_prb -- stays far below the 1 / N_prb that separates a quotient from the next
-        // integer.  The exact magic number (0xFFFFFFFF / N_prb + 1) was a 32-bit division of a workgroup-uniform value on the vector unit.
-        const float r_prb = __builtin_amdgcn_rcpf((float)N_prb) * (1.0f + 0x1.8p-22f);
-        uint32_t local = 0;
-        for (uint32_t q = q0; q < q1; q++) {
-            const uint32_t L = (uint32_t)((float)q * r_prb), prb = al.prb[L >= 7 ? 1 : 0][q - __umul24(L, N_prb)];
-            const uint32_t m = L < cfi ? 0u : pdsch_mask(N_ant, cell, sf, L, prb, first_sc, last_sc);
-            tab[q].y = m | ((L * N_SC_MAX + prb * 12) << 12); // low 12 bits: RE mask, high 20 bits: L*1200 + first sub-carrier
-            local += __popc(m);
-        }
-        uint32_t incl = local;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t n = __shfl_up(incl, o);
-            if ((int)ln >= o) incl += n;
-        }
-        uint32_t run = incl - local;
-        for (uint32_t q = q0; q < q1; q++) {
-            tab[q].x = run;
-            run += __popc(tab[q].y & 0xFFFu);
-        }
-        if (ln == 63) tab[n_pairs] = make_uint2(incl, 0u); // total
-    } else {
+    if (threadIdx.x < 64) pair_table_scan(tab, al, N_ant, cell, sf, cfi, n_pairs, first_sc, last_sc);
+    else {
         const uint32_t n_words_ub = ((n_pairs - pair0) * 12 * Qm + 31) / 32; // <= max_words; one word of slack for the 2-word window in put_bits
         if (threadIdx.x < 128) qam_lut[threadIdx.x - 64] = qam_lut_entry(threadIdx.x - 64);
         for (uint32_t w = threadIdx.x - 64; w <= n_words_ub; w += blockDim.x - 64) cw[w] = gold_word(gt, c_init, w);
@@ -331,6 +340,163 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
     }
 }
 
+// ---- MI_LTE_DEMAP_MAXLOG (include/mi_lte.h, "PDSCH, 3GPP mode: max-log soft-decision demapping"): the 3GPP plans' opt-in demapper.
+// The max-log LLRs of one axis of the Gray-mapped square constellation (36.211 7.1.2-7.1.4) in their piecewise-linear closed form, from
+// t = Re or Im of z = y conj(h) and w = |h|^2, without dividing: with a = |t| and D = A w the axis levels sit at a = D, 3D, 5D, 7D, and
+// w (min_{S1} (u - s)^2 - min_{S0} (u - s)^2) = min_{S1} s (w s - 2 t) - min_{S0} s (w s - 2 t).  lam[0]: the sign bit, lam[1] / lam[2]: the
+// amplitude bits (b2 / b4 of the real part, b3 / b5 of the imaginary part).  In double: the differences a - k D cancel where a symbol sits next
+// to a level, and in float their rounding alone -- some 2^-24 T k (k + 1) w / wbar of a soft-bit step under the automatic gain -- would reach
+// the 2^-16 the bytes are pinned to the float64 model with (tests/demap_llr_model.py); in double the products of two floats are exact and
+// kernel and model run the same operations.  The kernel waits for its loads, not for its arithmetic (profiles/demap_llr_timing.txt).
+template <uint32_t MOD> __device__ __forceinline__ void llr_axis(double t, double w, double (&lam)[3])
+{
+    constexpr double A = MOD == 3 ? 0.15430334996209191 : MOD == 2 ? 0.31622776601683794 : 0.70710678118654752; // 1/sqrt(42), 1/sqrt(10), 1/sqrt(2)
+    const double a = fabs(t), D = A * w;
+    if (MOD == 1) lam[0] = 4 * A * t;
+    else if (MOD == 2) {
+        lam[0] = a <= 2 * D ? 4 * A * t : copysign(8 * A * (a - D), t);
+        lam[1] = 4 * A * (2 * D - a);
+    } else {
+        const double k = a < 2 * D ? 0.0 : a < 4 * D ? 1.0 : a < 6 * D ? 2.0 : 3.0;
+        lam[0] = copysign(4 * A * (k + 1) * (a - k * D), t);
+        lam[1] = a < 2 * D ? 8 * A * (3 * D - a) : a < 6 * D ? 4 * A * (4 * D - a) : 8 * A * (5 * D - a);
+        lam[2] = a < 4 * D ? 4 * A * (a - 2 * D) : 4 * A * (6 * D - a);
+    }
+}
+// v = clamp(rint(g lam), -127, 127), ties to even; 0 when g lam is not finite
+__device__ __forceinline__ int llr_byte(double g, double lam)
+{
+    const double x = g * lam;
+    return fabs(x) <= 1.7976931348623157e308 ? (int)fmin(fmax(rint(x), -127.0), 127.0) : 0;
+}
+
+// k_pdsch_demod's single-port path with that demapper in place of the reference's: same pair table, scrambling words, thread per (pair,
+// sub-carrier), LDS assembly and soft-bit layout.  gain > 0: g = gain.  gain == 0: a first sweep over the allocation's estimate planes sums
+// w (per thread, then inside each wave, then over the waves in LDS, always in that order: a run is reproducible) and
+// g = T / (4 A^2 wbar) (T = auto_t: MI_LTE_DEMAP_AUTO_T), rounded to float -- the value llr_gain[allocation] reports is the value the soft bits were scaled with.
+__global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict__ subframes, DemodGeom g, const mi_lte_pdsch_alloc *__restrict__ allocs,
+                                                         const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell, GoldTables gt,
+                                                         int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len,
+                                                         uint32_t max_pairs, uint32_t max_words, uint32_t e_lds_cap, float gain, float auto_t,
+                                                         float *__restrict__ llr_gain)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // tab[max_pairs+1] (offset, mask | position) | cw[...] | soft bits
+    __shared__ double w_wave[4];
+    const uint32_t a_idx = blockIdx.x;
+    const mi_lte_pdsch_alloc &al = allocs[a_idx];
+    const uint32_t unit = al.unit, sf = subfr_num[unit], cell = n_id_cell[unit], N_prb = al.N_prb;
+    const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : 2; // (a 3GPP plan holds no BPSK allocation)
+    uint2    *tab = reinterpret_cast<uint2 *>(smu);
+    uint32_t *cw  = smu + ((2 * (max_pairs + 1) + 3u) & ~3u);
+    uint32_t first_sc, last_sc;
+    sync_window(g.N_rb_dl, first_sc, last_sc);
+    const uint32_t cfi = al.n_pdcch_symbs ? al.n_pdcch_symbs : g.cfi;
+    const uint32_t n_pairs = 14 * N_prb, pair0 = cfi * N_prb;
+    const uint32_t c_init = ((al.rnti << 14) | (0u << 13) | (sf << 9) | cell) & 0x7FFFFFFFu;
+    if (threadIdx.x < 64) pair_table_scan(tab, al, 1u, cell, sf, cfi, n_pairs, first_sc, last_sc);
+    else {
+        const uint32_t n_words_ub = ((n_pairs - pair0) * 12 * Qm + 31) / 32;
+        for (uint32_t w = threadIdx.x - 64; w <= n_words_ub; w += blockDim.x - 64) cw[w] = gold_word(gt, c_init, w);
+    }
+    __syncthreads();
+    const uint32_t M_symb = tab[n_pairs].x, N_bits = M_symb * Qm;
+    if (threadIdx.x == 0) e_len[a_idx] = N_bits;
+
+    const float *base = subframes + (size_t)unit * g.sf_stride;
+    const char  *y_re_p = reinterpret_cast<const char *>(base), *y_im_p = y_re_p + 16 * N_SC_MAX * 4;
+    const char  *h_re_p = y_im_p + 16 * N_SC_MAX * 4, *h_im_p = h_re_p + 16 * N_SC_MAX * 4;
+    constexpr int  UNR = 4;
+    const uint32_t q_thr = threadIdx.x / 12, j = threadIdx.x - 12 * q_thr, below = (1u << j) - 1u;
+    const bool     lane_on = threadIdx.x < 252;
+    // byte offset of the thread's resource element in pair q (one register serves the four planes), whether it carries PDSCH, its index
+    auto element = [&](uint32_t q, uint32_t &ob, uint32_t &idx) __attribute__((always_inline)) -> bool {
+        const bool  in = lane_on && q < n_pairs;
+        const uint2 pr = tab[in ? q : 0u];
+        const bool  on = in && ((pr.y >> j) & 1u);
+        idx = pr.x + __popc(pr.y & below);
+        ob  = on ? ((pr.y >> 12) + j) << 2 : 0u;
+        return on;
+    };
+    double gd = (double)gain;
+    if (gain == 0.0f) { // wbar: the mean of |h|^2 over the allocation's resource elements
+        double part = 0.0;
+        for (uint32_t qb = pair0; qb < n_pairs; qb += 21 * UNR) {
+            float hr[UNR], hi[UNR];
+            bool  on[UNR];
+#pragma unroll
+            for (int r = 0; r < UNR; r++) {
+                uint32_t ob, idx;
+                on[r] = element(qb + 21 * r + q_thr, ob, idx);
+                hr[r] = *reinterpret_cast<const float *>(h_re_p + ob);
+                hi[r] = *reinterpret_cast<const float *>(h_im_p + ob);
+            }
+#pragma unroll
+            for (int r = 0; r < UNR; r++)
+                if (on[r]) part += (double)hr[r] * hr[r] + (double)hi[r] * hi[r];
+        }
+        for (int o = 32; o; o >>= 1) part += __shfl_xor(part, o);
+        if ((threadIdx.x & 63u) == 0) w_wave[threadIdx.x >> 6] = part;
+        __syncthreads();
+        const double wbar = (((w_wave[0] + w_wave[1]) + w_wave[2]) + w_wave[3]) / (double)M_symb;
+        const double a4 = al.mod_type == 3 ? 4.0 / 42 : al.mod_type == 2 ? 4.0 / 10 : 2.0; // 4 A^2
+        const float  gf = (float)((double)auto_t / (a4 * wbar));
+        gd = (wbar > 0.0 && fabsf(gf) <= 3.4028234e38f) ? (double)gf : 0.0; // wbar 0, NaN or infinite, or a gain past float: every soft bit 0
+    }
+    if (threadIdx.x == 0) llr_gain[a_idx] = (float)gd;
+
+    int8_t    *e      = e_base + (size_t)e_off[a_idx] * 64;
+    int8_t    *e_lds  = reinterpret_cast<int8_t *>(cw + max_words);
+    const bool via_lds = N_bits <= e_lds_cap;
+    auto run = [&](auto modc, auto *dst) __attribute__((always_inline)) {
+        constexpr uint32_t MOD = decltype(modc)::value, QM = MOD == 3 ? 6 : MOD == 2 ? 4 : 2;
+        for (uint32_t qb = pair0; qb < n_pairs; qb += 21 * UNR) {
+            float    yr[UNR], yi[UNR], hr[UNR], hi[UNR];
+            uint32_t idx[UNR];
+            bool     on[UNR];
+#pragma unroll
+            for (int r = 0; r < UNR; r++) {
+                uint32_t ob;
+                on[r] = element(qb + 21 * r + q_thr, ob, idx[r]);
+                yr[r] = *reinterpret_cast<const float *>(y_re_p + ob);
+                yi[r] = *reinterpret_cast<const float *>(y_im_p + ob);
+                hr[r] = *reinterpret_cast<const float *>(h_re_p + ob);
+                hi[r] = *reinterpret_cast<const float *>(h_im_p + ob);
+            }
+#pragma unroll
+            for (int r = 0; r < UNR; r++) {
+                if (!on[r]) continue;
+                const double Yr = yr[r], Yi = yi[r], Hr = hr[r], Hi = hi[r];
+                const double w = Hr * Hr + Hi * Hi;
+                double li[3], lq[3];
+                llr_axis<MOD>(Yr * Hr + Yi * Hi, w, li);
+                llr_axis<MOD>(Yi * Hr - Yr * Hi, w, lq);
+                // descramble (c bit set -> negate) and store: Q_m idx is even, so the bytes leave in pairs (bit 2k on the real axis, 2k + 1 on the imaginary)
+                const uint32_t n0 = idx[r] * QM, c = __builtin_amdgcn_alignbit(cw[(n0 >> 5) + 1], cw[n0 >> 5], n0 & 31);
+#pragma unroll
+                for (uint32_t k = 0; k < QM; k += 2) {
+                    const int vi = llr_byte(gd, li[k >> 1]), vq = llr_byte(gd, lq[k >> 1]);
+                    const int lo = ((c >> k) & 1u) ? -vi : vi, hi8 = ((c >> (k + 1)) & 1u) ? -vq : vq;
+                    *reinterpret_cast<uint16_t *>(dst + n0 + k) = (uint16_t)((lo & 0xFF) | ((hi8 & 0xFF) << 8));
+                }
+            }
+        }
+    };
+    auto per_mod = [&](auto *dst) __attribute__((always_inline)) {
+        switch (al.mod_type) {
+        case 1:  run(std::integral_constant<uint32_t, 1>{}, dst); break;
+        case 2:  run(std::integral_constant<uint32_t, 2>{}, dst); break;
+        default: run(std::integral_constant<uint32_t, 3>{}, dst); break;
+        }
+    };
+    if (via_lds) {
+        per_mod(e_lds);
+        __syncthreads();
+        const uint32_t nq = (N_bits + 15) >> 4; // the allocation's slot in e_base is padded to 64 bytes
+        for (uint32_t w = threadIdx.x; w < nq; w += blockDim.x) reinterpret_cast<uint4 *>(e)[w] = reinterpret_cast<const uint4 *>(e_lds)[w];
+    } else
+        per_mod(e);
+}
+
 } // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -353,6 +519,8 @@ struct mi_lte_pdsch_plan {
     std::vector<uint8_t>  h_row;    // plan_layout's per-allocation scratch: kept, so that a re-assignment (tens of thousands of allocations per
     std::vector<uint32_t> h_e_bits; // chunk of a capture) allocates nothing
     MiDlsch3   *g3 = nullptr; // 3GPP transport-block mode (mi_lte_pdsch_plan_create_3gpp): its code blocks and buffers (dlsch3gpp.hip)
+    uint32_t    demap = MI_LTE_DEMAP_REF; // mi_lte_pdsch_plan_set_demapper (3GPP mode)
+    float       demap_gain = 0.0f, *d_llr_gain = nullptr; // MAXLOG: the fixed gain (0: automatic); [n_alloc] the gain of the last run (3GPP plans)
 };
 
 static void plan_set_stride(mi_lte_pdsch_plan *pl)
@@ -531,6 +699,8 @@ int mi_lte_pdsch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uin
     MI_HIP_CHECK(ctx, pl->core.allocate(n_alloc, pl->core.e_bytes));
     rc = mi_dlsch3_create(ctx, dlsch, h_allocs, n_alloc, &pl->g3);
     if (rc != MI_LTE_OK) return rc;
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_llr_gain, sizeof(float) * n_alloc));
+    MI_HIP_CHECK(ctx, hipMemsetAsync(pl->d_llr_gain, 0, sizeof(float) * n_alloc, ctx->stream));
     MI_H2D(ctx, pl->core.d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
     MI_H2D(ctx, pl->core.d_e_off, pl->core.h_e_off.data(), sizeof(uint32_t) * n_alloc);
     MI_HIP_CHECK(ctx, mi_stream_wait_polling(ctx));
@@ -640,6 +810,7 @@ void mi_lte_pdsch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl)
     pl->core.release(); // (mapped: the three descriptor arrays are views of h_stage)
     if (pl->d_bcjr_soft) (void)hipFree(pl->d_bcjr_soft);
     if (pl->d_bcjr_bits) (void)hipFree(pl->d_bcjr_bits);
+    if (pl->d_llr_gain) (void)hipFree(pl->d_llr_gain);
     if (pl->h_stage) (void)hipHostFree(pl->h_stage);
     if (pl->staged) (void)hipEventDestroy(pl->staged);
     mi_dlsch3_free(pl->g3);
@@ -671,6 +842,23 @@ int mi_lte_pdsch_plan_set_decoder(mi_lte_pdsch_plan *pl, uint32_t mode, uint32_t
     if (pl->g3 && mode == MI_LTE_TURBO_REF) return MI_LTE_ERR_UNSUPPORTED; // (the 3GPP mode: BCJR decoders, exact interleaver)
     if (pl->g3 && !qpp_spec) return MI_LTE_ERR_INVALID_ARG;
     pl->decoder = mode; pl->n_iter = n_iter; pl->qpp_spec = qpp_spec;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pdsch_plan_set_demapper(mi_lte_pdsch_plan *pl, uint32_t mode, float gain)
+{
+    if (!pl || mode > MI_LTE_DEMAP_MAXLOG) return MI_LTE_ERR_INVALID_ARG;
+    if (mode == MI_LTE_DEMAP_REF) { pl->demap = MI_LTE_DEMAP_REF; return MI_LTE_OK; }
+    if (!(gain >= 0.0f) || gain > 3.4028234e38f) return MI_LTE_ERR_INVALID_ARG; // negative, NaN or infinite
+    if (!pl->g3 || (pl->cfg.sample_format & MI_LTE_CE_COMPACT)) return MI_LTE_ERR_UNSUPPORTED;
+    pl->demap = mode; pl->demap_gain = gain;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pdsch_plan_llr_gain(const mi_lte_pdsch_plan *pl, const float **d_gain)
+{
+    if (!pl || !d_gain || !pl->d_llr_gain) return MI_LTE_ERR_INVALID_ARG;
+    *d_gain = pl->d_llr_gain;
     return MI_LTE_OK;
 }
 
@@ -706,7 +894,15 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
         MI_LAUNCH(ctx, "k_pdsch_demod", kernel, dim3(pl->core.n_alloc), dim3(threads), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt,
                   pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap);
     };
-    if (g.N_ant == 1 && (pl->cfg.sample_format & MI_LTE_CE_COMPACT)) launch(k_pdsch_demod<true, true>);
+    if (pl->demap == MI_LTE_DEMAP_MAXLOG) { // (a single-port 3GPP plan on full estimate planes: mi_lte_pdsch_plan_set_demapper)
+        float auto_t = (float)MI_LTE_DEMAP_AUTO_T;
+        if (const char *ev = getenv("MI_LTE_DEMAP_AUTO_T")) { // (tuning aid: tools/demap_llr_sweep.py chooses the header's constant with it)
+            const float t = (float)atof(ev);
+            if (t >= 1.0f && t <= 127.0f) auto_t = t;
+        }
+        MI_LAUNCH(ctx, "k_pdsch_demod_llr", k_pdsch_demod_llr, dim3(pl->core.n_alloc), dim3(256), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num,
+                  d_n_id_cell, gt, pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain);
+    } else if (g.N_ant == 1 && (pl->cfg.sample_format & MI_LTE_CE_COMPACT)) launch(k_pdsch_demod<true, true>);
     else if (g.N_ant == 1) launch(k_pdsch_demod<true>);
     else launch(k_pdsch_demod<false>);
     MI_HIP_CHECK(ctx, hipGetLastError());
@@ -727,7 +923,11 @@ static int pdsch_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *p
     if (pl->core.n_alloc == 0) { ctx->err = "the dynamic plan holds no allocations (mi_lte_pdsch_plan_assign)"; return MI_LTE_ERR_INVALID_ARG; }
     if ((rc = pdsch_demod(ctx, pl, d_subframes, d_subfr_num, d_n_id_cell)) != MI_LTE_OK) return rc;
     const MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/false);
-    if (pl->g3) return mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter);
+    if (pl->g3) {
+        rc = mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter);
+        if (rc == MI_LTE_OK && pl->demap == MI_LTE_DEMAP_MAXLOG) ctx->last_kernels.replace(0, strlen("k_pdsch_demod"), "k_pdsch_demod_llr");
+        return rc;
+    }
     if (!mi_is_bcjr(pl->decoder)) {
         rc = mi_turbo_ref_dispatch(ctx, pl->core.groups.data(), (uint32_t)pl->core.groups.size(), io, &pl->core.multi);
         if (rc != MI_LTE_OK) return rc;

@@ -174,11 +174,14 @@ __device__ __forceinline__ uint32_t wave_xor(uint32_t v)
 // One code block's decisions: CRC24B over its K bits (C > 1), its payload into the output row, and its share of the transport block's
 // CRC24A -- the remainder of its payload bits times x^s, s = the bits that follow them in the transport block -- so that the shares of a
 // transport block XOR to its CRC24A remainder.  tab_a / tab_b: x^e mod g for e < 6144.
+// A block whose 3 (K + 4) channel values (soft: the decoder's input) are ALL zero is an erasure: the decoder's decisions are then all 0, and
+// the all-zero block divides by both generators -- CB_ERASED in its ok word makes k_dl3_tb_finish fail the transport block whatever the CRCs say.
+constexpr uint32_t CB_ERASED = 0x80000000u;
 __global__ __launch_bounds__(256) void k_dl3_cb_finish(const Dl3Desc *__restrict__ desc, const uint8_t *__restrict__ c_bits, const uint32_t *__restrict__ tab_a,
                                                        const uint32_t *__restrict__ tab_b, uint8_t *__restrict__ out_bits, uint32_t out_stride, uint32_t packed,
-                                                       uint32_t *__restrict__ part, uint32_t *__restrict__ ok)
+                                                       uint32_t *__restrict__ part, uint32_t *__restrict__ ok, const int8_t *__restrict__ soft)
 {
-    __shared__ uint32_t red[2][4];
+    __shared__ uint32_t red[3][4];
     const Dl3Desc &d = desc[blockIdx.x];
     const uint32_t K = d.K, C = d.C, tbs = d.tbs, nb = C > 1 ? K - 24 : K, q0 = d.r * (K - 24); // (C = 1: q0 = 0)
     const uint8_t *c = c_bits + (size_t)d.bits_off8 * 8;
@@ -205,15 +208,20 @@ __global__ __launch_bounds__(256) void k_dl3_cb_finish(const Dl3Desc *__restrict
             else        *reinterpret_cast<uint2 *>(o + q) = make_uint2(lo, hi);
         }
     }
+    // (the block's channel values start on a 4-byte boundary and 3 (K + 4) is a multiple of 4: K is a multiple of 8)
+    const uint32_t *sw = reinterpret_cast<const uint32_t *>(soft + (size_t)d.soft_off4 * 4);
+    uint32_t any = 0;
+    for (uint32_t w = threadIdx.x; w < 3 * (K + 4) / 4; w += blockDim.x) any |= sw[w];
     crc_a = wave_xor(crc_a);
     crc_b = wave_xor(crc_b);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = crc_a; red[1][threadIdx.x >> 6] = crc_b; }
+    const bool wave_any = __builtin_amdgcn_ballot_w64(any != 0) != 0;
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = crc_a; red[1][threadIdx.x >> 6] = crc_b; red[2][threadIdx.x >> 6] = wave_any ? 1u : 0u; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        uint32_t a = 0, b = 0;
-        for (uint32_t w = 0; w < blockDim.x / 64; w++) { a ^= red[0][w]; b ^= red[1][w]; }
+        uint32_t a = 0, b = 0, nz = 0;
+        for (uint32_t w = 0; w < blockDim.x / 64; w++) { a ^= red[0][w]; b ^= red[1][w]; nz |= red[2][w]; }
         part[blockIdx.x] = mulmod(a, d.xs, G_CRC24A);
-        ok[blockIdx.x]   = (C == 1 || b == 0) ? 1u : 0u;
+        ok[blockIdx.x]   = !nz ? CB_ERASED : (C == 1 || b == 0) ? 1u : 0u;
     }
 }
 
@@ -225,12 +233,13 @@ __global__ __launch_bounds__(256) void k_dl3_tb_finish(const uint32_t *__restric
     const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n_alloc) return;
     const uint32_t s0 = a_slot[a], C = a_nc[a];
-    uint32_t rem = 0, mask = 0;
+    uint32_t rem = 0, mask = 0, erased = 0;
     for (uint32_t r = 0; r < C; r++) {
         rem ^= part[s0 + r];
-        mask |= ok[s0 + r] << r;
+        mask |= (ok[s0 + r] & 1u) << r;
+        erased |= ok[s0 + r] & CB_ERASED;
     }
-    const bool crc_a = rem == 0;
+    const bool crc_a = rem == 0 && !erased; // (an erased block: no verdict can be read from its CRCs, k_dl3_cb_finish)
     if (C == 1) mask = crc_a ? 1u : 0u;
     status[a] = (crc_a && mask == (1u << C) - 1u) ? 0 : 2;
     cb_ok[a]  = mask;
@@ -527,7 +536,7 @@ int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lt
         if (rc != MI_LTE_OK) return rc;
     }
     MI_LAUNCH(ctx, "k_dl3_cb_finish", k_dl3_cb_finish, dim3(g->n_slot), dim3(256), 0, (const Dl3Desc *)g->d_desc, (const uint8_t *)g->d_bits,
-              (const uint32_t *)g->d_tab, (const uint32_t *)(g->d_tab + 6144), io.d_out_bits, io.out_stride, io.packed ? 1u : 0u, g->d_part, g->d_ok);
+              (const uint32_t *)g->d_tab, (const uint32_t *)(g->d_tab + 6144), io.d_out_bits, io.out_stride, io.packed ? 1u : 0u, g->d_part, g->d_ok, (const int8_t *)g->d_soft);
     MI_LAUNCH(ctx, "k_dl3_tb_finish", k_dl3_tb_finish, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const uint32_t *)g->d_a_slot,
               (const uint32_t *)g->d_a_nc, g->n_alloc, (const uint32_t *)g->d_part, (const uint32_t *)g->d_ok, io.d_status, g->d_cb_ok);
     if (p)

@@ -210,6 +210,8 @@ def pucch2_modulate(tab, fmt, b, ack=None, grid=None):
 
 
 HARQ_NONE, HARQ_NEW_DATA = 0xFFFFFFFF, 1
+DEMAP_REF, DEMAP_MAXLOG = 0, 1  # mi_lte_pdsch_plan_set_demapper (3GPP plans)
+DEMAP_AUTO_T = 16               # MI_LTE_DEMAP_AUTO_T
 
 
 class HarqBind(C.Structure):
@@ -406,6 +408,8 @@ def load_library():
     L.mi_lte_pdsch_alloc_decodable_3gpp.restype = C.c_int
     L.mi_lte_pdsch_plan_cb_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
     L.mi_lte_pdsch_plan_cb_ok.argtypes = [vp, C.POINTER(vp)]
+    L.mi_lte_pdsch_plan_set_demapper.argtypes = [vp, u32, C.c_float]
+    L.mi_lte_pdsch_plan_llr_gain.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_harq_buffer_bytes.argtypes = [u32]
     L.mi_lte_harq_buffer_bytes.restype = sz
     L.mi_lte_harq_pool_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
@@ -635,6 +639,19 @@ class PdschPlan:
         p = C.c_void_p()
         self.ctx._check(self.ctx.L.mi_lte_pdsch_plan_cb_ok(self.h, C.byref(p)))
         out = np.empty(self.n_alloc, np.uint32)
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
+        return out
+
+    def set_demapper(self, mode, gain=0.0):
+        """3GPP mode: DEMAP_REF (default, the reference's demapper) or DEMAP_MAXLOG (max-log LLRs; gain 0: automatic per allocation,
+        > 0: that gain for every allocation)."""
+        self.ctx._check(self.ctx.L.mi_lte_pdsch_plan_set_demapper(self.h, mode, gain))
+
+    def llr_gain(self):
+        """3GPP mode, after a run: float32 [n_alloc], the gain the MAXLOG demapper used per allocation (stage tap)."""
+        p = C.c_void_p()
+        self.ctx._check(self.ctx.L.mi_lte_pdsch_plan_llr_gain(self.h, C.byref(p)))
+        out = np.empty(self.n_alloc, np.float32)
         self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
         return out
 
