@@ -612,6 +612,43 @@ int mi_lte_pusch_plan_set_cqi_decode(mi_lte_pusch_plan *plan, const uint32_t *h_
 /* the n_alloc records (device pointer into the plan): all zero before a first run with decoding on and for allocations left opaque */
 int mi_lte_pusch_plan_cqi_results(const mi_lte_pusch_plan *plan, const mi_lte_cqi_result **d_records);
 
+/* ---------------------------------------------------------------- PUSCH, 3GPP mode: max-log soft-decision demapping (opt-in per plan)
+ * By default a 3GPP plan de-maps with the reference's modulation_demapper (MI_LTE_DEMAP_REF): +-127 for every 16QAM / 64QAM bit, for QPSK a
+ * distance grade that ignores what the equaliser did to the noise.  MI_LTE_DEMAP_MAXLOG (the constants of the PDSCH section above) replaces it
+ * by log-likelihood ratios; everything after the soft-bit buffer -- control-information gather and decisions, the CQI decoder, rate
+ * un-matching, the code blocks and their erasure rule -- is unchanged and sums and saturates the graded bytes.
+ *
+ * Equalised symbol.  For allocation a (M = 12 N_prb sub-carriers) and data symbol s = 0 .. 11 (the twelve non-DMRS symbols in order): h_k(s)
+ *   the channel estimate of sub-carrier k as the demodulator interpolates it in polar form between the two DMRS estimates (float, see
+ *   uplink.hip), hn_k(s) = 1 / (Re h^2 + Im h^2) the float the one-tap zero-forcing equaliser multiplies with, and x_s[k] the transform
+ *   pre-decoder's output times (float)(1 / sqrt(M)) (36.211 5.3.3): the float pair the default de-mapper receives.
+ * Per-symbol reliability.  rho_s = (float)(M / sum_k (double)hn_k(s)), the harmonic mean of the channel power over the allocation: zero
+ *   forcing colours the noise and the 1 / sqrt(M) inverse DFT spreads it evenly, so every time-domain sample of symbol s carries noise of
+ *   variance sigma^2 / rho_s.  rho_s = 0 when the sum, the quotient or its float value is not finite (an infinite or NaN hn makes the sum so;
+ *   a zero sum the quotient).  The sum is formed in double in a fixed order, without atomics: two runs give identical bytes.
+ * LLR.  Bit 2j of symbol x = x_s[k] sits on the real axis, bit 2j + 1 on the imaginary one: L is the PDSCH section's max-log LLR of that axis
+ *   with w = rho_s and z = rho_s x, i.e. rho_s (min_{S1} (u - s)^2 - min_{S0} (u - s)^2) for u = Re x or Im x, evaluated in double in the same
+ *   piecewise-linear closed form from t = (double)rho_s * (double)u and w = (double)rho_s.  Positive: bit 0.
+ * Soft bit.  v = clamp(rint(g_a L), -127, 127), ties to even, 0 where g_a L is not finite; then descrambled and written to the same byte
+ *   (k 12 + s) Q_m + q of the allocation, with the same e_len, as the default de-mapper (mi_lte_pusch_plan_soft_bits).  QPSK, 16QAM, 64QAM.
+ * Gain.  gain > 0: g_a = gain for every allocation.  gain == 0, automatic, per allocation and per run: g_a = (float)(T / (4 A^2 rhobar)),
+ *   rhobar the mean in double of the twelve rho_s floats (summed s = 0 .. 11) and T = MI_LTE_DEMAP_AUTO_T.  A rhobar that is 0 or not finite,
+ *   or a g_a past the float range, gives g_a = 0 and an all-zero allocation, which decodes to status 2 by the erasure rule of the mode's verdict.
+ * Refusals (nothing is launched, the plan stays as it was): MI_LTE_ERR_INVALID_ARG for a NULL plan, an unknown mode, a negative or non-finite
+ *   gain; MI_LTE_ERR_UNSUPPORTED for MAXLOG on a plan of mi_lte_pusch_plan_create (reference mode).  MI_LTE_DEMAP_REF is accepted on every
+ *   plan, ignores gain and restores the default.  Plans with control information (mi_lte_pusch_plan_create_3gpp_uci, with or without
+ *   mi_lte_pusch_plan_set_cqi_decode) accept MAXLOG.  A MAXLOG run launches k_pusch_demod_llr in place of k_pusch_demod. */
+int mi_lte_pusch_plan_set_demapper(mi_lte_pusch_plan *plan, uint32_t mode, float gain);
+/* taps, device pointers owned by the plan, holding the last MAXLOG run's values (zeros before one): the gain g_a, float [n_alloc], and
+ * rho_s, float [n_alloc][12].  MI_LTE_ERR_INVALID_ARG on a reference-mode plan. */
+int mi_lte_pusch_plan_llr_gain(const mi_lte_pusch_plan *plan, const float **d_gain);
+int mi_lte_pusch_plan_llr_rho(const mi_lte_pusch_plan *plan, const float **d_rho);
+/* the symbol tap, opt-in (on != 0 allocates it, on = 0 frees it; without it nothing extra is stored or allocated): MAXLOG runs also store
+ * the x_s[k] of every allocation.  _llr_symbols: allocation alloc's n = 12 M float pairs (re, im) in [s][k] order; zeros before a MAXLOG
+ * run.  MI_LTE_ERR_INVALID_ARG on a reference-mode plan and, for _llr_symbols, while the tap is off. */
+int mi_lte_pusch_plan_set_llr_tap(mi_lte_pusch_plan *plan, uint32_t on);
+int mi_lte_pusch_plan_llr_symbols(const mi_lte_pusch_plan *plan, uint32_t alloc, const float **d_x, uint32_t *n);
+
 /* PRACH detection: replaces liblte_phy_detect_prach() (liblte_phy.h:862-868, implementation liblte_phy.cc:3299-3479)
  * for a batch of PRACH occasions (d_occ_start[o] = sample index of the occasion's first cyclic-prefix sample; an
  * occasion spans mi_lte_prach_occasion_samples() samples), preamble formats 0-4 (format 4, the TDD UpPTS preamble of

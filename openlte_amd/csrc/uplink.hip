@@ -32,6 +32,7 @@
 #include "plan_core.hpp"
 #include "phy_dev.hpp"
 #include "ulsch_uci.h"
+#include "demap_llr.h"
 
 namespace {
 
@@ -211,14 +212,52 @@ __device__ __forceinline__ void dft_pass(const float2 *__restrict__ in, float2 *
 // compiler knows) -- and the index products are 24-bit multiplies (v_mul_lo_u32 / v_mad_u64_u32 issue at a quarter of the rate)
 // SPEC = the 3GPP mode's demodulator (mi_lte_pusch_plan_create_3gpp): the pre-decoder's output scaled by 1 / sqrt(M) as 36.211 5.3.3 has it,
 // where the reference -- and SPEC = false -- multiplies by sqrt(M).  One factor; everything else is the same code.
-template <uint32_t THREADS, bool SPEC = false>
-__attribute__((amdgpu_waves_per_eu(WPE, 8)))
+// LLR = the 3GPP mode's opt-in max-log demapper (MI_LTE_DEMAP_MAXLOG, include/mi_lte.h "PUSCH, 3GPP mode: max-log soft-decision demapping"):
+// a pass of its own over the LDS-resident estimates forms the twelve rho_s = M / sum_k hn_k(s) and the allocation's gain before the
+// symbol-group loop, and the de-mapper writes clamp(rint(g L)) with llr_axis / llr_byte (demap_llr.h) in place of demap_symbol.  It is the
+// instantiation with one more kernel argument, k_pusch_demod<THREADS, true, PuschLlr> (launched and listed as k_pusch_demod_llr); without
+// that argument every `if constexpr (LLR)` drops out and k_pusch_demod<THREADS, SPEC> has the signature and the code it had.
+struct PuschNoLlr {};
+struct PuschLlr {
+    float           gain, auto_t; // gain > 0: fixed; 0: automatic, g = auto_t / (4 A^2 mean rho)
+    uint32_t        lds_off;      // float offset in the dynamic LDS of wsum[4][12] (double) | rho[12] (float)
+    float          *g_out, *rho_out; // [n_alloc], [n_alloc][12]: the taps
+    float2         *x_tap;        // the symbol tap (mi_lte_pusch_plan_set_llr_tap) or NULL
+    const uint32_t *x_off;        // [n_alloc]: float2 offset of the allocation's 12 M symbols in x_tap
+};
+constexpr uint32_t LLR_LDS_BYTES = 4 * 12 * sizeof(double) + 12 * sizeof(float);
+
+// h(s) of data symbol sp (0 .. 5) of a slot and hn = 1 / |h|^2 as the one-tap equaliser uses it, from the slot's DMRS estimate: magnitude and
+// slope, u = exp(i ang_b), f1 .. f3 = exp(i n f_ang) for n = 1, 2, 3 (liblte_phy.cc:13770-13780: symbols 0-2 / 3-5 of a slot lie -3..-1 /
+// +1..+3 steps from its DMRS symbol, symbol 3 of 7)
+__device__ __forceinline__ void slot_h(float mag, float f_mag, float2 u, float2 f1, float2 f2, float2 f3, uint32_t sp, float &h_re, float &h_im, float &hn)
+{
+    const int    n = sp < 3 ? (int)sp - 3 : (int)sp - 2;
+    const float2 fa = n == 1 || n == -1 ? f1 : n == 2 || n == -2 ? f2 : f3;
+    const float2 f = make_float2(fa.x, n < 0 ? -fa.y : fa.y);
+    const float  cm = mag + (float)n * f_mag;
+    const float2 ph = cmul(u, f);
+    h_re = cm * ph.x; h_im = cm * ph.y;
+    hn = 1.0f / (h_re * h_re + h_im * h_im);
+}
+
+__device__ __forceinline__ PuschNoLlr llr_args() { return PuschNoLlr{}; }
+__device__ __forceinline__ const PuschLlr &llr_args(const PuschLlr &la) { return la; }
+#ifndef WPE_LLR
+#define WPE_LLR 4
+#endif
+
+template <uint32_t THREADS, bool SPEC = false, typename... LlrArgs>
+__attribute__((amdgpu_waves_per_eu(sizeof...(LlrArgs) ? WPE_LLR : WPE, 8)))
 __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict__ subframes, uint32_t sf_stride,
                                                      const mi_lte_pdsch_alloc *__restrict__ allocs, const PuschDesc *__restrict__ desc,
                                                      const float *__restrict__ dmrs_pool, GoldTables gt, int8_t *__restrict__ e_base,
                                                      const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len, uint32_t M_max,
-                                                     uint32_t S_par, float r_S_par, const PuschShape *__restrict__ shapes)
+                                                     uint32_t S_par, float r_S_par, const PuschShape *__restrict__ shapes, LlrArgs... la_pack)
 {
+    constexpr bool LLR = sizeof...(LlrArgs) == 1;
+    static_assert(sizeof...(LlrArgs) <= 1 && (!LLR || SPEC), "the max-log de-mapper belongs to the 3GPP mode");
+    [[maybe_unused]] const auto la = llr_args(la_pack...);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     // LDS: est[9][M_max] (mag0 mag1 dmag | unit vectors of ang0, ang1, dang) | tw[M_max] | buf A[S_par][M_max] | buf B[S_par][M_max] (float2) | scrambling words
     float    *est  = sm;
@@ -282,6 +321,58 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
     const float scale = SPEC ? sh.r_sqrt_M : sh.sqrt_M;
     int8_t     *e      = e_base + (size_t)e_off[a_idx] * 64; // 64-byte units
 
+    // ---- LLR: rho_s = M / sum_k hn_k(s) for all twelve data symbols, then the gain -- before the first soft bit of the first symbol group
+    // is written (the automatic gain needs every rho_s, and S_par < 12 above M = 213).  hn is the equaliser's own float (slot_h); the sum is
+    // in double and in a fixed order: each thread over its sub-carriers i = t, t + THREADS, .., then the xor butterfly inside the wavefront,
+    // then the wavefronts' LDS slots in ascending order.  No atomics: two runs give the same bytes.
+    [[maybe_unused]] const float *rho = nullptr;
+    [[maybe_unused]] double       gd  = 0.0;
+    if constexpr (LLR) {
+        double *wsum  = reinterpret_cast<double *>(sm + la.lds_off); // [THREADS / 64][12]
+        float  *rho_w = reinterpret_cast<float *>(wsum + 4 * 12);
+        for (uint32_t b = 0; b < 2; b++) { // slot: six data symbols per pass, so a thread carries six partial sums
+            double part[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            for (uint32_t i = threadIdx.x; i < M; i += THREADS) {
+                const float    mag = est[b * M_max + i], f_mag = est[2 * M_max + i];
+                const float2   u = make_float2(est[(3 + 2 * b) * M_max + i], est[(4 + 2 * b) * M_max + i]);
+                const float2   f1 = make_float2(est[7 * M_max + i], est[8 * M_max + i]), f2 = cmul(f1, f1), f3 = cmul(f2, f1);
+#pragma unroll
+                for (uint32_t sp = 0; sp < 6; sp++) {
+                    float h_re, h_im, hn;
+                    slot_h(mag, f_mag, u, f1, f2, f3, sp, h_re, h_im, hn);
+                    part[sp] += (double)hn;
+                }
+            }
+#pragma unroll
+            for (uint32_t sp = 0; sp < 6; sp++) {
+                for (int o = 32; o; o >>= 1) part[sp] += __shfl_xor(part[sp], o);
+                if ((threadIdx.x & 63u) == 0) wsum[(threadIdx.x >> 6) * 12 + 6 * b + sp] = part[sp];
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < 12) {
+            double sum = wsum[threadIdx.x];
+            for (uint32_t w = 1; w < THREADS / 64; w++) sum += wsum[w * 12 + threadIdx.x];
+            const float r = (float)((double)M / sum);
+            // an infinite or NaN hn makes the sum infinite or NaN; a zero sum the quotient: rho_s = 0 in each case
+            const float r_ok = (fabs(sum) <= 1.7976931348623157e308 && fabsf(r) <= 3.4028234e38f) ? r : 0.0f;
+            rho_w[threadIdx.x] = r_ok;
+            la.rho_out[a_idx * 12 + threadIdx.x] = r_ok;
+        }
+        __syncthreads();
+        rho = rho_w;
+        gd  = (double)la.gain;
+        if (la.gain == 0.0f) { // automatic: the mean of the twelve floats in double, s = 0 .. 11 in order
+            double rbar = 0.0;
+            for (uint32_t s = 0; s < 12; s++) rbar += (double)rho_w[s];
+            rbar /= 12.0;
+            const double a4 = al.mod_type == 3 ? 4.0 / 42 : al.mod_type == 2 ? 4.0 / 10 : 2.0; // 4 A^2
+            const float  gf = (float)((double)la.auto_t / (a4 * rbar));
+            gd = (rbar > 0.0 && fabsf(gf) <= 3.4028234e38f) ? (double)gf : 0.0; // rbar 0 or not finite, or a gain past float: every soft bit 0
+        }
+        if (threadIdx.x == 0) la.g_out[a_idx] = (float)gd;
+    }
+
     for (uint32_t s0 = 0; s0 < 12; s0 += S_par) { // S_par data symbols at a time (all 12 when they fit in LDS)
         const uint32_t S = S_par; // (12, 6, 3, 2 or 1: always a divisor of 12)
         // ---- channel estimate of each symbol and the one-tap equaliser.  One item per (subcarrier, slot): the slot's DMRS
@@ -300,16 +391,10 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
 #pragma unroll
             for (uint32_t sp = 0; sp < 6; sp++) {
                 if (sp < sp0 || sp >= sp1) continue; // uniform
-                // liblte_phy.cc:13770-13780: symbols 0-2 / 3-5 of a slot lie -3..-1 / +1..+3 steps from its DMRS symbol (symbol 3 of 7)
-                const int    n = sp < 3 ? (int)sp - 3 : (int)sp - 2;
                 const uint32_t l = sp < 3 ? sp : sp + 1; // position in the slot, skipping the DMRS symbol
-                const float2 fa = n == 1 || n == -1 ? f1 : n == 2 || n == -2 ? f2 : f3;
-                const float2 f = make_float2(fa.x, n < 0 ? -fa.y : fa.y);
-                const float  cm = mag + (float)n * f_mag;
-                const float2 ph = cmul(u, f);
-                const float  h_re = cm * ph.x, h_im = cm * ph.y;
+                float          h_re, h_im, hn;
+                slot_h(mag, f_mag, u, f1, f2, f3, sp, h_re, h_im, hn);
                 const float  zr = z_re[l * N_SC_MAX], zi = z_im[l * N_SC_MAX];
-                const float  hn = 1.0f / (h_re * h_re + h_im * h_im);
                 dst[sp * M_max] = make_float2((zr * h_re + zi * h_im) * hn, (zi * h_re - zr * h_im) * hn);
             }
         }
@@ -341,6 +426,16 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
             const uint32_t k = S == 12 ? __umul24(o, 43691u) >> 19 : quot(o, r_S_par), sy = o - __umul24(k, S), s = s0 + sy; // neighbouring threads write neighbouring bytes of e
             const float2   x = src[__umul24(sy, M_max) + k];
             int8_t         b[6] = {0, 0, 0, 0, 0, 0};
+            if constexpr (LLR) { // t = rho_s x, w = rho_s; bit 2k on the real axis, 2k + 1 on the imaginary
+                const float xr = scale * x.x, xi = scale * x.y;
+                if (la.x_tap) la.x_tap[la.x_off[a_idx] + __umul24(s, M) + k] = make_float2(xr, xi);
+                const double w = (double)rho[s];
+                double       li[3] = {0.0, 0.0, 0.0}, lq[3] = {0.0, 0.0, 0.0};
+                llr_axis<(MOD < 1 ? 1u : MOD)>(w * (double)xr, w, li);
+                llr_axis<(MOD < 1 ? 1u : MOD)>(w * (double)xi, w, lq);
+#pragma unroll
+                for (uint32_t q = 0; q < QM; q += 2) { b[q] = (int8_t)llr_byte(gd, li[q >> 1]); b[q + 1] = (int8_t)llr_byte(gd, lq[q >> 1]); }
+            } else
             demap_symbol(scale * x.x, scale * x.y, MOD, b);
             const uint32_t n0 = (__umul24(s, M) + k) * QM, w = n0 >> 5, sh = n0 & 31;
             const uint32_t c  = __builtin_amdgcn_alignbit(cw[w + 1], cw[w], sh);
@@ -360,7 +455,7 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
         }
         };
         switch (al.mod_type) {
-        case 0:  demap_all(std::integral_constant<uint32_t, 0>{}); break;
+        case 0:  if constexpr (!LLR) { demap_all(std::integral_constant<uint32_t, 0>{}); break; } // (a 3GPP plan holds no BPSK allocation)
         case 1:  demap_all(std::integral_constant<uint32_t, 1>{}); break;
         case 2:  demap_all(std::integral_constant<uint32_t, 2>{}); break;
         default: demap_all(std::integral_constant<uint32_t, 3>{}); break;
@@ -466,6 +561,14 @@ struct mi_lte_pusch_plan {
     MiDlsch3     *g3 = nullptr;
     uint32_t      decoder = MI_LTE_TURBO_BCJR, n_iter = 8, max_tbs = 0;
     MiUlschUci   *uci = nullptr; // control information on the allocations (mi_lte_pusch_plan_create_3gpp_uci): ulsch_uci.hip's part
+    // 3GPP mode, mi_lte_pusch_plan_set_demapper: MAXLOG's fixed gain (0: automatic); the last MAXLOG run's gain [n_alloc] and rho [n_alloc][12]
+    int           device = 0;
+    uint32_t      demap = MI_LTE_DEMAP_REF;
+    float         demap_gain = 0.0f, *d_llr_gain = nullptr, *d_llr_rho = nullptr;
+    // mi_lte_pusch_plan_set_llr_tap: the de-mapper's input symbols, 12 M float2 per allocation at h_x_off (nothing of it exists until asked for)
+    float2       *d_llr_x = nullptr;
+    uint32_t     *d_x_off = nullptr;
+    std::vector<uint32_t> h_x_off;
 };
 
 // UL-SCH rate matching has no soft-buffer limit (36.212 5.2.2.5: N_cb = K_w).  As a DL-SCH soft-buffer configuration: an N_IR no block reaches
@@ -533,6 +636,7 @@ static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
     auto *pl    = new mi_lte_pusch_plan();
     auto  guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_lte_pusch_plan_destroy(nullptr, pl); });
     pl->cfg     = *cfg;
+    pl->device  = ctx->device;
     pl->core.n_alloc = n_alloc;
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> dmrs_at; // (cell, subframe, N_prb) -> float offset
     std::vector<float>     dmrs;
@@ -614,6 +718,14 @@ static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
     if (spec) {
         const int rc = mi_dlsch3_create(ctx, &ULSCH_AS_DLSCH, h_allocs, n_alloc, &pl->g3);
         if (rc != MI_LTE_OK) return rc;
+        MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_llr_gain, sizeof(float) * 13 * (size_t)n_alloc)); // gain [n_alloc] | rho [n_alloc][12]
+        MI_HIP_CHECK(ctx, hipMemsetAsync(pl->d_llr_gain, 0, sizeof(float) * 13 * (size_t)n_alloc, ctx->stream));
+        pl->d_llr_rho = pl->d_llr_gain + n_alloc;
+        pl->h_x_off.resize(n_alloc + 1);
+        uint64_t at = 0;
+        for (uint32_t a = 0; a < n_alloc; a++) { pl->h_x_off[a] = (uint32_t)at; at += 144ull * h_allocs[a].N_prb; }
+        if (at > 0xFFFFFFFFull) { ctx->err = "plan larger than the symbol tap's 32-bit offsets"; return MI_LTE_ERR_UNSUPPORTED; }
+        pl->h_x_off[n_alloc] = (uint32_t)at;
     }
     if (h_uci) {
         const int rc = mi_ulsch_uci_create(ctx, h_allocs, h_uci, c_init.data(), pl->core.h_e_off.data(), n_alloc, pl->core.e_bytes, &pl->uci);
@@ -719,6 +831,62 @@ int mi_lte_pusch_plan_set_decoder(mi_lte_pusch_plan *pl, uint32_t mode, uint32_t
     return MI_LTE_OK;
 }
 
+int mi_lte_pusch_plan_set_demapper(mi_lte_pusch_plan *pl, uint32_t mode, float gain)
+{
+    if (!pl || mode > MI_LTE_DEMAP_MAXLOG) return MI_LTE_ERR_INVALID_ARG;
+    if (mode == MI_LTE_DEMAP_REF) { pl->demap = MI_LTE_DEMAP_REF; return MI_LTE_OK; }
+    if (!(gain >= 0.0f) || gain > 3.4028234e38f) return MI_LTE_ERR_INVALID_ARG; // negative, NaN or infinite
+    if (!pl->g3) return MI_LTE_ERR_UNSUPPORTED; // a reference-mode plan keeps the reference's de-mapper
+    pl->demap = mode; pl->demap_gain = gain;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_llr_gain(const mi_lte_pusch_plan *pl, const float **d_gain)
+{
+    if (!pl || !d_gain || !pl->d_llr_gain) return MI_LTE_ERR_INVALID_ARG;
+    *d_gain = pl->d_llr_gain;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_llr_rho(const mi_lte_pusch_plan *pl, const float **d_rho)
+{
+    if (!pl || !d_rho || !pl->d_llr_rho) return MI_LTE_ERR_INVALID_ARG;
+    *d_rho = pl->d_llr_rho;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_set_llr_tap(mi_lte_pusch_plan *pl, uint32_t on)
+{
+    if (!pl || !pl->g3) return MI_LTE_ERR_INVALID_ARG;
+    if (hipSetDevice(pl->device) != hipSuccess) return MI_LTE_ERR_HIP;
+    if (!on) { // (hipFree waits for a run that may still be writing the buffer)
+        (void)hipFree(pl->d_llr_x); (void)hipFree(pl->d_x_off);
+        pl->d_llr_x = nullptr; pl->d_x_off = nullptr;
+        return MI_LTE_OK;
+    }
+    if (pl->d_llr_x) return MI_LTE_OK;
+    const uint32_t n = pl->core.n_alloc;
+    const size_t   bytes = sizeof(float2) * (size_t)pl->h_x_off[n];
+    float2   *x = nullptr;
+    uint32_t *off = nullptr;
+    if (hipMalloc((void **)&x, bytes) != hipSuccess) return MI_LTE_ERR_HIP;
+    if (hipMalloc((void **)&off, sizeof(uint32_t) * n) != hipSuccess || hipMemset(x, 0, bytes) != hipSuccess ||
+        hipMemcpy(off, pl->h_x_off.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(x); (void)hipFree(off);
+        return MI_LTE_ERR_HIP;
+    }
+    pl->d_llr_x = x; pl->d_x_off = off;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_llr_symbols(const mi_lte_pusch_plan *pl, uint32_t alloc, const float **d_x, uint32_t *n)
+{
+    if (!pl || !pl->g3 || !pl->d_llr_x || alloc >= pl->core.n_alloc || !d_x || !n) return MI_LTE_ERR_INVALID_ARG;
+    *d_x = reinterpret_cast<const float *>(pl->d_llr_x + pl->h_x_off[alloc]);
+    *n   = pl->h_x_off[alloc + 1] - pl->h_x_off[alloc];
+    return MI_LTE_OK;
+}
+
 int mi_lte_pusch_plan_set_output(mi_lte_pusch_plan *pl, uint32_t packed)
 {
     if (!pl) return MI_LTE_ERR_INVALID_ARG;
@@ -751,6 +919,9 @@ void mi_lte_pusch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl)
     pl->core.release();
     (void)hipFree(pl->d_desc);
     (void)hipFree(pl->d_dmrs);
+    (void)hipFree(pl->d_llr_gain);
+    (void)hipFree(pl->d_llr_x);
+    (void)hipFree(pl->d_x_off);
     mi_dlsch3_free(pl->g3);
     mi_ulsch_uci_free(pl->uci);
     delete pl;
@@ -792,7 +963,21 @@ int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float 
                                     pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->M_max, S_par, recip_up(S_par), \
                                     static_cast<const PuschShape *>(ctx->d_pusch_shapes))
 #define MI_PUSCH_LAUNCH(T) do { if (pl->g3) MI_PUSCH_LAUNCH_V(T, true); else MI_PUSCH_LAUNCH_V(T, false); } while (0)
-    if (threads == 64) MI_PUSCH_LAUNCH(64); else if (threads == 128) MI_PUSCH_LAUNCH(128); else if (threads == 192) MI_PUSCH_LAUNCH(192); else MI_PUSCH_LAUNCH(256);
+    const bool llr = pl->g3 && pl->demap == MI_LTE_DEMAP_MAXLOG; // (mi_lte_pusch_plan_set_demapper)
+    if (llr) { // the same launch with the LLR block behind the scrambling words: the only instantiation whose dynamic LDS grows
+        const size_t   lds_off = (lds + 7) & ~(size_t)7;
+        float          auto_t  = (float)MI_LTE_DEMAP_AUTO_T;
+        if (const char *ev = getenv("MI_LTE_DEMAP_AUTO_T")) { // (tuning aid: tools/pusch_llr_sweep.py checks the header's constant with it)
+            const float t = (float)atof(ev);
+            if (t >= 1.0f && t <= 127.0f) auto_t = t;
+        }
+        const PuschLlr la{pl->demap_gain, auto_t,(uint32_t)(lds_off / sizeof(float)), pl->d_llr_gain, pl->d_llr_rho, pl->d_llr_x, pl->d_x_off};
+#define MI_PUSCH_LAUNCH_LLR(T) MI_LAUNCH(ctx, "k_pusch_demod_llr", (k_pusch_demod<T, true, PuschLlr>), dim3(pl->core.n_alloc), dim3(T), lds_off + LLR_LDS_BYTES, d_subframes, \
+                                         (uint32_t)mi_lte_ul_subframe_floats(), pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, \
+                                         pl->core.d_e_len, pl->M_max, S_par, recip_up(S_par), static_cast<const PuschShape *>(ctx->d_pusch_shapes), la)
+        if (threads == 64) MI_PUSCH_LAUNCH_LLR(64); else if (threads == 128) MI_PUSCH_LAUNCH_LLR(128); else if (threads == 192) MI_PUSCH_LAUNCH_LLR(192); else MI_PUSCH_LAUNCH_LLR(256);
+#undef MI_PUSCH_LAUNCH_LLR
+    } else if (threads == 64) MI_PUSCH_LAUNCH(64); else if (threads == 128) MI_PUSCH_LAUNCH(128); else if (threads == 192) MI_PUSCH_LAUNCH(192); else MI_PUSCH_LAUNCH(256);
 #undef MI_PUSCH_LAUNCH
 #undef MI_PUSCH_LAUNCH_V
     MI_HIP_CHECK(ctx, hipGetLastError());
@@ -806,9 +991,10 @@ int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float 
         if ((rc = mi_dlsch3_run(ctx, pl->g3, nullptr, nullptr, io, pl->decoder, pl->n_iter)) != MI_LTE_OK) return rc;
         const size_t at = ctx->last_kernels.find(','); // (mi_dlsch3_run lists the downlink's demodulator in front of its own kernels)
         ctx->last_kernels.replace(0, at == std::string::npos ? 0 : at,
-                                  !pl->uci        ? "k_pusch_demod:1"
-                                  : pl->uci->cqi_on ? "k_pusch_demod:1,k_ulsch_uci_gather:1,k_ulsch_uci_decide:1,k_ulsch_cqi_decode:1"
-                                                    : "k_pusch_demod:1,k_ulsch_uci_gather:1,k_ulsch_uci_decide:1");
+                                  std::string(llr ? "k_pusch_demod_llr:1" : "k_pusch_demod:1") +
+                                      (!pl->uci          ? ""
+                                       : pl->uci->cqi_on ? ",k_ulsch_uci_gather:1,k_ulsch_uci_decide:1,k_ulsch_cqi_decode:1"
+                                                         : ",k_ulsch_uci_gather:1,k_ulsch_uci_decide:1"));
         return MI_LTE_OK;
     }
     // several block sizes (the UEs of a subframe rarely share one): one launch set over all of them, as in the PDSCH chain

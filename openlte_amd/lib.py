@@ -210,7 +210,7 @@ def pucch2_modulate(tab, fmt, b, ack=None, grid=None):
 
 
 HARQ_NONE, HARQ_NEW_DATA = 0xFFFFFFFF, 1
-DEMAP_REF, DEMAP_MAXLOG = 0, 1  # mi_lte_pdsch_plan_set_demapper (3GPP plans)
+DEMAP_REF, DEMAP_MAXLOG = 0, 1  # mi_lte_pdsch_plan_set_demapper, mi_lte_pusch_plan_set_demapper (3GPP plans)
 DEMAP_AUTO_T = 16               # MI_LTE_DEMAP_AUTO_T
 
 
@@ -447,6 +447,11 @@ def load_library():
     L.mi_lte_cqi_decode_batch.argtypes = [vp, vp, vp, u32, vp]
     L.mi_lte_pusch_plan_set_cqi_decode.argtypes = [vp, vp]
     L.mi_lte_pusch_plan_cqi_results.argtypes = [vp, C.POINTER(vp)]
+    L.mi_lte_pusch_plan_set_demapper.argtypes = [vp, u32, C.c_float]
+    L.mi_lte_pusch_plan_llr_gain.argtypes = [vp, C.POINTER(vp)]
+    L.mi_lte_pusch_plan_llr_rho.argtypes = [vp, C.POINTER(vp)]
+    L.mi_lte_pusch_plan_set_llr_tap.argtypes = [vp, u32]
+    L.mi_lte_pusch_plan_llr_symbols.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32)]
     L.mi_lte_prach_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), C.POINTER(vp)]
     L.mi_lte_prach_plan_create_roots.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), f32p, f32p, u32, C.POINTER(vp)]
     L.mi_lte_prach_plan_destroy.argtypes = [vp, vp]
@@ -921,6 +926,38 @@ class PuschPlan:
         rec = (CqiResult * self.n_alloc)()
         self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, C.addressof(rec), p.value, C.sizeof(rec)))
         return [r.as_dict() for r in rec]
+
+    def set_demapper(self, mode, gain=0.0):
+        """3GPP mode: DEMAP_REF (default, the reference's de-mapper) or DEMAP_MAXLOG (max-log LLRs weighted by the per-symbol reliability
+        rho_s; gain 0: automatic per allocation, > 0: that gain for every allocation)."""
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_set_demapper(self.h, mode, gain))
+
+    def _llr_floats(self, fn, shape):
+        p = C.c_void_p()
+        self.ctx._check(fn(self.h, C.byref(p)))
+        out = np.empty(shape, np.float32)
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
+        return out
+
+    def llr_gain(self):
+        """3GPP mode, after a MAXLOG run: float32 [n_alloc], the gain that run used per allocation (stage tap)."""
+        return self._llr_floats(self.ctx.L.mi_lte_pusch_plan_llr_gain, self.n_alloc)
+
+    def llr_rho(self):
+        """3GPP mode, after a MAXLOG run: float32 [n_alloc, 12], the reliability rho_s of every data symbol (stage tap)."""
+        return self._llr_floats(self.ctx.L.mi_lte_pusch_plan_llr_rho, (self.n_alloc, 12))
+
+    def set_llr_tap(self, on=True):
+        """3GPP mode: have MAXLOG runs also store the de-mapper's input symbols (llr_symbols); off frees the buffer again."""
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_set_llr_tap(self.h, 1 if on else 0))
+
+    def llr_symbols(self, alloc):
+        """With set_llr_tap, after a MAXLOG run: complex64 [12, M], the equalised, pre-decoded and 1 / sqrt(M)-scaled symbols of one allocation."""
+        p, n = C.c_void_p(), C.c_uint32()
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_llr_symbols(self.h, alloc, C.byref(p), C.byref(n)))
+        out = np.empty(int(n.value), np.complex64)
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
+        return out.reshape(12, -1)
 
     def close(self):
         if self.h:
