@@ -649,6 +649,56 @@ int mi_lte_pusch_plan_llr_rho(const mi_lte_pusch_plan *plan, const float **d_rho
 int mi_lte_pusch_plan_set_llr_tap(mi_lte_pusch_plan *plan, uint32_t on);
 int mi_lte_pusch_plan_llr_symbols(const mi_lte_pusch_plan *plan, uint32_t alloc, const float **d_x, uint32_t *n);
 
+/* ---------------------------------------------------------------- PUSCH, 3GPP mode: DMRS noise estimate and the noise-referenced gain
+ * The automatic gain above normalises every transmission to T at its own mean channel power: a convention, not 1 / sigma^2.  For HARQ
+ * combining (next section) the LLRs of different transmissions have to be on one scale, so a MAXLOG run can take its gain from a noise
+ * estimate instead: g_a = scale / sigma2_a, and v is then `scale` times the max-log LLR in natural units (zero forcing plus the 1 / sqrt(M)
+ * inverse DFT leave noise sigma^2 / rho_s per sample, and L = rho_s (min_{S1} - min_{S0})).
+ * Inputs.  For allocation a with M = 12 N_prb and slot b = 0, 1: t_b[i], the least-squares product rx conj(dmrs) of sub-carrier i as the
+ *   demodulator keeps it after its first phase: the complex float (mag_b[i] u_b[i].re, mag_b[i] u_b[i].im) of the magnitude
+ *   mag = sqrtf(re^2 + im^2) and the unit vector u = t / mag it stores ((1, 0) for mag = 0, so mag = 0 gives 0).
+ * Second difference.  For every PRB j = 0 .. N_prb - 1 of the allocation's list and i = 12 j + 1 .. 12 j + 10:
+ *   d_b[i] = t_b[i - 1] - 2 t_b[i] + t_b[i + 1], in double.  It never crosses a PRB boundary, so a non-contiguous or hopping PRB list needs
+ *   no special case, and it removes any channel that is linear in frequency over three sub-carriers: a timing offset of 4 samples (of 2048)
+ *   leaves 2e-8 |h|^2.
+ * Sum and estimate.  S = sum_b sum_i |d_b[i]|^2 in double, in the fixed order of the rho pass (each thread its own i, i + THREADS, ..; the
+ *   xor butterfly within the wavefront; the wavefronts' slots in ascending order; no atomics: two runs give identical bytes).
+ *   sigma2_a = (float)(S / (120 N_prb)): white noise of variance sigma^2 per sub-carrier gives E|d|^2 = 6 sigma^2, over 20 N_prb terms.
+ * Gain.  g_a = (float)((double)scale / (double)sigma2_a).  A sigma2_a that is 0 or not finite, or a g_a past the float range, gives g_a = 0:
+ *   an all-zero allocation and status 2 by the erasure rule.  Everything else of the LLR is as above: v = clamp(rint(g_a L), -127, 127).
+ *   mi_lte_pusch_plan_llr_gain reports the g_a used.
+ * Limits.  The estimate's relative standard deviation is about 1.36 / sqrt(20 N_prb): 29 % at 1 PRB, 6 % at 25 PRB.  Channel curvature over
+ *   three sub-carriers biases it upwards.  The error of the unsmoothed channel estimate itself is not in sigma2.
+ * Scale.  scale = 8 is the convention the tests and tools use: an LLR of 16 meets the int8 clamp.  It is not a measured optimum: over
+ *   profiles/pusch_harq_sweep.txt's classes of two combined transmissions 4, 8 and 16 decode the same number of blocks to within the
+ *   sweep's noise -- the decoder is not sensitive to it.
+ * Kernel.  A run with the noise gain on launches a further instantiation of k_pusch_demod_llr (listed under that name) that holds the
+ *   noise pass, its two arguments and its LDS slots; with it off the launch, and so every byte, is what it was.
+ * mi_lte_pusch_plan_set_llr_noise: scale > 0: MAXLOG runs of the plan use g_a = (float)(scale / sigma2_a) in place of the gain given to
+ *   mi_lte_pusch_plan_set_demapper; scale == 0: off (the default).  Accepted whatever the plan's current demapper; takes effect on MAXLOG
+ *   runs only, and with it off a MAXLOG run gives the bytes it gave before.  Refusals, the plan left as it was: MI_LTE_ERR_INVALID_ARG for a
+ *   NULL plan and a negative or non-finite scale; MI_LTE_ERR_UNSUPPORTED on a reference-mode plan. */
+int mi_lte_pusch_plan_set_llr_noise(mi_lte_pusch_plan *plan, float scale);
+/* tap: float [n_alloc], sigma2_a of the last MAXLOG run with the noise gain on (zeros before one); device pointer owned by the plan.
+ * MI_LTE_ERR_INVALID_ARG on a reference-mode plan. */
+int mi_lte_pusch_plan_llr_noise(const mi_lte_pusch_plan *plan, const float **d_sigma2);
+
+/* ---------------------------------------------------------------- PUSCH, 3GPP mode: HARQ soft combining
+ * mi_lte_pusch_decode_run on a 3GPP plan with the allocations' soft bits combined into the pool's buffers.  The pool is the type of
+ * "PDSCH, 3GPP mode: HARQ soft combining" above, and one pool of a context serves its PDSCH and PUSCH plans alike; the contract is that
+ * section's: the binding with MI_LTE_HARQ_NONE and MI_LTE_HARQ_NEW_DATA, the flush rule, buf[t] = sat16(buf[t] + sat16(v)), the decoder
+ * input clamp(buf[t], -127, 127), the state record and the ordering.
+ * Uplink specifics.  N_cb = K_w (36.212 5.2.2.5), so the flush rule's N_cb test only fires against a buffer last written by a PDSCH plan
+ *   with a limited soft buffer.  Plans with control information combine the gathered data run (mi_lte_pusch_plan_data_soft): G differs
+ *   between transmissions with and without control information, which the rule allows.  ACK / RI decisions and the CQI decoder are
+ *   untouched by the pool.  Transmissions of different modulation or SNR combine on one scale only under the noise-referenced gain above.
+ * Refusals, returned before anything is launched, leaving pool and plan usable: MI_LTE_ERR_UNSUPPORTED for a plan of
+ *   mi_lte_pusch_plan_create; MI_LTE_ERR_INVALID_ARG for a NULL binding, buf >= n_buf, one buf bound twice in a run, or an allocation
+ *   whose tbs exceeds the pool's max_tbs.
+ * last_kernels: the plain run's demodulator prefix, then k_dl3_desc:1,k_harq_bind:1,k_harq_rm:1, .. ,k_harq_commit:1. */
+int mi_lte_pusch_decode_run_harq(mi_lte_ctx *ctx, mi_lte_pusch_plan *plan, mi_lte_harq_pool *pool, const mi_lte_harq_bind *h_bind,
+                                 const float *d_subframes, uint8_t *d_out_bits, int32_t *d_status);
+
 /* PRACH detection: replaces liblte_phy_detect_prach() (liblte_phy.h:862-868, implementation liblte_phy.cc:3299-3479)
  * for a batch of PRACH occasions (d_occ_start[o] = sample index of the occasion's first cyclic-prefix sample; an
  * occasion spans mi_lte_prach_occasion_samples() samples), preamble formats 0-4 (format 4, the TDD UpPTS preamble of
@@ -1353,6 +1403,15 @@ int    mi_lte_synth_ul_units_3gpp_uci_i8(const mi_lte_dl_cfg *cfg, const mi_lte_
                                          uint32_t n_alloc, const mi_lte_synth_channel *chan, const mi_lte_ulsch_uci *h_uci,
                                          const uint8_t *h_ack, const uint8_t *h_ri, const uint8_t *h_cqi, uint32_t h_cqi_stride,
                                          int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride);
+/* mi_lte_synth_ul_units_3gpp_i8 (h_uci = NULL) or mi_lte_synth_ul_units_3gpp_uci_i8 (h_uci and its companions as there) with the caller's
+ * transport blocks: h_payload[(u * n_alloc + a) * tbs_stride + i], i < tbs, one bit per byte.  The random numbers the payload would have
+ * taken are still drawn and discarded, so given the bits the plain generator drew with the same seed, it writes the same IQ byte for byte;
+ * a HARQ retransmission is the same payload with another rv and another seed.  Refuses what its sibling refuses, and a NULL h_payload. */
+int    mi_lte_synth_ul_units_3gpp_payload_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units,
+                                             const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs,
+                                             uint32_t n_alloc, const mi_lte_synth_channel *chan, const mi_lte_ulsch_uci *h_uci,
+                                             const uint8_t *h_ack, const uint8_t *h_ri, const uint8_t *h_cqi, uint32_t h_cqi_stride,
+                                             const uint8_t *h_payload, uint32_t tbs_stride, int8_t *h_iq);
 
 /* n_occ PRACH occasions (format 0-3 preambles per 36.211 5.7.2-5.7.3): preamble h_preamble_idx[o] of the cell's 64,
  * delayed by h_delay[o] samples, through a flat channel + AWGN; mi_lte_synth_prach_len() complex int8 samples each. */

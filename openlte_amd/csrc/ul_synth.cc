@@ -95,7 +95,8 @@ extern "C" int mi_lte_ulsch_mux_3gpp(uint32_t N_prb, uint32_t Q_m, const mi_lte_
 struct UlUci { const mi_lte_ulsch_uci *uci; const uint8_t *ack, *ri, *cqi; uint32_t cqi_stride; };
 static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units, const uint32_t *h_subfr_num,
                           const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
-                          const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride, bool spec, const UlUci *uu = nullptr)
+                          const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride, bool spec, const UlUci *uu = nullptr,
+                          const uint8_t *h_payload = nullptr)
 {
     if (!cfg || !ul || !h_subfr_num || !h_n_id_cell || !h_allocs || !chan || !h_iq) return MI_LTE_ERR_INVALID_ARG;
     if (uu && (!spec || !uu->uci || !uu->ack || !uu->ri)) return MI_LTE_ERR_INVALID_ARG;
@@ -110,7 +111,7 @@ static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uin
     for (uint32_t u = 0; u < n_units; u++) {
         if (h_n_id_cell[u] > 503) return MI_LTE_ERR_INVALID_ARG;
         for (uint32_t a = 0; a < n_alloc; a++)
-            if (!valid(h_allocs[(size_t)u * n_alloc + a]) || (h_tx_bits && h_allocs[(size_t)u * n_alloc + a].tbs > tbs_stride))
+            if (!valid(h_allocs[(size_t)u * n_alloc + a]) || ((h_tx_bits || h_payload) && h_allocs[(size_t)u * n_alloc + a].tbs > tbs_stride))
                 return MI_LTE_ERR_INVALID_ARG;
     }
     for (size_t k = 0; uu && k < (size_t)n_units * n_alloc; k++) { // the descriptors, and the transport block over the G they leave
@@ -149,6 +150,8 @@ static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uin
             // UL-SCH: CRC24A, turbo code, rate matching with N_cb = K_w (36.212 5.2.2.1-5.2.2.5)
             std::vector<uint8_t> b(spec ? al.tbs : K), g(G), h(N_bits), c(N_bits);
             for (uint32_t i = 0; i < al.tbs; i++) b[i] = (uint8_t)(rng.next() & 1u);
+            if (h_payload) // the caller's transport block; the draws above keep the rest of the stream where the generator has it
+                for (uint32_t i = 0; i < al.tbs; i++) b[i] = h_payload[((size_t)u * n_alloc + a) * tbs_stride + i] & 1u;
             if (h_tx_bits) memcpy(h_tx_bits + ((size_t)u * n_alloc + a) * tbs_stride, b.data(), al.tbs);
             if (spec) { // segmentation and CRC24B as well, the exact interleaver
                 const int rc = mi_lte_ulsch_encode_3gpp(al.tbs, b.data(), G, Qm, al.rv_idx, g.data());
@@ -279,6 +282,16 @@ int mi_lte_synth_ul_units_3gpp_uci_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_
     const UlUci uu = {h_uci, h_ack, h_ri, h_cqi, h_cqi_stride};
     if (!h_uci) return MI_LTE_ERR_INVALID_ARG;
     return synth_ul_units(cfg, ul, n_units, h_subfr_num, h_n_id_cell, h_allocs, n_alloc, chan, h_iq, h_tx_bits, tbs_stride, true, &uu);
+}
+
+int mi_lte_synth_ul_units_3gpp_payload_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units, const uint32_t *h_subfr_num,
+                                          const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                          const mi_lte_synth_channel *chan, const mi_lte_ulsch_uci *h_uci, const uint8_t *h_ack, const uint8_t *h_ri,
+                                          const uint8_t *h_cqi, uint32_t h_cqi_stride, const uint8_t *h_payload, uint32_t tbs_stride, int8_t *h_iq)
+{
+    const UlUci uu = {h_uci, h_ack, h_ri, h_cqi, h_cqi_stride};
+    if (!h_payload) return MI_LTE_ERR_INVALID_ARG;
+    return synth_ul_units(cfg, ul, n_units, h_subfr_num, h_n_id_cell, h_allocs, n_alloc, chan, h_iq, nullptr, tbs_stride, true, h_uci ? &uu : nullptr, h_payload);
 }
 
 // ---- PRACH (36.211 5.7.2-5.7.3): preamble v of root u is x_u((n + C_v) mod 839); its 839-point DFT sits on the PRACH

@@ -217,6 +217,10 @@ __device__ __forceinline__ void dft_pass(const float2 *__restrict__ in, float2 *
 // symbol-group loop, and the de-mapper writes clamp(rint(g L)) with llr_axis / llr_byte (demap_llr.h) in place of demap_symbol.  It is the
 // instantiation with one more kernel argument, k_pusch_demod<THREADS, true, PuschLlr> (launched and listed as k_pusch_demod_llr); without
 // that argument every `if constexpr (LLR)` drops out and k_pusch_demod<THREADS, SPEC> has the signature and the code it had.
+// The noise-referenced gain (mi_lte_pusch_plan_set_llr_noise) is a further instantiation, k_pusch_demod<THREADS, true, PuschLlrNoise> (launched
+// and listed as k_pusch_demod_llr too): one more pass over the LDS-resident estimates in front of the rho pass, the second differences of
+// the two DMRS least-squares rows, gives sigma2_a, and g_a = noise / sigma2_a.  Its two arguments and its LDS slots are PuschLlrNoise's alone:
+// with the setter off the launch is PuschLlr's, with the code, the argument block and the LDS it had.
 struct PuschNoLlr {};
 struct PuschLlr {
     float           gain, auto_t; // gain > 0: fixed; 0: automatic, g = auto_t / (4 A^2 mean rho)
@@ -226,6 +230,12 @@ struct PuschLlr {
     const uint32_t *x_off;        // [n_alloc]: float2 offset of the allocation's 12 M symbols in x_tap
 };
 constexpr uint32_t LLR_LDS_BYTES = 4 * 12 * sizeof(double) + 12 * sizeof(float);
+struct PuschLlrNoise : PuschLlr {
+    float  noise;  // g = noise / sigma2 of the DMRS noise estimate in place of either gain of PuschLlr
+    float *s2_out; // [n_alloc]: the sigma2 tap
+};
+constexpr uint32_t LLR_NOISE_LDS_BYTES = LLR_LDS_BYTES + 4 * sizeof(double); // nsum[4] (double) behind rho
+static_assert(LLR_LDS_BYTES % sizeof(double) == 0, "nsum is read as double");
 
 // h(s) of data symbol sp (0 .. 5) of a slot and hn = 1 / |h|^2 as the one-tap equaliser uses it, from the slot's DMRS estimate: magnitude and
 // slope, u = exp(i ang_b), f1 .. f3 = exp(i n f_ang) for n = 1, 2, 3 (liblte_phy.cc:13770-13780: symbols 0-2 / 3-5 of a slot lie -3..-1 /
@@ -243,6 +253,7 @@ __device__ __forceinline__ void slot_h(float mag, float f_mag, float2 u, float2 
 
 __device__ __forceinline__ PuschNoLlr llr_args() { return PuschNoLlr{}; }
 __device__ __forceinline__ const PuschLlr &llr_args(const PuschLlr &la) { return la; }
+__device__ __forceinline__ const PuschLlrNoise &llr_args(const PuschLlrNoise &la) { return la; }
 #ifndef WPE_LLR
 #define WPE_LLR 4
 #endif
@@ -255,7 +266,7 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
                                                      const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len, uint32_t M_max,
                                                      uint32_t S_par, float r_S_par, const PuschShape *__restrict__ shapes, LlrArgs... la_pack)
 {
-    constexpr bool LLR = sizeof...(LlrArgs) == 1;
+    constexpr bool LLR = sizeof...(LlrArgs) == 1, NOISE = (std::is_same<LlrArgs, PuschLlrNoise>::value || ...);
     static_assert(sizeof...(LlrArgs) <= 1 && (!LLR || SPEC), "the max-log de-mapper belongs to the 3GPP mode");
     [[maybe_unused]] const auto la = llr_args(la_pack...);
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -330,6 +341,28 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
     if constexpr (LLR) {
         double *wsum  = reinterpret_cast<double *>(sm + la.lds_off); // [THREADS / 64][12]
         float  *rho_w = reinterpret_cast<float *>(wsum + 4 * 12);
+        [[maybe_unused]] double *nsum = reinterpret_cast<double *>(rho_w + 12); // [THREADS / 64]: PuschLlrNoise's launch alone has them
+        // ---- noise estimate (only in the noise-referenced instantiation): t_b[i] = mag_b[i] u_b[i] is the least-squares product of
+        // sub-carrier i on DMRS symbol b, from the rows the slope step left alone.  Inside a resource block (i mod 12 = 1 .. 10, so a PRB
+        // list with gaps needs no special case) the second difference t[i-1] - 2 t[i] + t[i+1] removes a channel that is linear over three
+        // sub-carriers and leaves 6 sigma^2 of white noise: S = sum |d|^2 over 2 slots x 10 N_prb terms, in double and in the rho pass's
+        // fixed order (thread, xor butterfly, wavefront slots; the slots are read behind the rho pass's first barrier).
+        if constexpr (NOISE) {
+            double part = 0.0;
+            for (uint32_t b = 0; b < 2; b++) {
+                const float *mg = est + b * M_max, *ur = est + (3 + 2 * b) * M_max, *ui = est + (4 + 2 * b) * M_max;
+                for (uint32_t i = threadIdx.x; i < M; i += THREADS) {
+                    const uint32_t r = i - 12 * (__umul24(i, 10923u) >> 17); // i mod 12 for i < 1536
+                    if (r == 0 || r == 11) continue; // (so i - 1 and i + 1 stay inside the block, and inside 0 .. M - 1)
+                    const float m0 = mg[i - 1], m1 = mg[i], m2 = mg[i + 1];
+                    const float ar = m0 * ur[i - 1], ai = m0 * ui[i - 1], br = m1 * ur[i], bi = m1 * ui[i], cr = m2 * ur[i + 1], ci = m2 * ui[i + 1];
+                    const double dr = (double)ar - 2.0 * (double)br + (double)cr, di = (double)ai - 2.0 * (double)bi + (double)ci;
+                    part += dr * dr + di * di;
+                }
+            }
+            for (int o = 32; o; o >>= 1) part += __shfl_xor(part, o);
+            if ((threadIdx.x & 63u) == 0) nsum[threadIdx.x >> 6] = part;
+        }
         for (uint32_t b = 0; b < 2; b++) { // slot: six data symbols per pass, so a thread carries six partial sums
             double part[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             for (uint32_t i = threadIdx.x; i < M; i += THREADS) {
@@ -362,7 +395,15 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
         __syncthreads();
         rho = rho_w;
         gd  = (double)la.gain;
-        if (la.gain == 0.0f) { // automatic: the mean of the twelve floats in double, s = 0 .. 11 in order
+        if constexpr (NOISE) { // every thread forms the same sum in the same order
+            double S = nsum[0];
+            for (uint32_t w = 1; w < THREADS / 64; w++) S += nsum[w];
+            const float s2 = (float)(S / (120.0 * (double)N_prb));
+            const float gf = (float)((double)la.noise / (double)s2);
+            // sigma2 0 or not finite, or a gain past float: every soft bit 0
+            gd = (s2 > 0.0f && s2 <= 3.4028234e38f && fabsf(gf) <= 3.4028234e38f) ? (double)gf : 0.0;
+            if (threadIdx.x == 0) la.s2_out[a_idx] = s2;
+        } else if (la.gain == 0.0f) { // automatic: the mean of the twelve floats in double, s = 0 .. 11 in order
             double rbar = 0.0;
             for (uint32_t s = 0; s < 12; s++) rbar += (double)rho_w[s];
             rbar /= 12.0;
@@ -565,6 +606,8 @@ struct mi_lte_pusch_plan {
     int           device = 0;
     uint32_t      demap = MI_LTE_DEMAP_REF;
     float         demap_gain = 0.0f, *d_llr_gain = nullptr, *d_llr_rho = nullptr;
+    // mi_lte_pusch_plan_set_llr_noise: the noise-referenced gain's scale (0: off) and the last such run's sigma2 [n_alloc]
+    float         llr_noise = 0.0f, *d_llr_s2 = nullptr;
     // mi_lte_pusch_plan_set_llr_tap: the de-mapper's input symbols, 12 M float2 per allocation at h_x_off (nothing of it exists until asked for)
     float2       *d_llr_x = nullptr;
     uint32_t     *d_x_off = nullptr;
@@ -718,9 +761,10 @@ static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
     if (spec) {
         const int rc = mi_dlsch3_create(ctx, &ULSCH_AS_DLSCH, h_allocs, n_alloc, &pl->g3);
         if (rc != MI_LTE_OK) return rc;
-        MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_llr_gain, sizeof(float) * 13 * (size_t)n_alloc)); // gain [n_alloc] | rho [n_alloc][12]
-        MI_HIP_CHECK(ctx, hipMemsetAsync(pl->d_llr_gain, 0, sizeof(float) * 13 * (size_t)n_alloc, ctx->stream));
+        MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_llr_gain, sizeof(float) * 14 * (size_t)n_alloc)); // gain [n_alloc] | rho [n_alloc][12] | sigma2 [n_alloc]
+        MI_HIP_CHECK(ctx, hipMemsetAsync(pl->d_llr_gain, 0, sizeof(float) * 14 * (size_t)n_alloc, ctx->stream));
         pl->d_llr_rho = pl->d_llr_gain + n_alloc;
+        pl->d_llr_s2  = pl->d_llr_gain + 13 * (size_t)n_alloc;
         pl->h_x_off.resize(n_alloc + 1);
         uint64_t at = 0;
         for (uint32_t a = 0; a < n_alloc; a++) { pl->h_x_off[a] = (uint32_t)at; at += 144ull * h_allocs[a].N_prb; }
@@ -855,6 +899,21 @@ int mi_lte_pusch_plan_llr_rho(const mi_lte_pusch_plan *pl, const float **d_rho)
     return MI_LTE_OK;
 }
 
+int mi_lte_pusch_plan_set_llr_noise(mi_lte_pusch_plan *pl, float scale)
+{
+    if (!pl || !(scale >= 0.0f) || scale > 3.4028234e38f) return MI_LTE_ERR_INVALID_ARG; // negative, NaN or infinite
+    if (!pl->g3) return MI_LTE_ERR_UNSUPPORTED; // a reference-mode plan has no LLR to scale
+    pl->llr_noise = scale;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_llr_noise(const mi_lte_pusch_plan *pl, const float **d_sigma2)
+{
+    if (!pl || !d_sigma2 || !pl->d_llr_s2) return MI_LTE_ERR_INVALID_ARG;
+    *d_sigma2 = pl->d_llr_s2;
+    return MI_LTE_OK;
+}
+
 int mi_lte_pusch_plan_set_llr_tap(mi_lte_pusch_plan *pl, uint32_t on)
 {
     if (!pl || !pl->g3) return MI_LTE_ERR_INVALID_ARG;
@@ -937,11 +996,21 @@ int mi_lte_pusch_plan_soft_bits(const mi_lte_pusch_plan *pl, uint32_t alloc, con
     return MI_LTE_OK;
 }
 
-int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float *d_subframes, uint8_t *d_out_bits, int32_t *d_status)
+} // extern "C"
+
+// A plan run: the demodulator, then the 3GPP mode's control information and code blocks (ulsch_uci.hip, dlsch3gpp.hip) or the REF dispatch
+// (turbo.hip).  pool / h_bind: a HARQ run (mi_lte_pusch_decode_run_harq), nullptr otherwise.  Every refusal returns before a launch.
+static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *pool, const mi_lte_harq_bind *h_bind, const float *d_subframes,
+                     uint8_t *d_out_bits, int32_t *d_status)
 {
     if (!ctx || !pl || !d_subframes || !d_out_bits || !d_status) return MI_LTE_ERR_INVALID_ARG;
+    int rc;
+    if (pool) {
+        if (!pl->g3) { ctx->err = "HARQ soft combining needs a plan in the 3GPP transport-block mode"; return MI_LTE_ERR_UNSUPPORTED; }
+        if ((rc = mi_dlsch3_harq_check(ctx, pl->g3, pool, h_bind)) != MI_LTE_OK) return rc;
+    }
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    int rc = mi_ctx_gold_tables(ctx);
+    rc = mi_ctx_gold_tables(ctx);
     if (rc != MI_LTE_OK) return rc;
     if ((rc = pusch_shapes(ctx)) != MI_LTE_OK) return rc;
     GoldTables   gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
@@ -971,24 +1040,27 @@ int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float 
             const float t = (float)atof(ev);
             if (t >= 1.0f && t <= 127.0f) auto_t = t;
         }
-        const PuschLlr la{pl->demap_gain, auto_t,(uint32_t)(lds_off / sizeof(float)), pl->d_llr_gain, pl->d_llr_rho, pl->d_llr_x, pl->d_x_off};
-#define MI_PUSCH_LAUNCH_LLR(T) MI_LAUNCH(ctx, "k_pusch_demod_llr", (k_pusch_demod<T, true, PuschLlr>), dim3(pl->core.n_alloc), dim3(T), lds_off + LLR_LDS_BYTES, d_subframes, \
+        const PuschLlr      la{pl->demap_gain, auto_t,(uint32_t)(lds_off / sizeof(float)), pl->d_llr_gain, pl->d_llr_rho, pl->d_llr_x, pl->d_x_off};
+        const PuschLlrNoise ln{la, pl->llr_noise, pl->d_llr_s2};
+#define MI_PUSCH_LAUNCH_LLR_V(T, ARG, LDS, la) MI_LAUNCH(ctx, "k_pusch_demod_llr", (k_pusch_demod<T, true, ARG>), dim3(pl->core.n_alloc), dim3(T), lds_off + LDS, d_subframes, \
                                          (uint32_t)mi_lte_ul_subframe_floats(), pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, \
                                          pl->core.d_e_len, pl->M_max, S_par, recip_up(S_par), static_cast<const PuschShape *>(ctx->d_pusch_shapes), la)
+#define MI_PUSCH_LAUNCH_LLR(T) do { if (pl->llr_noise > 0.0f) MI_PUSCH_LAUNCH_LLR_V(T, PuschLlrNoise, LLR_NOISE_LDS_BYTES, ln); else MI_PUSCH_LAUNCH_LLR_V(T, PuschLlr, LLR_LDS_BYTES, la); } while (0)
         if (threads == 64) MI_PUSCH_LAUNCH_LLR(64); else if (threads == 128) MI_PUSCH_LAUNCH_LLR(128); else if (threads == 192) MI_PUSCH_LAUNCH_LLR(192); else MI_PUSCH_LAUNCH_LLR(256);
 #undef MI_PUSCH_LAUNCH_LLR
+#undef MI_PUSCH_LAUNCH_LLR_V
     } else if (threads == 64) MI_PUSCH_LAUNCH(64); else if (threads == 128) MI_PUSCH_LAUNCH(128); else if (threads == 192) MI_PUSCH_LAUNCH(192); else MI_PUSCH_LAUNCH(256);
 #undef MI_PUSCH_LAUNCH
 #undef MI_PUSCH_LAUNCH_V
     MI_HIP_CHECK(ctx, hipGetLastError());
-    if (pl->g3) { // 3GPP mode: the code blocks of dlsch3gpp.hip, no HARQ pool bound
+    if (pl->g3) { // 3GPP mode: the code blocks of dlsch3gpp.hip, combined into the pool's buffers on a HARQ run
         MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/true);
         if (pl->uci) { // control information: rate un-matching reads the gathered data run (G soft bits per allocation, the same offsets)
             if ((rc = mi_ulsch_uci_run(ctx, pl->uci, pl->core.d_e, pl->core.d_e_off)) != MI_LTE_OK) return rc;
             if (pl->uci->cqi_on && (rc = mi_ulsch_cqi_run(ctx, pl->uci)) != MI_LTE_OK) return rc; // (opt-in: mi_lte_pusch_plan_set_cqi_decode)
             io.d_e = pl->uci->d_e; io.d_e_len = pl->uci->d_e_len;
         }
-        if ((rc = mi_dlsch3_run(ctx, pl->g3, nullptr, nullptr, io, pl->decoder, pl->n_iter)) != MI_LTE_OK) return rc;
+        if ((rc = mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter)) != MI_LTE_OK) return rc;
         const size_t at = ctx->last_kernels.find(','); // (mi_dlsch3_run lists the downlink's demodulator in front of its own kernels)
         ctx->last_kernels.replace(0, at == std::string::npos ? 0 : at,
                                   std::string(llr ? "k_pusch_demod_llr:1" : "k_pusch_demod:1") +
@@ -1002,6 +1074,20 @@ int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float 
     if (rc != MI_LTE_OK) return rc;
     ctx->last_kernels.insert(0, "k_pusch_demod:1,");
     return MI_LTE_OK;
+}
+
+extern "C" {
+
+int mi_lte_pusch_decode_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const float *d_subframes, uint8_t *d_out_bits, int32_t *d_status)
+{
+    return pusch_run(ctx, pl, nullptr, nullptr, d_subframes, d_out_bits, d_status);
+}
+
+int mi_lte_pusch_decode_run_harq(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *pool, const mi_lte_harq_bind *h_bind,
+                                 const float *d_subframes, uint8_t *d_out_bits, int32_t *d_status)
+{
+    if (!pool || !h_bind) return MI_LTE_ERR_INVALID_ARG;
+    return pusch_run(ctx, pl, pool, h_bind, d_subframes, d_out_bits, d_status);
 }
 
 } // extern "C"

@@ -451,6 +451,9 @@ def load_library():
     L.mi_lte_pusch_plan_llr_gain.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_pusch_plan_llr_rho.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_pusch_plan_set_llr_tap.argtypes = [vp, u32]
+    L.mi_lte_pusch_plan_set_llr_noise.argtypes = [vp, C.c_float]
+    L.mi_lte_pusch_plan_llr_noise.argtypes = [vp, C.POINTER(vp)]
+    L.mi_lte_pusch_decode_run_harq.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.mi_lte_pusch_plan_llr_symbols.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32)]
     L.mi_lte_prach_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), C.POINTER(vp)]
     L.mi_lte_prach_plan_create_roots.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), f32p, f32p, u32, C.POINTER(vp)]
@@ -826,6 +829,12 @@ class PuschPlan:
     def run_dev(self, d_subframes, d_out, d_status):
         self.ctx._check(self.ctx.L.mi_lte_pusch_decode_run(self.ctx.h, self.h, d_subframes.ptr, d_out.ptr, d_status.ptr))
 
+    def run_harq_dev(self, pool, binds, d_subframes, d_out, d_status):
+        """mi_lte_pusch_decode_run_harq (3GPP mode): binds is a ctypes array of HarqBind, one per allocation (harq_binds), or None -- a NULL
+        binding, which the library refuses."""
+        self.ctx._check(self.ctx.L.mi_lte_pusch_decode_run_harq(self.ctx.h, self.h, pool.h, None if binds is None else C.cast(binds, C.c_void_p),
+                                                                d_subframes.ptr, d_out.ptr, d_status.ptr))
+
     def run(self, d_subframes):
         """Returns (status int32 [n_alloc], list of uint8 bit arrays)."""
         ctx = self.ctx
@@ -946,6 +955,15 @@ class PuschPlan:
     def llr_rho(self):
         """3GPP mode, after a MAXLOG run: float32 [n_alloc, 12], the reliability rho_s of every data symbol (stage tap)."""
         return self._llr_floats(self.ctx.L.mi_lte_pusch_plan_llr_rho, (self.n_alloc, 12))
+
+    def set_llr_noise(self, scale):
+        """3GPP mode: scale > 0: MAXLOG runs use the noise-referenced gain g_a = scale / sigma2_a of the DMRS noise estimate in place of
+        set_demapper's gain (so retransmissions combine on one scale); 0: off."""
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_set_llr_noise(self.h, scale))
+
+    def llr_noise(self):
+        """3GPP mode: float32 [n_alloc], sigma2_a of the last MAXLOG run with the noise gain on (stage tap; zeros before one)."""
+        return self._llr_floats(self.ctx.L.mi_lte_pusch_plan_llr_noise, self.n_alloc)
 
     def set_llr_tap(self, on=True):
         """3GPP mode: have MAXLOG runs also store the de-mapper's input symbols (llr_symbols); off frees the buffer again."""

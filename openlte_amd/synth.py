@@ -42,6 +42,9 @@ def _lib():
         L.mi_lte_ulsch_encode_3gpp.argtypes = [C.c_uint32, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, _u8p]
         L.mi_lte_synth_ul_units_3gpp_uci_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(UlCfg), C.c_uint32, _u32p, _u32p, C.c_void_p, C.c_uint32,
                                                         C.POINTER(SynthChannel), C.c_void_p, _u8p, _u8p, _u8p, C.c_uint32, _i8p, _u8p, C.c_uint32]
+        L.mi_lte_synth_ul_units_3gpp_payload_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(UlCfg), C.c_uint32, _u32p, _u32p, C.c_void_p, C.c_uint32,
+                                                            C.POINTER(SynthChannel), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                            C.c_void_p, C.c_uint32, _i8p]
         L.mi_lte_ulsch_mux_3gpp.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(UlschUci), _u8p, _u8p, _u8p, _u8p, C.c_uint32, _u8p, _u8p]
         L.mi_lte_synth_prach_len.argtypes = [C.c_uint32, C.c_uint32]
         L.mi_lte_synth_prach_len.restype = C.c_size_t
@@ -165,31 +168,46 @@ def ul_units(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, gain=(0.5, 1.5),
 
 
 def ul_units_3gpp(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, uci=None, ack=None, ri=None, cqi=None, gain=(0.5, 1.5), max_delay=4,
-                  snr_db=30.0, peak=100.0, seed=1):
+                  snr_db=30.0, peak=100.0, seed=1, payload=None):
     """ul_units with the 3GPP UL-SCH transmitter (mi_lte_synth_ul_units_3gpp_i8): any tbs of Table 7.1.7.2.1-1, the exact interleaver.
     uci: one UlschUci per allocation (unit-major, as allocs) -- mi_lte_synth_ul_units_3gpp_uci_i8, with the control values the caller's:
-    ack[k], ri[k] the allocation's information bits (sequences of O_ack / O_ri bits) and cqi[k] its Q_cqi coded CQI bits."""
+    ack[k], ri[k] the allocation's information bits (sequences of O_ack / O_ri bits) and cqi[k] its Q_cqi coded CQI bits.
+    payload: the transport blocks to send, uint8 [n_units, n_alloc, >= max tbs] one bit per byte (mi_lte_synth_ul_units_3gpp_payload_i8:
+    a HARQ retransmission is the same payload with another rv and seed); returned as tx."""
+    n, na = len(subfr_num), len(allocs)
+    max_tbs = max([a.tbs for a in allocs], default=8)
+    arr = (PdschAlloc * max(na, 1))(*allocs)
+    ch = SynthChannel(gain[0], gain[1], float(max_delay), float(snr_db), float(peak), int(seed))
+    sf, cell = np.ascontiguousarray(subfr_num, np.uint32), np.ascontiguousarray(n_id_cell, np.uint32)
+    iq = np.zeros((n, ul_unit_len(cfg.fft_size), 2), np.int8)
+    ctrl = (None, None, None, None, 0)  # descriptors, ack, ri, cqi, cqi stride: the C entries' arguments, NULL without control information
+    if uci is not None:
+        if len(uci) != na:
+            raise ValueError("uci: one UlschUci per allocation")
+        stride = max([u.Q_cqi for u in uci] + [1])
+        h_ack, h_ri, h_cqi = np.zeros((max(na, 1), 2), np.uint8), np.zeros((max(na, 1), 2), np.uint8), np.zeros((max(na, 1), stride), np.uint8)
+        for k, u in enumerate(uci):
+            for dst, src, cnt, what in ((h_ack, ack, u.O_ack, "ack"), (h_ri, ri, u.O_ri, "ri"), (h_cqi, cqi, u.Q_cqi, "cqi")):
+                if cnt:
+                    if src is None or len(src[k]) != cnt:
+                        raise ValueError("%s[%d]: %d bits" % (what, k, cnt))
+                    dst[k, :min(cnt, dst.shape[1])] = np.asarray(src[k], np.uint8)[:dst.shape[1]]  # (O > 2 is the library's to refuse)
+        u_arr = (UlschUci * max(na, 1))(*uci)
+        ctrl = (C.cast(u_arr, C.c_void_p), h_ack, h_ri, h_cqi, stride)
+    if payload is not None:
+        pl = np.ascontiguousarray(payload, np.uint8)
+        if pl.ndim != 3 or pl.shape[0] != n or pl.shape[1] != max(n_alloc, 1):
+            raise ValueError("payload: uint8 [n_units, n_alloc, >= max tbs]")
+        rc = _lib().mi_lte_synth_ul_units_3gpp_payload_i8(C.byref(cfg), C.byref(ulcfg), n, sf, cell, C.cast(arr, C.c_void_p), n_alloc, C.byref(ch),
+                                                          *[None if v is None else v if isinstance(v, (int, C.c_void_p)) else v.ctypes.data for v in ctrl],
+                                                          pl.ctypes.data, pl.shape[2], iq)
+        if rc != 0:
+            raise MiLteError("mi_lte_synth_ul_units_3gpp_payload_i8 failed: %d" % rc, rc)
+        return iq, pl[:, :, :max_tbs].copy()
     if uci is None:
         return ul_units(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, gain=gain, max_delay=max_delay, snr_db=snr_db, peak=peak, seed=seed, spec=True)
-    n, na = len(subfr_num), len(allocs)
-    if len(uci) != na:
-        raise ValueError("uci: one UlschUci per allocation")
-    iq = np.zeros((n, ul_unit_len(cfg.fft_size), 2), np.int8)
-    max_tbs = max([a.tbs for a in allocs], default=8)
     tx = np.zeros((n, max(n_alloc, 1), max_tbs), np.uint8)
-    stride = max([u.Q_cqi for u in uci] + [1])
-    h_ack, h_ri, h_cqi = np.zeros((max(na, 1), 2), np.uint8), np.zeros((max(na, 1), 2), np.uint8), np.zeros((max(na, 1), stride), np.uint8)
-    for k, u in enumerate(uci):
-        for dst, src, cnt, what in ((h_ack, ack, u.O_ack, "ack"), (h_ri, ri, u.O_ri, "ri"), (h_cqi, cqi, u.Q_cqi, "cqi")):
-            if cnt:
-                if src is None or len(src[k]) != cnt:
-                    raise ValueError("%s[%d]: %d bits" % (what, k, cnt))
-                dst[k, :min(cnt, dst.shape[1])] = np.asarray(src[k], np.uint8)[:dst.shape[1]]  # (O > 2 is the library's to refuse)
-    arr, u_arr = (PdschAlloc * max(na, 1))(*allocs), (UlschUci * max(na, 1))(*uci)
-    ch = SynthChannel(gain[0], gain[1], float(max_delay), float(snr_db), float(peak), int(seed))
-    rc = _lib().mi_lte_synth_ul_units_3gpp_uci_i8(C.byref(cfg), C.byref(ulcfg), n, np.ascontiguousarray(subfr_num, np.uint32),
-                                                  np.ascontiguousarray(n_id_cell, np.uint32), C.cast(arr, C.c_void_p), n_alloc, C.byref(ch),
-                                                  C.cast(u_arr, C.c_void_p), h_ack, h_ri, h_cqi, stride, iq, tx, max_tbs)
+    rc = _lib().mi_lte_synth_ul_units_3gpp_uci_i8(C.byref(cfg), C.byref(ulcfg), n, sf, cell, C.cast(arr, C.c_void_p), n_alloc, C.byref(ch), *ctrl, iq, tx, max_tbs)
     if rc != 0:
         raise MiLteError("mi_lte_synth_ul_units_3gpp_uci_i8 failed: %d" % rc, rc)
     return iq, tx
