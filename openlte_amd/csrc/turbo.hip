@@ -855,9 +855,10 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(Src::kPacke
 struct SisoPass {
     const uint8_t *in_a; // first soft value of each pair  (in[2t])
     const uint8_t *in_b; // second soft value of each pair (in[2t+1])
-    uint32_t      *sgn;  // the SISO output's signs, one bit per step (set: the path's output is negative, whatever its magnitude): [tile][blk][lane][2 words],
-                         // step t of the 64-step block in bit t % 32 of word t / 32.  The magnitude does not depend on the path (k_turbo_prep, k_turbo_perm
-                         // have it), so the sign is all the trellis adds: perm and vote join the two (turbo_swar.h: joined_from_bits)
+    uint32_t      *sgn;  // the SISO output's signs, one bit per step (set: the path's output is negative, whatever its magnitude): [tile][lane][word],
+                         // a code block's words next to each other, 32 steps per word by plane (turbo_swar.h, "the trellis kernels' sign words", has the
+                         // definition).  The magnitude does not depend on the path (k_turbo_prep, k_turbo_perm have it), so the sign is all the trellis
+                         // adds: perm and vote join the two (load_unit_signed)
     uint32_t      *dec;  // traceback bits: [tile][blk][lane][8 words]
 };
 struct SisoArgs { SisoPass p[2]; };
@@ -915,7 +916,7 @@ template <int R> __device__ __forceinline__ v2s byte_pair2(uint32_t w0, uint32_t
 // Traceback two steps at a time.  One step of the reference's traceback (liblte_phy.cc:10483-10527) maps (state at t+1, the four stored
 // compare bits of time t) to (state at t, sign of the output); two of them are a function of 3 + 8 bits, kept as a 2048-entry LDS
 // table per workgroup (turbo_swar.h: traceback_entry): the state after both steps in bits 0-2, the two outputs' sign bits on top, where
-// one v_alignbit moves them into the block's sign word.
+// one v_lshl_or appends them to the two planes of a sign word's byte pair (turbo_swar.h: sign_acc_push).
 
 // Workgroups of four independent wavefronts (they only share the traceback table).  mode 0: trellis h of wavefront b is tile 2b + h of
 // pass p[0] (first pass, two tiles per lane); mode 1: trellis h is tile b of pass p[h] (passes 2 and 3 of one tile)
@@ -950,15 +951,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
     const uint32_t Kp = kpad64(K), nblk = Kp >> 6;
     if (wv >= n_wv) return; // wavefront-uniform
     const uint8_t *pa[2], *pb[2];
-    uint32_t      *dec[2], *sgn[2];
+    uint32_t      *dec[2];
+    const uint32_t dec_at = lane * 8;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const SisoPass &ps   = args.p[mode ? h : 0];
         const uint32_t  tile = mode ? wv : min(2 * wv + h, n_tiles - 1); // an odd tile count: the last one twice
         const size_t    off  = seg_off + (size_t)tile * Kp * 64 + lane * 64;
         pa[h] = ps.in_a + off; pb[h] = ps.in_b + off;
-        dec[h] = ps.dec + (seg_off >> 3) + ((size_t)tile * nblk * 64 + lane) * 8; // (traceback: 32 bytes per step and tile = half an array's 64)
-        sgn[h] = ps.sgn + (seg_off >> 5) + ((size_t)tile * nblk * 64 + lane) * 2; // (signs: 8 bytes per step and tile = an eighth)
+        // (traceback: 32 bytes per step and tile = half an array's 64.)  A wavefront's tile is uniform: the tile's base is a scalar, the lane's
+        // words follow from a 32-bit index (dec_at, sgn_at)
+        dec[h] = ps.dec + (seg_off >> 3) + (size_t)__builtin_amdgcn_readfirstlane(tile) * nblk * 64 * 8;
     }
 
     v2s pm[8];
@@ -1016,7 +1019,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
         }
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-            uint4 *dp = reinterpret_cast<uint4 *>(dec[h] + (size_t)blk * 64 * 8);
+            uint4 *dp = reinterpret_cast<uint4 *>(dec[h] + (dec_at + blk * 64 * 8));
             dp[0] = make_uint4(dw[h][0], dw[h][1], dw[h][2], dw[h][3]);
             dp[1] = make_uint4(dw[h][4], dw[h][5], dw[h][6], dw[h][7]);
         }
@@ -1037,11 +1040,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
     }
 
     // ---- traceback (liblte_phy.cc:10483-10527), the two trellises interleaved: only the decision words are in flight, and what is stored
-    // is the output's sign bit per step, a block's 64 as two words per trellis (a wavefront's store: 512 contiguous bytes)
-    uint4 D[2][2], Dn[2][2];
+    // is the output's sign bit per step, a block's 64 as two words per trellis, next to the code block's other words (perm and vote read a code
+    // block's words as one run).  The lanes' words lie 8 nblk bytes apart, so a lane holds its words back until a 32-byte sector of the array is
+    // complete (four blocks; where in a lane's run the sectors begin depends on the lane) and stores the sector whole: written a word or a block
+    // at a time, every store touched 64 sectors for 4 or 8 bytes each, which the L2 had long written back in part when the next piece came
+    // 2 200 instructions later -- 0.6 ms per step (profiles/r09_variants_sign_planes.txt)
+    typedef uint32_t sign4_t __attribute__((ext_vector_type(4), aligned(8))); // (a lane's words start at a multiple of 8 bytes)
+    uint32_t  stg[2][8] = {}; // [trellis][word of the sector]: the finished words of the sector that block blk lies in
+    uint4     D[2][2], Dn[2][2];
+    // the sign words' addresses are formed here, not next to dec[]: a code block's words have a stride of their own, and the forward pass has no
+    // registers to hold them.  A tile's base is uniform, the lane's words follow from its 32-bit index
+    uint32_t      *sgn[2];
+    const uint32_t sgn_at = (uint32_t)turbo_swar::sign_word_index(lane, nblk, 0);
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-        const uint4 *dp = reinterpret_cast<const uint4 *>(dec[h] + (size_t)(nblk - 1) * 64 * 8);
+        const uint32_t tile = __builtin_amdgcn_readfirstlane(mode ? wv : min(2 * wv + h, n_tiles - 1)); // (a wavefront's tiles: uniform)
+        sgn[h] = args.p[mode ? h : 0].sgn + (seg_off >> 5) + (size_t)tile * nblk * 64 * 2; // the tile's words (8 bytes per step and tile = an eighth of an array's 64)
+        const uint4 *dp = reinterpret_cast<const uint4 *>(dec[h] + (dec_at + (nblk - 1) * 64 * 8));
         D[h][0] = dp[0];
         D[h][1] = dp[1];
     }
@@ -1049,14 +1064,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
         const int prv = blk > 0 ? blk - 1 : 0; // prefetch the block below while this one is traced back
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-            const uint4 *dpn = reinterpret_cast<const uint4 *>(dec[h] + (size_t)prv * 64 * 8);
+            const uint4 *dpn = reinterpret_cast<const uint4 *>(dec[h] + (dec_at + (uint32_t)prv * 64 * 8));
             Dn[h][0] = dpn[0];
             Dn[h][1] = dpn[1];
         }
-        uint32_t sbits[2][2]; // [trellis][word]: steps 32-63, then steps 0-31; a step past the block end leaves a 0 (the groups skipped are the first)
+        // a block's words: steps 32-63, then steps 0-31; a step past the block end leaves a 0 (the groups skipped are the first)
+        const uint32_t slot = (lane * nblk + (uint32_t)blk) & 3u; // the block's 8 bytes within their 32-byte sector of the sign array (a tile begins on one)
+        uint32_t sacc[2][2]; // [trellis][byte pair]: the planes of steps 4 w + (3, 2) and of steps 4 w + (1, 0) of the word being traced
 #pragma unroll
         for (int g = 7; g >= 0; g--) {
-            if ((g & 3) == 3) sbits[0][g >> 2] = sbits[1][g >> 2] = 0;
+            if ((g & 3) == 3) sacc[0][0] = sacc[0][1] = sacc[1][0] = sacc[1][1] = 0;
             if ((uint32_t)blk * 64 + g * 8 < K) {
                 uint32_t word[2];
 #pragma unroll
@@ -1071,14 +1088,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SISO_WPE, 8
                     for (int h = 0; h < 2; h++) {
                         const uint32_t e = tb_lut[((word[h] >> (8 * b)) & 0xFFu) << 3 | (uint32_t)cur[h]];
                         cur[h]           = (int)(e & 7u);
-                        sbits[h][g >> 2]   = __builtin_amdgcn_alignbit(sbits[h][g >> 2], e, 30); // << 2 | the two signs, the later step's on top
+                        sacc[h][b & 1]   = turbo_swar::sign_acc_push(sacc[h][b & 1], e); // << 1 | the two signs, eight bits apart
                     }
+                }
+            }
+            if ((g & 3) == 0) {
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const uint32_t w = turbo_swar::sign_word_join(sacc[h][0], sacc[h][1]);
+#pragma unroll
+                    for (int k = 0; k < 4; k++) stg[h][2 * k + (g >> 2)] = slot == (uint32_t)k ? w : stg[h][2 * k + (g >> 2)]; // (no indexed registers)
+                }
+            }
+        }
+        // a lane's sector is complete when the block traced was its first (slot 0); at the code block's first block what there is leaves too
+        if (slot == 0 || blk == 0) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                uint32_t *sp = sgn[h] + (sgn_at + 2 * (uint32_t)blk); // block blk's words; the sector begins 2 * slot words below
+                if (slot == 0 && (uint32_t)blk + 4 <= nblk) {
+                    *reinterpret_cast<sign4_t *>(sp)     = sign4_t{stg[h][0], stg[h][1], stg[h][2], stg[h][3]};
+                    *reinterpret_cast<sign4_t *>(sp + 4) = sign4_t{stg[h][4], stg[h][5], stg[h][6], stg[h][7]};
+                } else { // the ends of the code block's run: only its own blocks (slot k holds block blk + k - slot), the next lane's words begin behind them
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if ((uint32_t)k >= slot && (uint32_t)blk + k - slot < nblk) *reinterpret_cast<uint2 *>(sp + 2 * k - 2 * slot) = make_uint2(stg[h][2 * k], stg[h][2 * k + 1]);
                 }
             }
         }
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-            *reinterpret_cast<uint2 *>(sgn[h] + (size_t)blk * 64 * 2) = make_uint2(sbits[h][0], sbits[h][1]);
             D[h][0] = Dn[h][0];
             D[h][1] = Dn[h][1];
         }
@@ -1234,13 +1273,13 @@ __global__ __launch_bounds__(64) void k_turbo_siso_small(SisoArgs args, uint32_t
         }
     }
 
-    // ---- traceback (liblte_phy.cc:10483-10527) by function composition, one trellis after the other, lanes = steps: a chunk's 64 signs are one
-    // ballot, which is the block's two sign words as k_turbo_siso writes them
+    // ---- traceback (liblte_phy.cc:10483-10527) by function composition, one trellis after the other, lanes = steps: a chunk's 64 signs, each
+    // fetched by the lane of its bit (turbo_swar.h: sign_plane_lane), are one ballot, which is the block's two sign words as k_turbo_siso writes them
     const uint2 MAP_ID = make_uint2(0x03020100u, 0x07060504u);
     for (uint32_t g = 0; g < n_g; g++) {
         uint32_t       end = (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)(g * 4)); // state after the last step
         const uint32_t cb  = mode ? (T0 + g) >> 1 : T0 + g;
-        uint32_t      *sgn = pass_of(g).sgn + (seg_off >> 5) + ((size_t)(cb >> 6) * n_chunk * 64 + (cb & 63u)) * 2;
+        uint32_t      *sgn = pass_of(g).sgn + (seg_off >> 5) + (size_t)(cb >> 6) * n_chunk * 64 * 2 + turbo_swar::sign_word_index(cb & 63u, n_chunk, 0);
         for (int ch = (int)n_chunk - 1; ch >= 0; ch--) {
             const uint32_t t = (uint32_t)ch * 64 + lane;
             const uint4    w = *reinterpret_cast<const uint4 *>(&decw[(g * n_w32 + (t >> 5)) * 4]);
@@ -1266,8 +1305,8 @@ __global__ __launch_bounds__(64) void k_turbo_siso_small(SisoArgs args, uint32_t
             const uint32_t nxt = lane == 63 ? end : map_at(Gn, end); // state at t + 1
             const uint32_t st  = map_at(G, end);                      // state at t
             const bool     pos = (nxt < st) || (nxt == st && nxt == 0); // "+" when the step moved to a lower state, or stayed in state 0
-            const uint64_t neg = __ballot(t < K && !pos);
-            if (lane == 0) *reinterpret_cast<uint2 *>(sgn + (size_t)ch * 64 * 2) = make_uint2((uint32_t)neg, (uint32_t)(neg >> 32));
+            const uint64_t neg = __ballot(__shfl((int)(t < K && !pos), (int)turbo_swar::sign_plane_lane(lane)) != 0);
+            if (lane == 0) *reinterpret_cast<uint2 *>(sgn + 2 * ch) = make_uint2((uint32_t)neg, (uint32_t)(neg >> 32));
             end = (uint32_t)__builtin_amdgcn_readlane((int)st, 0);
         }
     }
@@ -1285,19 +1324,24 @@ __device__ __forceinline__ UnitWords load_unit_words(const uint8_t *arr, size_t 
     if (u > 0) prev = *reinterpret_cast<const uint32_t *>(arr + unit_off(tile_off, lane, u - 1) + 12);
     return UnitWords{{prev, c.x, c.y, c.z, c.w}};
 }
-// the same for a trellis pass's signed output: the magnitudes (M1 / M2 / M3) joined with the pass's sign bits (SisoPass::sgn)
-__device__ __forceinline__ UnitWords load_unit_joined(const uint8_t *mag, const uint32_t *sgn, size_t tile_off, uint32_t lane, uint32_t u)
+// the same for a trellis pass's signed output: the magnitudes (M1 / M2 / M3) with the pass's sign bits (SisoPass::sgn).  halo: the joined
+// word before the unit, which the re-encoder's delays take; word(j): word j of the unit split (the magnitudes as loaded, the sign bits cleared
+// where the magnitude is 0), formed where it is used: a shift and a mask from x, the unit's half of its sign word.
+// A thread reads its unit's sign word (two units share one) and, for the halo of an even unit, the word before it.
+struct UnitSigned {
+    uint32_t halo, m[4], x;
+    __device__ __forceinline__ sw::SM4 word(int j) const { return sw::SM4{m[j], sw::signed_under(m[j], x, j)}; }
+};
+__device__ __forceinline__ UnitSigned load_unit_signed(const uint8_t *mag, const uint32_t *sgn, size_t tile_off, uint32_t lane, uint32_t nblk, uint32_t u)
 {
-    UnitWords      w = load_unit_words(mag, tile_off, lane, u);
-    const uint32_t *sp = sgn + (tile_off >> 5) + ((size_t)(u >> 2) * 64 + lane) * 2; // [tile][blk][lane][2 words]
-    const uint2    c = *reinterpret_cast<const uint2 *>(sp);
-    uint32_t       ph = 0;
-    if ((u & 3u) == 0 && u > 0) ph = sp[1 - 128]; // the halo's signs: the last four steps of the block before
-    const uint32_t b = sw::unit_sign_bits(c.x, c.y, ph, u);
-    if (u > 0) w.w[0] = sw::joined_from_bits(w.w[0], b & 15u);
-#pragma unroll
-    for (int j = 0; j < 4; j++) w.w[j + 1] = sw::joined_from_bits(w.w[j + 1], (b >> (4 * j + 4)) & 15u);
-    return w;
+    const UnitWords w  = load_unit_words(mag, tile_off, lane, u);
+    const uint32_t *sp = sgn + (tile_off >> 5) + sw::sign_word_index(lane, nblk, u >> 1);
+    const uint32_t  S = sp[0];
+    uint32_t        Sb = 0;
+    if ((u & 1u) == 0 && u > 0) Sb = sp[-1];
+    UnitSigned r{w.w[0], {w.w[1], w.w[2], w.w[3], w.w[4]}, sw::sign_unit(S, u)};
+    if (u > 0) r.halo |= sw::signed_under_flags(r.halo, sw::sign_halo(S, Sb, u));
+    return r;
 }
 // ------------------------------------------------------------------------------------------------
 // perm: Steps 2, 3, 5 and the pass-3 output magnitudes.  One workgroup per code block.
@@ -1353,14 +1397,14 @@ __global__ __launch_bounds__(384) void k_turbo_perm(PermArgs a, uint32_t K_arg, 
         asm volatile("" : "+v"(u), "+v"(praw.lo.x), "+v"(praw.lo.y), "+v"(praw.lo.z), "+v"(praw.lo.w), "+v"(praw.hi.x), "+v"(praw.hi.y), "+v"(praw.hi.z), "+v"(praw.hi.w));
         uint4          X2 = make_uint4(0, 0, 0, 0);
         if (nv >= 0) {
-            const UnitWords wa = load_unit_joined(a.M1, a.S1, tile_off, lane, u);
-            uint32_t        pa = wa.w[0];
+            const UnitSigned ua = load_unit_signed(a.M1, a.S1, tile_off, lane, n_units >> 2, u);
+            uint32_t         pa = ua.halo;
             X2 = *reinterpret_cast<const uint4 *>(a.X2 + unit_off(tile_off, lane, u));
             uint32_t c1[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) { // Steps 2-3, four positions per instruction; 0 past the block end
-                const uint32_t ja = wa.w[j + 1];
-                const sw::SM4  A  = sw::unjoin(ja);
+                const sw::SM4  A  = ua.word(j);
+                const uint32_t ja = sw::join(A);
                 c1[j] = (4 * j < nv) ? sw::to_tc(sw::step3(A, sw::feedback(ja, pa))) : 0u; // two's complement again: pass 3 reads it
                 pa    = ja;
             }
@@ -1439,9 +1483,9 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     v2s            s0e[4], s0o[4]; // s0 = q(d0) + C1, the part of the vote that is not de-interleaved
     if (threadIdx.x == 0) *reinterpret_cast<uint32_t *>(d12 + 2 * Kp) = 0u; // what a hole of the de-interleaver reads
     if (nv >= 0) {
-        const UnitWords wa = load_unit_joined(a.M1, a.S1, tile_off, lane, u), wb = load_unit_joined(a.M2, a.S2, tile_off, lane, u),
-                        wc = load_unit_joined(a.M3, a.S3, tile_off, lane, u);
-        uint32_t        pa = wa.w[0], pb = wb.w[0], pc = wc.w[0];
+        const UnitSigned ua = load_unit_signed(a.M1, a.S1, tile_off, lane, n_units >> 2, u), ub = load_unit_signed(a.M2, a.S2, tile_off, lane, n_units >> 2, u),
+                         uc = load_unit_signed(a.M3, a.S3, tile_off, lane, n_units >> 2, u);
+        uint32_t        pa = ua.halo, pb = ub.halo, pc = uc.halo;
         const uint4    x0 = *reinterpret_cast<const uint4 *>(a.X0 + unit_off(tile_off, lane, u));
         const uint32_t x0w[4] = {x0.x, x0.y, x0.z, x0.w};
         uint32_t       dn[8]; // D1 + D2 of the unit in natural order, two int16 per word
@@ -1449,8 +1493,8 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         for (int j = 0; j < 4; j++) {
             // sign-magnitude bytes, four positions per instruction (turbo_swar.h); only the two nine-bit sums are formed in int16 pairs,
             // from biased bytes: even pairs (positions 0, 2), odd pairs (1, 3)
-            const uint32_t ja = wa.w[j + 1], jb = wb.w[j + 1], jc = wc.w[j + 1];
-            const sw::SM4  A = sw::unjoin(ja), B = sw::unjoin(jb), B_ = sw::unjoin(jc);
+            const sw::SM4  A = ua.word(j), B = ub.word(j), B_ = uc.word(j);
+            const uint32_t ja = sw::join(A), jb = sw::join(B), jc = sw::join(B_);
             const sw::SM4  F  = sw::feedback(ja, pa);
             const sw::SM4  G  = sw::feedback(jb, pb); // G  = soft_xor(B1[k-2], B1[k-3])
             const sw::SM4  G_ = sw::feedback(jc, pc); // G' = soft_xor(B2[k-2], B2[k-3])

@@ -11,6 +11,7 @@
 // scalar restatement of the reference's case ladders, exhaustively where the domain allows).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 #ifdef __HIPCC__
@@ -56,21 +57,52 @@ SWAR_FN uint32_t to_joined(uint32_t w)
     const uint32_t s = w & HI, t = s >> 7;
     return (w ^ (s - t)) + t;
 }
-// magnitudes (<= 127) and a mask with 0xFF in the negative bytes -> joined bytes, the sign bit cleared where the magnitude is 0: what
-// the trellis kernels' traceback writes
+// magnitudes (<= 127) and a mask with 0xFF in the negative bytes -> joined bytes, the sign bit cleared where the magnitude is 0: the
+// byte form of what the sign words below carry
 SWAR_FN uint32_t joined_from(uint32_t m, uint32_t neg_mask) { return m | (neg_mask & (m + LO7) & HI); }
-// the same from four sign BITS (bit i set: byte i is negative; bits 4 and up clear): what the trellis kernels' traceback writes now, one bit
-// per step, and perm and vote expand.  The product puts bit i at bit 8i + 7; its other fifteen partial products land on distinct bits below
-// bit 7 of some byte (14 21 28 | 8 22 29 | 9 16 30 | 10 17 24), so nothing carries and the mask removes them
-SWAR_FN uint32_t joined_from_bits(uint32_t m, uint32_t nib) { return m | ((nib * 0x10204080u) & (m + LO7) & HI); }
-// The sixteen sign bits of unit u (steps 16u .. 16u + 15, bit k = step 16u + k) behind the four of the steps before it (bits 0-3: the halo,
-// whose joined form the re-encoder's delays need) out of the trellis kernels' sign words: c = the two words of the unit's 64-step block,
-// prev_hi = the second word of the block before (read only where u % 4 == 0; the first unit's halo is the preset, not a sign)
-SWAR_FN uint32_t unit_sign_bits(uint32_t c_lo, uint32_t c_hi, uint32_t prev_hi, uint32_t u)
+
+// ---- The trellis kernels' sign words (turbo.hip: SisoPass::sgn): the one definition of their layout.
+// One bit per trellis step, set where the path's output is negative (whatever its magnitude), 0 for a step past the block end.
+//   * Per code block, contiguous: [tile][lane][word], word = step t >> 5, 2 * nblk words per lane (nblk = kpad64(K) >> 6 blocks of 64 steps).
+//     A tile takes nblk * 64 * 2 words: sign_word_index() from the tile's base, which is the magnitude arrays' tile offset >> 5.
+//   * By plane inside a word: word S covers steps 32 s .. 32 s + 31, and step 32 s + 4 w + b (w = 0..7: the group of four steps that is one
+//     byte word of the magnitude arrays, b = 0..3: the byte in it) is bit 8 b + w (sign_plane_bit).  The bit-7 flags of magnitude word
+//     g = t / 4 are then ((S[g >> 3] >> (g & 7)) & ONES) << 7: a shift and a mask (sign_flags).
+//   * A unit's halo (steps 16 u - 4 .. 16 u - 1: magnitude word 4 u - 1) is in the unit's own sign word for odd u and in the word before
+//     it for even u > 0; the first unit's halo is the re-encoder's preset, not a sign.
+SWAR_FN uint32_t sign_plane_bit(uint32_t t) { return 8u * (t & 3u) + ((t >> 2) & 7u); }  // step t % 32 -> its bit
+SWAR_FN uint32_t sign_plane_step(uint32_t p) { return 4u * (p & 7u) + ((p >> 3) & 3u); } // bit p -> its step % 32 (the inverse)
+SWAR_FN size_t   sign_word_index(uint32_t lane, uint32_t nblk, uint32_t word) { return (size_t)lane * 2u * nblk + word; }
+SWAR_FN uint32_t sign_flags(uint32_t S, uint32_t g) { return ((S >> (g & 7u)) & ONES) << 7; }
+// The expansion perm and vote run per unit: x = sign_unit(S, u) once, then word j = 0..3 of the unit takes its flags with one shift and
+// the mask that also removes "-0": signed_under(m, x, j) = the sign bits of the bytes of m (magnitudes, bit 7 clear) that are negative
+// and not 0 -- SM4{m, that} is the word split, m | that the joined word.  signed_under_flags is the same from bit-7 flags (the halo).
+SWAR_FN uint32_t sign_unit(uint32_t S, uint32_t u) { return S >> (4u * (u & 1u)); }
+SWAR_FN uint32_t signed_under_flags(uint32_t m, uint32_t flags) { return flags & (m + LO7) & HI; }
+SWAR_FN uint32_t signed_under(uint32_t m, uint32_t x, int j) { return signed_under_flags(m, x << (7 - j)); }
+// the flags of a unit's halo word: bit 3 of every plane of its own word (odd u), bit 7 of the word before (even u > 0)
+SWAR_FN uint32_t sign_halo(uint32_t S, uint32_t S_before, uint32_t u) { return (u & 1u) ? S << 4 : S_before; }
+// Packing, the lock-step kernel's way: traceback_entry (below) carries the signs of its two steps -- steps 4 w + b of one w, b = (3, 2) or
+// (1, 0) -- in bits 24 and 16, eight apart like their planes.  A 32-step word is traced back from w = 7 down to 0, so one accumulator per
+// byte pair takes its eight entries by (acc << 1) | entry: the planes end in bits 16-31 (the entries' state bits stay below bit 10), and
+// the two accumulators are joined once per word.
+SWAR_FN uint32_t sign_acc_push(uint32_t acc, uint32_t entry) { return (acc << 1) | entry; }
+SWAR_FN uint32_t sign_word_join(uint32_t acc32, uint32_t acc10)
 {
-    const uint32_t q = u & 3u;
-    const uint64_t c = ((uint64_t)c_hi << 32) | c_lo;
-    return q ? (uint32_t)(c >> (16u * q - 4u)) & 0xFFFFFu : (c_lo & 0xFFFFu) << 4 | prev_hi >> 28;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(acc32, acc10, 0x07060302u);
+#else
+    return (acc32 & 0xFFFF0000u) | (acc10 >> 16);
+#endif
+}
+// ... and the state-parallel kernel's way: from the 64 signs of a block in step order (a ballot, lanes = steps): bit p of word h is step
+// 32 h + sign_plane_step(p).  On the device lane L fetches the flag of lane sign_plane_lane(L) and the ballot is taken again.
+SWAR_FN uint32_t sign_plane_lane(uint32_t L) { return (L & 32u) | sign_plane_step(L & 31u); }
+SWAR_FN uint32_t sign_word_from_steps(uint64_t steps, uint32_t h)
+{
+    uint32_t S = 0;
+    for (uint32_t p = 0; p < 32; p++) S |= (uint32_t)((steps >> sign_plane_lane(32u * h + p)) & 1u) << p;
+    return S;
 }
 SWAR_FN SM4 unjoin(uint32_t j) { return SM4{j & LO7, j & HI}; }
 SWAR_FN SM4 split(uint32_t w) { return unjoin(to_joined(w)); }
@@ -149,8 +181,8 @@ SWAR_FN uint32_t step11_neg_biased(const SM4 &B, const SM4 &G)
 
 // One entry of the trellis kernels' traceback table: two steps of the reference's traceback (liblte_phy.cc:10483-10527) from state `cur`,
 // `byte` = the stored compare bits of the two steps, the step traced first (the later one) in the low nibble.  Bits 0-2: the state after
-// both; bit 31: the first-traced step's output is negative, bit 30: the second's -- alignbit(acc, entry, 30) appends them to a sign word
-// in step order.
+// both; bit 24: the first-traced step's output is negative, bit 16: the second's -- sign_acc_push appends them to the two planes of a
+// sign word's byte pair.
 SWAR_FN uint32_t traceback_entry(uint32_t byte, uint32_t cur)
 {
     uint32_t sgn = 0;
@@ -158,7 +190,7 @@ SWAR_FN uint32_t traceback_entry(uint32_t byte, uint32_t cur)
         const uint32_t nib = k ? byte >> 4 : byte & 15u;
         const uint32_t j = cur & 3u, bit = (nib >> (3 - j)) & 1u, st = 2 * j + bit; // pair j is bit (3-j) of the nibble
         const bool     pos = (cur < st) || (cur == st && cur == 0); // "+" when the step moved to a lower state, or stayed in state 0
-        if (!pos) sgn |= k ? 1u << 30 : 1u << 31;
+        if (!pos) sgn |= k ? 1u << 16 : 1u << 24;
         cur = st;
     }
     return cur | sgn;

@@ -1,6 +1,6 @@
 #!/bin/bash
-# tools/asan/run_turbo_signs.sh: the sign-bit hand-over of the turbo trellis kernels (openlte_amd/csrc/turbo_swar.h: joined_from_bits, unit_sign_bits,
-# traceback_entry) built with g++ -fsanitize=address,undefined and checked against the byte form it replaces (turbo_signs_driver.cc).  CPU only.
+# tools/asan/run_turbo_signs.sh: the sign-bit hand-over of the turbo trellis kernels (openlte_amd/csrc/turbo_swar.h: the sign words'
+# layout and helpers, traceback_entry) built with g++ -fsanitize=address,undefined and checked against the byte form it replaces (turbo_signs_driver.cc).  CPU only.
 set -e
 cd "$(dirname "$0")/../.."
 OUT=${TMPDIR:-/tmp}/mi_lte_asan_turbo_signs
