@@ -202,7 +202,12 @@ uint32_t mi_lte_pdsch_plan_out_stride(const mi_lte_pdsch_plan *plan);
 int      mi_lte_pdsch_decode_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *plan, const float *d_subframes,
                                  const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell, uint8_t *d_out_bits,
                                  int32_t *d_status);
-/* stage tap: device pointers to the descrambled soft bits (int8) of one allocation and to their count */
+/* stage tap: device pointers to the descrambled soft bits (int8) of one allocation and to their count.
+ * Always bytes.  Where the last run handed its 16QAM / 64QAM soft bits to the decoder as bits (mi_lte_set_soft_packed), the FIRST tap after
+ * that run enqueues one kernel on the stream of the context that ran the plan, which turns every such allocation's slot into bytes in place
+ * (zeros from e_len to the next 16-byte boundary); later taps before the next run only return pointers.  So read the pointers on that stream,
+ * or after waiting for it, as for the run itself; the context must still exist.  The next run overwrites the slots, and a re-assignment of a
+ * dynamic plan voids them. */
 int      mi_lte_pdsch_plan_soft_bits(const mi_lte_pdsch_plan *plan, uint32_t alloc, const int8_t **d_e,
                                      const uint32_t **d_len);
 
@@ -399,6 +404,12 @@ int mi_lte_set_turbo_small_batch(mi_lte_ctx *ctx, uint32_t n_cb_max);
  * (the per-code-block kernels once per workgroup width) instead of size by size; on = 0 keeps the per-size launches.  Identical results
  * (tests/test_mixed_gpu.py); a test / tuning knob like the one above.  Default on. */
 int mi_lte_set_turbo_merged(mi_lte_ctx *ctx, uint32_t on);
+/* A PDSCH plan run with the reference-faithful demapper and MI_LTE_TURBO_REF hands its 16QAM / 64QAM soft bits -- each exactly +127 or -127 --
+ * from the demodulator to the decoder as one BIT per soft bit instead of one byte (an eighth of that array's traffic); BPSK / QPSK allocations,
+ * the BCJR decoders, the 3GPP mode and PUSCH plans keep bytes.  on = 0 keeps bytes everywhere.  Identical results (tests/test_soft_pack_gpu.py),
+ * and mi_lte_pdsch_plan_soft_bits returns bytes either way.  Default on; MI_LTE_NO_SOFT_PACK=1 in the environment makes every context of the
+ * process start with it off.  A test / tuning knob like the two above. */
+int mi_lte_set_soft_packed(mi_lte_ctx *ctx, uint32_t on);
 
 /* ---------------------------------------------------------------- turbo rate un-matching
  * Replaces liblte_phy_rate_unmatch_turbo() (liblte/hdr/liblte_phy.h:1311-1323, implementation

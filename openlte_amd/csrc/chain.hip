@@ -11,6 +11,7 @@
 #include "plan_core.hpp"
 #include "phy_dev.hpp"
 #include "demap_llr.h"
+#include "soft_pack.h"
 
 namespace {
 
@@ -98,9 +99,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
                                                      const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell,
                                                      GoldTables gt, int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off,
                                                      uint32_t *__restrict__ e_len, uint32_t max_pairs, uint32_t max_words,
-                                                     uint32_t e_lds_cap)
+                                                     uint32_t e_lds_cap, uint32_t pack)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // tab[max_pairs+1] (offset, mask | position) | cw[...] | soft bits
+    extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // tab[max_pairs+1] (offset, mask | position) | cw[...] | soft bits (packed hand-over: one mask byte per symbol)
     __shared__ uint2 qam_lut[64]; // hard-decision mask -> six soft bits (16QAM / 64QAM)
     const uint32_t a_idx = blockIdx.x;
     const mi_lte_pdsch_alloc &al = allocs[a_idx];
@@ -156,9 +157,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
     // soft bits are assembled in LDS when they fit and leave with 16-byte stores
     int8_t    *e_lds  = reinterpret_cast<int8_t *>(cw + max_words);
     const bool via_lds = N_bits <= e_lds_cap;
-    auto run = [&](auto modc) {
+    // the packed hand-over (soft_pack.h): a 16QAM / 64QAM allocation leaves as one bit per soft bit.  Its symbols' masks are collected in LDS,
+    // one byte per symbol (at most 15 600 of them: the host sizes the block for it), and packed after the barrier below
+    const bool pk = pack && al.mod_type >= 2;
+    auto run = [&](auto modc, auto pkc) {
     constexpr uint32_t MOD = decltype(modc)::value, QM = MOD == 3 ? 6 : MOD == 2 ? 4 : MOD == 1 ? 2 : 1;
-    constexpr bool     QAM = MOD >= 2;
+    constexpr bool     QAM = MOD >= 2, PK = decltype(pkc)::value;
+    static_assert(QAM || !PK, "only hard-decision modulations are packed");
+    auto each_dst = [&](auto f) { // where the symbols' soft bits go: the LDS block, or the allocation's slot itself when they do not fit
+        if constexpr (PK) f(e_lds);
+        else if (via_lds) f(e_lds);
+        else f(e);
+    };
     // descramble + store the Q_m soft bits of symbol idx: c bit set -> negate (liblte_phy.cc:3833-3836).
     // Q_m*idx is even for Q_m >= 2, so pairs of bytes leave as one 16-bit store.
     auto put_bits = [&](auto *dst, uint32_t idx, const int8_t (&b)[6]) {
@@ -189,8 +199,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
     };
     // equalised symbol (nr, ni) / den -> soft bits of RE idx.  16QAM / 64QAM: the decisions without the divisions (qam_neg_bits_nodiv:
     // the reference's own divisions under a guard next to the thresholds); BPSK / QPSK grade the quotient, so they divide.
+    // the packed hand-over's: the XORed mask itself, one byte per symbol
+    auto put_mask = [&](auto *dst, uint32_t idx, uint32_t neg) {
+        const uint32_t n0 = QM == 4 ? idx << 2 : __umul24(idx, 6u), w = n0 >> 5, sh = n0 & 31;
+        const uint32_t c  = __builtin_amdgcn_alignbit(cw[w + 1], cw[w], sh);
+        reinterpret_cast<uint8_t *>(dst)[idx] = (uint8_t)((neg ^ c) & (QM == 4 ? 15u : 63u));
+    };
     auto put_symbol = [&](auto *dst, uint32_t idx, float nr, float ni, float den) {
-        if constexpr (QAM) put_qam(dst, idx, qam_neg_bits_nodiv<MOD>(nr, ni, den));
+        if constexpr (PK) put_mask(dst, idx, qam_neg_bits_nodiv<MOD>(nr, ni, den));
+        else if constexpr (QAM) put_qam(dst, idx, qam_neg_bits_nodiv<MOD>(nr, ni, den));
         else {
             int8_t b[6] = {0, 0, 0, 0, 0, 0};
             demap_symbol<true>(nr / den, ni / den, MOD, b);
@@ -255,7 +272,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
                 }
             }
         };
-        if (via_lds) body(e_lds); else body(e);
+        each_dst(body);
     } else if (ONE_PORT) { // one RE = one symbol (liblte_phy.cc:7684-7690): thread per (PRB-symbol pair, sub-carrier), no search
         constexpr int UNR = 4; // loads of UNR independent REs in flight per thread (the kernel is latency-bound otherwise)
         // 21 pairs x 12 sub-carriers per sweep of the workgroup: a thread keeps its sub-carrier, so nothing is divided in the loop
@@ -287,7 +304,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
                 }
             }
         };
-        if (via_lds) body(e_lds); else body(e);
+        each_dst(body);
     } else
     for (uint32_t i = threadIdx.x; i < n_grp; i += blockDim.x) {
         float n_re[4], n_im[4], den[4]; // x_p = (n_re, n_im) / den
@@ -322,19 +339,47 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
             n_im[3] = -(-h3r * y2i + h3i * y2r - h1r * y3i + h1i * y3r);
         }
         // layer de-mapping d[i*N_ant + p] = x_p[i] (liblte_phy.cc:7506-7513), de-map, descramble (:3833-3836)
-        for (uint32_t p = 0; p < N_ant; p++) {
-            if (via_lds) put_symbol(e_lds, i * N_ant + p, n_re[p], n_im[p], den[p]);
-            else         put_symbol(e, i * N_ant + p, n_re[p], n_im[p], den[p]);
+#pragma unroll
+        for (uint32_t p = 0; p < 4; p++) {
+            if (p >= N_ant) break;
+            if (PK || via_lds) put_symbol(e_lds, i * N_ant + p, n_re[p], n_im[p], den[p]);
+            else               put_symbol(e, i * N_ant + p, n_re[p], n_im[p], den[p]);
         }
     }
     };
     switch (al.mod_type) {
-    case 0:  run(std::integral_constant<uint32_t, 0>{}); break;
-    case 1:  run(std::integral_constant<uint32_t, 1>{}); break;
-    case 2:  run(std::integral_constant<uint32_t, 2>{}); break;
-    default: run(std::integral_constant<uint32_t, 3>{}); break;
+    case 0:  run(std::integral_constant<uint32_t, 0>{}, std::false_type{}); break;
+    case 1:  run(std::integral_constant<uint32_t, 1>{}, std::false_type{}); break;
+    case 2:  if (pk) run(std::integral_constant<uint32_t, 2>{}, std::true_type{}); else run(std::integral_constant<uint32_t, 2>{}, std::false_type{}); break;
+    default: if (pk) run(std::integral_constant<uint32_t, 3>{}, std::true_type{}); else run(std::integral_constant<uint32_t, 3>{}, std::false_type{}); break;
     }
-    if (via_lds) {
+    if (pk) {
+        // sixteen symbols' masks -> two (16QAM) or three (64QAM) dwords per thread: every dword of the slot is written by exactly one thread,
+        // none behind the last one, and the last one's bits from N_bits on are 0 (soft_pack16 drops the masks past the last symbol)
+        __syncthreads();
+        const uint32_t nd = (N_bits + 31) >> 5, ng = (M_symb + 15) >> 4;
+        uint32_t      *eo = reinterpret_cast<uint32_t *>(e);
+        for (uint32_t gi = threadIdx.x; gi < ng; gi += blockDim.x) {
+            const uint4    m4 = reinterpret_cast<const uint4 *>(e_lds)[gi];
+            const uint32_t m[4] = {m4.x, m4.y, m4.z, m4.w}, nv = min(16u, M_symb - 16 * gi);
+            if (Qm == 4) {
+                uint32_t o[2];
+                soft_pack16<4>(m, nv, o);
+                const uint32_t d0 = 2 * gi;
+                if (d0 + 2 <= nd) *reinterpret_cast<uint2 *>(eo + d0) = make_uint2(o[0], o[1]); // (8-byte aligned: the slot starts on a 64-byte line)
+                else eo[d0] = o[0];
+            } else {
+                uint32_t o[3];
+                soft_pack16<6>(m, nv, o);
+                const uint32_t d0 = 3 * gi;
+                if (d0 + 3 <= nd) { eo[d0] = o[0]; eo[d0 + 1] = o[1]; eo[d0 + 2] = o[2]; } // (twelve bytes on a 4-byte boundary: one three-dword store)
+                else {
+                    eo[d0] = o[0];
+                    if (d0 + 1 < nd) eo[d0 + 1] = o[1];
+                }
+            }
+        }
+    } else if (via_lds) {
         __syncthreads();
         const uint32_t nq = (N_bits + 15) >> 4; // the allocation's slot in e_base is padded to 64 bytes
         for (uint32_t w = threadIdx.x; w < nq; w += blockDim.x) reinterpret_cast<uint4 *>(e)[w] = reinterpret_cast<const uint4 *>(e_lds)[w];
@@ -471,6 +516,25 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict
         per_mod(e);
 }
 
+// The stage tap after a run with the packed hand-over (mi_lte_pdsch_plan_soft_bits): one workgroup per allocation turns a packed slot back into
+// the byte form IN PLACE -- all of the allocation's dwords into LDS, a barrier, then the bytes (zeros behind e_len up to the next 16 bytes).
+__global__ __launch_bounds__(256) void k_soft_expand(const mi_lte_pdsch_alloc *__restrict__ allocs, int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off,
+                                                     const uint32_t *__restrict__ e_len, uint32_t max_words)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // [max_words] the allocation's dwords
+    const uint32_t a_idx = blockIdx.x;
+    if (allocs[a_idx].mod_type < 2) return; // (uniform) bytes already
+    const uint32_t E = e_len[a_idx], nd = min((E + 31) >> 5, max_words), nq = min((E + 15) >> 4, 2 * max_words);
+    int8_t *e = e_base + (size_t)e_off[a_idx] * 64;
+    for (uint32_t w = threadIdx.x; w < nd; w += blockDim.x) smu[w] = reinterpret_cast<const uint32_t *>(e)[w];
+    __syncthreads();
+    for (uint32_t q = threadIdx.x; q < nq; q += blockDim.x) {
+        uint32_t w[4];
+        soft_stage_quad(smu, q, min(16u, E - 16 * q), w);
+        reinterpret_cast<uint4 *>(e)[q] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
 } // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -495,6 +559,12 @@ struct mi_lte_pdsch_plan {
     MiDlsch3   *g3 = nullptr; // 3GPP transport-block mode (mi_lte_pdsch_plan_create_3gpp): its code blocks and buffers (dlsch3gpp.hip)
     uint32_t    demap = MI_LTE_DEMAP_REF; // mi_lte_pdsch_plan_set_demapper (3GPP mode)
     float       demap_gain = 0.0f, *d_llr_gain = nullptr; // MAXLOG: the fixed gain (0: automatic); [n_alloc] the gain of the last run (3GPP plans)
+    // the packed hand-over (soft_pack.h): what the demodulator's LDS block must hold -- the soft bits of the longest allocation that stays
+    // bytes (BPSK / QPSK, in words) and the symbols of the longest 16QAM / 64QAM one -- and the stage tap's debt: the context of the last run and whether
+    // its 16QAM / 64QAM slots still hold bits (mi_lte_pdsch_plan_soft_bits expands them once; a re-assignment voids them)
+    uint32_t            max_words_lo = 0, max_symb_hi = 0;
+    mutable mi_lte_ctx *tap_ctx = nullptr;
+    mutable bool        tap_packed = false;
 };
 
 static void plan_set_stride(mi_lte_pdsch_plan *pl)
@@ -515,7 +585,8 @@ static int plan_layout(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t N_pdcch_
     const mi_lte_dl_cfg *cfg = &pl->cfg;
     pl->cfi          = N_pdcch_symbs;
     pl->core.n_alloc = n_alloc;
-    pl->max_pairs = pl->max_words = pl->max_tbs = 0;
+    pl->max_pairs = pl->max_words = pl->max_tbs = pl->max_words_lo = pl->max_symb_hi = 0;
+    pl->tap_packed = false; // (the slots move: what a last run left in them is no allocation's any more)
     pl->core.groups.clear();
     for (uint32_t a = 0; a < n_alloc; a++) {
         const mi_lte_pdsch_alloc &al = h_allocs[a];
@@ -538,6 +609,8 @@ static int plan_layout(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t N_pdcch_
         const uint32_t pairs = (14 - cfi) * al.N_prb, e_max = pairs * 12 * Qm;
         pl->max_pairs = std::max(pl->max_pairs, 14 * al.N_prb); // the demodulator's pair table spans all 14 symbols
         pl->max_words = std::max(pl->max_words, (e_max + 31) / 32);
+        if (al.mod_type >= 2) pl->max_symb_hi = std::max(pl->max_symb_hi, pairs * 12);
+        else pl->max_words_lo = std::max(pl->max_words_lo, (e_max + 31) / 32);
         e_bits[a]     = e_max;
     }
     if (pl->max_words > 4095) { // the demodulator reads one word past the allocation's last scrambling word
@@ -804,6 +877,14 @@ int mi_lte_model_atan2f(const float *h_y, const float *h_x, float *h_out, size_t
 int mi_lte_pdsch_plan_soft_bits(const mi_lte_pdsch_plan *pl, uint32_t alloc, const int8_t **d_e, const uint32_t **d_len)
 {
     if (!pl || alloc >= pl->core.n_alloc || !d_e || !d_len) return MI_LTE_ERR_INVALID_ARG;
+    if (pl->tap_packed) { // the last run handed its 16QAM / 64QAM soft bits over as bits: the first tap after it turns them into bytes, once
+        mi_lte_ctx *ctx = pl->tap_ctx;
+        MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        hipLaunchKernelGGL(k_soft_expand, dim3(pl->core.n_alloc), dim3(256), sizeof(uint32_t) * (pl->max_words + 4u), ctx->stream, pl->core.d_allocs, pl->core.d_e,
+                           pl->core.d_e_off, pl->core.d_e_len, pl->max_words);
+        MI_HIP_CHECK(ctx, hipGetLastError());
+        pl->tap_packed = false;
+    }
     *d_e   = pl->core.d_e + (size_t)pl->core.h_e_off[alloc] * 64;
     *d_len = pl->core.d_e_len + alloc;
     return MI_LTE_OK;
@@ -847,7 +928,8 @@ int mi_lte_pdsch_plan_set_output(mi_lte_pdsch_plan *pl, uint32_t packed)
 } // extern "C"
 
 // the plan's demodulator: every allocation's descrambled soft bits and their count
-static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell)
+// pack: 16QAM / 64QAM allocations leave as bits (soft_pack.h; pdsch_run decides per run)
+static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell, bool pack)
 {
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     int rc = mi_ctx_gold_tables(ctx);
@@ -855,10 +937,12 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
     DemodGeom  g{pl->cfg.N_rb_dl, pl->cfg.N_ant, pl->cfi, (uint32_t)mi_lte_subframe_floats(pl->cfg.N_ant)};
     GoldTables gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
     // LDS: pair table | scrambling words | (when it fits in 32 KiB) the allocation's soft bits
-    const uint32_t words_al = (pl->max_words + 1u + 3u) & ~3u, e_bytes = (pl->max_words * 32 + 63u) & ~63u;
+    // A packed run: only the allocations that stay bytes count for e_cap, and a packed allocation's symbol masks (one byte each, at most 15 600: 100
+    // resource blocks, 13 symbols) ALWAYS go through the block -- a long QPSK allocation next to them still finds its own rule (e_cap = 0: direct)
+    const uint32_t words_al = (pl->max_words + 1u + 3u) & ~3u, e_bytes = ((pack ? pl->max_words_lo : pl->max_words) * 32 + 63u) & ~63u;
     const uint32_t e_cap = (e_bytes <= 32 * 1024) ? e_bytes : 0;
     const uint32_t pairs_al = ((2 * (pl->max_pairs + 1) + 3u) & ~3u);
-    const size_t lds = sizeof(uint32_t) * ((size_t)pairs_al + words_al) + e_cap;
+    const size_t lds = sizeof(uint32_t) * ((size_t)pairs_al + words_al) + std::max(e_cap, pack ? (pl->max_symb_hi + 15u) & ~15u : 0u);
     uint32_t threads = 256;
     if (const char *ev = getenv("MI_LTE_PDSCH_THREADS")) { // (tuning aid)
         const int t = atoi(ev);
@@ -866,7 +950,7 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
     }
     auto launch = [&](auto kernel) {
         MI_LAUNCH(ctx, "k_pdsch_demod", kernel, dim3(pl->core.n_alloc), dim3(threads), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt,
-                  pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap);
+                  pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pack ? 1u : 0u);
     };
     if (pl->demap == MI_LTE_DEMAP_MAXLOG) { // (a single-port 3GPP plan on full estimate planes: mi_lte_pdsch_plan_set_demapper)
         float auto_t = (float)MI_LTE_DEMAP_AUTO_T;
@@ -895,8 +979,14 @@ static int pdsch_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *p
         if ((rc = mi_dlsch3_harq_check(ctx, pl->g3, pool, h_bind)) != MI_LTE_OK) return rc;
     }
     if (pl->core.n_alloc == 0) { ctx->err = "the dynamic plan holds no allocations (mi_lte_pdsch_plan_assign)"; return MI_LTE_ERR_INVALID_ARG; }
-    if ((rc = pdsch_demod(ctx, pl, d_subframes, d_subfr_num, d_n_id_cell)) != MI_LTE_OK) return rc;
-    const MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/false);
+    // The packed hand-over (soft_pack.h), decided per run -- the decoder may change between two of them: only where the soft bits go to
+    // mi_turbo_ref_dispatch and nowhere else.  The BCJR decoders, the 3GPP mode (HARQ and the max-log demapper with it) keep bytes.
+    // Nor does a run one of whose block-size groups would be gathered straight from global memory (mi_turbo_ref_reads_packed).
+    bool pack = ctx->soft_packed && !pl->g3 && !mi_is_bcjr(pl->decoder) && pl->demap == MI_LTE_DEMAP_REF;
+    for (const MiKGroup &gr : pl->core.groups) pack = pack && turbo_geom::mi_turbo_ref_reads_packed(gr.K, gr.e_max);
+    if ((rc = pdsch_demod(ctx, pl, d_subframes, d_subfr_num, d_n_id_cell, pack)) != MI_LTE_OK) return rc;
+    pl->tap_ctx = ctx; pl->tap_packed = pack; // what the slots hold from here on (mi_lte_pdsch_plan_soft_bits)
+    const MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/false, pack);
     if (pl->g3) {
         rc = mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter);
         if (rc == MI_LTE_OK && pl->demap == MI_LTE_DEMAP_MAXLOG) ctx->last_kernels.replace(0, strlen("k_pdsch_demod"), "k_pdsch_demod_llr");

@@ -39,6 +39,8 @@ int mi_lte_ctx_create(int device, mi_lte_ctx **out)
     // MI_LTE_NO_MERGED_DECODE=1: every context starts with the per-size launches (mi_lte_set_turbo_merged; the only way to reach the host
     // pipeline's own contexts)
     if (const char *e = getenv("MI_LTE_NO_MERGED_DECODE")) ctx->merged_decode = atoi(e) == 0;
+    // MI_LTE_NO_SOFT_PACK=1: every context starts with the byte hand-over between PDSCH demodulation and the REF decoder (mi_lte_set_soft_packed)
+    if (const char *e = getenv("MI_LTE_NO_SOFT_PACK")) ctx->soft_packed = atoi(e) == 0;
     hipDeviceProp_t prop;
     if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) {
         delete ctx;
@@ -90,6 +92,13 @@ int mi_lte_set_turbo_merged(mi_lte_ctx *ctx, uint32_t on)
 {
     if (!ctx) return MI_LTE_ERR_INVALID_ARG;
     ctx->merged_decode = on != 0;
+    return MI_LTE_OK;
+}
+
+int mi_lte_set_soft_packed(mi_lte_ctx *ctx, uint32_t on)
+{
+    if (!ctx) return MI_LTE_ERR_INVALID_ARG;
+    ctx->soft_packed = on != 0;
     return MI_LTE_OK;
 }
 

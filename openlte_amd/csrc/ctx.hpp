@@ -52,6 +52,7 @@ struct mi_lte_ctx {
     bool               bcjr_block_lds_set = false; // hipFuncSetAttribute(k_bcjr_block, max dynamic LDS) made on this context's device
     uint32_t           siso_small_max = 4096; // code blocks per decode up to which k_turbo_siso_small runs (mi_lte_set_turbo_small_batch)
     bool               merged_decode = true;  // several block sizes in one decode: one launch set over all of them (mi_lte_set_turbo_merged; turbo.hip: KSeg)
+    bool               soft_packed = true;    // PDSCH plans hand 16QAM / 64QAM soft bits to the REF decoder as bits, not bytes (mi_lte_set_soft_packed; soft_pack.h)
     void              *h_small = nullptr, *d_small = nullptr; // MI_SMALL_BYTES of pinned host memory the kernels can write (mi_ctx_small_results)
     void              *h_bounce = nullptr, *d_bounce = nullptr; // 4 MiB of pinned host memory mapped into the device: mi_lte_memcpy_* move mid-size copies through it with a kernel
     hipEvent_t         ev_bounce[2] = {nullptr, nullptr};       // ... in two halves: one event behind the copy kernel of each

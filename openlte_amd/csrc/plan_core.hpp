@@ -28,6 +28,7 @@ struct MiDecodeIO {
     int32_t        *d_status;
     uint32_t        out_stride;
     bool            ul, packed;
+    bool            soft_packed; // d_e holds the 16QAM / 64QAM allocations one bit per soft bit (soft_pack.h): PDSCH plans into mi_turbo_ref_dispatch only
 };
 
 // What every plan holds
@@ -48,7 +49,7 @@ struct MiPlanCore {
     // d_desc_block: device memory of the caller's that holds allocs | e_off | cb_alloc, n_alloc_max entries each, instead of three arrays of the plan's own
     hipError_t allocate(uint32_t n_alloc_max, size_t e_bytes_max, void *d_desc_block = nullptr);
     void       release();
-    MiDecodeIO io(uint8_t *d_out_bits, int32_t *d_status, bool ul) const { return {d_allocs, d_cb_alloc, d_e_off, d_e_len, d_e, d_out_bits, d_status, out_stride, ul, packed != 0}; }
+    MiDecodeIO io(uint8_t *d_out_bits, int32_t *d_status, bool ul, bool soft_packed = false) const { return {d_allocs, d_cb_alloc, d_e_off, d_e_len, d_e, d_out_bits, d_status, out_stride, ul, packed != 0, soft_packed}; }
 };
 
 int   mi_turbo_ref_dispatch(mi_lte_ctx *ctx, const MiKGroup *groups, uint32_t n_groups, const MiDecodeIO &io, MiMultiCache *cache);

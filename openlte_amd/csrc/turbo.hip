@@ -26,6 +26,7 @@
 
 #include "plan_core.hpp"
 #include "turbo_swar.h"
+#include "soft_pack.h"
 
 using namespace turbo_geom;
 
@@ -309,7 +310,7 @@ struct RmGeom {
 // Everything the per-code-block kernels need to know about their block, gathered once per decode by k_cb_desc: read through the
 // allocation tables it is a chain of three dependent L2 round trips at the start of every workgroup (slot -> allocation -> its fields ->
 // its soft bits), which was a third of a k_turbo_prep workgroup's lifetime
-struct CbDesc { uint32_t alloc, e_off, E, combo, Nnn, hard, tbs, pad; }; // 32 bytes
+struct CbDesc { uint32_t alloc, e_off, E, combo, Nnn, hard, tbs, pk; }; // 32 bytes; pk: the allocation's soft bits are bits, not bytes (soft_pack.h)
 
 struct GroupDesc {                 // one launch = the code blocks of one size K out of a PDSCH batch
     const mi_lte_pdsch_alloc *allocs;
@@ -323,6 +324,7 @@ struct GroupDesc {                 // one launch = the code blocks of one size K
     const uint32_t *crc_tab;       // (x^e mod gCRC24A) << 8 at index MI_CRC_TAB_BIAS + e (ctx.cc)
     uint32_t        ul;            // 1: UL-SCH soft-buffer rule (N_cb = K_w: chan_type ULSCH, liblte_phy.cc:11387-11398, :12437-12449)
     uint32_t        packed;        // 1: out_bits holds eight bits per byte, first bit in the most significant position (liblte_value_2_bits order)
+    uint32_t        soft_pk;       // 1: e_base holds the 16QAM / 64QAM allocations one bit per soft bit (soft_pack.h; k_cb_desc records it per block)
     const CbDesc   *desc;          // [n_cb] filled by k_cb_desc before the first kernel of the group (REF decoder)
 };
 
@@ -359,16 +361,26 @@ struct SrcRateUnmatch {
         // (through the constant address space: written by the launch before this one, uniform -> scalar loads, also where the pointer itself
         // came out of a merged decode's table and the compiler no longer sees a kernel argument behind it)
         const_u32x4_t *dp = reinterpret_cast<const_u32x4_t *>(reinterpret_cast<uintptr_t>(g.desc + cb));
-        const u32x4_t  d0 = dp[0], d1 = dp[1]; // alloc e_off E combo | Nnn hard tbs -
+        const u32x4_t  d0 = dp[0], d1 = dp[1]; // alloc e_off E combo | Nnn hard tbs pk
         tab = tabs + (size_t)d0.w * 3 * K;
         Nnn = d1.x;
         K_  = K;
         e   = g.e_base + (size_t)d0.y * 64;
         E   = d0.z;
         hard = d1.y != 0;
+        pk   = d1.w != 0;
     }
-    bool hard;
+    // pk: e is the packed form (soft_pack.h).  The two staging paths below expand it on the way into LDS; the unstaged gather16(e, ..) does NOT
+    // read it, and the host packs no run that would get there (mi_turbo_ref_reads_packed; mi_turbo_ref_group keeps its packed runs on the staged paths)
+    bool hard, pk;
     __device__ __forceinline__ bool hard_inputs() const { return hard; }
+    // quarter line q of a packed allocation as bytes, zero from byte `keep` on (soft_pack.h: soft_stage_quad)
+    __device__ __forceinline__ static uint4 packed_quad(const int8_t *slot, uint32_t q, uint32_t keep)
+    {
+        uint32_t w[4];
+        soft_stage_quad(slot, q, keep, w);
+        return make_uint4(w[0], w[1], w[2], w[3]);
+    }
     // copy the allocation's soft bits into LDS with wide loads (the gather is otherwise a chain of
     // dependent byte loads from L2), followed by zeros up to the next 16-byte boundary and at least at index E: the
     // gather below reads "nothing" (a NULL slot, a rank the allocation does not reach) as e[min(rank, E)] = 0.
@@ -379,6 +391,13 @@ struct SrcRateUnmatch {
         const uint32_t nq = E >> 4, tail = E & 15u; // e_off is 64-byte aligned and padded
         const uint4   *gp = reinterpret_cast<const uint4 *>(e);
         uint4         *l  = reinterpret_cast<uint4 *>(lds);
+        if (pk) { // (uniform) bits: expanded on the way, the same bytes and the same LDS lines as below
+#pragma unroll 4
+            for (uint32_t w = threadIdx.x; w < nq; w += blockDim.x) l[w] = packed_quad(e, w, 16u);
+            if (threadIdx.x == (nq & 63u)) l[nq] = tail ? packed_quad(e, nq, tail) : make_uint4(0, 0, 0, 0);
+            __syncthreads();
+            return true;
+        }
 #pragma unroll 4
         for (uint32_t w = threadIdx.x; w < nq; w += blockDim.x) l[w] = gp[w];
         if (threadIdx.x == (nq & 63u)) { // the quarter line that holds index E
@@ -523,6 +542,14 @@ struct SrcRateUnmatch {
             RankWords rw;
             load_ranks(u, nvalid, rw); // (per lap: a few L2 hits under the copy, instead of 24 registers across the barriers)
             if (base) __syncthreads(); // the lap before has been read
+            if (pk) { // (uniform) the lap's first line is quarter line (base - shift) / 16 of the allocation: a half-dword of the packed form
+                const uint32_t q0 = (base - shift) >> 4;
+#pragma unroll 1 // (the rank words and the sums live across this loop: nothing to spare for a second expansion in flight)
+                for (uint32_t w = threadIdx.x; w <= nq; w += blockDim.x) { // line nq holds index `end`: zero from there on, and not read when nothing is kept
+                    const uint32_t keep = w < nq ? 16u : tail;
+                    l[w] = keep ? packed_quad(e, q0 + w, keep) : make_uint4(0, 0, 0, 0);
+                }
+            } else {
 #pragma unroll 4
             for (uint32_t w = threadIdx.x; w < nq; w += blockDim.x) l[w] = gp[w];
             if (threadIdx.x == (nq & 63u)) { // the quarter line that holds index `end`: zero from there on
@@ -538,6 +565,7 @@ struct SrcRateUnmatch {
                     t = make_uint4(c[0], c[1], c[2], c[3]);
                 }
                 l[nq] = t;
+            }
             }
             __syncthreads();
             if (nvalid > 0) {
@@ -1617,7 +1645,7 @@ __global__ __launch_bounds__(256) void k_cb_desc(GroupDesc g, uint32_t n_cb, con
     CbDesc d;
     d.alloc = a; d.e_off = g.e_off[a]; d.E = g.e_len[a]; d.combo = combo; d.Nnn = nnn[combo];
     d.hard  = (g.allocs[a].mod_type >= 2 && d.E <= d.Nnn) ? 1u : 0u; // the de-mapper's 16QAM / 64QAM soft bits are all +-127 (liblte_phy.cc:9573-9659), and no position is summed
-    d.tbs   = g.allocs[a].tbs; d.pad = 0;
+    d.tbs   = g.allocs[a].tbs; d.pk = (g.soft_pk && g.allocs[a].mod_type >= 2) ? 1u : 0u;
     out[cb] = d;
 }
 
@@ -1637,7 +1665,7 @@ __global__ __launch_bounds__(256) void k_cb_desc_multi(GroupDesc g, uint32_t n_c
     CbDesc d;
     d.alloc = a; d.e_off = g.e_off[a]; d.E = g.e_len[a]; d.combo = combo; d.Nnn = segs[lo].nnn[combo];
     d.hard  = (g.allocs[a].mod_type >= 2 && d.E <= d.Nnn) ? 1u : 0u;
-    d.tbs   = g.allocs[a].tbs; d.pad = 0;
+    d.tbs   = g.allocs[a].tbs; d.pk = (g.soft_pk && g.allocs[a].mod_type >= 2) ? 1u : 0u;
     out[cb] = d;
 }
 
@@ -2008,7 +2036,7 @@ static int rm_rank_tables(mi_lte_ctx *ctx, uint32_t K, RmTables *out)
 // the kernels' view of a plan's hand-over; cb_base: the first code-block slot the launch covers
 static GroupDesc group_desc(const mi_lte_ctx *ctx, const MiDecodeIO &io, uint32_t cb_base = 0)
 {
-    return {io.d_allocs, io.d_cb_alloc + cb_base, io.d_e, io.d_e_off, io.d_e_len, io.d_out_bits, io.out_stride, io.d_status, ctx->d_crc_tab, io.ul ? 1u : 0u, io.packed ? 1u : 0u};
+    return {io.d_allocs, io.d_cb_alloc + cb_base, io.d_e, io.d_e_off, io.d_e_len, io.d_out_bits, io.out_stride, io.d_status, ctx->d_crc_tab, io.ul ? 1u : 0u, io.packed ? 1u : 0u, io.soft_packed ? 1u : 0u};
 }
 
 // the per-size path of mi_turbo_ref_dispatch: decode the code blocks of one size K straight from the demodulator's soft bits
@@ -2027,6 +2055,8 @@ static int mi_turbo_ref_group(mi_lte_ctx *ctx, const MiKGroup &gr, const MiDecod
     const uint32_t cap = stage_cap(gr.e_max);
     src.e_cap          = prep_stages(gr.K, cap) ? cap : 0;
     if (mi_turbo_ref_multi_takes(gr.K, gr.e_max)) {
+        // bits (soft_pack.h) are read by the staging paths alone: an allocation too long to stage whole is staged lap by lap, as a merged decode does
+        if (io.soft_packed && !src.e_cap) src.e_cap = merged_e_cap(gr.K, gr.e_max);
         SrcRateUnmatchPk pk;
         static_cast<SrcRateUnmatch &>(pk) = src;
         return turbo_ref_run<SrcRateUnmatchPk, true>(ctx, pk, gr.K, gr.n_cb, nullptr, gd, src.e_cap);

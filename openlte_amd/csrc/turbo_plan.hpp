@@ -78,6 +78,10 @@ inline uint32_t merged_e_cap(uint32_t K, uint32_t e_max_bytes)
 // 3K - 81 soft bits: while the longest allocation makes no more than 258 laps no sum of int8 values leaves int16, and the kernels may keep the
 // rate un-matching sums in pairs (SrcRateUnmatchPk), as the merged kernels do; a group beyond that takes the per-size path with 32-bit sums.
 inline bool mi_turbo_ref_multi_takes(uint32_t K, uint32_t e_max_bytes) { return (e_max_bytes + (3 * K - 81) - 1) / (3 * K - 81) <= 258; }
+// May the group's 16QAM / 64QAM allocations arrive as bits (soft_pack.h)?  k_turbo_prep expands them where it stages an allocation in LDS, whole or
+// lap by lap; its gather straight from global memory reads bytes.  That gather is what a group with 32-bit sums gets when its longest allocation
+// does not fit the LDS block (hundreds of laps at a small size) -- a run that holds such a group keeps the byte hand-over for all its allocations.
+inline bool mi_turbo_ref_reads_packed(uint32_t K, uint32_t e_max_bytes) { return mi_turbo_ref_multi_takes(K, e_max_bytes) || prep_stages(K, stage_cap(e_max_bytes)); }
 
 // The scratch of one REF decode: eight byte arrays of arr_bytes each (every size's tiles of 64 code blocks x kpad64(K) steps), three
 // arrays of traceback words of half that, three of the trellis passes' sign words of an eighth (a bit per step; arr_bytes is a multiple of

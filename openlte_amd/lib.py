@@ -1542,6 +1542,11 @@ class Context:
         self.L.mi_lte_set_turbo_merged.argtypes = [C.c_void_p, C.c_uint32]
         self._check(self.L.mi_lte_set_turbo_merged(self.h, 1 if on else 0))
 
+    def set_soft_packed(self, on=True):
+        """PDSCH plans hand 16QAM / 64QAM soft bits to the REF decoder one bit per soft bit (default) or, off, one byte (mi_lte_set_soft_packed)."""
+        self.L.mi_lte_set_soft_packed.argtypes = [C.c_void_p, C.c_uint32]
+        self._check(self.L.mi_lte_set_soft_packed(self.h, 1 if on else 0))
+
     def set_turbo_small_batch(self, n_cb_max):
         """Code blocks per decode up to which the REF decoder's state-parallel trellis kernel runs (0: always the lock-step one)."""
         self._check(self.L.mi_lte_set_turbo_small_batch(self.h, int(n_cb_max)))
