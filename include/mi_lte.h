@@ -307,6 +307,52 @@ int mi_lte_pdsch_plan_set_demapper(mi_lte_pdsch_plan *plan, uint32_t mode, float
  * MI_LTE_ERR_INVALID_ARG on a plan that is not in the 3GPP mode. */
 int mi_lte_pdsch_plan_llr_gain(const mi_lte_pdsch_plan *plan, const float **d_gain);
 
+/* ---------------------------------------------------------------- PDSCH, 3GPP mode: transmit diversity on 2 or 4 ports (opt-in)
+ * The 3GPP transport-block mode for cells with two or four CRS ports: PDSCH sent with transmit diversity (36.211 6.3.3.3 layer mapping,
+ * 6.3.4.3 pre-coding; TM2 and the fallback of every other mode), tx_mode = 2 in every allocation.  mi_lte_pdsch_plan_create_3gpp keeps
+ * refusing such cells; these plans are made by mi_lte_pdsch_plan_create_3gpp_txdiv.  The reference's receiver for this case is
+ * pre_decoder_and_matched_filter_dl (liblte_phy.cc:7694-7765), which the default demapper below restates.
+ *
+ * Code-block concatenation (36.212 5.1.4.1.2) with N_L = 2 (transmit diversity): G' = G / (N_L Q_m), gamma = G' mod C,
+ *   E_r = N_L Q_m floor(G' / C) for r <= C - gamma - 1, N_L Q_m ceil(G' / C) otherwise -- a code block ends on a symbol pair.
+ *   mi_lte_dlsch_layout_nl is mi_lte_dlsch_layout with N_L as an argument (1 or 2; G a multiple of N_L Q_m; N_L = 1 gives
+ *   mi_lte_dlsch_layout's results).  Segmentation, soft buffer (N_IR with K_MIMO = 1 for tx_mode 2), channel values, decoders, verdict and
+ *   HARQ combining are those of the sections above: after the soft-bit buffer only E_r and the offsets differ.
+ * Extraction: the allocation's resource elements in the order of every plan (symbol -> PRB -> sub-carrier, the CRS positions of the cell's
+ *   port count and the PBCH / PSS / SSS window left out); RE index idx counts them.  Their number M_ap is a multiple of N_ant for every
+ *   allocation; M_symb = M_ap, G = M_symb Q_m (e_len).  Element pair n holds RE indices a = 2n and b = 2n + 1 and was sent from ports
+ *   (pa, pb) = (0, 1) on two ports; on four ports from (0, 2) when n is even and (1, 3) when n is odd.  The grouping goes by RE index alone:
+ *   a four-port quad may straddle two PRBs and, next to the PBCH / PSS / SSS window of an odd bandwidth, two OFDM symbols, as in the
+ *   transmitter's mapping.
+ * MI_LTE_DEMAP_REF (the default): the plan demodulates exactly as a plan of mi_lte_pdsch_plan_create on the same cell does -- the
+ *   reference's combiner, with the estimates of the pair's first element for both, its normaliser and its modulation_demapper.  That
+ *   normaliser, sqrt(a0^2 + a1^2) with a_p = |h_p|^2, equals the correct (a0 + a1) / sqrt 2 only when the two ports are equally strong;
+ *   otherwise it is larger, the equalised symbols shrink and 16QAM / 64QAM decisions are biased inwards.  It is the baseline
+ *   MI_LTE_DEMAP_MAXLOG is measured against (profiles/txdiv_llr_sweep.txt).
+ * MI_LTE_DEMAP_MAXLOG, with y(.) and h_p(.) from the subframe planes at the pair's two resource elements, each element with its own estimates:
+ *   z0 = conj(h_pa(a)) y(a) + h_pb(b) conj(y(b)),   w0 = (|h_pa(a)|^2 + |h_pb(b)|^2) / 2
+ *   z1 = conj(h_pa(b)) y(b) - h_pb(a) conj(y(a)),   w1 = (|h_pa(b)|^2 + |h_pb(a)|^2) / 2
+ *   t_i = z_i / sqrt 2;  symbol idx a has (t, w) = (t0, w0), symbol idx b has (t1, w1).
+ *   t / w is the symbol estimate and w its reliability, 1 / sigma^2 up to the common factor; the cross term a channel that differs between
+ *   a and b leaves is ignored.  L_k is the single-port section's with u = Re or Im of t / w (evaluated from t and w without dividing), and the
+ *   soft byte clamp(rint(g_a L_k)) with ties to even, the descrambling, the buffer layout and e_len are that section's.
+ *   Automatic gain: g_a = T / (4 A^2 wbar), wbar the mean of w over the allocation's M_symb symbols, summed in double in a fixed order (so a
+ *   run is reproducible), g_a rounded to float and reported by mi_lte_pdsch_plan_llr_gain.  With both ports at unit gain w = 1: the
+ *   convention T is the single-port one.  Degenerate input as there: w = 0 gives 0 for the symbol's bits, a wbar that is 0 or not finite gives
+ *   g_a = 0, an all-zero code block is an erasure (status 2).
+ * mi_lte_pdsch_plan_create_3gpp_txdiv: cfg->N_ant 2 or 4.  MI_LTE_ERR_UNSUPPORTED: N_ant = 1 (use mi_lte_pdsch_plan_create_3gpp), an allocation
+ *   whose tx_mode is not 2, BPSK, a tbs the layout refuses, MI_LTE_CE_COMPACT in the sample format; every other condition is
+ *   mi_lte_pdsch_plan_create's.  The plan works with mi_lte_pdsch_decode_run, _decode_run_harq (any pool of the context, shared with its
+ *   single-port plans), _set_decoder (BCJR decoders, exact interleaver), _set_output, _soft_bits, _cb_soft, _cb_ok, _set_demapper, _llr_gain and
+ *   _destroy.  Spatial multiplexing (K_MIMO = 2), dynamic plans and the packed soft-bit hand-over are not part of it. */
+int mi_lte_dlsch_layout_nl(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t N_L, uint32_t tx_mode, uint32_t rv, const mi_lte_dlsch_cfg *dlsch,
+                           mi_lte_dlsch_layout_t *out);
+int mi_lte_pdsch_plan_create_3gpp_txdiv(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t N_pdcch_symbs, const mi_lte_dlsch_cfg *dlsch,
+                                        const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, mi_lte_pdsch_plan **out);
+/* 1 when mi_lte_pdsch_plan_create_3gpp_txdiv accepts this allocation, 0 when it refuses it */
+int mi_lte_pdsch_alloc_decodable_3gpp_txdiv(const mi_lte_dl_cfg *cfg, const mi_lte_dlsch_cfg *dlsch, const mi_lte_pdsch_alloc *alloc,
+                                            uint32_t N_pdcch_symbs);
+
 /* ---------------------------------------------------------------- PDSCH, 3GPP mode: HARQ soft combining
  * Incremental-redundancy combining of the retransmissions of a transport block in device-resident soft buffers (36.212 5.1.4.1.2: the
  * circular buffer of N_cb positions per code block that every redundancy version reads from; 36.321 5.3.2.2: when a buffer is flushed).
@@ -1349,6 +1395,29 @@ int mi_lte_synth_dl_units_3gpp_payload_i8(const mi_lte_dl_cfg *cfg, uint32_t n_u
                                           uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
                                           const mi_lte_dlsch_cfg *dlsch, const mi_lte_synth_channel *chan, const uint8_t *h_payload,
                                           uint32_t tbs_stride, int8_t *h_iq);
+/* The transmit side of the transmit-diversity plans ("PDSCH, 3GPP mode: transmit diversity" above).
+ * mi_lte_dlsch_encode_3gpp_nl: mi_lte_dlsch_encode_3gpp over mi_lte_dlsch_layout_nl's E_r (N_L = 1: the same bits).
+ * mi_lte_txdiv_precode: the layer mapper and pre-coder of 36.211 6.3.3.3 / 6.3.4.3 in one step, host arithmetic.  d: M_symb modulation
+ *   symbols (M_symb a multiple of N_ant, N_ant 2 or 4; anything else MI_LTE_ERR_INVALID_ARG); y[p * M_symb + n]: what port p sends in
+ *   place n.  Two ports, pair (d(2i), d(2i+1)) = (x0, x1): port 0 sends x0, x1 and port 1 sends -conj(x1), conj(x0), all over sqrt 2.  Four
+ *   ports: places 4i, 4i+1 carry (d(4i), d(4i+1)) in that form on ports (0, 2), places 4i+2, 4i+3 carry (d(4i+2), d(4i+3)) on ports (1, 3);
+ *   the other two ports send 0 there.
+ * mi_lte_synth_dl_units_3gpp_txdiv_i8: mi_lte_synth_dl_units_3gpp_i8 for cfg->N_ant = 2 or 4.  CRS for every port (36.211 6.10.1); each
+ *   allocation's resource elements in the same mapping order with the 2 / 4-port CRS exclusions, from the allocation's own n_pdcch_symbs when
+ *   it has one; mi_lte_dlsch_encode_3gpp_nl with N_L = 2, scrambling, modulation, mi_lte_txdiv_precode; one OFDM signal per port.  Channel,
+ *   per unit: one integer delay common to all ports (co-located antennas; a delay per port would put a phase step between the two elements
+ *   of a pair, which at FFT 128 already breaks 64QAM without noise), then per port, in port order, a gain from gain_min..gain_max and a
+ *   phase (max_delay < 0: no delay and no phase).  The ports are summed; AWGN at snr_db relative to the power of that sum; int8 with the
+ *   sum's peak at `peak`, per unit.  h_payload (may be NULL): the caller's transport blocks as in mi_lte_synth_dl_units_3gpp_payload_i8, the
+ *   random ones' draws still made; h_tx_bits (may be NULL): the blocks sent.  MI_LTE_ERR_INVALID_ARG: N_ant = 1 (use the calls above), an
+ *   allocation with tx_mode != 2, BPSK, or a tbs mi_lte_dlsch_layout_nl refuses.  The generators above and their byte streams are untouched. */
+int mi_lte_dlsch_encode_3gpp_nl(uint32_t tbs, const uint8_t *bits, uint32_t G, uint32_t Q_m, uint32_t N_L, uint32_t tx_mode, uint32_t rv,
+                                const mi_lte_dlsch_cfg *dlsch, uint8_t *e_out);
+int mi_lte_txdiv_precode(uint32_t N_ant, const float *d_re, const float *d_im, uint32_t M_symb, float *y_re, float *y_im);
+int mi_lte_synth_dl_units_3gpp_txdiv_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
+                                        uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                        const mi_lte_dlsch_cfg *dlsch, const mi_lte_synth_channel *chan, const uint8_t *h_payload /* may be NULL */,
+                                        uint32_t tbs_stride, int8_t *h_iq, uint8_t *h_tx_bits /* may be NULL */);
 
 /* control regions: PCFICH + n_dci format-1A DCIs (rnti = 0: slot unused) at aggregation level 4 in candidates 0..n_dci-1,
  * standard transmit diversity on cfg->N_ant ports, through a smooth random channel per port (gain_min..gain_max) and

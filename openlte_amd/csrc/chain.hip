@@ -516,6 +516,174 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict
         per_mod(e);
 }
 
+// MI_LTE_DEMAP_MAXLOG on a transmit-diversity plan (include/mi_lte.h, "PDSCH, 3GPP mode: transmit diversity"): k_pdsch_demod_llr's pair table,
+// scrambling words, thread per (pair, sub-carrier), LDS assembly and soft-bit layout over the N_ANT-port extraction.  Every thread does the
+// symbol of its own resource element s; the other element o of its pair is the neighbouring set bit of the same 12-bit mask -- the next one for
+// an even RE index, the previous one for an odd one -- and only where the mask has none (the pair straddles two PRBs, or next to the PBCH / PSS /
+// SSS window two symbols) a search of the table.  Both symbols of a pair have one form,
+//     z = conj(h_pa(s)) y(s) +- h_pb(o) conj(y(o)),  w = (|h_pa(s)|^2 + |h_pb(o)|^2) / 2     (+: even index, -: odd),
+// so a thread loads two y and two h values, and t = z / sqrt 2 and w go into llr_axis / llr_byte as the single-port kernel's z and w do.
+// The automatic gain's wbar is summed as there: per thread, inside each wave, over the waves' LDS slots in order, in double.
+template <uint32_t N_ANT>
+__global__ __launch_bounds__(256) void k_pdsch_demod_llr_txd(const float *__restrict__ subframes, DemodGeom g, const mi_lte_pdsch_alloc *__restrict__ allocs,
+                                                             const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell, GoldTables gt,
+                                                             int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len,
+                                                             uint32_t max_pairs, uint32_t max_words, uint32_t e_lds_cap, float gain, float auto_t,
+                                                             float *__restrict__ llr_gain)
+{
+    static_assert(N_ANT == 2 || N_ANT == 4, "transmit diversity: two or four ports");
+    extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // tab[max_pairs+1] (offset, mask | position) | cw[...] | soft bits
+    __shared__ double w_wave[4];
+    const uint32_t a_idx = blockIdx.x;
+    const mi_lte_pdsch_alloc &al = allocs[a_idx];
+    const uint32_t unit = al.unit, sf = subfr_num[unit], cell = n_id_cell[unit], N_prb = al.N_prb;
+    const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : 2; // (a 3GPP plan holds no BPSK allocation)
+    uint2    *tab = reinterpret_cast<uint2 *>(smu);
+    uint32_t *cw  = smu + ((2 * (max_pairs + 1) + 3u) & ~3u);
+    uint32_t first_sc, last_sc;
+    sync_window(g.N_rb_dl, first_sc, last_sc);
+    const uint32_t cfi = al.n_pdcch_symbs ? al.n_pdcch_symbs : g.cfi;
+    const uint32_t n_pairs = 14 * N_prb, pair0 = cfi * N_prb;
+    const uint32_t c_init = ((al.rnti << 14) | (0u << 13) | (sf << 9) | cell) & 0x7FFFFFFFu;
+    if (threadIdx.x < 64) pair_table_scan(tab, al, N_ANT, cell, sf, cfi, n_pairs, first_sc, last_sc);
+    else {
+        const uint32_t n_words_ub = ((n_pairs - pair0) * 12 * Qm + 31) / 32;
+        for (uint32_t w = threadIdx.x - 64; w <= n_words_ub; w += blockDim.x - 64) cw[w] = gold_word(gt, c_init, w);
+    }
+    __syncthreads();
+    // (M_ap is a multiple of N_ANT for every allocation: the note at k_pdsch_demod's n_grp)
+    const uint32_t M_symb = (tab[n_pairs].x / N_ANT) * N_ANT, N_bits = M_symb * Qm;
+    if (threadIdx.x == 0) e_len[a_idx] = N_bits;
+
+    constexpr uint32_t PL = 16 * N_SC_MAX * 4; // bytes of one plane: y_re | y_im | h_re of the N_ANT ports | h_im of the N_ANT ports
+    const float *base = subframes + (size_t)unit * g.sf_stride;
+    const char  *y_re_p = reinterpret_cast<const char *>(base), *y_im_p = y_re_p + PL;
+    const char  *h_re_p = y_im_p + PL, *h_im_p = h_re_p + N_ANT * PL;
+    constexpr int  UNR = 4; // symbols in flight per thread: eight loads each
+    const uint32_t q_thr = threadIdx.x / 12, j = threadIdx.x - 12 * q_thr, below = (1u << j) - 1u;
+    const bool     lane_on = threadIdx.x < 252;
+    auto locate = [&](uint32_t idx) -> uint32_t { // RE index -> L * 1200 + sub-carrier (k_pdsch_demod's)
+        uint32_t lo = pair0, hi = n_pairs; // tab[lo].x <= idx < tab[hi].x
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (tab[mid].x <= idx) lo = mid; else hi = mid;
+        }
+        const uint2 t = tab[lo];
+        uint32_t r = idx - t.x, m = t.y & 0xFFFu;
+        for (; r; r--) m &= m - 1;
+        return (t.y >> 12) + (uint32_t)__builtin_ctz(m | 0x1000u);
+    };
+    // The thread's symbol in table pair q: byte offsets inside a plane of its own resource element (os) and of the other element of its pair (oo),
+    // of its pair's two port planes (pa, pb), all 0 where the thread has no symbol (every load stays inside the unit); the RE index
+    struct Elem { uint32_t os, oo, pa, pb, idx; bool on; };
+    auto element = [&](uint32_t q) __attribute__((always_inline)) -> Elem {
+        const bool     in  = lane_on && q < n_pairs;
+        const uint2    pr  = tab[in ? q : 0u];
+        const uint32_t lowm = pr.y & below, idx = pr.x + __popc(lowm);
+        const bool     on  = in && ((pr.y >> j) & 1u) && idx < M_symb;
+        const uint32_t up  = (pr.y & 0xFFFu) >> (j + 1); // the mask's elements above this one
+        uint32_t       po;                               // the other element's position
+        if (idx & 1u) {
+            po = (pr.y >> 12) + 31u - (uint32_t)__builtin_clz(lowm | 1u);
+            if (on && !lowm) po = locate(idx - 1);
+        } else {
+            po = (pr.y >> 12) + j + 1 + (uint32_t)__builtin_ctz(up | 0x800u);
+            if (on && !up) po = locate(idx + 1);
+        }
+        const uint32_t port = N_ANT == 4 ? ((idx >> 1) & 1u) * PL : 0u; // four ports: pair n = idx / 2 on ports (0, 2) for even n, (1, 3) for odd n
+        Elem e;
+        e.on = on; e.idx = idx;
+        e.os = on ? ((pr.y >> 12) + j) << 2 : 0u;
+        e.oo = on ? po << 2 : 0u;
+        e.pa = on ? port : 0u;
+        e.pb = on ? port + (N_ANT == 4 ? 2 * PL : PL) : 0u;
+        return e;
+    };
+    auto ldf = [](const char *p, uint32_t off) __attribute__((always_inline)) { return *reinterpret_cast<const float *>(p + off); };
+    double gd = (double)gain;
+    if (gain == 0.0f) { // wbar: the mean of w over the allocation's symbols
+        double part = 0.0;
+        for (uint32_t qb = pair0; qb < n_pairs; qb += 21 * UNR) {
+            float h[UNR][4];
+            bool  on[UNR];
+#pragma unroll
+            for (int r = 0; r < UNR; r++) {
+                const Elem e = element(qb + 21 * r + q_thr);
+                on[r]   = e.on;
+                h[r][0] = ldf(h_re_p, e.pa + e.os); h[r][1] = ldf(h_im_p, e.pa + e.os); // h_pa(s)
+                h[r][2] = ldf(h_re_p, e.pb + e.oo); h[r][3] = ldf(h_im_p, e.pb + e.oo); // h_pb(o)
+            }
+#pragma unroll
+            for (int r = 0; r < UNR; r++)
+                if (on[r]) part += (((double)h[r][0] * h[r][0] + (double)h[r][1] * h[r][1]) + ((double)h[r][2] * h[r][2] + (double)h[r][3] * h[r][3])) * 0.5;
+        }
+        for (int o = 32; o; o >>= 1) part += __shfl_xor(part, o);
+        if ((threadIdx.x & 63u) == 0) w_wave[threadIdx.x >> 6] = part;
+        __syncthreads();
+        const double wbar = (((w_wave[0] + w_wave[1]) + w_wave[2]) + w_wave[3]) / (double)M_symb;
+        const double a4 = al.mod_type == 3 ? 4.0 / 42 : al.mod_type == 2 ? 4.0 / 10 : 2.0; // 4 A^2
+        const float  gf = (float)((double)auto_t / (a4 * wbar));
+        gd = (wbar > 0.0 && fabsf(gf) <= 3.4028234e38f) ? (double)gf : 0.0; // wbar 0, NaN or infinite, or a gain past float: every soft bit 0
+    }
+    if (threadIdx.x == 0) llr_gain[a_idx] = (float)gd;
+
+    int8_t    *e      = e_base + (size_t)e_off[a_idx] * 64;
+    int8_t    *e_lds  = reinterpret_cast<int8_t *>(cw + max_words);
+    const bool via_lds = N_bits <= e_lds_cap;
+    auto run = [&](auto modc, auto *dst) __attribute__((always_inline)) {
+        constexpr uint32_t MOD = decltype(modc)::value, QM = MOD == 3 ? 6 : MOD == 2 ? 4 : 2;
+        for (uint32_t qb = pair0; qb < n_pairs; qb += 21 * UNR) {
+            float    y[UNR][4], h[UNR][4];
+            uint32_t idx[UNR];
+            bool     on[UNR];
+#pragma unroll
+            for (int r = 0; r < UNR; r++) {
+                const Elem e = element(qb + 21 * r + q_thr);
+                on[r] = e.on; idx[r] = e.idx;
+                y[r][0] = ldf(y_re_p, e.os);        y[r][1] = ldf(y_im_p, e.os);        // y(s)
+                y[r][2] = ldf(y_re_p, e.oo);        y[r][3] = ldf(y_im_p, e.oo);        // y(o)
+                h[r][0] = ldf(h_re_p, e.pa + e.os); h[r][1] = ldf(h_im_p, e.pa + e.os); // h_pa(s)
+                h[r][2] = ldf(h_re_p, e.pb + e.oo); h[r][3] = ldf(h_im_p, e.pb + e.oo); // h_pb(o)
+            }
+#pragma unroll
+            for (int r = 0; r < UNR; r++) {
+                if (!on[r]) continue;
+                constexpr double RS2 = 0.70710678118654752; // 1 / sqrt 2
+                const double sg = (idx[r] & 1u) ? -1.0 : 1.0; // z0 = conj(h_pa(a)) y(a) + h_pb(b) conj(y(b)),  z1 = conj(h_pa(b)) y(b) - h_pb(a) conj(y(a))
+                const double sr = y[r][0], si = y[r][1], yor = y[r][2], yoi = y[r][3];
+                const double har = h[r][0], hai = h[r][1], hbr = sg * h[r][2], hbi = sg * h[r][3];
+                const double zr = ((har * sr + hai * si) + hbr * yor) + hbi * yoi, zi = ((har * si - hai * sr) + hbi * yor) - hbr * yoi;
+                const double w  = ((har * har + hai * hai) + (hbr * hbr + hbi * hbi)) * 0.5;
+                double li[3], lq[3];
+                llr_axis<MOD>(zr * RS2, w, li);
+                llr_axis<MOD>(zi * RS2, w, lq);
+                // descramble (c bit set -> negate) and store in pairs, as k_pdsch_demod_llr does
+                const uint32_t n0 = idx[r] * QM, c = __builtin_amdgcn_alignbit(cw[(n0 >> 5) + 1], cw[n0 >> 5], n0 & 31);
+#pragma unroll
+                for (uint32_t k = 0; k < QM; k += 2) {
+                    const int vi = llr_byte(gd, li[k >> 1]), vq = llr_byte(gd, lq[k >> 1]);
+                    const int lo = ((c >> k) & 1u) ? -vi : vi, hi8 = ((c >> (k + 1)) & 1u) ? -vq : vq;
+                    *reinterpret_cast<uint16_t *>(dst + n0 + k) = (uint16_t)((lo & 0xFF) | ((hi8 & 0xFF) << 8));
+                }
+            }
+        }
+    };
+    auto per_mod = [&](auto *dst) __attribute__((always_inline)) {
+        switch (al.mod_type) {
+        case 1:  run(std::integral_constant<uint32_t, 1>{}, dst); break;
+        case 2:  run(std::integral_constant<uint32_t, 2>{}, dst); break;
+        default: run(std::integral_constant<uint32_t, 3>{}, dst); break;
+        }
+    };
+    if (via_lds) {
+        per_mod(e_lds);
+        __syncthreads();
+        const uint32_t nq = (N_bits + 15) >> 4; // the allocation's slot in e_base is padded to 64 bytes
+        for (uint32_t w = threadIdx.x; w < nq; w += blockDim.x) reinterpret_cast<uint4 *>(e)[w] = reinterpret_cast<const uint4 *>(e_lds)[w];
+    } else
+        per_mod(e);
+}
+
 // The stage tap after a run with the packed hand-over (mi_lte_pdsch_plan_soft_bits): one workgroup per allocation turns a packed slot back into
 // the byte form IN PLACE -- all of the allocation's dwords into LDS, a barrier, then the bytes (zeros behind e_len up to the next 16 bytes).
 __global__ __launch_bounds__(256) void k_soft_expand(const mi_lte_pdsch_alloc *__restrict__ allocs, int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off,
@@ -724,13 +892,24 @@ int mi_lte_pdsch_alloc_decodable_3gpp(const mi_lte_dl_cfg *cfg, const mi_lte_dls
     return alloc_geometry_ok(cfg, al, N_pdcch_symbs);
 }
 
+int mi_lte_pdsch_alloc_decodable_3gpp_txdiv(const mi_lte_dl_cfg *cfg, const mi_lte_dlsch_cfg *dlsch, const mi_lte_pdsch_alloc *al, uint32_t N_pdcch_symbs)
+{ // the same for mi_lte_pdsch_plan_create_3gpp_txdiv: two or four ports, transmit diversity, full estimate planes
+    if (!cfg || !dlsch || !al || !(cfg->N_ant == 2 || cfg->N_ant == 4) || (cfg->sample_format & MI_LTE_CE_COMPACT)) return 0;
+    if (al->tx_mode != 2 || al->mod_type == 0 || al->mod_type > 3) return 0;
+    mi_lte_dlsch_layout_t lay;
+    if (mi_lte_dlsch_layout_nl(al->tbs, 0, 2, 2, al->tx_mode, al->rv_idx & 3u, dlsch, &lay) != MI_LTE_OK) return 0;
+    return alloc_geometry_ok(cfg, al, N_pdcch_symbs);
+}
+
+} // extern "C"
+
 // A static plan in the 3GPP transport-block mode: the demodulator's layout is that of any plan -- it does not depend on the transport block
 // size -- and the code blocks are dlsch3gpp.hip's.
-int mi_lte_pdsch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t N_pdcch_symbs, const mi_lte_dlsch_cfg *dlsch,
-                                  const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, mi_lte_pdsch_plan **out)
+// n_l: N_L of the code-block concatenation -- 1: a single-port cell (mi_lte_pdsch_plan_create_3gpp), 2: transmit diversity on the cell's two or
+// four ports (mi_lte_pdsch_plan_create_3gpp_txdiv).  The callers have checked the port count.
+static int plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t N_pdcch_symbs, const mi_lte_dlsch_cfg *dlsch, const mi_lte_pdsch_alloc *h_allocs,
+                            uint32_t n_alloc, uint32_t n_l, mi_lte_pdsch_plan **out)
 {
-    if (!ctx || !cfg || !dlsch || !h_allocs || !out || n_alloc == 0 || N_pdcch_symbs < 1 || N_pdcch_symbs > 4 || dlsch->M_dl_harq == 0) return MI_LTE_ERR_INVALID_ARG;
-    if (cfg->N_ant != 1) { ctx->err = "3GPP transport-block mode: single-port cells only"; return MI_LTE_ERR_UNSUPPORTED; }
     for (uint32_t a = 0; a < n_alloc; a++) {
         mi_lte_dlsch_layout_t lay;
         const int rc = h_allocs[a].mod_type == 0 ? MI_LTE_ERR_UNSUPPORTED : mi_lte_dlsch_layout(h_allocs[a].tbs, 0, 2, h_allocs[a].tx_mode, h_allocs[a].rv_idx & 3u, dlsch, &lay);
@@ -744,7 +923,7 @@ int mi_lte_pdsch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uin
     int rc = plan_layout(ctx, pl, N_pdcch_symbs, h_allocs, n_alloc, nullptr);
     if (rc != MI_LTE_OK) return rc;
     MI_HIP_CHECK(ctx, pl->core.allocate(n_alloc, pl->core.e_bytes));
-    rc = mi_dlsch3_create(ctx, dlsch, h_allocs, n_alloc, &pl->g3);
+    rc = mi_dlsch3_create(ctx, dlsch, h_allocs, n_alloc, &pl->g3, n_l);
     if (rc != MI_LTE_OK) return rc;
     MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_llr_gain, sizeof(float) * n_alloc));
     MI_HIP_CHECK(ctx, hipMemsetAsync(pl->d_llr_gain, 0, sizeof(float) * n_alloc, ctx->stream));
@@ -754,6 +933,30 @@ int mi_lte_pdsch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uin
     guard.armed = false;
     *out = pl;
     return MI_LTE_OK;
+}
+
+extern "C" {
+
+int mi_lte_pdsch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t N_pdcch_symbs, const mi_lte_dlsch_cfg *dlsch,
+                                  const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, mi_lte_pdsch_plan **out)
+{
+    if (!ctx || !cfg || !dlsch || !h_allocs || !out || n_alloc == 0 || N_pdcch_symbs < 1 || N_pdcch_symbs > 4 || dlsch->M_dl_harq == 0) return MI_LTE_ERR_INVALID_ARG;
+    if (cfg->N_ant != 1) { ctx->err = "3GPP transport-block mode: single-port cells only (two or four ports: mi_lte_pdsch_plan_create_3gpp_txdiv)"; return MI_LTE_ERR_UNSUPPORTED; }
+    return plan_create_3gpp(ctx, cfg, N_pdcch_symbs, dlsch, h_allocs, n_alloc, 1, out);
+}
+
+// The same mode on a cell of two or four CRS ports: every allocation in transmit diversity (36.211 6.3.3.3 / 6.3.4.3, tx_mode 2).  The default
+// demapper is the reference-mode plans' k_pdsch_demod<false>, MAXLOG is k_pdsch_demod_llr_txd, and the code-block concatenation runs with N_L = 2.
+int mi_lte_pdsch_plan_create_3gpp_txdiv(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t N_pdcch_symbs, const mi_lte_dlsch_cfg *dlsch,
+                                        const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, mi_lte_pdsch_plan **out)
+{
+    if (!ctx || !cfg || !dlsch || !h_allocs || !out || n_alloc == 0 || N_pdcch_symbs < 1 || N_pdcch_symbs > 4 || dlsch->M_dl_harq == 0) return MI_LTE_ERR_INVALID_ARG;
+    if (!(cfg->N_ant == 1 || cfg->N_ant == 2 || cfg->N_ant == 4)) return MI_LTE_ERR_INVALID_ARG;
+    if (cfg->N_ant == 1) { ctx->err = "transmit-diversity plan: two or four ports (one port: mi_lte_pdsch_plan_create_3gpp)"; return MI_LTE_ERR_UNSUPPORTED; }
+    if (cfg->sample_format & MI_LTE_CE_COMPACT) { ctx->err = "MI_LTE_CE_COMPACT: single-port cells only"; return MI_LTE_ERR_UNSUPPORTED; }
+    for (uint32_t a = 0; a < n_alloc; a++)
+        if (h_allocs[a].tx_mode != 2) { ctx->err = "transmit-diversity plan: every allocation must have tx_mode 2"; return MI_LTE_ERR_UNSUPPORTED; }
+    return plan_create_3gpp(ctx, cfg, N_pdcch_symbs, dlsch, h_allocs, n_alloc, 2, out);
 }
 
 int mi_lte_pdsch_plan_cb_soft(const mi_lte_pdsch_plan *pl, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K)
@@ -952,14 +1155,19 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
         MI_LAUNCH(ctx, "k_pdsch_demod", kernel, dim3(pl->core.n_alloc), dim3(threads), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt,
                   pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pack ? 1u : 0u);
     };
-    if (pl->demap == MI_LTE_DEMAP_MAXLOG) { // (a single-port 3GPP plan on full estimate planes: mi_lte_pdsch_plan_set_demapper)
+    if (pl->demap == MI_LTE_DEMAP_MAXLOG) { // (a 3GPP plan on full estimate planes: mi_lte_pdsch_plan_set_demapper)
         float auto_t = (float)MI_LTE_DEMAP_AUTO_T;
         if (const char *ev = getenv("MI_LTE_DEMAP_AUTO_T")) { // (tuning aid: tools/demap_llr_sweep.py chooses the header's constant with it)
             const float t = (float)atof(ev);
             if (t >= 1.0f && t <= 127.0f) auto_t = t;
         }
-        MI_LAUNCH(ctx, "k_pdsch_demod_llr", k_pdsch_demod_llr, dim3(pl->core.n_alloc), dim3(256), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num,
-                  d_n_id_cell, gt, pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain);
+        auto launch_llr = [&](const char *name, auto kernel) {
+            MI_LAUNCH(ctx, name, kernel, dim3(pl->core.n_alloc), dim3(256), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt, pl->core.d_e,
+                      pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain);
+        };
+        if (g.N_ant == 1) launch_llr("k_pdsch_demod_llr", k_pdsch_demod_llr);
+        else if (g.N_ant == 2) launch_llr("k_pdsch_demod_llr_txd", k_pdsch_demod_llr_txd<2>); // (a transmit-diversity plan)
+        else launch_llr("k_pdsch_demod_llr_txd", k_pdsch_demod_llr_txd<4>);
     } else if (g.N_ant == 1 && (pl->cfg.sample_format & MI_LTE_CE_COMPACT)) launch(k_pdsch_demod<true, true>);
     else if (g.N_ant == 1) launch(k_pdsch_demod<true>);
     else launch(k_pdsch_demod<false>);
@@ -989,7 +1197,7 @@ static int pdsch_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *p
     const MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/false, pack);
     if (pl->g3) {
         rc = mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter);
-        if (rc == MI_LTE_OK && pl->demap == MI_LTE_DEMAP_MAXLOG) ctx->last_kernels.replace(0, strlen("k_pdsch_demod"), "k_pdsch_demod_llr");
+        if (rc == MI_LTE_OK && pl->demap == MI_LTE_DEMAP_MAXLOG) ctx->last_kernels.replace(0, strlen("k_pdsch_demod"), pl->cfg.N_ant == 1 ? "k_pdsch_demod_llr" : "k_pdsch_demod_llr_txd");
         return rc;
     }
     if (!mi_is_bcjr(pl->decoder)) {

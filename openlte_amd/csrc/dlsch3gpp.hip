@@ -64,13 +64,14 @@ struct Dl3Desc {
 };
 
 __global__ __launch_bounds__(256) void k_dl3_desc(const Dl3Slot *__restrict__ slots, uint32_t n_slot, const mi_lte_pdsch_alloc *__restrict__ allocs,
-                                                  const uint32_t *__restrict__ e_len, uint32_t N_soft, uint32_t M_dl_harq, Dl3Desc *__restrict__ out)
+                                                  const uint32_t *__restrict__ e_len, uint32_t N_soft, uint32_t M_dl_harq, uint32_t N_L, Dl3Desc *__restrict__ out)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_slot) return;
     const Dl3Slot             sl = slots[s];
     const mi_lte_pdsch_alloc &al = allocs[sl.alloc];
-    const uint32_t Qm = q_m(al.mod_type), Gp = e_len[sl.alloc] / Qm, gam = Gp % sl.C, lo = Gp / sl.C, C = sl.C, r = sl.r;
+    // (N_L: 2 on a transmit-diversity plan, whose symbols stay in pairs; 1 on every other plan, the uplink's included)
+    const uint32_t Qm = N_L * q_m(al.mod_type), Gp = e_len[sl.alloc] / Qm, gam = Gp % sl.C, lo = Gp / sl.C, C = sl.C, r = sl.r;
     Dl3Desc d;
     d.alloc = sl.alloc; d.r = r; d.C = C; d.K = sl.K;
     d.E   = Qm * (r + gam < C ? lo : lo + 1);                    // r <= C - gamma - 1: floor(G' / C), else ceil
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(256) void k_harq_commit(const mi_lte_harq_bind *__r
 
 struct MiDlsch3 {
     mi_lte_dlsch_cfg cfg{};
-    uint32_t n_alloc = 0, n_slot = 0;
+    uint32_t n_alloc = 0, n_slot = 0, n_l = 1; // n_l: N_L of the code-block concatenation (36.212 5.1.4.1.2)
     std::vector<MiKGroup> groups;              // a block size's slots, contiguous; ...
     std::vector<size_t>   g_soft, g_bits;      // ... and where they start in d_soft / d_bits (bytes, on 256)
     std::vector<uint32_t> a_slot, a_nc, a_K, a_tbs; // per allocation: first slot, C, K, tbs
@@ -343,9 +344,10 @@ void mi_dlsch3_free(MiDlsch3 *g)
 
 // The plan's code-block slots: grouped by block size (ascending), inside a size allocation after allocation, block after block.
 // mi_lte_pdsch_plan_create_3gpp has checked every allocation against mi_lte_dlsch_layout.
-int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out)
+int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out, uint32_t n_l)
 {
     auto *g   = new MiDlsch3();
+    g->n_l     = n_l;
     auto guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_dlsch3_free(g); });
     g->cfg     = *cfg;
     g->n_alloc = n_alloc;
@@ -518,7 +520,7 @@ int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lt
         MI_HIP_CHECK(ctx, hipEventRecord(p->staged, ctx->stream));
     }
     MI_LAUNCH(ctx, "k_dl3_desc", k_dl3_desc, dim3((g->n_slot + 255) / 256), dim3(256), 0, (const Dl3Slot *)g->d_slot, g->n_slot, io.d_allocs, io.d_e_len,
-              g->cfg.N_soft, g->cfg.M_dl_harq, g->d_desc);
+              g->cfg.N_soft, g->cfg.M_dl_harq, g->n_l, g->d_desc);
     if (p) {
         MI_LAUNCH(ctx, "k_harq_bind", k_harq_bind, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const Dl3Desc *)g->d_desc, (const uint32_t *)g->d_a_slot,
                   g->n_alloc, (const mi_lte_harq_bind *)p->d_bind, p->d_state, g->d_slot_buf);

@@ -58,7 +58,7 @@ int   mi_turbo_bcjr_group(mi_lte_ctx *ctx, const MiKGroup &gr, const MiDecodeIO 
 
 // the 3GPP transport-block mode's part of a plan (dlsch3gpp.hip)
 struct MiDlsch3;
-int             mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out);
+int             mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out, uint32_t n_l = 1);
 void            mi_dlsch3_free(MiDlsch3 *g);
 int             mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const MiDecodeIO &io, uint32_t decoder, uint32_t n_iter);
 int             mi_dlsch3_cb_soft(const MiDlsch3 *g, uint32_t alloc, const int8_t **d_blocks, uint32_t *C, uint32_t *K);

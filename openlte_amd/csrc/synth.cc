@@ -224,9 +224,12 @@ extern "C" {
 
 // 36.212 5.1.2 (segmentation with F = 0 and C- = 0: C blocks of one size K, K C = B') and 5.1.4.1.2 (soft buffer, code-block concatenation)
 // for the 3GPP transport-block mode: what the transmitter below, the 3GPP plans (chain.hip, dlsch3gpp.hip) and the tests lay a block out by
-int mi_lte_dlsch_layout(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t tx_mode, uint32_t rv, const mi_lte_dlsch_cfg *dlsch, mi_lte_dlsch_layout_t *out)
+// (N_L = 1: mi_lte_dlsch_layout; N_L = 2: the transmit-diversity plans, whose symbols leave in pairs)
+int mi_lte_dlsch_layout_nl(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t N_L, uint32_t tx_mode, uint32_t rv, const mi_lte_dlsch_cfg *dlsch,
+                           mi_lte_dlsch_layout_t *out)
 {
-    if (!dlsch || !out || !(Q_m == 1 || Q_m == 2 || Q_m == 4 || Q_m == 6) || G % Q_m || rv > 3 || dlsch->M_dl_harq == 0) return MI_LTE_ERR_INVALID_ARG;
+    if (!dlsch || !out || !(Q_m == 1 || Q_m == 2 || Q_m == 4 || Q_m == 6) || !(N_L == 1 || N_L == 2) || G % (N_L * Q_m) || rv > 3 || dlsch->M_dl_harq == 0)
+        return MI_LTE_ERR_INVALID_ARG;
     if (tbs == 0 || tbs > 75376) return MI_LTE_ERR_UNSUPPORTED; // the largest single-layer size of 36.213 Table 7.1.7.2.1-1 (13 blocks)
     const uint32_t B = tbs + 24, C = B <= 6144 ? 1u : (B + 6119) / 6120, Bp = C == 1 ? B : B + 24 * C;
     uint32_t K = 0;
@@ -240,13 +243,18 @@ int mi_lte_dlsch_layout(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t tx_mode
     out->N_cb = std::min(N_ir / C, K_w);
     out->k0   = R * (2 * ((out->N_cb + 8 * R - 1) / (8 * R)) * rv + 2);
     if (out->N_cb < 2) return MI_LTE_ERR_INVALID_ARG; // (position 1 of the buffer is the first that is never NULL)
-    const uint32_t Gp = G / Q_m, gam = Gp % C, lo = Gp / C;
+    const uint32_t Gp = G / (N_L * Q_m), gam = Gp % C, lo = Gp / C;
     for (uint32_t r = 0, off = 0; r < C; r++) {
-        out->E[r]   = Q_m * (r + gam < C ? lo : lo + 1); // r <= C - gamma - 1: floor(G' / C), else ceil
+        out->E[r]   = N_L * Q_m * (r + gam < C ? lo : lo + 1); // r <= C - gamma - 1: floor(G' / C), else ceil
         out->off[r] = off;
         off += out->E[r];
     }
     return MI_LTE_OK;
+}
+
+int mi_lte_dlsch_layout(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t tx_mode, uint32_t rv, const mi_lte_dlsch_cfg *dlsch, mi_lte_dlsch_layout_t *out)
+{
+    return mi_lte_dlsch_layout_nl(tbs, G, Q_m, 1, tx_mode, rv, dlsch, out);
 }
 
 // The HARQ pool's buffer (include/mi_lte.h): the largest C * 3 (K + 4) int16 positions over the sizes of 36.213 Table 7.1.7.2.1-1 up to max_tbs
@@ -266,12 +274,12 @@ size_t mi_lte_harq_buffer_bytes(uint32_t max_tbs)
 
 // 36.212 5.1.1-5.1.4.1 for one transport block in the 3GPP mode (include/mi_lte.h): CRC24A, C blocks of K bits (each with CRC24B when
 // C > 1), turbo encoding with the exact interleaver, rate matching with the layout's N_cb and E_r, concatenation
-int mi_lte_dlsch_encode_3gpp(uint32_t tbs, const uint8_t *bits, uint32_t G, uint32_t Q_m, uint32_t tx_mode, uint32_t rv, const mi_lte_dlsch_cfg *dlsch,
-                             uint8_t *e_out)
+int mi_lte_dlsch_encode_3gpp_nl(uint32_t tbs, const uint8_t *bits, uint32_t G, uint32_t Q_m, uint32_t N_L, uint32_t tx_mode, uint32_t rv,
+                                const mi_lte_dlsch_cfg *dlsch, uint8_t *e_out)
 {
     if (!bits || !e_out) return MI_LTE_ERR_INVALID_ARG;
     mi_lte_dlsch_layout_t lay;
-    const int rc = mi_lte_dlsch_layout(tbs, G, Q_m, tx_mode, rv, dlsch, &lay);
+    const int rc = mi_lte_dlsch_layout_nl(tbs, G, Q_m, N_L, tx_mode, rv, dlsch, &lay);
     if (rc != MI_LTE_OK) return rc;
     const uint32_t K = lay.K, C = lay.C, nb = C == 1 ? K : K - 24;
     std::vector<uint8_t> b(lay.B), c(K), d(3 * (K + 4));
@@ -282,6 +290,33 @@ int mi_lte_dlsch_encode_3gpp(uint32_t tbs, const uint8_t *bits, uint32_t G, uint
         if (C > 1) synth::crc24b(c.data(), nb, c.data() + nb);
         synth::turbo_encode(c.data(), K, false, d.data());
         synth::rate_match(d.data(), K + 4, lay.N_cb, rv, lay.E[r], e_out + lay.off[r]);
+    }
+    return MI_LTE_OK;
+}
+
+int mi_lte_dlsch_encode_3gpp(uint32_t tbs, const uint8_t *bits, uint32_t G, uint32_t Q_m, uint32_t tx_mode, uint32_t rv, const mi_lte_dlsch_cfg *dlsch,
+                             uint8_t *e_out)
+{
+    return mi_lte_dlsch_encode_3gpp_nl(tbs, bits, G, Q_m, 1, tx_mode, rv, dlsch, e_out);
+}
+
+// 36.211 6.3.3.3 (layer mapping: x_l(i) = d(N_ant i + l)) and 6.3.4.3 (pre-coding for transmit diversity), in one step: output place n of
+// port p at y[p * M_symb + n].  Two ports: the pair (d(2i), d(2i+1)) leaves as (x0, x1) on port 0 and (-x1*, x0*) on port 1, all over sqrt 2.
+// Four ports: places 4i, 4i+1 carry the pair (d(4i), d(4i+1)) on ports (0, 2), places 4i+2, 4i+3 the pair (d(4i+2), d(4i+3)) on ports (1, 3);
+// the other two ports rest.
+int mi_lte_txdiv_precode(uint32_t N_ant, const float *d_re, const float *d_im, uint32_t M_symb, float *y_re, float *y_im)
+{
+    if (!(N_ant == 2 || N_ant == 4) || !d_re || !d_im || !y_re || !y_im || M_symb % N_ant) return MI_LTE_ERR_INVALID_ARG;
+    const float a = (float)(1 / std::sqrt(2.0));
+    std::fill(y_re, y_re + (size_t)N_ant * M_symb, 0.f);
+    std::fill(y_im, y_im + (size_t)N_ant * M_symb, 0.f);
+    for (uint32_t n = 0; n < M_symb; n += 2) {
+        const uint32_t pa = N_ant == 2 ? 0u : (n >> 1) & 1u, pb = N_ant == 2 ? 1u : pa + 2;
+        float *ar = y_re + (size_t)pa * M_symb, *ai = y_im + (size_t)pa * M_symb, *br = y_re + (size_t)pb * M_symb, *bi = y_im + (size_t)pb * M_symb;
+        ar[n]     = a * d_re[n];      ai[n]     = a * d_im[n];      // x0
+        br[n]     = -a * d_re[n + 1]; bi[n]     = a * d_im[n + 1];  // -x1*
+        ar[n + 1] = a * d_re[n + 1];  ai[n + 1] = a * d_im[n + 1];  // x1
+        br[n + 1] = a * d_re[n];      bi[n + 1] = -a * d_im[n];     // x0*
     }
     return MI_LTE_OK;
 }
@@ -475,6 +510,147 @@ int mi_lte_synth_dl_units_3gpp_payload_i8(const mi_lte_dl_cfg *cfg, uint32_t n_u
 {
     if (!dlsch || (n_alloc && n_units && !h_payload)) return MI_LTE_ERR_INVALID_ARG;
     return synth_dl_units(cfg, n_units, h_subfr_num, h_n_id_cell, N_pdcch_symbs, h_allocs, n_alloc, dlsch, chan, h_iq, nullptr, tbs_stride, h_payload);
+}
+
+// The transmit-diversity generator (include/mi_lte.h): a cell of 2 or 4 CRS ports, every allocation sent as 36.211 6.3.3.3 / 6.3.4.3 specify
+// (tx_mode 2) over the N_L = 2 code-block concatenation.  One grid and one OFDM signal per port; the ports share the unit's delay (co-located
+// antennas) and have a gain and a phase each; the receiver sees their sum.  A function of its own: the single-port generators above keep their
+// byte streams.
+int mi_lte_synth_dl_units_3gpp_txdiv_i8(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
+                                        uint32_t N_pdcch_symbs, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, const mi_lte_dlsch_cfg *dlsch,
+                                        const mi_lte_synth_channel *chan, const uint8_t *h_payload, uint32_t tbs_stride, int8_t *h_iq,
+                                        uint8_t *h_tx_bits)
+{
+    if (!cfg || !h_subfr_num || !h_n_id_cell || !chan || !h_iq || !dlsch || (n_alloc && !h_allocs)) return MI_LTE_ERR_INVALID_ARG;
+    if (!(cfg->N_ant == 2 || cfg->N_ant == 4)) return MI_LTE_ERR_INVALID_ARG; // (one port: mi_lte_synth_dl_units_3gpp_i8)
+    if (!synth::valid_grid(cfg->fft_size, cfg->N_rb_dl) || N_pdcch_symbs < 1 || N_pdcch_symbs > 4) return MI_LTE_ERR_INVALID_ARG;
+    const uint32_t P = cfg->N_ant;
+    for (uint32_t u = 0; u < n_units; u++) {
+        if (h_n_id_cell[u] > 503) return MI_LTE_ERR_INVALID_ARG;
+        for (uint32_t a = 0; a < n_alloc; a++) {
+            const mi_lte_pdsch_alloc &al = h_allocs[(size_t)u * n_alloc + a];
+            mi_lte_pdsch_alloc one = al;
+            one.tbs = 16; // the grid conditions; the transport block's are the layout's
+            mi_lte_dlsch_layout_t lay;
+            if (!synth::valid_alloc(one, cfg->N_rb_dl) || al.mod_type == 0 || al.tx_mode != 2 || al.n_pdcch_symbs > 4 ||
+                mi_lte_dlsch_layout_nl(al.tbs, 0, 2, 2, al.tx_mode, al.rv_idx, dlsch, &lay) != MI_LTE_OK || ((h_tx_bits || h_payload) && al.tbs > tbs_stride))
+                return MI_LTE_ERR_INVALID_ARG;
+        }
+    }
+    const uint32_t N = cfg->fft_size, sc = 2048 / N, cp0 = 160 / sc, cpe = 144 / sc, N_rb = cfg->N_rb_dl, half = 6 * N_rb, N_sc = 12 * N_rb;
+    const size_t   unit_len = mi_lte_synth_unit_len(N);
+    uint32_t       first_sc, last_sc;
+    synth::sync_window(N_rb, &first_sc, &last_sc);
+    synth::Rng rng(chan->seed);
+    std::vector<float>  g_re((size_t)P * 16 * N_sc), g_im((size_t)P * 16 * N_sc);
+    std::vector<double> xr(N), xi(N), t_re(P * unit_len), t_im(P * unit_len), s_re(unit_len), s_im(unit_len);
+    const float         r2 = (float)(1 / std::sqrt(2.0));
+
+    for (uint32_t u = 0; u < n_units; u++) {
+        const uint32_t sf = h_subfr_num[u] % 10, cell = h_n_id_cell[u];
+        std::fill(g_re.begin(), g_re.end(), 0.f);
+        std::fill(g_im.begin(), g_im.end(), 0.f);
+        // CRS of every port over this subframe and the first two symbols of the next (36.211 6.10.1): ports 0 / 1 in symbols 0 and 4 of a slot
+        // with offsets 0 / 3 and 3 / 0, ports 2 / 3 in symbol 1 with offsets 3 (n_s mod 2) and 3 + 3 (n_s mod 2); where one port has a
+        // reference signal the others send nothing
+        for (uint32_t p = 0; p < P; p++)
+            for (uint32_t s = 0; s < 16; s++) {
+                const uint32_t l = s % 7, ns = (2 * sf + s / 7) % 20;
+                if (p < 2 ? !(l == 0 || l == 4) : l != 1) continue;
+                const uint32_t v = p == 0 ? (l == 0 ? 0 : 3) : p == 1 ? (l == 0 ? 3 : 0) : p == 2 ? 3 * (ns % 2) : 3 + 3 * (ns % 2);
+                uint8_t        c[440];
+                synth::gold(1024 * (7 * (ns + 1) + l + 1) * (2 * cell + 1) + 2 * cell + 1, 440, c);
+                for (uint32_t j = 0; j < 2 * N_rb; j++) {
+                    const uint32_t k = 6 * j + (v + cell % 6) % 6, mp = j + 110 - N_rb;
+                    g_re[((size_t)p * 16 + s) * N_sc + k] = r2 * (1 - 2 * (float)c[2 * mp]);
+                    g_im[((size_t)p * 16 + s) * N_sc + k] = r2 * (1 - 2 * (float)c[2 * mp + 1]);
+                }
+            }
+        for (uint32_t a = 0; a < n_alloc; a++) {
+            const mi_lte_pdsch_alloc &al = h_allocs[(size_t)u * n_alloc + a];
+            const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : 2, cfi = al.n_pdcch_symbs ? al.n_pdcch_symbs : N_pdcch_symbs;
+            std::vector<uint32_t> res; // the allocation's resource elements in mapping order: symbol -> PRB -> sub-carrier
+            for (uint32_t L = cfi; L < 14; L++)
+                for (uint32_t pi = 0; pi < al.N_prb; pi++)
+                    for (uint32_t j = 0; j < 12; j++) {
+                        const uint32_t scx = al.prb[L / 7][pi] * 12 + j;
+                        if (!synth::pdsch_re_excluded(P, cell, sf, L, j, scx, first_sc, last_sc)) res.push_back(L * N_sc + scx);
+                    }
+            const uint32_t M = (uint32_t)res.size(), G = M * Qm;
+            if (M % P) return MI_LTE_ERR_UNSUPPORTED; // (no allocation on the grid has such a count: tests/test_fuzz_cpu.py)
+            std::vector<uint8_t> b(al.tbs), e(G), c(G);
+            for (uint32_t i = 0; i < al.tbs; i++) b[i] = (uint8_t)(rng.next() & 1u);
+            if (h_payload) // the caller's transport block; the draws above keep the rest of the stream where it is without one
+                for (uint32_t i = 0; i < al.tbs; i++) b[i] = h_payload[((size_t)u * n_alloc + a) * tbs_stride + i] & 1u;
+            if (h_tx_bits) memcpy(h_tx_bits + ((size_t)u * n_alloc + a) * tbs_stride, b.data(), al.tbs);
+            const int rc = mi_lte_dlsch_encode_3gpp_nl(al.tbs, b.data(), G, Qm, 2, al.tx_mode, al.rv_idx, dlsch, e.data());
+            if (rc != MI_LTE_OK) return rc;
+            synth::gold((al.rnti << 14) | (sf << 9) | cell, G, c.data());
+            for (uint32_t i = 0; i < G; i++) e[i] ^= c[i];
+            std::vector<float> m_re(M), m_im(M), y_re((size_t)P * M), y_im((size_t)P * M);
+            synth::modulate(e.data(), M, al.mod_type, m_re.data(), m_im.data());
+            if (M && mi_lte_txdiv_precode(P, m_re.data(), m_im.data(), M, y_re.data(), y_im.data()) != MI_LTE_OK) return MI_LTE_ERR_INVALID_ARG;
+            for (uint32_t p = 0; p < P; p++)
+                for (uint32_t i = 0; i < M; i++) {
+                    g_re[(size_t)p * 16 * N_sc + res[i]] = y_re[(size_t)p * M + i];
+                    g_im[(size_t)p * 16 * N_sc + res[i]] = y_im[(size_t)p * M + i];
+                }
+        }
+        // OFDM modulation of every port's 14 + 2 symbols (36.211 6.12)
+        std::fill(t_re.begin(), t_re.end(), 0.0);
+        std::fill(t_im.begin(), t_im.end(), 0.0);
+        for (uint32_t p = 0; p < P; p++) {
+            double *tr = t_re.data() + p * unit_len, *ti = t_im.data() + p * unit_len;
+            const float *gr = g_re.data() + (size_t)p * 16 * N_sc, *gi = g_im.data() + (size_t)p * 16 * N_sc;
+            size_t pos = 0;
+            for (uint32_t s = 0; s < 16 && pos < unit_len; s++) {
+                const uint32_t cp = (s % 7 == 0) ? cp0 : cpe;
+                std::fill(xr.begin(), xr.end(), 0.0);
+                std::fill(xi.begin(), xi.end(), 0.0);
+                for (uint32_t i = 0; i < half; i++) {
+                    xr[i + 1]     = gr[s * N_sc + half + i];     xi[i + 1]     = gi[s * N_sc + half + i];
+                    xr[N - 1 - i] = gr[s * N_sc + half - 1 - i]; xi[N - 1 - i] = gi[s * N_sc + half - 1 - i];
+                }
+                synth::idft(xr, xi);
+                for (uint32_t i = 0; i < cp && pos + i < unit_len; i++) { tr[pos + i] = xr[N - cp + i]; ti[pos + i] = xi[N - cp + i]; }
+                for (uint32_t i = 0; i < N && pos + cp + i < unit_len; i++) { tr[pos + cp + i] = xr[i]; ti[pos + cp + i] = xi[i]; }
+                pos += cp + N;
+            }
+        }
+        // the channel: one integer delay for the unit, then a gain and a phase per port, in port order; the ports summed; AWGN relative to the
+        // sum's power; one int8 scale per unit from the sum's peak.  max_delay < 0: no delay and no phase
+        const bool     fixed = chan->max_delay < 0;
+        const double   ud    = rng.uniform();
+        const uint32_t dly   = fixed ? 0u : (uint32_t)(ud * (chan->max_delay + 0.999));
+        std::fill(s_re.begin(), s_re.end(), 0.0);
+        std::fill(s_im.begin(), s_im.end(), 0.0);
+        for (uint32_t p = 0; p < P; p++) {
+            const double gain = chan->gain_min + (chan->gain_max - chan->gain_min) * rng.uniform();
+            const double up = rng.uniform(), ph = fixed ? 0.0 : 2.0 * M_PI * up - M_PI;
+            const double hr = gain * std::cos(ph), hi = gain * std::sin(ph);
+            const double *tr = t_re.data() + p * unit_len, *ti = t_im.data() + p * unit_len;
+            for (size_t i = dly; i < unit_len; i++) {
+                s_re[i] += hr * tr[i - dly] - hi * ti[i - dly];
+                s_im[i] += hr * ti[i - dly] + hi * tr[i - dly];
+            }
+        }
+        double p_sig = 0, peak = 0;
+        for (size_t i = 0; i < unit_len; i++) {
+            p_sig += s_re[i] * s_re[i] + s_im[i] * s_im[i];
+            peak = std::max(peak, std::max(std::fabs(s_re[i]), std::fabs(s_im[i])));
+        }
+        p_sig /= (double)unit_len;
+        const double scale = peak > 0 ? chan->peak / peak : 1.0;
+        const double sigma = chan->snr_db >= 200 ? 0.0 : std::sqrt(p_sig / std::pow(10.0, chan->snr_db / 10.0) / 2.0);
+        int8_t *o = h_iq + (size_t)u * unit_len * 2;
+        for (size_t i = 0; i < unit_len; i++) {
+            const double yr = s_re[i] + sigma * rng.normal(), yi = s_im[i] + sigma * rng.normal();
+            const long   qr = std::lround(yr * scale), qi = std::lround(yi * scale);
+            o[2 * i]     = (int8_t)std::max(-127L, std::min(127L, qr));
+            o[2 * i + 1] = (int8_t)std::max(-127L, std::min(127L, qi));
+        }
+    }
+    return MI_LTE_OK;
 }
 
 

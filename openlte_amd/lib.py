@@ -50,12 +50,16 @@ class DlschLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("C", "K", "B", "N_cb", "k0")] + [("E", C.c_uint32 * 13), ("off", C.c_uint32 * 13)]
 
 
-def dlsch_layout(tbs, G, Q_m, tx_mode=1, rv=0, n_soft=1237248, m_dl_harq=8):
+def dlsch_layout(tbs, G, Q_m, tx_mode=1, rv=0, n_soft=1237248, m_dl_harq=8, n_l=None):
     """mi_lte_dlsch_layout (host arithmetic): 36.212 segmentation and code-block concatenation of one transport block.  Returns a dict
-    {C, K, B, N_cb, k0, E: [C], off: [C]}; raises MiLteError with the status on a refusal."""
+    {C, K, B, N_cb, k0, E: [C], off: [C]}; raises MiLteError with the status on a refusal.  n_l: mi_lte_dlsch_layout_nl with that N_L
+    (2: a transmit-diversity plan)."""
     L = load_library()
     out = DlschLayout()
-    rc = L.mi_lte_dlsch_layout(tbs, G, Q_m, tx_mode, rv, C.byref(DlschCfg(n_soft, m_dl_harq)), C.byref(out))
+    if n_l is None:
+        rc = L.mi_lte_dlsch_layout(tbs, G, Q_m, tx_mode, rv, C.byref(DlschCfg(n_soft, m_dl_harq)), C.byref(out))
+    else:
+        rc = L.mi_lte_dlsch_layout_nl(tbs, G, Q_m, n_l, tx_mode, rv, C.byref(DlschCfg(n_soft, m_dl_harq)), C.byref(out))
     if rc != 0:
         raise MiLteError("mi_lte_dlsch_layout(%d, %d, %d) failed: %d" % (tbs, G, Q_m, rc), rc)
     return {"C": out.C, "K": out.K, "B": out.B, "N_cb": out.N_cb, "k0": out.k0, "E": list(out.E[:out.C]), "off": list(out.off[:out.C])}
@@ -406,6 +410,10 @@ def load_library():
     L.mi_lte_pdsch_plan_create_3gpp.argtypes = [vp, C.POINTER(DlCfg), u32, C.POINTER(DlschCfg), vp, u32, C.POINTER(vp)]
     L.mi_lte_pdsch_alloc_decodable_3gpp.argtypes = [C.POINTER(DlCfg), C.POINTER(DlschCfg), C.POINTER(PdschAlloc), u32]
     L.mi_lte_pdsch_alloc_decodable_3gpp.restype = C.c_int
+    L.mi_lte_dlsch_layout_nl.argtypes = [u32, u32, u32, u32, u32, u32, C.POINTER(DlschCfg), C.POINTER(DlschLayout)]
+    L.mi_lte_pdsch_plan_create_3gpp_txdiv.argtypes = L.mi_lte_pdsch_plan_create_3gpp.argtypes
+    L.mi_lte_pdsch_alloc_decodable_3gpp_txdiv.argtypes = L.mi_lte_pdsch_alloc_decodable_3gpp.argtypes
+    L.mi_lte_pdsch_alloc_decodable_3gpp_txdiv.restype = C.c_int
     L.mi_lte_pdsch_plan_cb_soft.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]
     L.mi_lte_pdsch_plan_cb_ok.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_pdsch_plan_set_demapper.argtypes = [vp, u32, C.c_float]
@@ -547,15 +555,16 @@ class PdschPlan:
     """mi_lte_pdsch_plan: device copy of an allocation list, grouped by code-block size.  allocs=None: a dynamic plan of the given
     capacity (mi_lte_pdsch_plan_create_dynamic), filled and re-filled by assign()."""
 
-    def __init__(self, ctx, cfg, n_pdcch_symbs, allocs, max_alloc=0, max_soft_bytes=0, dlsch=None):
-        """dlsch: a DlschCfg -- a plan in the 3GPP transport-block mode (mi_lte_pdsch_plan_create_3gpp)."""
+    def __init__(self, ctx, cfg, n_pdcch_symbs, allocs, max_alloc=0, max_soft_bytes=0, dlsch=None, txdiv=False):
+        """dlsch: a DlschCfg -- a plan in the 3GPP transport-block mode (mi_lte_pdsch_plan_create_3gpp; txdiv: on a cell of two or four ports,
+        mi_lte_pdsch_plan_create_3gpp_txdiv)."""
         self.ctx = ctx
         h = C.c_void_p()
         if dlsch is not None:
             self.n_alloc = len(allocs)
             arr = (PdschAlloc * len(allocs))(*allocs)
-            ctx._check(ctx.L.mi_lte_pdsch_plan_create_3gpp(ctx.h, C.byref(cfg), n_pdcch_symbs, C.byref(dlsch), C.cast(arr, C.c_void_p),
-                                                           len(allocs), C.byref(h)))
+            create = ctx.L.mi_lte_pdsch_plan_create_3gpp_txdiv if txdiv else ctx.L.mi_lte_pdsch_plan_create_3gpp
+            ctx._check(create(ctx.h, C.byref(cfg), n_pdcch_symbs, C.byref(dlsch), C.cast(arr, C.c_void_p), len(allocs), C.byref(h)))
             self.h, self.tbs, self._arr = h, [a.tbs for a in allocs], arr
         elif allocs is None:
             ctx._check(ctx.L.mi_lte_pdsch_plan_create_dynamic(ctx.h, C.byref(cfg), max_alloc, max_soft_bytes, C.byref(h)))
@@ -1482,6 +1491,11 @@ class Context:
         """A plan in the 3GPP transport-block mode (36.212 segmentation, any tbs of Table 7.1.7.2.1-1): BCJR x 8 with the exact interleaver
         by default; n_soft / m_dl_harq size the soft buffer (no default: the UE category's N_soft)."""
         return PdschPlan(self, cfg, n_pdcch_symbs, allocs, dlsch=DlschCfg(n_soft, m_dl_harq))
+
+    def pdsch_plan_3gpp_txdiv(self, cfg, n_pdcch_symbs, allocs, n_soft, m_dl_harq=8):
+        """pdsch_plan_3gpp for a cell of two or four CRS ports (mi_lte_pdsch_plan_create_3gpp_txdiv): every allocation in transmit diversity
+        (tx_mode 2), code-block concatenation with N_L = 2; set_demapper(DEMAP_MAXLOG) runs k_pdsch_demod_llr_txd."""
+        return PdschPlan(self, cfg, n_pdcch_symbs, allocs, dlsch=DlschCfg(n_soft, m_dl_harq), txdiv=True)
 
     def harq_pool(self, n_buf, max_tbs=75376):
         """A HARQ soft-buffer pool (mi_lte_harq_pool_create) for the 3GPP plans of this context."""

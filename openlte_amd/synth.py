@@ -34,6 +34,10 @@ def _lib():
         L.mi_lte_synth_dl_units_3gpp_payload_i8.argtypes = [C.POINTER(DlCfg), C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                             C.POINTER(DlschCfg), C.POINTER(SynthChannel), C.c_void_p, C.c_uint32, _i8p]
         L.mi_lte_dlsch_encode_3gpp.argtypes = [C.c_uint32, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DlschCfg), _u8p]
+        L.mi_lte_dlsch_encode_3gpp_nl.argtypes = [C.c_uint32, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DlschCfg), _u8p]
+        L.mi_lte_txdiv_precode.argtypes = [C.c_uint32, _f32p, _f32p, C.c_uint32, _f32p, _f32p]
+        L.mi_lte_synth_dl_units_3gpp_txdiv_i8.argtypes = [C.POINTER(DlCfg), C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                          C.POINTER(DlschCfg), C.POINTER(SynthChannel), C.c_void_p, C.c_uint32, _i8p, C.c_void_p]
         L.mi_lte_synth_ul_unit_len.argtypes = [C.c_uint32]
         L.mi_lte_synth_ul_unit_len.restype = C.c_size_t
         L.mi_lte_synth_ul_units_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(UlCfg), C.c_uint32, _u32p, _u32p, C.c_void_p, C.c_uint32,
@@ -135,14 +139,54 @@ def dl_units_3gpp(cfg, subfr_num, n_id_cell, allocs, n_alloc, n_soft, m_dl_harq=
     return iq, tx
 
 
-def dlsch_encode_3gpp(bits, G, Q_m, tx_mode=1, rv=0, n_soft=1237248, m_dl_harq=8):
-    """mi_lte_dlsch_encode_3gpp: the G rate-matched bits (one per byte) of the transport block `bits`."""
+def dlsch_encode_3gpp(bits, G, Q_m, tx_mode=1, rv=0, n_soft=1237248, m_dl_harq=8, n_l=None):
+    """mi_lte_dlsch_encode_3gpp: the G rate-matched bits (one per byte) of the transport block `bits`.  n_l: mi_lte_dlsch_encode_3gpp_nl with
+    that N_L (2: transmit diversity)."""
     bits = np.ascontiguousarray(bits, np.uint8)
     e = np.zeros(max(G, 1), np.uint8)
-    rc = _lib().mi_lte_dlsch_encode_3gpp(len(bits), bits, G, Q_m, tx_mode, rv, C.byref(DlschCfg(n_soft, m_dl_harq)), e)
+    if n_l is None:
+        rc = _lib().mi_lte_dlsch_encode_3gpp(len(bits), bits, G, Q_m, tx_mode, rv, C.byref(DlschCfg(n_soft, m_dl_harq)), e)
+    else:
+        rc = _lib().mi_lte_dlsch_encode_3gpp_nl(len(bits), bits, G, Q_m, n_l, tx_mode, rv, C.byref(DlschCfg(n_soft, m_dl_harq)), e)
     if rc != 0:
         raise MiLteError("mi_lte_dlsch_encode_3gpp failed: %d" % rc, rc)
     return e[:G]
+
+
+def txdiv_precode(n_ant, d):
+    """mi_lte_txdiv_precode: complex64 [n_ant, M_symb], what each port sends for the modulation symbols d (36.211 6.3.3.3 / 6.3.4.3)."""
+    d = np.asarray(d, np.complex64).reshape(-1)
+    re, im = np.ascontiguousarray(d.real, np.float32), np.ascontiguousarray(d.imag, np.float32)
+    y_re, y_im = np.zeros((max(n_ant, 1), max(len(d), 1)), np.float32), np.zeros((max(n_ant, 1), max(len(d), 1)), np.float32)
+    rc = _lib().mi_lte_txdiv_precode(n_ant, re, im, len(d), y_re.reshape(-1), y_im.reshape(-1))
+    if rc != 0:
+        raise MiLteError("mi_lte_txdiv_precode failed: %d" % rc, rc)
+    return (y_re + 1j * y_im)[:, :len(d)].astype(np.complex64)
+
+
+def dl_units_3gpp_txdiv(cfg, subfr_num, n_id_cell, allocs, n_alloc, n_soft, m_dl_harq=8, n_pdcch_symbs=2, gain=(0.5, 1.5), max_delay=8,
+                        snr_db=30.0, peak=100.0, seed=1, payload=None):
+    """dl_units_3gpp for a cell of cfg.N_ant = 2 or 4 ports (mi_lte_synth_dl_units_3gpp_txdiv_i8): CRS on every port, every allocation
+    (tx_mode 2) in transmit diversity over the N_L = 2 concatenation, one delay per unit and a gain and a phase per port, the ports summed.
+    payload as in dl_units_3gpp.  Returns (iq int8 [n, unit_len, 2], tx uint8 [n, n_alloc, max tbs])."""
+    n = len(subfr_num)
+    iq = np.zeros((n, unit_len(cfg.fft_size), 2), np.int8)
+    max_tbs = max([a.tbs for a in allocs], default=8)
+    tx = np.zeros((n, max(n_alloc, 1), max_tbs), np.uint8)
+    arr = (PdschAlloc * max(len(allocs), 1))(*allocs)
+    ch = SynthChannel(gain[0], gain[1], float(max_delay), float(snr_db), float(peak), int(seed))
+    pl, stride = None, max_tbs
+    if payload is not None:
+        pl = np.ascontiguousarray(payload, np.uint8)
+        if pl.ndim != 3 or pl.shape[0] != n or pl.shape[1] != max(n_alloc, 1) or pl.shape[2] < max_tbs:
+            raise ValueError("payload: uint8 [n_units, n_alloc, >= max tbs]")
+        tx, stride = np.zeros(pl.shape, np.uint8), pl.shape[2]
+    rc = _lib().mi_lte_synth_dl_units_3gpp_txdiv_i8(C.byref(cfg), n, np.ascontiguousarray(subfr_num, np.uint32), np.ascontiguousarray(n_id_cell, np.uint32),
+                                                    n_pdcch_symbs, C.cast(arr, C.c_void_p), n_alloc, C.byref(DlschCfg(n_soft, m_dl_harq)), C.byref(ch),
+                                                    None if pl is None else pl.ctypes.data, stride, iq, tx.ctypes.data)
+    if rc != 0:
+        raise MiLteError("mi_lte_synth_dl_units_3gpp_txdiv_i8 failed: %d" % rc, rc)
+    return iq, tx[:, :, :max_tbs].copy()
 
 
 def ul_unit_len(fft_size=2048):
