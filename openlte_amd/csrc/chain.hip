@@ -389,149 +389,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
 // ---- MI_LTE_DEMAP_MAXLOG (include/mi_lte.h, "PDSCH, 3GPP mode: max-log soft-decision demapping"): the 3GPP plans' opt-in demapper.
 // The LLR arithmetic (llr_axis, llr_byte) is demap_llr.h's, shared with the uplink's demapper.
 
-// k_pdsch_demod's single-port path with that demapper in place of the reference's: same pair table, scrambling words, thread per (pair,
-// sub-carrier), LDS assembly and soft-bit layout.  gain > 0: g = gain.  gain == 0: a first sweep over the allocation's estimate planes sums
-// w (per thread, then inside each wave, then over the waves in LDS, always in that order: a run is reproducible) and
-// g = T / (4 A^2 wbar) (T = auto_t: MI_LTE_DEMAP_AUTO_T), rounded to float -- the value llr_gain[allocation] reports is the value the soft bits were scaled with.
+// One kernel for the single-port plans (N_ANT = 1) and the transmit-diversity plans (N_ANT = 2, 4: include/mi_lte.h, "PDSCH, 3GPP mode: transmit
+// diversity"): k_pdsch_demod's pair table, scrambling words, thread per (pair, sub-carrier), LDS assembly and soft-bit layout over the N_ANT-port
+// extraction, with that demapper in place of the reference's.  Every thread does the symbol of its own resource element s and hands
+// (t, w) to llr_axis / llr_byte.  One port: t = y(s) conj(h(s)), w = |h(s)|^2.  Two or four ports: the other element o of the thread's pair is the
+// neighbouring set bit of the same 12-bit mask -- the next one for an even RE index, the previous one for an odd one -- and only where the mask
+// has none (the pair straddles two PRBs, or next to the PBCH / PSS / SSS window two symbols) a search of the table.  Both symbols of a pair have
+// one form,
+//     z = conj(h_pa(s)) y(s) +- h_pb(o) conj(y(o)),  w = (|h_pa(s)|^2 + |h_pb(o)|^2) / 2     (+: even index, -: odd),
+// so a thread loads two y and two h values, and t = z / sqrt 2.
+// gain > 0: g = gain.  gain == 0: a first sweep over the allocation's estimate planes sums w (per thread, then inside each wave, then over the
+// waves' LDS slots, always in that order and in double: a run is reproducible) and g = T / (4 A^2 wbar) (T = auto_t: MI_LTE_DEMAP_AUTO_T),
+// rounded to float -- the value llr_gain[allocation] reports is the value the soft bits were scaled with.
+template <uint32_t N_ANT>
 __global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict__ subframes, DemodGeom g, const mi_lte_pdsch_alloc *__restrict__ allocs,
                                                          const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell, GoldTables gt,
                                                          int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len,
                                                          uint32_t max_pairs, uint32_t max_words, uint32_t e_lds_cap, float gain, float auto_t,
                                                          float *__restrict__ llr_gain)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // tab[max_pairs+1] (offset, mask | position) | cw[...] | soft bits
-    __shared__ double w_wave[4];
-    const uint32_t a_idx = blockIdx.x;
-    const mi_lte_pdsch_alloc &al = allocs[a_idx];
-    const uint32_t unit = al.unit, sf = subfr_num[unit], cell = n_id_cell[unit], N_prb = al.N_prb;
-    const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : 2; // (a 3GPP plan holds no BPSK allocation)
-    uint2    *tab = reinterpret_cast<uint2 *>(smu);
-    uint32_t *cw  = smu + ((2 * (max_pairs + 1) + 3u) & ~3u);
-    uint32_t first_sc, last_sc;
-    sync_window(g.N_rb_dl, first_sc, last_sc);
-    const uint32_t cfi = al.n_pdcch_symbs ? al.n_pdcch_symbs : g.cfi;
-    const uint32_t n_pairs = 14 * N_prb, pair0 = cfi * N_prb;
-    const uint32_t c_init = ((al.rnti << 14) | (0u << 13) | (sf << 9) | cell) & 0x7FFFFFFFu;
-    if (threadIdx.x < 64) pair_table_scan(tab, al, 1u, cell, sf, cfi, n_pairs, first_sc, last_sc);
-    else {
-        const uint32_t n_words_ub = ((n_pairs - pair0) * 12 * Qm + 31) / 32;
-        for (uint32_t w = threadIdx.x - 64; w <= n_words_ub; w += blockDim.x - 64) cw[w] = gold_word(gt, c_init, w);
-    }
-    __syncthreads();
-    const uint32_t M_symb = tab[n_pairs].x, N_bits = M_symb * Qm;
-    if (threadIdx.x == 0) e_len[a_idx] = N_bits;
-
-    const float *base = subframes + (size_t)unit * g.sf_stride;
-    const char  *y_re_p = reinterpret_cast<const char *>(base), *y_im_p = y_re_p + 16 * N_SC_MAX * 4;
-    const char  *h_re_p = y_im_p + 16 * N_SC_MAX * 4, *h_im_p = h_re_p + 16 * N_SC_MAX * 4;
-    constexpr int  UNR = 4;
-    const uint32_t q_thr = threadIdx.x / 12, j = threadIdx.x - 12 * q_thr, below = (1u << j) - 1u;
-    const bool     lane_on = threadIdx.x < 252;
-    // byte offset of the thread's resource element in pair q (one register serves the four planes), whether it carries PDSCH, its index
-    auto element = [&](uint32_t q, uint32_t &ob, uint32_t &idx) __attribute__((always_inline)) -> bool {
-        const bool  in = lane_on && q < n_pairs;
-        const uint2 pr = tab[in ? q : 0u];
-        const bool  on = in && ((pr.y >> j) & 1u);
-        idx = pr.x + __popc(pr.y & below);
-        ob  = on ? ((pr.y >> 12) + j) << 2 : 0u;
-        return on;
-    };
-    double gd = (double)gain;
-    if (gain == 0.0f) { // wbar: the mean of |h|^2 over the allocation's resource elements
-        double part = 0.0;
-        for (uint32_t qb = pair0; qb < n_pairs; qb += 21 * UNR) {
-            float hr[UNR], hi[UNR];
-            bool  on[UNR];
-#pragma unroll
-            for (int r = 0; r < UNR; r++) {
-                uint32_t ob, idx;
-                on[r] = element(qb + 21 * r + q_thr, ob, idx);
-                hr[r] = *reinterpret_cast<const float *>(h_re_p + ob);
-                hi[r] = *reinterpret_cast<const float *>(h_im_p + ob);
-            }
-#pragma unroll
-            for (int r = 0; r < UNR; r++)
-                if (on[r]) part += (double)hr[r] * hr[r] + (double)hi[r] * hi[r];
-        }
-        for (int o = 32; o; o >>= 1) part += __shfl_xor(part, o);
-        if ((threadIdx.x & 63u) == 0) w_wave[threadIdx.x >> 6] = part;
-        __syncthreads();
-        const double wbar = (((w_wave[0] + w_wave[1]) + w_wave[2]) + w_wave[3]) / (double)M_symb;
-        const double a4 = al.mod_type == 3 ? 4.0 / 42 : al.mod_type == 2 ? 4.0 / 10 : 2.0; // 4 A^2
-        const float  gf = (float)((double)auto_t / (a4 * wbar));
-        gd = (wbar > 0.0 && fabsf(gf) <= 3.4028234e38f) ? (double)gf : 0.0; // wbar 0, NaN or infinite, or a gain past float: every soft bit 0
-    }
-    if (threadIdx.x == 0) llr_gain[a_idx] = (float)gd;
-
-    int8_t    *e      = e_base + (size_t)e_off[a_idx] * 64;
-    int8_t    *e_lds  = reinterpret_cast<int8_t *>(cw + max_words);
-    const bool via_lds = N_bits <= e_lds_cap;
-    auto run = [&](auto modc, auto *dst) __attribute__((always_inline)) {
-        constexpr uint32_t MOD = decltype(modc)::value, QM = MOD == 3 ? 6 : MOD == 2 ? 4 : 2;
-        for (uint32_t qb = pair0; qb < n_pairs; qb += 21 * UNR) {
-            float    yr[UNR], yi[UNR], hr[UNR], hi[UNR];
-            uint32_t idx[UNR];
-            bool     on[UNR];
-#pragma unroll
-            for (int r = 0; r < UNR; r++) {
-                uint32_t ob;
-                on[r] = element(qb + 21 * r + q_thr, ob, idx[r]);
-                yr[r] = *reinterpret_cast<const float *>(y_re_p + ob);
-                yi[r] = *reinterpret_cast<const float *>(y_im_p + ob);
-                hr[r] = *reinterpret_cast<const float *>(h_re_p + ob);
-                hi[r] = *reinterpret_cast<const float *>(h_im_p + ob);
-            }
-#pragma unroll
-            for (int r = 0; r < UNR; r++) {
-                if (!on[r]) continue;
-                const double Yr = yr[r], Yi = yi[r], Hr = hr[r], Hi = hi[r];
-                const double w = Hr * Hr + Hi * Hi;
-                double li[3], lq[3];
-                llr_axis<MOD>(Yr * Hr + Yi * Hi, w, li);
-                llr_axis<MOD>(Yi * Hr - Yr * Hi, w, lq);
-                // descramble (c bit set -> negate) and store: Q_m idx is even, so the bytes leave in pairs (bit 2k on the real axis, 2k + 1 on the imaginary)
-                const uint32_t n0 = idx[r] * QM, c = __builtin_amdgcn_alignbit(cw[(n0 >> 5) + 1], cw[n0 >> 5], n0 & 31);
-#pragma unroll
-                for (uint32_t k = 0; k < QM; k += 2) {
-                    const int vi = llr_byte(gd, li[k >> 1]), vq = llr_byte(gd, lq[k >> 1]);
-                    const int lo = ((c >> k) & 1u) ? -vi : vi, hi8 = ((c >> (k + 1)) & 1u) ? -vq : vq;
-                    *reinterpret_cast<uint16_t *>(dst + n0 + k) = (uint16_t)((lo & 0xFF) | ((hi8 & 0xFF) << 8));
-                }
-            }
-        }
-    };
-    auto per_mod = [&](auto *dst) __attribute__((always_inline)) {
-        switch (al.mod_type) {
-        case 1:  run(std::integral_constant<uint32_t, 1>{}, dst); break;
-        case 2:  run(std::integral_constant<uint32_t, 2>{}, dst); break;
-        default: run(std::integral_constant<uint32_t, 3>{}, dst); break;
-        }
-    };
-    if (via_lds) {
-        per_mod(e_lds);
-        __syncthreads();
-        const uint32_t nq = (N_bits + 15) >> 4; // the allocation's slot in e_base is padded to 64 bytes
-        for (uint32_t w = threadIdx.x; w < nq; w += blockDim.x) reinterpret_cast<uint4 *>(e)[w] = reinterpret_cast<const uint4 *>(e_lds)[w];
-    } else
-        per_mod(e);
-}
-
-// MI_LTE_DEMAP_MAXLOG on a transmit-diversity plan (include/mi_lte.h, "PDSCH, 3GPP mode: transmit diversity"): k_pdsch_demod_llr's pair table,
-// scrambling words, thread per (pair, sub-carrier), LDS assembly and soft-bit layout over the N_ANT-port extraction.  Every thread does the
-// symbol of its own resource element s; the other element o of its pair is the neighbouring set bit of the same 12-bit mask -- the next one for
-// an even RE index, the previous one for an odd one -- and only where the mask has none (the pair straddles two PRBs, or next to the PBCH / PSS /
-// SSS window two symbols) a search of the table.  Both symbols of a pair have one form,
-//     z = conj(h_pa(s)) y(s) +- h_pb(o) conj(y(o)),  w = (|h_pa(s)|^2 + |h_pb(o)|^2) / 2     (+: even index, -: odd),
-// so a thread loads two y and two h values, and t = z / sqrt 2 and w go into llr_axis / llr_byte as the single-port kernel's z and w do.
-// The automatic gain's wbar is summed as there: per thread, inside each wave, over the waves' LDS slots in order, in double.
-template <uint32_t N_ANT>
-__global__ __launch_bounds__(256) void k_pdsch_demod_llr_txd(const float *__restrict__ subframes, DemodGeom g, const mi_lte_pdsch_alloc *__restrict__ allocs,
-                                                             const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell, GoldTables gt,
-                                                             int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len,
-                                                             uint32_t max_pairs, uint32_t max_words, uint32_t e_lds_cap, float gain, float auto_t,
-                                                             float *__restrict__ llr_gain)
-{
-    static_assert(N_ANT == 2 || N_ANT == 4, "transmit diversity: two or four ports");
+    static_assert(N_ANT == 1 || N_ANT == 2 || N_ANT == 4, "one port, or transmit diversity on two or four");
     extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // tab[max_pairs+1] (offset, mask | position) | cw[...] | soft bits
     __shared__ double w_wave[4];
     const uint32_t a_idx = blockIdx.x;
@@ -559,10 +436,10 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr_txd(const float *__rest
     const float *base = subframes + (size_t)unit * g.sf_stride;
     const char  *y_re_p = reinterpret_cast<const char *>(base), *y_im_p = y_re_p + PL;
     const char  *h_re_p = y_im_p + PL, *h_im_p = h_re_p + N_ANT * PL;
-    constexpr int  UNR = 4; // symbols in flight per thread: eight loads each
+    constexpr int  UNR = 4; // symbols in flight per thread: four loads each on one port, eight on two or four
     const uint32_t q_thr = threadIdx.x / 12, j = threadIdx.x - 12 * q_thr, below = (1u << j) - 1u;
     const bool     lane_on = threadIdx.x < 252;
-    auto locate = [&](uint32_t idx) -> uint32_t { // RE index -> L * 1200 + sub-carrier (k_pdsch_demod's)
+    auto locate = [&](uint32_t idx) -> uint32_t { // RE index -> L * 1200 + sub-carrier (k_pdsch_demod's; two or four ports only)
         uint32_t lo = pair0, hi = n_pairs; // tab[lo].x <= idx < tab[hi].x
         while (hi - lo > 1) {
             const uint32_t mid = (lo + hi) >> 1;
@@ -573,30 +450,33 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr_txd(const float *__rest
         for (; r; r--) m &= m - 1;
         return (t.y >> 12) + (uint32_t)__builtin_ctz(m | 0x1000u);
     };
-    // The thread's symbol in table pair q: byte offsets inside a plane of its own resource element (os) and of the other element of its pair (oo),
-    // of its pair's two port planes (pa, pb), all 0 where the thread has no symbol (every load stays inside the unit); the RE index
+    // The thread's symbol in table pair q: whether it has one, its RE index, the byte offset inside a plane of its own resource element (os) and,
+    // on two or four ports, of the other element of its pair (oo) and of its pair's two port planes (pa, pb).  The offsets are 0 where the thread
+    // has no symbol (every load stays inside the unit)
     struct Elem { uint32_t os, oo, pa, pb, idx; bool on; };
     auto element = [&](uint32_t q) __attribute__((always_inline)) -> Elem {
         const bool     in  = lane_on && q < n_pairs;
         const uint2    pr  = tab[in ? q : 0u];
         const uint32_t lowm = pr.y & below, idx = pr.x + __popc(lowm);
-        const bool     on  = in && ((pr.y >> j) & 1u) && idx < M_symb;
-        const uint32_t up  = (pr.y & 0xFFFu) >> (j + 1); // the mask's elements above this one
-        uint32_t       po;                               // the other element's position
-        if (idx & 1u) {
-            po = (pr.y >> 12) + 31u - (uint32_t)__builtin_clz(lowm | 1u);
-            if (on && !lowm) po = locate(idx - 1);
-        } else {
-            po = (pr.y >> 12) + j + 1 + (uint32_t)__builtin_ctz(up | 0x800u);
-            if (on && !up) po = locate(idx + 1);
-        }
-        const uint32_t port = N_ANT == 4 ? ((idx >> 1) & 1u) * PL : 0u; // four ports: pair n = idx / 2 on ports (0, 2) for even n, (1, 3) for odd n
-        Elem e;
+        const bool     on  = in && ((pr.y >> j) & 1u) && (N_ANT == 1 || idx < M_symb);
+        Elem e = {};
         e.on = on; e.idx = idx;
         e.os = on ? ((pr.y >> 12) + j) << 2 : 0u;
-        e.oo = on ? po << 2 : 0u;
-        e.pa = on ? port : 0u;
-        e.pb = on ? port + (N_ANT == 4 ? 2 * PL : PL) : 0u;
+        if constexpr (N_ANT > 1) {
+            const uint32_t up = (pr.y & 0xFFFu) >> (j + 1); // the mask's elements above this one
+            uint32_t       po;                              // the other element's position
+            if (idx & 1u) {
+                po = (pr.y >> 12) + 31u - (uint32_t)__builtin_clz(lowm | 1u);
+                if (on && !lowm) po = locate(idx - 1);
+            } else {
+                po = (pr.y >> 12) + j + 1 + (uint32_t)__builtin_ctz(up | 0x800u);
+                if (on && !up) po = locate(idx + 1);
+            }
+            const uint32_t port = N_ANT == 4 ? ((idx >> 1) & 1u) * PL : 0u; // four ports: pair n = idx / 2 on ports (0, 2) for even n, (1, 3) for odd n
+            e.oo = on ? po << 2 : 0u;
+            e.pa = on ? port : 0u;
+            e.pb = on ? port + (N_ANT == 4 ? 2 * PL : PL) : 0u;
+        }
         return e;
     };
     auto ldf = [](const char *p, uint32_t off) __attribute__((always_inline)) { return *reinterpret_cast<const float *>(p + off); };
@@ -610,12 +490,16 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr_txd(const float *__rest
             for (int r = 0; r < UNR; r++) {
                 const Elem e = element(qb + 21 * r + q_thr);
                 on[r]   = e.on;
-                h[r][0] = ldf(h_re_p, e.pa + e.os); h[r][1] = ldf(h_im_p, e.pa + e.os); // h_pa(s)
-                h[r][2] = ldf(h_re_p, e.pb + e.oo); h[r][3] = ldf(h_im_p, e.pb + e.oo); // h_pb(o)
+                h[r][0] = ldf(h_re_p, e.pa + e.os); h[r][1] = ldf(h_im_p, e.pa + e.os); // h_pa(s)  (one port: h(s), pa = 0)
+                if constexpr (N_ANT > 1) { h[r][2] = ldf(h_re_p, e.pb + e.oo); h[r][3] = ldf(h_im_p, e.pb + e.oo); } // h_pb(o)
             }
 #pragma unroll
-            for (int r = 0; r < UNR; r++)
-                if (on[r]) part += (((double)h[r][0] * h[r][0] + (double)h[r][1] * h[r][1]) + ((double)h[r][2] * h[r][2] + (double)h[r][3] * h[r][3])) * 0.5;
+            for (int r = 0; r < UNR; r++) {
+                if (!on[r]) continue;
+                const double wa = (double)h[r][0] * h[r][0] + (double)h[r][1] * h[r][1];
+                if constexpr (N_ANT == 1) part += wa;
+                else part += (wa + ((double)h[r][2] * h[r][2] + (double)h[r][3] * h[r][3])) * 0.5;
+            }
         }
         for (int o = 32; o; o >>= 1) part += __shfl_xor(part, o);
         if ((threadIdx.x & 63u) == 0) w_wave[threadIdx.x >> 6] = part;
@@ -641,23 +525,34 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr_txd(const float *__rest
                 const Elem e = element(qb + 21 * r + q_thr);
                 on[r] = e.on; idx[r] = e.idx;
                 y[r][0] = ldf(y_re_p, e.os);        y[r][1] = ldf(y_im_p, e.os);        // y(s)
-                y[r][2] = ldf(y_re_p, e.oo);        y[r][3] = ldf(y_im_p, e.oo);        // y(o)
-                h[r][0] = ldf(h_re_p, e.pa + e.os); h[r][1] = ldf(h_im_p, e.pa + e.os); // h_pa(s)
-                h[r][2] = ldf(h_re_p, e.pb + e.oo); h[r][3] = ldf(h_im_p, e.pb + e.oo); // h_pb(o)
+                h[r][0] = ldf(h_re_p, e.pa + e.os); h[r][1] = ldf(h_im_p, e.pa + e.os); // h_pa(s)  (one port: h(s), pa = 0)
+                if constexpr (N_ANT > 1) {
+                    y[r][2] = ldf(y_re_p, e.oo);        y[r][3] = ldf(y_im_p, e.oo);        // y(o)
+                    h[r][2] = ldf(h_re_p, e.pb + e.oo); h[r][3] = ldf(h_im_p, e.pb + e.oo); // h_pb(o)
+                }
             }
 #pragma unroll
             for (int r = 0; r < UNR; r++) {
                 if (!on[r]) continue;
-                constexpr double RS2 = 0.70710678118654752; // 1 / sqrt 2
-                const double sg = (idx[r] & 1u) ? -1.0 : 1.0; // z0 = conj(h_pa(a)) y(a) + h_pb(b) conj(y(b)),  z1 = conj(h_pa(b)) y(b) - h_pb(a) conj(y(a))
-                const double sr = y[r][0], si = y[r][1], yor = y[r][2], yoi = y[r][3];
-                const double har = h[r][0], hai = h[r][1], hbr = sg * h[r][2], hbi = sg * h[r][3];
-                const double zr = ((har * sr + hai * si) + hbr * yor) + hbi * yoi, zi = ((har * si - hai * sr) + hbi * yor) - hbr * yoi;
-                const double w  = ((har * har + hai * hai) + (hbr * hbr + hbi * hbi)) * 0.5;
+                const double sr = y[r][0], si = y[r][1], har = h[r][0], hai = h[r][1];
+                double       t_re, t_im, w;
+                if constexpr (N_ANT == 1) {
+                    w    = har * har + hai * hai;
+                    t_re = sr * har + si * hai;
+                    t_im = si * har - sr * hai;
+                } else {
+                    constexpr double RS2 = 0.70710678118654752; // 1 / sqrt 2
+                    const double sg = (idx[r] & 1u) ? -1.0 : 1.0; // z0 = conj(h_pa(a)) y(a) + h_pb(b) conj(y(b)),  z1 = conj(h_pa(b)) y(b) - h_pb(a) conj(y(a))
+                    const double yor = y[r][2], yoi = y[r][3], hbr = sg * h[r][2], hbi = sg * h[r][3];
+                    const double zr = ((har * sr + hai * si) + hbr * yor) + hbi * yoi, zi = ((har * si - hai * sr) + hbi * yor) - hbr * yoi;
+                    w    = ((har * har + hai * hai) + (hbr * hbr + hbi * hbi)) * 0.5;
+                    t_re = zr * RS2;
+                    t_im = zi * RS2;
+                }
                 double li[3], lq[3];
-                llr_axis<MOD>(zr * RS2, w, li);
-                llr_axis<MOD>(zi * RS2, w, lq);
-                // descramble (c bit set -> negate) and store in pairs, as k_pdsch_demod_llr does
+                llr_axis<MOD>(t_re, w, li);
+                llr_axis<MOD>(t_im, w, lq);
+                // descramble (c bit set -> negate) and store: Q_m idx is even, so the bytes leave in pairs (bit 2k on the real axis, 2k + 1 on the imaginary)
                 const uint32_t n0 = idx[r] * QM, c = __builtin_amdgcn_alignbit(cw[(n0 >> 5) + 1], cw[n0 >> 5], n0 & 31);
 #pragma unroll
                 for (uint32_t k = 0; k < QM; k += 2) {
@@ -946,7 +841,7 @@ int mi_lte_pdsch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uin
 }
 
 // The same mode on a cell of two or four CRS ports: every allocation in transmit diversity (36.211 6.3.3.3 / 6.3.4.3, tx_mode 2).  The default
-// demapper is the reference-mode plans' k_pdsch_demod<false>, MAXLOG is k_pdsch_demod_llr_txd, and the code-block concatenation runs with N_L = 2.
+// demapper is the reference-mode plans' k_pdsch_demod<false>, MAXLOG is k_pdsch_demod_llr<2 | 4> (labelled k_pdsch_demod_llr_txd), and the code-block concatenation runs with N_L = 2.
 int mi_lte_pdsch_plan_create_3gpp_txdiv(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t N_pdcch_symbs, const mi_lte_dlsch_cfg *dlsch,
                                         const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, mi_lte_pdsch_plan **out)
 {
@@ -1165,9 +1060,9 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
             MI_LAUNCH(ctx, name, kernel, dim3(pl->core.n_alloc), dim3(256), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt, pl->core.d_e,
                       pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain);
         };
-        if (g.N_ant == 1) launch_llr("k_pdsch_demod_llr", k_pdsch_demod_llr);
-        else if (g.N_ant == 2) launch_llr("k_pdsch_demod_llr_txd", k_pdsch_demod_llr_txd<2>); // (a transmit-diversity plan)
-        else launch_llr("k_pdsch_demod_llr_txd", k_pdsch_demod_llr_txd<4>);
+        if (g.N_ant == 1) launch_llr("k_pdsch_demod_llr", k_pdsch_demod_llr<1>);
+        else if (g.N_ant == 2) launch_llr("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<2>); // (a transmit-diversity plan: its own profiling label)
+        else launch_llr("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<4>);
     } else if (g.N_ant == 1 && (pl->cfg.sample_format & MI_LTE_CE_COMPACT)) launch(k_pdsch_demod<true, true>);
     else if (g.N_ant == 1) launch(k_pdsch_demod<true>);
     else launch(k_pdsch_demod<false>);

@@ -1,5 +1,5 @@
-// MI_LTE_DEMAP_MAXLOG (include/mi_lte.h): the max-log LLR arithmetic shared by the 3GPP plans' opt-in demappers, k_pdsch_demod_llr (chain.hip)
-// and k_pusch_demod_llr (uplink.hip).
+// MI_LTE_DEMAP_MAXLOG (include/mi_lte.h): the max-log LLR arithmetic shared by the 3GPP plans' opt-in demappers, k_pdsch_demod_llr<N_ANT>
+// (chain.hip: one kernel for one port and for transmit diversity on two or four) and k_pusch_demod_llr (uplink.hip).
 #pragma once
 #include <cstdint>
 

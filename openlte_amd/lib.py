@@ -1494,7 +1494,8 @@ class Context:
 
     def pdsch_plan_3gpp_txdiv(self, cfg, n_pdcch_symbs, allocs, n_soft, m_dl_harq=8):
         """pdsch_plan_3gpp for a cell of two or four CRS ports (mi_lte_pdsch_plan_create_3gpp_txdiv): every allocation in transmit diversity
-        (tx_mode 2), code-block concatenation with N_L = 2; set_demapper(DEMAP_MAXLOG) runs k_pdsch_demod_llr_txd."""
+        (tx_mode 2), code-block concatenation with N_L = 2; set_demapper(DEMAP_MAXLOG) runs the single-port plans' k_pdsch_demod_llr on the cell's port
+        count (its runs are labelled k_pdsch_demod_llr_txd)."""
         return PdschPlan(self, cfg, n_pdcch_symbs, allocs, dlsch=DlschCfg(n_soft, m_dl_harq), txdiv=True)
 
     def harq_pool(self, n_buf, max_tbs=75376):

@@ -1,11 +1,12 @@
-"""float64 numpy model of MI_LTE_DEMAP_MAXLOG (include/mi_lte.h, "PDSCH, 3GPP mode: max-log soft-decision demapping"): the resource elements
-of every allocation of one single-port unit in the demodulator's order (symbol -> PRB -> sub-carrier, CRS and, in subframes 0 and 5, the PBCH /
-PSS / SSS window left out), the max-log LLRs in their piecewise-linear form from z = y conj(h) and w = |h|^2, the gain, the rounding and the
-descrambling.  The tests compare the kernel's bytes and gains with it (tests/test_demap_llr_gpu.py) and the piecewise form with the brute-force
-minimum over the whole constellation (tests/test_demap_llr_cpu.py)."""
+"""float64 numpy model of MI_LTE_DEMAP_MAXLOG (include/mi_lte.h, "PDSCH, 3GPP mode: max-log soft-decision demapping" and "transmit diversity on
+2 or 4 ports"): the resource elements of every allocation of one unit of a 1-, 2- or 4-port cell in the demodulator's order (symbol -> PRB ->
+sub-carrier, CRS and, in subframes 0 and 5, the PBCH / PSS / SSS window left out), each symbol's (t, w) of the header's text, the max-log LLRs in
+their piecewise-linear form, the gain, the rounding and the descrambling.  The GPU tests compare the kernel's bytes and gains with it
+(tests/test_demap_llr_gpu.py, tests/test_txdiv_gpu.py); tests/test_demap_llr_cpu.py and tests/test_txdiv_cpu.py check the model itself."""
 import numpy as np
 
 N_SC = 1200
+RS2 = 0.70710678118654752  # 1 / sqrt 2, the kernel's literal
 A = {1: 1 / np.sqrt(2.0), 2: 1 / np.sqrt(10.0), 3: 1 / np.sqrt(42.0)}
 A_LIT = {1: 0.70710678118654752, 2: 0.31622776601683794, 3: 0.15430334996209191}  # the kernel's literals
 FOUR_A2 = {1: 2.0, 2: 4.0 / 10, 3: 4.0 / 42}
@@ -29,8 +30,9 @@ def sync_window(n_rb):
     return {6: (0, 71), 15: (54, 125), 25: (114, 185), 50: (264, 335), 75: (414, 485)}.get(n_rb, (564, 635))
 
 
-def pdsch_res(al, sf, cell, n_rb, cfi):
-    """Plane indices L * 1200 + sub-carrier of the allocation's resource elements, in the demodulator's order (single port)."""
+def pdsch_res(al, sf, cell, n_rb, cfi, n_ant=1):
+    """Plane indices L * 1200 + sub-carrier of the allocation's resource elements, in the demodulator's order, for a cell of n_ant ports
+    (36.211 6.10.1.2: ports 0 / 1 take sub-carriers k = cell mod 3 (mod 3) in symbols 0 and 4 of a slot, ports 2 / 3 the same in symbol 1)."""
     first, last = sync_window(n_rb)
     cfi = al.n_pdcch_symbs if al.n_pdcch_symbs else cfi
     out = []
@@ -41,10 +43,13 @@ def pdsch_res(al, sf, cell, n_rb, cfi):
         for i in range(al.N_prb):
             sc = al.prb[1 if L >= 7 else 0][i] * 12 + j
             keep = np.ones(12, bool)
-            if l7 == 0:
-                keep &= (j % 6) != cell % 6
-            elif l7 == 4:
-                keep &= (j % 6) != (cell + 3) % 6
+            if n_ant == 1:
+                if l7 == 0:
+                    keep &= (j % 6) != cell % 6
+                elif l7 == 4:
+                    keep &= (j % 6) != (cell + 3) % 6
+            elif l7 in (0, 4) or (n_ant == 4 and l7 == 1):
+                keep &= (j % 3) != cell % 3
             if win:
                 keep &= (sc < first) | (sc > last)
             out.append(L * N_SC + sc[keep])
@@ -67,16 +72,64 @@ def llr_axis(t, w, mod):
             np.where(a < 4 * D, a4 * (a - 2 * D), a4 * (6 * D - a))]
 
 
-def llr_symbols(y, h, mod):
-    """[n, Q_m] LLRs L_k of n received symbols y (complex128) over channel h: bit 2k on the real axis, 2k + 1 on the imaginary."""
+def one_port(y, h):
+    """(t, w) of received symbols y (complex128) over channel h on one port: t = y conj(h), w = |h|^2, in the kernel's order of operations"""
     w = h.real * h.real + h.imag * h.imag
-    zr = y.real * h.real + y.imag * h.imag
-    zi = y.imag * h.real - y.real * h.imag
-    out = np.zeros((len(y), QM[mod]))
+    t = (y.real * h.real + y.imag * h.imag).astype(np.complex128)
+    t.imag = y.imag * h.real - y.real * h.imag
+    return t, w
+
+
+def pair_ports(n_pairs, n_ant):
+    """(pa, pb) per element pair n: (0, 1) on two ports; on four, (0, 2) for even n and (1, 3) for odd n"""
+    n = np.arange(n_pairs)
+    if n_ant == 2:
+        return np.zeros(n_pairs, np.int64), np.ones(n_pairs, np.int64)
+    return n % 2, n % 2 + 2
+
+
+def combine(ya, yb, ha_a, hb_b, ha_b, hb_a):
+    """The header's combiner for arrays of element pairs (complex128): (t0, w0, t1, w1).  ha_a = h_pa(a), hb_b = h_pb(b), ha_b = h_pa(b),
+    hb_a = h_pb(a).  Real arithmetic in the kernel's order of operations."""
+    ar, ai, br, bi = ya.real, ya.imag, yb.real, yb.imag
+    h0r, h0i, h1r, h1i, h2r, h2i, h3r, h3i = ha_a.real, ha_a.imag, hb_b.real, hb_b.imag, ha_b.real, ha_b.imag, hb_a.real, hb_a.imag
+    z0r = ((h0r * ar + h0i * ai) + h1r * br) + h1i * bi
+    z0i = ((h0r * ai - h0i * ar) + h1i * br) - h1r * bi
+    z1r = ((h2r * br + h2i * bi) - h3r * ar) - h3i * ai
+    z1i = ((h2r * bi - h2i * br) - h3i * ar) + h3r * ai
+    w0 = ((h0r * h0r + h0i * h0i) + (h1r * h1r + h1i * h1i)) * 0.5
+    w1 = ((h2r * h2r + h2i * h2i) + (h3r * h3r + h3i * h3i)) * 0.5
+    return (z0r + 1j * z0i) * RS2, w0, (z1r + 1j * z1i) * RS2, w1
+
+
+def symbols(planes, re, n_ant):
+    """(t complex128 [M_symb], w [M_symb]) of one allocation: planes float64 [2 + 2 n_ant, 16 * 1200] (y_re, y_im, h_re of every port, h_im of
+    every port), re its resource elements."""
+    y = planes[0] + 1j * planes[1]
+    h = planes[2:2 + n_ant] + 1j * planes[2 + n_ant:2 + 2 * n_ant]
+    if n_ant == 1:
+        return one_port(y[re], h[0, re])
+    m = len(re) // n_ant * n_ant
+    a, b = re[0:m:2], re[1:m:2]
+    pa, pb = pair_ports(m // 2, n_ant)
+    t0, w0, t1, w1 = combine(y[a], y[b], h[pa, a], h[pb, b], h[pa, b], h[pb, a])
+    t, w = np.zeros(m, np.complex128), np.zeros(m)
+    t[0::2], t[1::2], w[0::2], w[1::2] = t0, t1, w0, w1
+    return t, w
+
+
+def llr_tw(t, w, mod):
+    """[n, Q_m] LLRs L_k from (t, w): bit 2k on the real axis, 2k + 1 on the imaginary."""
+    out = np.zeros((len(t), QM[mod]))
     with np.errstate(all="ignore"):
-        out[:, 0::2] = np.stack(llr_axis(zr, w, mod), 1)
-        out[:, 1::2] = np.stack(llr_axis(zi, w, mod), 1)
+        out[:, 0::2] = np.stack(llr_axis(t.real, w, mod), 1)
+        out[:, 1::2] = np.stack(llr_axis(t.imag, w, mod), 1)
     return out
+
+
+def llr_symbols(y, h, mod):
+    """[n, Q_m] LLRs L_k of n received symbols y (complex128) over channel h on one port."""
+    return llr_tw(*one_port(y, h), mod)
 
 
 def axis_levels(mod):
@@ -140,20 +193,16 @@ class Demapped:
         self.bytes, self.gain, self.x, self.c = bytes_, gain, x, c
 
 
-def demap(planes, allocs, sf, cell, n_rb, cfi, gain=0.0, T=16):
-    """planes: one unit's float32 [4, 16, 1200] (y_re, y_im, h_re, h_im); allocs: its allocations; gain 0: automatic.  One Demapped each."""
-    p = np.asarray(planes, np.float32).reshape(4, -1).astype(np.float64)
+def demap(planes, allocs, sf, cell, n_rb, cfi, n_ant=1, gain=0.0, T=16):
+    """planes: one unit's float32 [2 + 2 n_ant, 16, 1200] (symbols' order); allocs: its allocations; gain 0: automatic.  One Demapped each."""
+    p = np.asarray(planes, np.float32).reshape(2 + 2 * n_ant, -1).astype(np.float64)
     out = []
     for al in allocs:
         mod = al.mod_type
-        re = pdsch_res(al, sf, cell, n_rb, cfi)
-        y, h = p[0, re] + 1j * p[1, re], p[2, re] + 1j * p[3, re]
-        if gain == 0:
-            g_used, g_tap = auto_gain(h.real * h.real + h.imag * h.imag, mod, T)
-        else:
-            g_used = g_tap = float(np.float32(gain))
+        t, w = symbols(p, pdsch_res(al, sf, cell, n_rb, cfi, n_ant), n_ant)
+        g_used, g_tap = auto_gain(w, mod, T) if gain == 0 else (float(np.float32(gain)),) * 2
         with np.errstate(all="ignore"):
-            x = (g_used * llr_symbols(y, h, mod)).reshape(-1)
+            x = (g_used * llr_tw(t, w, mod)).reshape(-1)
         c = gold(((al.rnti << 14) | (sf << 9) | cell) & 0x7FFFFFFF, len(x))
         x = np.where(c == 1, -x, x)
         out.append(Demapped(soft_byte(x), g_tap, x, c))

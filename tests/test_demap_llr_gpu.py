@@ -1,5 +1,5 @@
-"""GPU: the 3GPP PDSCH plans' max-log soft-decision demapper (mi_lte_pdsch_plan_set_demapper, k_pdsch_demod_llr).  Its bytes and gains against
-the float64 model of include/mi_lte.h's text (tests/demap_llr_model.py); a plan that never opts in, or opts out again, is the plan it was;
+"""GPU: the 3GPP PDSCH plans' max-log soft-decision demapper (mi_lte_pdsch_plan_set_demapper, k_pdsch_demod_llr<1>; tests/test_txdiv_gpu.py runs
+the same kernel and the same model on two and four ports).  Its bytes and gains against the float64 model of include/mi_lte.h's text (tests/demap_llr_model.py); a plan that never opts in, or opts out again, is the plan it was;
 everything after the soft-bit buffer does with the graded bytes what it does with the default demapper's (rate un-matching, the BCJR model,
 the HARQ sat16 chain); and what the soft decisions buy: at an SNR profiles/demap_llr_sweep.txt names, every transport block of the sweep's
 64QAM class decodes with them and none without."""

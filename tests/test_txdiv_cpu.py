@@ -1,13 +1,13 @@
 """CPU: the host arithmetic of the transmit-diversity mode of the 3GPP PDSCH plans (include/mi_lte.h, "PDSCH, 3GPP mode: transmit diversity on 2
 or 4 ports"): mi_lte_dlsch_layout_nl against a restatement of 36.212 5.1.2 / 5.1.4.1.2 with N_L, mi_lte_txdiv_precode against the matrices of
-36.211 6.3.4.3, the combiner of tests/txdiv_llr_model.py against both (it returns the symbols, its w is the stated one, and the noise on
+36.211 6.3.4.3, the combiner of tests/demap_llr_model.py against both (it returns the symbols, its w is the stated one, and the noise on
 t / w has variance sigma^2 / w), and the generator's refusals and payload hand-back.  No GPU."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import txdiv_llr_model as tm
+import demap_llr_model as tm
 from test_dlsch3gpp_cpu import all_tbs, seg
 
 ERR_INVALID, ERR_UNSUPPORTED = -1, -4

@@ -1,7 +1,7 @@
 """GPU: the 3GPP PDSCH plans on cells of two and four CRS ports (mi_lte_pdsch_plan_create_3gpp_txdiv): transmit diversity, the N_L = 2 code-block
-concatenation and the max-log demapper of the Alamouti pairs (k_pdsch_demod_llr_txd).  Units come from the library's transmit-diversity
-generator (mi_lte_synth_dl_units_3gpp_txdiv_i8) through the front end with the cell's port count.  The default demapper is the reference-mode
-plan's byte for byte; MAXLOG's bytes and gains are the float64 model's of include/mi_lte.h's text (tests/txdiv_llr_model.py) under the rules of
+concatenation and the max-log demapper of the Alamouti pairs (k_pdsch_demod_llr<2 | 4>, labelled k_pdsch_demod_llr_txd).  Units come from the
+library's transmit-diversity generator (mi_lte_synth_dl_units_3gpp_txdiv_i8) through the front end with the cell's port count.  The default demapper is the reference-mode
+plan's byte for byte; MAXLOG's bytes and gains are the float64 model's of include/mi_lte.h's text (tests/demap_llr_model.py) under the rules of
 tests/test_demap_llr_gpu.py; noiseless units decode with every soft bit's sign right; E_r and the offsets follow N_L = 2; HARQ combining,
 inertness, the refusals, and what the soft decisions buy at the point profiles/txdiv_llr_sweep.txt names."""
 import ctypes as C
@@ -12,7 +12,6 @@ import numpy as np
 import pytest
 
 import demap_llr_model as dm
-import txdiv_llr_model as tm
 from test_demap_llr_gpu import check_against_model, slots
 from test_dlsch3gpp_gpu import FFT, tbs
 from test_harq_gpu import NULL, Tx, decode, sat16
@@ -97,7 +96,7 @@ def model_of(t, planes, gain):
     import openlte_amd as m
     out = []
     for u in range(len(t.sfs)):
-        out += tm.demap(planes[u], [al for al in t.allocs if al.unit == u], t.sfs[u], t.cells[u], t.n_rb, t.cfi, t.n_ant, gain=gain, T=m.DEMAP_AUTO_T)
+        out += dm.demap(planes[u], [al for al in t.allocs if al.unit == u], t.sfs[u], t.cells[u], t.n_rb, t.cfi, t.n_ant, gain=gain, T=m.DEMAP_AUTO_T)
     return out
 
 
