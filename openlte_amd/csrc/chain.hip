@@ -393,9 +393,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
 // diversity"): k_pdsch_demod's pair table, scrambling words, thread per (pair, sub-carrier), LDS assembly and soft-bit layout over the N_ANT-port
 // extraction, with that demapper in place of the reference's.  Every thread does the symbol of its own resource element s and hands
 // (t, w) to llr_axis / llr_byte.  One port: t = y(s) conj(h(s)), w = |h(s)|^2.  Two or four ports: the other element o of the thread's pair is the
-// neighbouring set bit of the same 12-bit mask -- the next one for an even RE index, the previous one for an odd one -- and only where the mask
-// has none (the pair straddles two PRBs, or next to the PBCH / PSS / SSS window two symbols) a search of the table.  Both symbols of a pair have
-// one form,
+// neighbouring set bit of the same 12-bit mask -- the next one for an even RE index, the previous one for an odd one.  The mask always has it: on
+// two and four ports every (symbol, PRB) entry holds 4, 6, 8 or 12 resource elements, so every entry starts at an even RE index and no pair leaves
+// its entry (tests/test_demap_geometry_cpu.py, test_every_txdiv_table_entry_is_even: all six bandwidths, every PRB, the window's half PRBs
+// included).  The search of the table where the mask has none (`locate`) is a fallback that no valid geometry reaches.  Both symbols of a pair
+// have one form,
 //     z = conj(h_pa(s)) y(s) +- h_pb(o) conj(y(o)),  w = (|h_pa(s)|^2 + |h_pb(o)|^2) / 2     (+: even index, -: odd),
 // so a thread loads two y and two h values, and t = z / sqrt 2.
 // gain > 0: g = gain.  gain == 0: a first sweep over the allocation's estimate planes sums w (per thread, then inside each wave, then over the

@@ -74,8 +74,9 @@ def case(name):
     carrier the front end's estimate (extrapolated past the last pilot, interpolated across the unused centre sub-carrier) is off by more than
     their decision distance under a timing offset, with or without transmit diversity, and the noiseless test would measure that.
     B: a 25-RB four-port cell in subframes 0 and 5, PRBs [8, 9, 10] and [14 .. 17] astride the PBCH / PSS / SSS window (sub-carriers
-    114 .. 185: the half PRBs 9 and 15; [8, 9, 10] has 30 elements in symbols 5 and 6, so a quad straddles two symbols and pairs straddle
-    PRBs) and one allocation clear of it.  C: B's allocations on two ports.  D: one 100-PRB 64QAM allocation on two
+    114 .. 185: the half PRBs 9 and 15; [8, 9, 10] has 30 elements in symbols 5 and 6, so a quad straddles two symbols and the four-port pair
+    parity continues across table entries; no pair leaves its entry: tests/test_demap_geometry_cpu.py) and one allocation clear of it.
+    C: B's allocations on two ports.  D: one 100-PRB 64QAM allocation on two
     ports: past the LDS cap, so stored directly, and the largest pair table."""
     if name == "A":
         return 6, 2, 3, [0, 5, 3], [11, 250, 77], [[mk(u, 1, tbs(0, 1), [0], 0x21), mk(u, 2, tbs(0, 1), [1], 0x22), mk(u, 3, tbs(0, 1), [4], 0x23, cfi=2)]
