@@ -292,7 +292,8 @@ int mi_lte_pdsch_plan_cb_ok(const mi_lte_pdsch_plan *plan, const uint32_t **d_ma
  *   across transmissions.  gain == 0, automatic, per allocation and per run: g_a = T / (4 A^2 wbar), wbar the mean of w over the allocation's
  *   M_symb resource elements and T = MI_LTE_DEMAP_AUTO_T: a noiseless symbol at the mean channel power has its least reliable bit at +-T.
  *   g_a is rounded to float before use; mi_lte_pdsch_plan_llr_gain reports it.  Under the automatic gain, retransmissions with different
- *   modulations (or channel powers) combine on this convention and not on 1 / sigma^2.
+ *   modulations (or channel powers) combine on this convention and not on 1 / sigma^2; mi_lte_pdsch_plan_set_llr_noise ("PDSCH, 3GPP mode:
+ *   noise-referenced gain" below) puts them on 1 / sigma^2 of a CRS noise estimate.
  * Degenerate input, no NaN and no trap: a wbar that is 0 or not finite (or a g_a past the float range) gives g_a = 0 and 0 for every soft bit
  *   of the allocation; w = 0 on a resource element gives 0 for its Q_m soft bits; a non-finite g_a L_k gives 0 for that bit.  An allocation
  *   whose soft bits are all 0 decodes to status 2 (the erasure rule of the mode's verdict, above).
@@ -352,6 +353,60 @@ int mi_lte_pdsch_plan_create_3gpp_txdiv(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cf
 /* 1 when mi_lte_pdsch_plan_create_3gpp_txdiv accepts this allocation, 0 when it refuses it */
 int mi_lte_pdsch_alloc_decodable_3gpp_txdiv(const mi_lte_dl_cfg *cfg, const mi_lte_dlsch_cfg *dlsch, const mi_lte_pdsch_alloc *alloc,
                                             uint32_t N_pdcch_symbs);
+
+/* ---------------------------------------------------------------- DL: CRS noise estimate
+ * One noise variance per subframe unit from the cell-specific reference signals, for SNR and CQI reporting and for the noise-referenced
+ * gain of the next section.  It reads only the received-symbol (y) planes of a unit, so it is valid on full and on MI_LTE_CE_COMPACT planes.
+ * Rows.  CRS ports p = 0 .. min(N_ant, 2) - 1 on the subframe's own CRS symbols 0, 4, 7, 11 (i = 0 .. 3; the look-ahead symbol 14 is not
+ *   used): n_rows = 4 on one port, 8 on two or four.  Ports 2 and 3 are not used.
+ * Pilots.  Row (p, i) has n_pil = 2 N_rb_dl pilots; pilot j sits at sub-carrier k_j = 6 j + (voff(p, i) + N_id_cell mod 6) mod 6 with
+ *   voff = 3 where i + p is odd and 0 otherwise.  Its CRS value crs_j = ((1 - 2 c(2 m)) + j (1 - 2 c(2 m + 1))) / sqrt 2, m = j + 110 - N_rb_dl,
+ *   c the Gold sequence of c_init = 2^10 (7 (n_s + 1) + l + 1) (2 N_id_cell + 1) + 2 N_id_cell + 1 (36.211 6.10.1.1, normal cyclic prefix),
+ *   n_s = 2 subfr_num + (symbol >= 7), l = symbol mod 7 -- exactly what the channel estimator forms.
+ * Least-squares product.  t_j = y(symbol, k_j) conj(crs_j) in float.  The other ports are silent on these resource elements, so
+ *   t_j = h_p + noise.
+ * Second difference.  d_j = t_{j-1} - 2 t_j + t_{j+1} for j = 1 .. n_pil - 2, in double: a channel that is linear over three pilots
+ *   (12 sub-carriers) cancels, white noise of variance sigma^2 gives E|d|^2 = 6 sigma^2.  A delay of 4 samples at N_fft = 2048 leaves
+ *   4.9e-6 |h|^2.
+ * Sum and estimate.  S = sum over rows and j of |d_j|^2 in double and in a fixed order (each thread its own terms; an xor butterfly within
+ *   the wavefront; the wavefronts' slots in ascending order; no atomics: two runs give identical bytes).
+ *   sigma2 = (float)(S / (6 n_rows (n_pil - 2))).
+ * Limits.  The relative standard deviation is about 1.36 / sqrt(n_rows (n_pil - 2)) (the PUSCH section's constant; neighbouring differences
+ *   share samples); measured over 300 seeded draws (tests/test_pdsch_noise_cpu.py): 22.5 % (formula 21.5 %) at 6 RB on one port and
+ *   15.2 % (15.2 %) on two, 4.6 % (4.8 %) at 100 RB on one port and 3.6 % (3.4 %) on two.
+ *   Channel curvature over +-6 sub-carriers biases the estimate upwards: a delay of d samples leaves (2 - 2 cos(2 pi 6 d / N_fft))^2 / 6 of
+ *   |h|^2, which is 4.9e-6 at d = 4 and N_fft = 2048 but 0.26 at N_fft = 128 (6 RB) -- there the estimate of a delayed channel is
+ *   curvature, not noise.  The error of the channel estimate itself is not in sigma2.
+ * mi_lte_dl_crs_noise_run: d_sigma2[unit] for n_units units of d_subframes (the layout of mi_lte_dl_frontend_batch; cfg's N_rb_dl and N_ant
+ *   are used), asynchronous on the context's stream; one launch, k_dl_crs_noise.  MI_LTE_ERR_INVALID_ARG for a NULL pointer, n_units = 0, an
+ *   N_rb_dl other than 6, 15, 25, 50, 75, 100, or an N_ant other than 1, 2, 4. */
+int mi_lte_dl_crs_noise_run(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const float *d_subframes, const uint32_t *d_subfr_num,
+                            const uint32_t *d_n_id_cell, uint32_t n_units, float *d_sigma2);
+
+/* ---------------------------------------------------------------- PDSCH, 3GPP mode: noise-referenced gain
+ * The automatic gain of MI_LTE_DEMAP_MAXLOG normalises every transmission to T at its own mean channel power: a convention, not
+ * 1 / sigma^2.  For HARQ combining (next section) the LLRs of different transmissions have to be on one scale, so a MAXLOG run can take
+ * its gain from the CRS noise estimate above instead: with w = |h|^2 (the mean over the pair's ports in transmit diversity) the noise on
+ * t / w has variance sigma^2 / w, so g L = (scale / sigma2) L is `scale` times the max-log LLR in natural units.
+ * Gain.  A run with the noise gain on first estimates sigma2[u] for u = 0 .. n_units - 1, n_units = 1 + the largest unit an allocation of
+ *   the plan names (fixed at creation; the run's d_subfr_num / d_n_id_cell hold at least that many entries), then every allocation a uses
+ *   g_a = (float)((double)scale / (double)sigma2[unit_a]) in place of the gain given to mi_lte_pdsch_plan_set_demapper; the sweep over the
+ *   estimate planes that forms wbar is not made.  A sigma2 that is 0 or not finite, or a g_a past the float range, gives g_a = 0: every soft
+ *   bit of the allocation is 0 and its status is 2 by the erasure rule.  Everything else of the LLR is as in the sections above:
+ *   v = clamp(rint(g_a L), -127, 127).  mi_lte_pdsch_plan_llr_gain reports the g_a used.
+ * Scale.  scale = 8 is the convention the tests and tools use: an LLR of 16 meets the int8 clamp (profiles/pdsch_harq_sweep.txt).
+ * Kernels.  k_dl_crs_noise over the plan's units, then a further instantiation of k_pdsch_demod_llr (listed under that name, _txd on two and
+ *   four ports) that holds the one argument more; with the setter off every run launches what it launched before, and so gives the bytes it
+ *   gave.  A plan whose N_rb_dl is none of the six bandwidths refuses a noise-on run with MI_LTE_ERR_INVALID_ARG.
+ * mi_lte_pdsch_plan_set_llr_noise: scale > 0: MAXLOG runs of the plan use g_a = (float)(scale / sigma2[unit_a]) in place of the gain given to
+ *   mi_lte_pdsch_plan_set_demapper; scale == 0: off (the default).  Accepted on any 3GPP plan (mi_lte_pdsch_plan_create_3gpp and _3gpp_txdiv)
+ *   whatever its current demapper; takes effect on MAXLOG runs only, and with it off a MAXLOG run gives the bytes it gave before.
+ *   Refusals, the plan left as it was: MI_LTE_ERR_INVALID_ARG for a NULL plan and a negative or non-finite scale; MI_LTE_ERR_UNSUPPORTED on a
+ *   plan that is not in the 3GPP mode. */
+int mi_lte_pdsch_plan_set_llr_noise(mi_lte_pdsch_plan *plan, float scale);
+/* tap: float [*n_units], sigma2 of the last MAXLOG run with the noise gain on (zeros before one); device pointer owned by the plan.
+ * MI_LTE_ERR_INVALID_ARG for a NULL argument and on a plan that is not in the 3GPP mode. */
+int mi_lte_pdsch_plan_llr_noise(const mi_lte_pdsch_plan *plan, const float **d_sigma2, uint32_t *n_units);
 
 /* ---------------------------------------------------------------- PDSCH, 3GPP mode: HARQ soft combining
  * Incremental-redundancy combining of the retransmissions of a transport block in device-resident soft buffers (36.212 5.1.4.1.2: the

@@ -403,14 +403,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
 // gain > 0: g = gain.  gain == 0: a first sweep over the allocation's estimate planes sums w (per thread, then inside each wave, then over the
 // waves' LDS slots, always in that order and in double: a run is reproducible) and g = T / (4 A^2 wbar) (T = auto_t: MI_LTE_DEMAP_AUTO_T),
 // rounded to float -- the value llr_gain[allocation] reports is the value the soft bits were scaled with.
-template <uint32_t N_ANT>
+// The noise-referenced gain (mi_lte_pdsch_plan_set_llr_noise) is a further instantiation, k_pdsch_demod_llr<N_ANT, PdschLlrNoise> (launched and
+// listed under the same names): one more argument, no wbar sweep, g = scale / sigma2[unit] of the CRS noise estimate k_dl_crs_noise left
+// (dl_noise.hip).  Without that argument every `if constexpr (NOISE)` drops out and k_pdsch_demod_llr<N_ANT> has the arguments, the LDS and the
+// code it had.
+struct PdschLlrNoise {
+    const float *sigma2; // [n_units]: k_dl_crs_noise's estimates of this run
+    float        scale;  // g = scale / sigma2[unit] in place of either gain
+};
+template <uint32_t N_ANT, typename... Noise>
 __global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict__ subframes, DemodGeom g, const mi_lte_pdsch_alloc *__restrict__ allocs,
                                                          const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell, GoldTables gt,
                                                          int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len,
                                                          uint32_t max_pairs, uint32_t max_words, uint32_t e_lds_cap, float gain, float auto_t,
-                                                         float *__restrict__ llr_gain)
+                                                         float *__restrict__ llr_gain, Noise... noise)
 {
     static_assert(N_ANT == 1 || N_ANT == 2 || N_ANT == 4, "one port, or transmit diversity on two or four");
+    static_assert(sizeof...(Noise) <= 1 && (std::is_same<Noise, PdschLlrNoise>::value && ...), "at most the noise-referenced gain's argument");
+    constexpr bool NOISE = sizeof...(Noise) == 1;
     extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // tab[max_pairs+1] (offset, mask | position) | cw[...] | soft bits
     __shared__ double w_wave[4];
     const uint32_t a_idx = blockIdx.x;
@@ -483,7 +493,10 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict
     };
     auto ldf = [](const char *p, uint32_t off) __attribute__((always_inline)) { return *reinterpret_cast<const float *>(p + off); };
     double gd = (double)gain;
-    if (gain == 0.0f) { // wbar: the mean of w over the allocation's symbols
+    if constexpr (NOISE) { // every thread forms the same quotient
+        const float s2 = (noise.sigma2[unit], ...), gf = (float)((double)(noise.scale, ...) / (double)s2);
+        gd = (s2 > 0.0f && s2 <= 3.4028234e38f && fabsf(gf) <= 3.4028234e38f) ? (double)gf : 0.0; // sigma2 0 or not finite, or a gain past float: every soft bit 0
+    } else if (gain == 0.0f) { // wbar: the mean of w over the allocation's symbols
         double part = 0.0;
         for (uint32_t qb = pair0; qb < n_pairs; qb += 21 * UNR) {
             float h[UNR][4];
@@ -624,6 +637,10 @@ struct mi_lte_pdsch_plan {
     MiDlsch3   *g3 = nullptr; // 3GPP transport-block mode (mi_lte_pdsch_plan_create_3gpp): its code blocks and buffers (dlsch3gpp.hip)
     uint32_t    demap = MI_LTE_DEMAP_REF; // mi_lte_pdsch_plan_set_demapper (3GPP mode)
     float       demap_gain = 0.0f, *d_llr_gain = nullptr; // MAXLOG: the fixed gain (0: automatic); [n_alloc] the gain of the last run (3GPP plans)
+    // mi_lte_pdsch_plan_set_llr_noise: the noise-referenced gain's scale (0: off); the last such run's sigma2 [n_units] (behind d_llr_gain's
+    // floats); n_units = 1 + the largest unit an allocation names
+    float       llr_noise = 0.0f, *d_llr_s2 = nullptr;
+    uint32_t    n_units = 0;
     // the packed hand-over (soft_pack.h): what the demodulator's LDS block must hold -- the soft bits of the longest allocation that stays
     // bytes (BPSK / QPSK, in words) and the symbols of the longest 16QAM / 64QAM one -- and the stage tap's debt: the context of the last run and whether
     // its 16QAM / 64QAM slots still hold bits (mi_lte_pdsch_plan_soft_bits expands them once; a re-assignment voids them)
@@ -822,8 +839,10 @@ static int plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, uint32_t 
     MI_HIP_CHECK(ctx, pl->core.allocate(n_alloc, pl->core.e_bytes));
     rc = mi_dlsch3_create(ctx, dlsch, h_allocs, n_alloc, &pl->g3, n_l);
     if (rc != MI_LTE_OK) return rc;
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_llr_gain, sizeof(float) * n_alloc));
-    MI_HIP_CHECK(ctx, hipMemsetAsync(pl->d_llr_gain, 0, sizeof(float) * n_alloc, ctx->stream));
+    for (uint32_t a = 0; a < n_alloc; a++) pl->n_units = std::max(pl->n_units, h_allocs[a].unit + 1u);
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_llr_gain, sizeof(float) * ((size_t)n_alloc + pl->n_units))); // gain [n_alloc] | sigma2 [n_units]
+    MI_HIP_CHECK(ctx, hipMemsetAsync(pl->d_llr_gain, 0, sizeof(float) * ((size_t)n_alloc + pl->n_units), ctx->stream));
+    pl->d_llr_s2 = pl->d_llr_gain + n_alloc;
     MI_H2D(ctx, pl->core.d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
     MI_H2D(ctx, pl->core.d_e_off, pl->core.h_e_off.data(), sizeof(uint32_t) * n_alloc);
     MI_HIP_CHECK(ctx, mi_stream_wait_polling(ctx));
@@ -1017,6 +1036,22 @@ int mi_lte_pdsch_plan_llr_gain(const mi_lte_pdsch_plan *pl, const float **d_gain
     return MI_LTE_OK;
 }
 
+int mi_lte_pdsch_plan_set_llr_noise(mi_lte_pdsch_plan *pl, float scale)
+{
+    if (!pl || !(scale >= 0.0f) || scale > 3.4028234e38f) return MI_LTE_ERR_INVALID_ARG; // negative, NaN or infinite
+    if (!pl->g3) return MI_LTE_ERR_UNSUPPORTED; // a reference-mode plan has no LLR to scale
+    pl->llr_noise = scale;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pdsch_plan_llr_noise(const mi_lte_pdsch_plan *pl, const float **d_sigma2, uint32_t *n_units)
+{
+    if (!pl || !d_sigma2 || !n_units || !pl->d_llr_s2) return MI_LTE_ERR_INVALID_ARG;
+    *d_sigma2 = pl->d_llr_s2;
+    *n_units  = pl->n_units;
+    return MI_LTE_OK;
+}
+
 int mi_lte_pdsch_plan_set_output(mi_lte_pdsch_plan *pl, uint32_t packed)
 {
     if (!pl) return MI_LTE_ERR_INVALID_ARG;
@@ -1026,6 +1061,11 @@ int mi_lte_pdsch_plan_set_output(mi_lte_pdsch_plan *pl, uint32_t packed)
 }
 
 } // extern "C"
+
+// dl_noise.hip: k_dl_crs_noise on the context's stream; it checks the bandwidth and the port count.  (Declared here and not in ctx.hpp: the
+// shared headers are part of every file's build id, and the committed profiler tables of the other files stay current this way.)
+int mi_dl_crs_noise(mi_lte_ctx *ctx, uint32_t N_rb_dl, uint32_t N_ant, const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell,
+                    uint32_t n_units, float *d_sigma2);
 
 // the plan's demodulator: every allocation's descrambled soft bits and their count
 // pack: 16QAM / 64QAM allocations leave as bits (soft_pack.h; pdsch_run decides per run)
@@ -1062,7 +1102,17 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
             MI_LAUNCH(ctx, name, kernel, dim3(pl->core.n_alloc), dim3(256), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt, pl->core.d_e,
                       pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain);
         };
-        if (g.N_ant == 1) launch_llr("k_pdsch_demod_llr", k_pdsch_demod_llr<1>);
+        if (pl->llr_noise > 0.0f) { // the noise-referenced gain: the CRS noise estimate of the plan's units, then the instantiation that divides by it
+            if ((rc = mi_dl_crs_noise(ctx, g.N_rb_dl, g.N_ant, d_subframes, d_subfr_num, d_n_id_cell, pl->n_units, pl->d_llr_s2)) != MI_LTE_OK) return rc;
+            const PdschLlrNoise nz{pl->d_llr_s2, pl->llr_noise};
+            auto launch_llr_noise = [&](const char *name, auto kernel) {
+                MI_LAUNCH(ctx, name, kernel, dim3(pl->core.n_alloc), dim3(256), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt, pl->core.d_e,
+                          pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain, nz);
+            };
+            if (g.N_ant == 1) launch_llr_noise("k_pdsch_demod_llr", k_pdsch_demod_llr<1, PdschLlrNoise>);
+            else if (g.N_ant == 2) launch_llr_noise("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<2, PdschLlrNoise>);
+            else launch_llr_noise("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<4, PdschLlrNoise>);
+        } else if (g.N_ant == 1) launch_llr("k_pdsch_demod_llr", k_pdsch_demod_llr<1>);
         else if (g.N_ant == 2) launch_llr("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<2>); // (a transmit-diversity plan: its own profiling label)
         else launch_llr("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<4>);
     } else if (g.N_ant == 1 && (pl->cfg.sample_format & MI_LTE_CE_COMPACT)) launch(k_pdsch_demod<true, true>);
@@ -1094,7 +1144,10 @@ static int pdsch_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *p
     const MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/false, pack);
     if (pl->g3) {
         rc = mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter);
-        if (rc == MI_LTE_OK && pl->demap == MI_LTE_DEMAP_MAXLOG) ctx->last_kernels.replace(0, strlen("k_pdsch_demod"), pl->cfg.N_ant == 1 ? "k_pdsch_demod_llr" : "k_pdsch_demod_llr_txd");
+        if (rc == MI_LTE_OK && pl->demap == MI_LTE_DEMAP_MAXLOG) {
+            ctx->last_kernels.replace(0, strlen("k_pdsch_demod"), pl->cfg.N_ant == 1 ? "k_pdsch_demod_llr" : "k_pdsch_demod_llr_txd");
+            if (pl->llr_noise > 0.0f) ctx->last_kernels.insert(0, "k_dl_crs_noise:1,");
+        }
         return rc;
     }
     if (!mi_is_bcjr(pl->decoder)) {

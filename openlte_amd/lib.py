@@ -418,6 +418,9 @@ def load_library():
     L.mi_lte_pdsch_plan_cb_ok.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_pdsch_plan_set_demapper.argtypes = [vp, u32, C.c_float]
     L.mi_lte_pdsch_plan_llr_gain.argtypes = [vp, C.POINTER(vp)]
+    L.mi_lte_pdsch_plan_set_llr_noise.argtypes = [vp, C.c_float]
+    L.mi_lte_pdsch_plan_llr_noise.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
+    L.mi_lte_dl_crs_noise_run.argtypes = [vp, C.POINTER(DlCfg), vp, vp, vp, u32, vp]
     L.mi_lte_harq_buffer_bytes.argtypes = [u32]
     L.mi_lte_harq_buffer_bytes.restype = sz
     L.mi_lte_harq_pool_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
@@ -669,6 +672,20 @@ class PdschPlan:
         p = C.c_void_p()
         self.ctx._check(self.ctx.L.mi_lte_pdsch_plan_llr_gain(self.h, C.byref(p)))
         out = np.empty(self.n_alloc, np.float32)
+        self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
+        return out
+
+    def set_llr_noise(self, scale):
+        """3GPP mode: scale > 0: MAXLOG runs use the noise-referenced gain g_a = scale / sigma2[unit] of the CRS noise estimate in place of
+        set_demapper's gain (so retransmissions combine on one scale); 0: off."""
+        self.ctx._check(self.ctx.L.mi_lte_pdsch_plan_set_llr_noise(self.h, scale))
+
+    def llr_noise(self):
+        """3GPP mode: float32 [n_units], sigma2 per unit of the last MAXLOG run with the noise gain on (stage tap; zeros before one);
+        n_units = 1 + the largest unit an allocation of the plan names."""
+        p, n = C.c_void_p(), C.c_uint32()
+        self.ctx._check(self.ctx.L.mi_lte_pdsch_plan_llr_noise(self.h, C.byref(p), C.byref(n)))
+        out = np.empty(n.value, np.float32)
         self.ctx._check(self.ctx.L.mi_lte_memcpy_d2h(self.ctx.h, out.ctypes.data, p.value, out.nbytes))
         return out
 
@@ -1305,6 +1322,23 @@ class Context:
     def dl_frontend_dev(self, cfg, d_a, d_b, d_start, d_sf, d_cell, n_units, d_subframes):
         self._check(self.L.mi_lte_dl_frontend_batch(self.h, C.byref(cfg), d_a.ptr, d_b.ptr if d_b is not None else None,
                                                     d_start.ptr, d_sf.ptr, d_cell.ptr, n_units, d_subframes.ptr))
+
+    def dl_crs_noise_dev(self, cfg, d_subframes, d_sf, d_cell, n_units, d_sigma2):
+        """mi_lte_dl_crs_noise_run: the CRS noise estimate of n_units units of subframe planes (full or CE_COMPACT), float32 [n_units] into
+        d_sigma2; asynchronous on the context's stream."""
+        self._check(self.L.mi_lte_dl_crs_noise_run(self.h, C.byref(cfg), d_subframes.ptr, d_sf.ptr, d_cell.ptr, n_units, d_sigma2.ptr))
+
+    def dl_crs_noise(self, cfg, d_subframes, subfr_num, n_id_cell):
+        """Host convenience: float32 [n_units] for device planes d_subframes and host subframe / cell numbers."""
+        n = len(subfr_num)
+        d_sf, d_cell = self.to_device(np.asarray(subfr_num, np.uint32)), self.to_device(np.asarray(n_id_cell, np.uint32))
+        d_s2 = self.alloc(4 * n)
+        try:
+            self.dl_crs_noise_dev(cfg, d_subframes, d_sf, d_cell, n, d_s2)
+            return d_s2.download(np.float32)
+        finally:
+            for b in (d_sf, d_cell, d_s2):
+                b.free()
 
     def dl_frontend(self, cfg, samples, unit_start, subfr_num, n_id_cell):
         """Host convenience.  samples: int8 [..., 2] interleaved I,Q, or a (i, q) pair of float32 arrays.
