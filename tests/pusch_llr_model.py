@@ -4,7 +4,9 @@ built on demap_llr_model's llr_axis / soft_byte / in_guard / gold.  Two layers:
   exact      demap(): from the tapped symbols x_s[k], the tapped rho_s and the gain to the descrambled bytes at (k 12 + s) Q_m + q -- the
              kernel runs the same double operations in the same order, so the bytes agree outside the 2^-16 guard band.
   tolerance  rho(): from the subframe planes and mi_lte_ul_dmrs_pusch, the demodulator's polar interpolation between the two DMRS estimates
-             (uplink.hip, "DMRS estimates and their interpolation slopes") restated in float64, and rho_s = M / sum_k 1 / |h_k(s)|^2.
+             (uplink.hip, "DMRS estimates and their interpolation slopes") restated in float64, and rho_s = M / sum_k 1 / |h_k(s)|^2;
+             equalise_predecode(): from the same planes, the tapped symbols themselves -- the one-tap equaliser on that estimate and the
+             transform pre-decoder as numpy's float64 inverse FFT (test_pusch_predecode_gpu.py).
 """
 import numpy as np
 
@@ -50,6 +52,26 @@ def h_polar(planes, al, dmrs):
         b = s // 6
         h[s] = (mag[b] + n * f_mag) * np.exp(1j * (ang[b] + n * f_ang))
     return h
+
+
+def equalised(planes, al, dmrs):
+    """complex128 [12, M]: the one-tap equaliser's output z_s[k] = y_s[k] conj(h_s[k]) / |h_s[k]|^2 on the allocation's sub-carriers, y_s the
+    subframe row data_rows()[s] of the symbol's slot and h = h_polar"""
+    p = np.asarray(planes, np.float64)
+    h = h_polar(planes, al, dmrs)
+    z = np.zeros_like(h)
+    for s, L in enumerate(data_rows()):
+        sc = subcarriers(al, s // 6)
+        y = p[0, L, sc] + 1j * p[1, L, sc]
+        z[s] = y * np.conj(h[s]) / (h[s].real * h[s].real + h[s].imag * h[s].imag)
+    return z
+
+
+def equalise_predecode(planes, al, dmrs):
+    """complex128 [12, M]: what k_pusch_demod<.., SPEC = true> taps (mi_lte_pusch_plan_set_llr_tap) -- the equalised symbols through the
+    transform pre-decoder of 36.211 5.3.3, the unnormalised backward DFT times 1 / sqrt(M).  numpy's ifft divides by M, hence times sqrt(M)."""
+    z = equalised(planes, al, dmrs)
+    return np.fft.ifft(z, axis=1) * np.sqrt(z.shape[1])
 
 
 def rho_of(h):
