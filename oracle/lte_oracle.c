@@ -891,9 +891,10 @@ static void wrap_phase(float *phase_1, float phase_2)
     while ((*phase_1 - phase_2) <= -M_PI) *phase_1 = *phase_1 + 2 * M_PI;
 }
 
-/* liblte_phy_get_dl_subframe_and_ce (liblte_phy.cc:5905-6200) */
-int lo_get_dl_subframe_and_ce(const lo_cfg_t *cfg, const float *i_samps, const float *q_samps, uint32_t frame_start_idx,
-                              uint32_t subfr_num, uint32_t N_id_cell, uint32_t N_ant, lo_subframe_t *sf)
+/* liblte_phy_get_dl_subframe_and_ce (liblte_phy.cc:5905-6200).  rows_mag / rows_ang (NULL or float [4][5][LO_N_SC_MAX]): a tap of the
+ * magnitude / phase rows at each port's CRS symbols as they stand after the frequency direction, before the time direction wraps them. */
+static int dl_subframe_and_ce(const lo_cfg_t *cfg, const float *i_samps, const float *q_samps, uint32_t frame_start_idx,
+                              uint32_t subfr_num, uint32_t N_id_cell, uint32_t N_ant, lo_subframe_t *sf, float *rows_mag, float *rows_ang)
 {
     static const uint32_t SYM01[5] = {0, 4, 7, 11, 14}, SYM23[3] = {1, 8, 15};
     static const uint32_t V[4][5] = {{0, 3, 0, 3, 0}, {3, 0, 3, 0, 3}, {0, 3, 0, 0, 0}, {3, 6, 3, 0, 0}};
@@ -951,6 +952,8 @@ int lo_get_dl_subframe_and_ce(const lo_cfg_t *cfg, const float *i_samps, const f
                 ang[i][k + z] = ang[i][k + (z - 1)] - frac_ang;
             }
         }
+        if (rows_mag) memcpy(rows_mag + (size_t)p * 5 * LO_N_SC_MAX, mag, sizeof(float) * N_sym * LO_N_SC_MAX);
+        if (rows_ang) memcpy(rows_ang + (size_t)p * 5 * LO_N_SC_MAX, ang, sizeof(float) * N_sym * LO_N_SC_MAX);
         /* time direction */
         for (uint32_t j = 0; j < N_sc; j++) {
             float(*ce_re)[LO_N_SC_MAX] = sf->rx_ce_re[p], (*ce_im)[LO_N_SC_MAX] = sf->rx_ce_im[p];
@@ -994,6 +997,19 @@ int lo_get_dl_subframe_and_ce(const lo_cfg_t *cfg, const float *i_samps, const f
     free(crs_re);
     free(mag);
     return LO_SUCCESS;
+}
+
+int lo_get_dl_subframe_and_ce(const lo_cfg_t *cfg, const float *i_samps, const float *q_samps, uint32_t frame_start_idx,
+                              uint32_t subfr_num, uint32_t N_id_cell, uint32_t N_ant, lo_subframe_t *sf)
+{
+    return dl_subframe_and_ce(cfg, i_samps, q_samps, frame_start_idx, subfr_num, N_id_cell, N_ant, sf, NULL, NULL);
+}
+
+int lo_get_dl_subframe_and_ce_rows(const lo_cfg_t *cfg, const float *i_samps, const float *q_samps, uint32_t frame_start_idx,
+                                   uint32_t subfr_num, uint32_t N_id_cell, uint32_t N_ant, lo_subframe_t *sf, float *rows_mag,
+                                   float *rows_ang)
+{
+    return dl_subframe_and_ce(cfg, i_samps, q_samps, frame_start_idx, subfr_num, N_id_cell, N_ant, sf, rows_mag, rows_ang);
 }
 
 /* liblte_phy_pdsch_channel_decode (liblte_phy.cc:3690-3853).  The reference's static buffers cap

@@ -113,6 +113,11 @@ void lo_samples_to_symbols_dl(const lo_cfg_t *cfg, const float *samps_re, const 
 int  lo_get_dl_subframe_and_ce(const lo_cfg_t *cfg, const float *i_samps, const float *q_samps,
                                uint32_t frame_start_idx, uint32_t subfr_num, uint32_t N_id_cell, uint32_t N_ant,
                                lo_subframe_t *sf);
+/* the same, with the magnitude / phase rows at every port's CRS symbols after the frequency direction (float [4][5][LO_N_SC_MAX] each,
+ * rows 0..2 for ports 2 and 3; unused rows are left as they were) */
+int  lo_get_dl_subframe_and_ce_rows(const lo_cfg_t *cfg, const float *i_samps, const float *q_samps,
+                                    uint32_t frame_start_idx, uint32_t subfr_num, uint32_t N_id_cell, uint32_t N_ant,
+                                    lo_subframe_t *sf, float *rows_mag, float *rows_ang);
 int  lo_pdsch_channel_decode(const lo_cfg_t *cfg, const lo_subframe_t *sf, const lo_alloc_t *alloc,
                              uint32_t N_pdcch_symbs, uint32_t N_id_cell, uint32_t N_ant, uint8_t *out_bits,
                              uint32_t *N_out_bits, int8_t *soft_bits_tap /* may be NULL */,

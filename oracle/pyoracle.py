@@ -118,6 +118,8 @@ def port():
     L.lo_dlsch_channel_decode.argtypes = [f32p, u32, u32, u32, u32, u32, u32, u8p, C.POINTER(u32), C.c_void_p]
     L.lo_samples_to_symbols_dl.argtypes = [C.POINTER(LoCfg), f32p, f32p, u32, u32, f32p, f32p]
     L.lo_get_dl_subframe_and_ce.argtypes = [C.POINTER(LoCfg), f32p, f32p, u32, u32, u32, u32, C.POINTER(LoSubframe)]
+    if hasattr(L, "lo_get_dl_subframe_and_ce_rows"):  # (absent from a liblte_oracle.so built before the frequency-row tap)
+        L.lo_get_dl_subframe_and_ce_rows.argtypes = [C.POINTER(LoCfg), f32p, f32p, u32, u32, u32, u32, C.POINTER(LoSubframe), f32p, f32p]
     L.lo_pdsch_channel_decode.argtypes = [C.POINTER(LoCfg), C.POINTER(LoSubframe), C.POINTER(LoAlloc), u32, u32, u32,
                                           u8p, C.POINTER(u32), C.c_void_p, C.POINTER(u32)]
     L.lo_time_turbo_decode_ref.argtypes = [f32p, u32, u32, u8p]
