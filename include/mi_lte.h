@@ -511,6 +511,11 @@ int mi_lte_set_turbo_merged(mi_lte_ctx *ctx, uint32_t on);
  * and mi_lte_pdsch_plan_soft_bits returns bytes either way.  Default on; MI_LTE_NO_SOFT_PACK=1 in the environment makes every context of the
  * process start with it off.  A test / tuning knob like the two above. */
 int mi_lte_set_soft_packed(mi_lte_ctx *ctx, uint32_t on);
+/* The PDSCH demodulators form their scrambling words (36.211 7.2) in runs: one word per run from the basis tables, the following ones by a
+ * word-wise step of the two shift registers.  on = 0 reads every word from the tables, as before.  Identical results
+ * (tests/test_gold_run_gpu.py).  Default on; MI_LTE_NO_GOLD_RUN=1 in the environment turns it off for every context of the process that has
+ * not been told otherwise here.  A test / tuning knob like the three above. */
+int mi_lte_set_gold_recurrence(mi_lte_ctx *ctx, uint32_t on);
 
 /* ---------------------------------------------------------------- turbo rate un-matching
  * Replaces liblte_phy_rate_unmatch_turbo() (liblte/hdr/liblte_phy.h:1311-1323, implementation

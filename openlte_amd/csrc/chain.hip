@@ -6,12 +6,15 @@
 // SURVEY F4).
 #include <algorithm>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <type_traits>
 
 #include "plan_core.hpp"
 #include "phy_dev.hpp"
 #include "demap_llr.h"
 #include "soft_pack.h"
+#include "gold_run.h"
 
 namespace {
 
@@ -84,6 +87,13 @@ __device__ __forceinline__ void pair_table_scan(uint2 *tab, const mi_lte_pdsch_a
     if (ln == 63) tab[n_pairs] = make_uint2(incl, 0u); // total
 }
 
+// k_pdsch_demod's `flags`: the packed hand-over (soft_pack.h), and the scrambling words word by word from the tables as before gold_run.h
+enum : uint32_t { DEMOD_PACK = 1u, DEMOD_GOLD_TABLE = 2u };
+// words per run of the scrambling sequence's recurrence (gold_run.h; 2 / 4 / 8 measured: profiles/r11_variants_demod_prologue.txt)
+#ifndef GOLD_RUN_R
+#define GOLD_RUN_R 2
+#endif
+
 // The kernel is latency-bound (a chain of dependent table reads, then scattered plane reads per resource element), so it lives on
 // occupancy: 8 waves per SIMD with a few spilled registers beat 4 without (2.80 -> 2.18 ms per 32k subframes); the single-port
 // case is its own instantiation so that the 2/4-port combiners do not set its register count.
@@ -99,8 +109,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
                                                      const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell,
                                                      GoldTables gt, int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off,
                                                      uint32_t *__restrict__ e_len, uint32_t max_pairs, uint32_t max_words,
-                                                     uint32_t e_lds_cap, uint32_t pack)
+                                                     uint32_t e_lds_cap, uint32_t flags)
 {
+    const uint32_t pack = flags & DEMOD_PACK;
     extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // tab[max_pairs+1] (offset, mask | position) | cw[...] | soft bits (packed hand-over: one mask byte per symbol)
     __shared__ uint2 qam_lut[64]; // hard-decision mask -> six soft bits (16QAM / 64QAM)
     const uint32_t a_idx = blockIdx.x;
@@ -124,7 +135,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
     else {
         const uint32_t n_words_ub = ((n_pairs - pair0) * 12 * Qm + 31) / 32; // <= max_words; one word of slack for the 2-word window in put_bits
         if (threadIdx.x < 128) qam_lut[threadIdx.x - 64] = qam_lut_entry(threadIdx.x - 64);
-        for (uint32_t w = threadIdx.x - 64; w <= n_words_ub; w += blockDim.x - 64) cw[w] = gold_word(gt, c_init, w);
+        gold_fill_words<GOLD_RUN_R>(cw, gt, c_init, n_words_ub, threadIdx.x - 64, blockDim.x - 64, (flags & DEMOD_GOLD_TABLE) != 0);
     }
     __syncthreads();
     const uint32_t M_ap = tab[n_pairs].x;
@@ -237,10 +248,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
                 const float M0 = ld(H_M, vh), M1 = ld(H_M + ROW, vh), M2 = ld(H_M + 2 * ROW, vh);
                 const float P0 = ld(H_A, vh), P1 = ld(H_A + ROW, vh), P2 = ld(H_A + 2 * ROW, vh);
                 const float Q0 = ld(H_A, vk), Q1 = ld(H_A + ROW, vk); // the first slot's phases (second slot only; the same rows again in the first)
-                // the slot's symbols: requested before the interpolation needs its inputs
+                // the slot's symbols: requested before the interpolation needs its inputs.  Not the control region's (first slot, symbols below
+                // cfi <= 4): their masks are empty and the loop below skips them, so nothing reads what is left in their place.  cfi is uniform
+                // over the workgroup, s over all but one of its wavefronts.  (Q0, Q1 stay unconditional: in the first slot they repeat P0, P1's
+                // addresses, and a branch around them cost what this one gains -- profiles/r11_variants_demod_prologue.txt)
                 float yr[7], yi[7];
 #pragma unroll
-                for (int t = 0; t < 7; t++) { yr[t] = ld(t * ROW, vy); yi[t] = ld(Y_IM + t * ROW, vy); }
+                for (int t = 0; t < 7; t++) {
+                    yr[t] = yi[t] = 0.0f;
+                    if (t >= 4 || s || (uint32_t)t >= cfi) { yr[t] = ld(t * ROW, vy); yi[t] = ld(Y_IM + t * ROW, vy); }
+                }
                 // liblte_phy.cc:6119-6190 for symbols 7s .. 7s+6 (ce_time_interp5 above is the whole subframe): symbols 7s and 7s+4 take
                 // the CRS-symbol values as estimated; the slopes see the phases wrapped against their predecessors, from symbol 0 on
                 float m[7], a[7];
@@ -416,7 +433,7 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict
                                                          const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell, GoldTables gt,
                                                          int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len,
                                                          uint32_t max_pairs, uint32_t max_words, uint32_t e_lds_cap, float gain, float auto_t,
-                                                         float *__restrict__ llr_gain, Noise... noise)
+                                                         float *__restrict__ llr_gain, uint32_t gold_table, Noise... noise)
 {
     static_assert(N_ANT == 1 || N_ANT == 2 || N_ANT == 4, "one port, or transmit diversity on two or four");
     static_assert(sizeof...(Noise) <= 1 && (std::is_same<Noise, PdschLlrNoise>::value && ...), "at most the noise-referenced gain's argument");
@@ -437,7 +454,7 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict
     if (threadIdx.x < 64) pair_table_scan(tab, al, N_ANT, cell, sf, cfi, n_pairs, first_sc, last_sc);
     else {
         const uint32_t n_words_ub = ((n_pairs - pair0) * 12 * Qm + 31) / 32;
-        for (uint32_t w = threadIdx.x - 64; w <= n_words_ub; w += blockDim.x - 64) cw[w] = gold_word(gt, c_init, w);
+        gold_fill_words<GOLD_RUN_R>(cw, gt, c_init, n_words_ub, threadIdx.x - 64, blockDim.x - 64, gold_table != 0);
     }
     __syncthreads();
     // (M_ap is a multiple of N_ANT for every allocation: the note at k_pdsch_demod's n_grp)
@@ -1062,6 +1079,32 @@ int mi_lte_pdsch_plan_set_output(mi_lte_pdsch_plan *pl, uint32_t packed)
 
 } // extern "C"
 
+// The scrambling words' A/B switch (gold_run.h): the contexts that were told which method to run, every other one follows the environment.
+// It lives here and not in mi_lte_ctx for the reason given below for mi_dl_crs_noise; mi_lte_ctx_destroy (ctx.cc) calls mi_chain_ctx_release.
+namespace {
+std::mutex                         g_gold_mu;
+std::map<const mi_lte_ctx *, bool> g_gold_table; // context -> word by word from the tables (the method before gold_run.h)
+bool gold_table_of(const mi_lte_ctx *ctx)
+{
+    static const bool env_table = [] { const char *e = getenv("MI_LTE_NO_GOLD_RUN"); return e && atoi(e) != 0; }();
+    std::lock_guard<std::mutex> lk(g_gold_mu);
+    const auto it = g_gold_table.find(ctx);
+    return it == g_gold_table.end() ? env_table : it->second;
+}
+} // namespace
+extern "C" int mi_lte_set_gold_recurrence(mi_lte_ctx *ctx, uint32_t on)
+{
+    if (!ctx) return MI_LTE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(g_gold_mu);
+    g_gold_table[ctx] = on == 0;
+    return MI_LTE_OK;
+}
+void mi_chain_ctx_release(const mi_lte_ctx *ctx)
+{
+    std::lock_guard<std::mutex> lk(g_gold_mu);
+    g_gold_table.erase(ctx);
+}
+
 // dl_noise.hip: k_dl_crs_noise on the context's stream; it checks the bandwidth and the port count.  (Declared here and not in ctx.hpp: the
 // shared headers are part of every file's build id, and the committed profiler tables of the other files stay current this way.)
 int mi_dl_crs_noise(mi_lte_ctx *ctx, uint32_t N_rb_dl, uint32_t N_ant, const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell,
@@ -1076,6 +1119,7 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
     if (rc != MI_LTE_OK) return rc;
     DemodGeom  g{pl->cfg.N_rb_dl, pl->cfg.N_ant, pl->cfi, (uint32_t)mi_lte_subframe_floats(pl->cfg.N_ant)};
     GoldTables gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
+    const bool gold_table = gold_table_of(ctx);
     // LDS: pair table | scrambling words | (when it fits in 32 KiB) the allocation's soft bits
     // A packed run: only the allocations that stay bytes count for e_cap, and a packed allocation's symbol masks (one byte each, at most 15 600: 100
     // resource blocks, 13 symbols) ALWAYS go through the block -- a long QPSK allocation next to them still finds its own rule (e_cap = 0: direct)
@@ -1090,7 +1134,7 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
     }
     auto launch = [&](auto kernel) {
         MI_LAUNCH(ctx, "k_pdsch_demod", kernel, dim3(pl->core.n_alloc), dim3(threads), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt,
-                  pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pack ? 1u : 0u);
+                  pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, (pack ? DEMOD_PACK : 0u) | (gold_table ? DEMOD_GOLD_TABLE : 0u));
     };
     if (pl->demap == MI_LTE_DEMAP_MAXLOG) { // (a 3GPP plan on full estimate planes: mi_lte_pdsch_plan_set_demapper)
         float auto_t = (float)MI_LTE_DEMAP_AUTO_T;
@@ -1100,14 +1144,14 @@ static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_su
         }
         auto launch_llr = [&](const char *name, auto kernel) {
             MI_LAUNCH(ctx, name, kernel, dim3(pl->core.n_alloc), dim3(256), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt, pl->core.d_e,
-                      pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain);
+                      pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain, gold_table ? 1u : 0u);
         };
         if (pl->llr_noise > 0.0f) { // the noise-referenced gain: the CRS noise estimate of the plan's units, then the instantiation that divides by it
             if ((rc = mi_dl_crs_noise(ctx, g.N_rb_dl, g.N_ant, d_subframes, d_subfr_num, d_n_id_cell, pl->n_units, pl->d_llr_s2)) != MI_LTE_OK) return rc;
             const PdschLlrNoise nz{pl->d_llr_s2, pl->llr_noise};
             auto launch_llr_noise = [&](const char *name, auto kernel) {
                 MI_LAUNCH(ctx, name, kernel, dim3(pl->core.n_alloc), dim3(256), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt, pl->core.d_e,
-                          pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain, nz);
+                          pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain, gold_table ? 1u : 0u, nz);
             };
             if (g.N_ant == 1) launch_llr_noise("k_pdsch_demod_llr", k_pdsch_demod_llr<1, PdschLlrNoise>);
             else if (g.N_ant == 2) launch_llr_noise("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<2, PdschLlrNoise>);

@@ -13,6 +13,8 @@
 
 #include "lte_tables.h"
 
+void mi_chain_ctx_release(const mi_lte_ctx *ctx); // chain.hip: forgets the context's mi_lte_set_gold_recurrence setting (declared here: ctx.hpp is part of every kernel file's build id)
+
 extern "C" {
 
 int mi_lte_version(void) { return MI_LTE_VERSION; }
@@ -67,6 +69,7 @@ void mi_lte_ctx_destroy(mi_lte_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->host_cache_free) ctx->host_cache_free(ctx);
+    mi_chain_ctx_release(ctx);
     for (void *p : ctx->owned) (void)hipFree(p);
     for (hipEvent_t e : ctx->prof_pool) (void)hipEventDestroy(e);
     if (ctx->scratch) (void)hipFree(ctx->scratch);

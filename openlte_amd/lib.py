@@ -1596,6 +1596,11 @@ class Context:
         self.L.mi_lte_set_soft_packed.argtypes = [C.c_void_p, C.c_uint32]
         self._check(self.L.mi_lte_set_soft_packed(self.h, 1 if on else 0))
 
+    def set_gold_recurrence(self, on=True):
+        """The PDSCH demodulators' scrambling words in runs by recurrence (default) or, off, word by word from the tables (mi_lte_set_gold_recurrence)."""
+        self.L.mi_lte_set_gold_recurrence.argtypes = [C.c_void_p, C.c_uint32]
+        self._check(self.L.mi_lte_set_gold_recurrence(self.h, 1 if on else 0))
+
     def set_turbo_small_batch(self, n_cb_max):
         """Code blocks per decode up to which the REF decoder's state-parallel trellis kernel runs (0: always the lock-step one)."""
         self._check(self.L.mi_lte_set_turbo_small_batch(self.h, int(n_cb_max)))
