@@ -800,6 +800,54 @@ int mi_lte_pusch_plan_set_llr_noise(mi_lte_pusch_plan *plan, float scale);
  * MI_LTE_ERR_INVALID_ARG on a reference-mode plan. */
 int mi_lte_pusch_plan_llr_noise(const mi_lte_pusch_plan *plan, const float **d_sigma2);
 
+/* ---------------------------------------------------------------- PUSCH, 3GPP mode: receive-antenna combining
+ * A MAXLOG run of a 3GPP plan can combine n_rx = 2 or 4 receive antennas by maximum-ratio combining in front of the transform pre-decoder:
+ * one channel estimate per antenna, one combined symbol per sub-carrier, then the single-antenna chain.  The reference has no counterpart
+ * (liblte_phy_pusch_channel_decode estimates and equalises one antenna); this text is the contract and tests/pusch_rxdiv_model.py restates
+ * it in float64.
+ * Layout of d_subframes on a run of a plan with n_rx > 1 (antenna-major).  The grid of receive antenna r = 0 .. n_rx - 1 of unit u is
+ *   subframe index r * ant_stride + u, each grid in the mi_lte_ul_subframe_floats() layout; ant_stride >= the plan's n_units.  One
+ *   mi_lte_ul_frontend_batch call over n_rx * ant_stride units, antenna r's captures at units r * ant_stride + u, produces it.  Units
+ *   n_units .. ant_stride - 1 of every antenna are not read.
+ * Per-antenna estimate.  For each antenna r the DMRS least-squares products t_{r,b}[i] and the polar interpolation h_r(s)[i] are formed as
+ *   the sections above describe them for the one antenna: the same float operations, the same zero-magnitude guards (mag = 0 gives the
+ *   unit vector (1, 0) and so h = 0) and the same +-pi wrap of the slot-to-slot phase step.
+ * Combining, in float with r ascending.  P_s[i] = sum_r (Re h_r(s)[i]^2 + Im h_r(s)[i]^2);
+ *   z_s[i] = (sum_r y_r(s)[i] conj(h_r(s)[i])) * (1 / P_s[i]), real and imaginary part each a sum over r of the two-product terms the
+ *   single-antenna equaliser forms.  The equaliser's hn becomes 1 / P_s[i]; x_s[k] is the pre-decoder's output for z times (float)(1 / sqrt(M)).
+ * Reliability.  rho_s = (float)(M / sum_i (double)(1 / P_s[i])): the double sum, the fixed order and the not-finite -> 0 rule of the max-log
+ *   section.  With equal noise sigma^2 per antenna the combined symbol carries noise sigma^2 / rho_s: that section's statement with P in
+ *   place of |h|^2.
+ * Noise.  S_r, the second-difference sum of the noise section on antenna r's t_{r,b}; sigma2_a = (float)((sum_r S_r) / (120 N_prb n_rx)),
+ *   summed in double, antenna by antenna inside the section's fixed order.  The antennas' mean: equal noise power per antenna is the
+ *   assumption maximum-ratio combining itself makes.
+ * Gains.  Automatic: g_a = (float)(T / (4 A^2 rhobar)) on the combined rho_s.  Noise-referenced: g_a = (float)(scale / sigma2_a).
+ * Downstream.  The LLR with t = rho_s x and w = rho_s, the soft byte, descrambling and de-interleaving are byte for byte those of the
+ *   max-log section; control information, the CQI decoder, the code blocks and HARQ combining take the bytes as they take any other.
+ *   mi_lte_pusch_plan_llr_gain, _llr_rho, _llr_noise and _llr_symbols report the combined quantities.
+ * Consequences.  An all-zero grid on one antenna gives h_r = 0 through the guards: the antenna drops out of z and rho_s, and it contributes
+ *   S_r = 0, so sigma2_a is the live antennas' sum over n_rx (half the live antenna's estimate at n_rx = 2).  All antennas zero: rho_s = 0
+ *   and every soft bit 0, as with one antenna.  The same grid on every antenna gives the single-antenna z, n_rx times its rho_s and its sigma2_a.
+ * Kernel.  k_pusch_demod_llr_rx, listed under that name in place of k_pusch_demod_llr: one workgroup per allocation, one launch per run, no
+ *   atomics (two runs give identical bytes), 192 threads for M_max <= 96 and 256 above.  Its dynamic LDS in bytes, with M_max = 12 times
+ *   the plan's largest N_prb and W = max over the allocations of ceil(12 M Q_m / 32) + 2 scrambling words:
+ *     LDS(n_rx, S_par) = roundup8(36 n_rx M_max + 8 M_max (1 + 2 S_par) + 4 W) + 464.
+ *   S_par, the data symbols transformed side by side, starts at the single-antenna value (the largest of 12, 6, 3, 2, 1 with
+ *   16 S_par M_max <= 40960) and steps further down that list until LDS(n_rx, S_par) is within the device's per-workgroup limit, which is
+ *   queried, not assumed.  On a 100-RB cell with 160 KiB per workgroup: n_rx = 2 admits every size a plan accepts, up to 99 PRB (144,224
+ *   bytes with 64QAM) at the single-antenna S_par throughout; n_rx = 4 admits up to 76 PRB with a 64QAM allocation of that size (S_par 3 up
+ *   to 65 PRB, 2 up to 70, 1 up to 76) and up to 78 PRB when the widest allocation is QPSK (S_par 3 up to 66 PRB, 2 up to 72, 1 up to 78).
+ * mi_lte_pusch_plan_set_rx_antennas: n_rx = 1 (the default) restores the single-antenna behaviour and ignores ant_stride: such a plan, like
+ *   one that never saw the setter, launches what it launched before with the same arguments and LDS.  Refusals, the plan left as it was:
+ *   MI_LTE_ERR_INVALID_ARG for a NULL plan, an n_rx other than 1, 2 or 4, and n_rx > 1 with ant_stride < n_units;
+ *   MI_LTE_ERR_UNSUPPORTED on a reference-mode plan (any n_rx) and when LDS(n_rx, 1) exceeds the device's limit.
+ *   Accepted whatever the plan's current demapper, but a run with n_rx > 1 while the demapper is MI_LTE_DEMAP_REF launches nothing, returns
+ *   MI_LTE_ERR_UNSUPPORTED and sets the context's error text (the hard-decision demapper has no combiner); the plan runs again once either
+ *   setting is changed.
+ * mi_lte_pusch_plan_rx_antennas: the plan's current n_rx and ant_stride (1 and 0 by default). */
+int mi_lte_pusch_plan_set_rx_antennas(mi_lte_pusch_plan *plan, uint32_t n_rx, uint32_t ant_stride);
+int mi_lte_pusch_plan_rx_antennas(const mi_lte_pusch_plan *plan, uint32_t *n_rx, uint32_t *ant_stride);
+
 /* ---------------------------------------------------------------- PUSCH, 3GPP mode: HARQ soft combining
  * mi_lte_pusch_decode_run on a 3GPP plan with the allocations' soft bits combined into the pool's buffers.  The pool is the type of
  * "PDSCH, 3GPP mode: HARQ soft combining" above, and one pool of a context serves its PDSCH and PUSCH plans alike; the contract is that

@@ -236,6 +236,19 @@ struct PuschLlrNoise : PuschLlr {
 };
 constexpr uint32_t LLR_NOISE_LDS_BYTES = LLR_LDS_BYTES + 4 * sizeof(double); // nsum[4] (double) behind rho
 static_assert(LLR_LDS_BYTES % sizeof(double) == 0, "nsum is read as double");
+// Receive-antenna combining (mi_lte_pusch_plan_set_rx_antennas, include/mi_lte.h "PUSCH, 3GPP mode: receive-antenna combining") is one more
+// family, k_pusch_demod<THREADS, true, PuschLlrRx<N_RX, NOISE>> (launched and listed as k_pusch_demod_llr_rx), N_RX = 2 or 4: the grid of
+// antenna r of unit u is subframe r ant_stride + u, the LDS holds N_RX sets of the nine estimate rows in front of the twiddles, the estimate
+// phase, the noise pass and the rho pass loop over the antennas, and the equaliser's (sub-carrier, slot) item forms
+// z = (sum_r y_r conj(h_r)) / sum_r |h_r|^2.  The transform, the de-mapper and every buffer are the single-antenna ones.  The argument block
+// and the LDS slots are PuschLlrNoise's (NOISE = false leaves noise and s2_out unused) plus the stride.  With N_RX = 1 -- every other
+// instantiation -- each antenna loop has one trip and each `if constexpr (N_RX > 1)` drops out.
+template <uint32_t N, bool NOISE_>
+struct PuschLlrRx : PuschLlrNoise {
+    uint32_t ant_stride; // subframes between the grids of antennas r and r + 1 of one unit
+};
+template <typename T> struct RxOf { static constexpr uint32_t N = 1; static constexpr bool NOISE = false; };
+template <uint32_t N_, bool NOISE_> struct RxOf<PuschLlrRx<N_, NOISE_>> { static constexpr uint32_t N = N_; static constexpr bool NOISE = NOISE_; };
 
 // h(s) of data symbol sp (0 .. 5) of a slot and hn = 1 / |h|^2 as the one-tap equaliser uses it, from the slot's DMRS estimate: magnitude and
 // slope, u = exp(i ang_b), f1 .. f3 = exp(i n f_ang) for n = 1, 2, 3 (liblte_phy.cc:13770-13780: symbols 0-2 / 3-5 of a slot lie -3..-1 /
@@ -254,25 +267,30 @@ __device__ __forceinline__ void slot_h(float mag, float f_mag, float2 u, float2 
 __device__ __forceinline__ PuschNoLlr llr_args() { return PuschNoLlr{}; }
 __device__ __forceinline__ const PuschLlr &llr_args(const PuschLlr &la) { return la; }
 __device__ __forceinline__ const PuschLlrNoise &llr_args(const PuschLlrNoise &la) { return la; }
+template <uint32_t N, bool NOISE_> __device__ __forceinline__ const PuschLlrRx<N, NOISE_> &llr_args(const PuschLlrRx<N, NOISE_> &la) { return la; }
 #ifndef WPE_LLR
 #define WPE_LLR 4
 #endif
 
 template <uint32_t THREADS, bool SPEC = false, typename... LlrArgs>
-__attribute__((amdgpu_waves_per_eu(sizeof...(LlrArgs) ? WPE_LLR : WPE, 8)))
+// (four antennas: the equaliser item carries four sets of estimates and grid values for six symbols, and the LDS of such a launch keeps the
+// occupancy under 4 from 10 PRB on anyway -- 3 waves per SIMD, 168 registers, in place of a spill)
+__attribute__((amdgpu_waves_per_eu((RxOf<LlrArgs>::N * ... * 1u) == 4 ? 3 : sizeof...(LlrArgs) ? WPE_LLR : WPE, 8)))
 __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict__ subframes, uint32_t sf_stride,
                                                      const mi_lte_pdsch_alloc *__restrict__ allocs, const PuschDesc *__restrict__ desc,
                                                      const float *__restrict__ dmrs_pool, GoldTables gt, int8_t *__restrict__ e_base,
                                                      const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len, uint32_t M_max,
                                                      uint32_t S_par, float r_S_par, const PuschShape *__restrict__ shapes, LlrArgs... la_pack)
 {
-    constexpr bool LLR = sizeof...(LlrArgs) == 1, NOISE = (std::is_same<LlrArgs, PuschLlrNoise>::value || ...);
+    constexpr bool LLR = sizeof...(LlrArgs) == 1, NOISE = (std::is_same<LlrArgs, PuschLlrNoise>::value || ...) || (RxOf<LlrArgs>::NOISE || ...);
+    constexpr uint32_t N_RX = (RxOf<LlrArgs>::N * ... * 1u); // receive antennas combined (PuschLlrRx); 1 everywhere else
     static_assert(sizeof...(LlrArgs) <= 1 && (!LLR || SPEC), "the max-log de-mapper belongs to the 3GPP mode");
     [[maybe_unused]] const auto la = llr_args(la_pack...);
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    // LDS: est[9][M_max] (mag0 mag1 dmag | unit vectors of ang0, ang1, dang) | tw[M_max] | buf A[S_par][M_max] | buf B[S_par][M_max] (float2) | scrambling words
+    // LDS: est[N_RX][9][M_max] (mag0 mag1 dmag | unit vectors of ang0, ang1, dang; one set per antenna) | tw[M_max] | buf A[S_par][M_max] |
+    // buf B[S_par][M_max] (float2) | scrambling words
     float    *est  = sm;
-    float2   *tw   = reinterpret_cast<float2 *>(sm + EST_ROWS * (size_t)M_max);
+    float2   *tw   = reinterpret_cast<float2 *>(sm + N_RX * EST_ROWS * (size_t)M_max);
     float2   *bufA = tw + M_max, *bufB = bufA + (size_t)S_par * M_max;
     uint32_t *cw   = reinterpret_cast<uint32_t *>(bufB + (size_t)S_par * M_max);
 
@@ -284,6 +302,8 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
     const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : al.mod_type == 1 ? 2 : 1;
     const uint32_t N_bits = 12 * M * Qm;
     const float   *rx_re = subframes + (size_t)al.unit * sf_stride, *rx_im = rx_re + 16 * N_SC_MAX;
+    [[maybe_unused]] size_t ant_floats = 0; // from the grid of antenna r of a unit to that of antenna r + 1
+    if constexpr (N_RX > 1) ant_floats = (size_t)la.ant_stride * sf_stride;
     if (threadIdx.x == 0) e_len[a_idx] = N_bits;
 
     // scrambling sequence (c_init per liblte_phy.cc:2893), one word of slack for the 2-word window below
@@ -295,8 +315,16 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
     // what is kept per subcarrier is exp(i ang_b) = t_b / |t_b| and exp(i f_ang), so the 12 data symbols cost complex products,
     // not 12 sin/cos pairs.  Work is spread as (subcarrier, task): task 0/1 = DMRS symbol 0/1, task 2 = the twiddle.
     const float *d_pool = dmrs_pool + ds.dmrs_off; // dmrs_0_re | dmrs_0_im | dmrs_1_re | dmrs_1_im (M each)
-    for (uint32_t o = threadIdx.x; o < 3 * M; o += THREADS) {
-        const uint32_t task = o >= 2 * M ? 2 : o >= M ? 1 : 0, i = o - task * M;
+    // With N_RX antennas the items are (subcarrier, 2 r + b) for antenna r, then the twiddle.
+    for (uint32_t o = threadIdx.x; o < (2 * N_RX + 1) * M; o += THREADS) {
+        uint32_t task, i, r = 0;
+        if constexpr (N_RX == 1) { task = o >= 2 * M ? 2 : o >= M ? 1 : 0; i = o - task * M; }
+        else {
+            const uint32_t q = quot(o, sh.r_M);
+            i = o - __umul24(q, M); r = q >> 1; task = q >= 2 * N_RX ? 2 : q & 1u;
+        }
+        float       *er = est + r * (EST_ROWS * M_max); // antenna r's nine rows
+        const float *ar_re = rx_re + r * ant_floats, *ar_im = rx_im + r * ant_floats; // and its grid
         if (task == 2) {
             float sn, cs;
             sincospif(2.0f * (float)i / (float)M, &sn, &cs);
@@ -304,27 +332,30 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
         } else {
             const uint32_t rb = __umul24(i, 10923u) >> 17; // i / 12 for i < 1536
             const uint32_t sc = al.prb[task][rb] * 12 + (i - 12 * rb), L = task ? 10 : 3;
-            const float    cr = rx_re[L * N_SC_MAX + sc], ci = rx_im[L * N_SC_MAX + sc];
+            const float    cr = ar_re[L * N_SC_MAX + sc], ci = ar_im[L * N_SC_MAX + sc];
             const float    dr = d_pool[2 * task * M + i], di = d_pool[(2 * task + 1) * M + i];
             const float    t_re = cr * dr + ci * di, t_im = ci * dr - cr * di;
             const float    mag = sqrtf(t_re * t_re + t_im * t_im);
-            est[task * M_max + i] = mag;
-            est[(3 + 2 * task) * M_max + i] = mag > 0.0f ? t_re / mag : 1.0f; // atan2f(0, 0) = 0
-            est[(4 + 2 * task) * M_max + i] = mag > 0.0f ? t_im / mag : 0.0f;
-            if (task == 0) est[8 * M_max + i] = atan2f(t_im, t_re);
-            else           est[2 * M_max + i] = atan2f(t_im, t_re); // parked in the rows the second step overwrites
+            er[task * M_max + i] = mag;
+            er[(3 + 2 * task) * M_max + i] = mag > 0.0f ? t_re / mag : 1.0f; // atan2f(0, 0) = 0
+            er[(4 + 2 * task) * M_max + i] = mag > 0.0f ? t_im / mag : 0.0f;
+            if (task == 0) er[8 * M_max + i] = atan2f(t_im, t_re);
+            else           er[2 * M_max + i] = atan2f(t_im, t_re); // parked in the rows the second step overwrites
         }
     }
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < M; i += THREADS) {
-        const float f_mag = (est[M_max + i] - est[i]) / 7;
-        float       f_ang = est[2 * M_max + i] - est[8 * M_max + i];
+    for (uint32_t o = threadIdx.x; o < N_RX * M; o += THREADS) { // (antenna, subcarrier)
+        uint32_t i = o, r = 0;
+        if constexpr (N_RX > 1) { r = quot(o, sh.r_M); i = o - __umul24(r, M); }
+        float      *er = est + r * (EST_ROWS * M_max);
+        const float f_mag = (er[M_max + i] - er[i]) / 7;
+        float       f_ang = er[2 * M_max + i] - er[8 * M_max + i];
         if ((double)f_ang >= M_PI) f_ang = (float)((double)f_ang - 2 * M_PI); // float compared / corrected in double (:13758-13764)
         else if ((double)f_ang <= -M_PI) f_ang = (float)((double)f_ang + 2 * M_PI);
         f_ang /= 7;
         float sn, cs;
         sincosf(f_ang, &sn, &cs);
-        est[2 * M_max + i] = f_mag; est[7 * M_max + i] = cs; est[8 * M_max + i] = sn;
+        er[2 * M_max + i] = f_mag; er[7 * M_max + i] = cs; er[8 * M_max + i] = sn;
     }
     __syncthreads();
 
@@ -348,9 +379,13 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
         // sub-carriers and leaves 6 sigma^2 of white noise: S = sum |d|^2 over 2 slots x 10 N_prb terms, in double and in the rho pass's
         // fixed order (thread, xor butterfly, wavefront slots; the slots are read behind the rho pass's first barrier).
         if constexpr (NOISE) {
+            // With N_RX antennas S = sum_r S_r, antenna by antenna in this order (the mean over the antennas is taken where sigma2 is formed).
             double part = 0.0;
+#pragma unroll
+            for (uint32_t r = 0; r < N_RX; r++)
             for (uint32_t b = 0; b < 2; b++) {
-                const float *mg = est + b * M_max, *ur = est + (3 + 2 * b) * M_max, *ui = est + (4 + 2 * b) * M_max;
+                const float *er = est + r * (EST_ROWS * M_max);
+                const float *mg = er + b * M_max, *ur = er + (3 + 2 * b) * M_max, *ui = er + (4 + 2 * b) * M_max;
                 for (uint32_t i = threadIdx.x; i < M; i += THREADS) {
                     const uint32_t r = i - 12 * (__umul24(i, 10923u) >> 17); // i mod 12 for i < 1536
                     if (r == 0 || r == 11) continue; // (so i - 1 and i + 1 stay inside the block, and inside 0 .. M - 1)
@@ -366,6 +401,25 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
         for (uint32_t b = 0; b < 2; b++) { // slot: six data symbols per pass, so a thread carries six partial sums
             double part[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             for (uint32_t i = threadIdx.x; i < M; i += THREADS) {
+                if constexpr (N_RX > 1) { // hn = 1 / P, P = sum_r |h_r|^2 in float with r ascending: the float the combining equaliser multiplies with
+                    float P[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                    for (uint32_t r = 0; r < N_RX; r++) {
+                        const float *er = est + r * (EST_ROWS * M_max);
+                        const float  mag = er[b * M_max + i], f_mag = er[2 * M_max + i];
+                        const float2 u = make_float2(er[(3 + 2 * b) * M_max + i], er[(4 + 2 * b) * M_max + i]);
+                        const float2 f1 = make_float2(er[7 * M_max + i], er[8 * M_max + i]), f2 = cmul(f1, f1), f3 = cmul(f2, f1);
+#pragma unroll
+                        for (uint32_t sp = 0; sp < 6; sp++) {
+                            float h_re, h_im, hn;
+                            slot_h(mag, f_mag, u, f1, f2, f3, sp, h_re, h_im, hn);
+                            P[sp] += h_re * h_re + h_im * h_im;
+                        }
+                    }
+#pragma unroll
+                    for (uint32_t sp = 0; sp < 6; sp++) part[sp] += (double)(1.0f / P[sp]);
+                    continue;
+                }
                 const float    mag = est[b * M_max + i], f_mag = est[2 * M_max + i];
                 const float2   u = make_float2(est[(3 + 2 * b) * M_max + i], est[(4 + 2 * b) * M_max + i]);
                 const float2   f1 = make_float2(est[7 * M_max + i], est[8 * M_max + i]), f2 = cmul(f1, f1), f3 = cmul(f2, f1);
@@ -398,7 +452,9 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
         if constexpr (NOISE) { // every thread forms the same sum in the same order
             double S = nsum[0];
             for (uint32_t w = 1; w < THREADS / 64; w++) S += nsum[w];
-            const float s2 = (float)(S / (120.0 * (double)N_prb));
+            float s2;
+            if constexpr (N_RX > 1) s2 = (float)(S / (120.0 * (double)N_prb * (double)N_RX)); // the antennas' mean: MRC assumes equal noise power per antenna
+            else s2 = (float)(S / (120.0 * (double)N_prb));
             const float gf = (float)((double)la.noise / (double)s2);
             // sigma2 0 or not finite, or a gain past float: every soft bit 0
             gd = (s2 > 0.0f && s2 <= 3.4028234e38f && fabsf(gf) <= 3.4028234e38f) ? (double)gf : 0.0;
@@ -422,6 +478,37 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
         const uint32_t slot0 = s0 >= 6, n_slots = S == 12 ? 2 : 1, sp0 = s0 - 6 * slot0, sp1 = sp0 + (S == 12 ? 6 : S);
         for (uint32_t o = threadIdx.x; o < n_slots * M; o += THREADS) {
             const uint32_t b = slot0 + (o >= M), i = o - (o >= M ? M : 0);
+            if constexpr (N_RX > 1) { // z = (sum_r y_r conj(h_r)) (1 / P), P = sum_r |h_r|^2: float sums with r ascending, the item's symbols side by side
+                const uint32_t rb = __umul24(i, 10923u) >> 17; // i / 12 for i < 1536
+                const uint32_t sc = al.prb[b][rb] * 12 + (i - 12 * rb);
+                float2        *dst = bufA + ((int)(6 * b) - (int)s0) * (int)M_max + (int)i;
+                float          c_re[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, c_im[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, P[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (uint32_t r = 0; r < N_RX; r++) {
+                    const float *er = est + r * (EST_ROWS * M_max);
+                    const float  mag = er[b * M_max + i], f_mag = er[2 * M_max + i];
+                    const float2 u = make_float2(er[(3 + 2 * b) * M_max + i], er[(4 + 2 * b) * M_max + i]);
+                    const float2 f1 = make_float2(er[7 * M_max + i], er[8 * M_max + i]), f2 = cmul(f1, f1), f3 = cmul(f2, f1);
+                    const float *z_re = rx_re + r * ant_floats + 7 * b * N_SC_MAX + sc, *z_im = rx_im + r * ant_floats + 7 * b * N_SC_MAX + sc;
+#pragma unroll
+                    for (uint32_t sp = 0; sp < 6; sp++) {
+                        if (sp < sp0 || sp >= sp1) continue; // uniform
+                        const uint32_t l = sp < 3 ? sp : sp + 1;
+                        float          h_re, h_im, hn;
+                        slot_h(mag, f_mag, u, f1, f2, f3, sp, h_re, h_im, hn);
+                        const float zr = z_re[l * N_SC_MAX], zi = z_im[l * N_SC_MAX];
+                        c_re[sp] += zr * h_re + zi * h_im; c_im[sp] += zi * h_re - zr * h_im;
+                        P[sp] += h_re * h_re + h_im * h_im;
+                    }
+                }
+#pragma unroll
+                for (uint32_t sp = 0; sp < 6; sp++) {
+                    if (sp < sp0 || sp >= sp1) continue; // uniform
+                    const float hn = 1.0f / P[sp];
+                    dst[sp * M_max] = make_float2(c_re[sp] * hn, c_im[sp] * hn);
+                }
+                continue;
+            }
             const float    mag = est[b * M_max + i], f_mag = est[2 * M_max + i];
             const float2   u = make_float2(est[(3 + 2 * b) * M_max + i], est[(4 + 2 * b) * M_max + i]);
             const float2   f1 = make_float2(est[7 * M_max + i], est[8 * M_max + i]), f2 = cmul(f1, f1), f3 = cmul(f2, f1);
@@ -612,7 +699,35 @@ struct mi_lte_pusch_plan {
     float2       *d_llr_x = nullptr;
     uint32_t     *d_x_off = nullptr;
     std::vector<uint32_t> h_x_off;
+    // mi_lte_pusch_plan_set_rx_antennas: antennas a MAXLOG run combines (1: off) and the subframes between two antennas' grids of one unit;
+    // the instantiations of k_pusch_demod_llr_rx whose dynamic-LDS attribute is set on the plan's device (one bit each)
+    uint32_t      n_units = 0, n_rx = 1, ant_stride = 0, rx_lds_set = 0;
 };
+
+// Data symbols a workgroup transforms side by side: as many of 12, 6, 3, 2, 1 as keep the two ping-pong buffers within ~40 KiB (all 12 up to 17 PRB)
+static uint32_t pusch_s_par(uint32_t M_max)
+{
+    uint32_t S_par = 12;
+    while (S_par > 1 && (size_t)S_par * M_max * 2 * sizeof(float2) > 40 * 1024) S_par = S_par == 12 ? 6 : S_par == 6 ? 3 : S_par - 1; // 12, or a divisor of 6
+    return S_par;
+}
+
+// Dynamic LDS of the demodulator in front of its LLR block: n_rx sets of estimate rows, the twiddles, the ping-pong buffers, the scrambling words
+static size_t pusch_lds(uint32_t n_rx, uint32_t M_max, uint32_t words_max, uint32_t S_par)
+{
+    return sizeof(float) * EST_ROWS * (size_t)n_rx * M_max + sizeof(float2) * (size_t)M_max * (1 + 2 * S_par) + sizeof(uint32_t) * (words_max + 1);
+}
+
+// S_par of a combining launch (include/mi_lte.h): pusch_s_par's value, stepped further down 3 -> 2 -> 1 until the launch's whole dynamic LDS
+// fits `limit` bytes; 0 when it does not fit at S_par = 1.  *lds: the bytes in front of the LLR block, as pusch_lds gives them.
+static uint32_t pusch_rx_s_par(uint32_t n_rx, uint32_t M_max, uint32_t words_max, size_t limit, size_t *lds)
+{
+    for (uint32_t S_par = pusch_s_par(M_max); S_par >= 1; S_par = S_par == 12 ? 6 : S_par == 6 ? 3 : S_par - 1) {
+        *lds = pusch_lds(n_rx, M_max, words_max, S_par);
+        if (((*lds + 7) & ~(size_t)7) + LLR_NOISE_LDS_BYTES <= limit) return S_par;
+    }
+    return 0;
+}
 
 // UL-SCH rate matching has no soft-buffer limit (36.212 5.2.2.5: N_cb = K_w).  As a DL-SCH soft-buffer configuration: an N_IR no block reaches
 static const mi_lte_dlsch_cfg ULSCH_AS_DLSCH = {MI_LTE_ULSCH_N_SOFT, MI_LTE_ULSCH_M_HARQ};
@@ -681,6 +796,7 @@ static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
     pl->cfg     = *cfg;
     pl->device  = ctx->device;
     pl->core.n_alloc = n_alloc;
+    pl->n_units = n_units;
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> dmrs_at; // (cell, subframe, N_prb) -> float offset
     std::vector<float>     dmrs;
     std::vector<PuschDesc> desc(n_alloc);
@@ -914,6 +1030,27 @@ int mi_lte_pusch_plan_llr_noise(const mi_lte_pusch_plan *pl, const float **d_sig
     return MI_LTE_OK;
 }
 
+int mi_lte_pusch_plan_set_rx_antennas(mi_lte_pusch_plan *pl, uint32_t n_rx, uint32_t ant_stride)
+{
+    if (!pl || !(n_rx == 1 || n_rx == 2 || n_rx == 4)) return MI_LTE_ERR_INVALID_ARG;
+    if (!pl->g3) return MI_LTE_ERR_UNSUPPORTED; // a reference-mode plan has no max-log de-mapper to combine for
+    if (n_rx == 1) { pl->n_rx = 1; pl->ant_stride = 0; return MI_LTE_OK; }
+    if (ant_stride < pl->n_units) return MI_LTE_ERR_INVALID_ARG;
+    int limit = 0; // the device's per-workgroup LDS: the combining launch has to fit it at some S_par
+    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, pl->device) != hipSuccess) return MI_LTE_ERR_HIP;
+    size_t lds;
+    if (!pusch_rx_s_par(n_rx, pl->M_max, pl->words_max, (size_t)std::max(limit, 0), &lds)) return MI_LTE_ERR_UNSUPPORTED;
+    pl->n_rx = n_rx; pl->ant_stride = ant_stride;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_rx_antennas(const mi_lte_pusch_plan *pl, uint32_t *n_rx, uint32_t *ant_stride)
+{
+    if (!pl || !n_rx || !ant_stride) return MI_LTE_ERR_INVALID_ARG;
+    *n_rx = pl->n_rx; *ant_stride = pl->ant_stride;
+    return MI_LTE_OK;
+}
+
 int mi_lte_pusch_plan_set_llr_tap(mi_lte_pusch_plan *pl, uint32_t on)
 {
     if (!pl || !pl->g3) return MI_LTE_ERR_INVALID_ARG;
@@ -1009,16 +1146,17 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
         if (!pl->g3) { ctx->err = "HARQ soft combining needs a plan in the 3GPP transport-block mode"; return MI_LTE_ERR_UNSUPPORTED; }
         if ((rc = mi_dlsch3_harq_check(ctx, pl->g3, pool, h_bind)) != MI_LTE_OK) return rc;
     }
+    if (pl->n_rx > 1 && pl->demap != MI_LTE_DEMAP_MAXLOG) { // (mi_lte_pusch_plan_set_rx_antennas: changing either setting makes the plan runnable again)
+        ctx->err = "receive-antenna combining needs the max-log demapper (mi_lte_pusch_plan_set_demapper, MI_LTE_DEMAP_MAXLOG)";
+        return MI_LTE_ERR_UNSUPPORTED;
+    }
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     rc = mi_ctx_gold_tables(ctx);
     if (rc != MI_LTE_OK) return rc;
     if ((rc = pusch_shapes(ctx)) != MI_LTE_OK) return rc;
     GoldTables   gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
-    // as many of the 12 data symbols side by side as fit in ~40 KiB of ping-pong buffers (all 12 up to 17 PRB)
-    uint32_t S_par = 12;
-    while (S_par > 1 && (size_t)S_par * pl->M_max * 2 * sizeof(float2) > 40 * 1024) S_par = S_par == 12 ? 6 : S_par == 6 ? 3 : S_par - 1; // 12, or a divisor of 6
-    const size_t lds = sizeof(float) * EST_ROWS * (size_t)pl->M_max + sizeof(float2) * (size_t)pl->M_max * (1 + 2 * S_par) +
-                       sizeof(uint32_t) * (pl->words_max + 1);
+    const uint32_t S_par = pusch_s_par(pl->M_max);
+    const size_t   lds   = pusch_lds(1, pl->M_max, pl->words_max, S_par);
     // Workgroup size: the kernel's phases hold 3 M, M, 2 M, 12 M / R and 12 M items (M = 12 N_prb sub-carriers) between barriers, and the
     // heavy ones (atan2f, sincosf, the divisions) are the short ones -- a workgroup much wider than 3 M leaves whole wavefronts waiting at
     // every barrier for the one that has the transcendental work (SQ_WAIT_ANY: 67 % of the wave time at 256 threads and M = 72).  Measured on
@@ -1034,7 +1172,17 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
 #define MI_PUSCH_LAUNCH(T) do { if (pl->g3) MI_PUSCH_LAUNCH_V(T, true); else MI_PUSCH_LAUNCH_V(T, false); } while (0)
     const bool llr = pl->g3 && pl->demap == MI_LTE_DEMAP_MAXLOG; // (mi_lte_pusch_plan_set_demapper)
     if (llr) { // the same launch with the LLR block behind the scrambling words: the only instantiation whose dynamic LDS grows
-        const size_t   lds_off = (lds + 7) & ~(size_t)7;
+        // combining: n_rx sets of estimate rows, and S_par stepped down until the whole launch fits the device's per-workgroup LDS
+        uint32_t S_rx = S_par;
+        size_t   lds_rx = lds, lds_limit = 0;
+        if (pl->n_rx > 1) {
+            int limit = 0;
+            MI_HIP_CHECK(ctx, hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+            lds_limit = (size_t)std::max(limit, 0);
+            S_rx      = pusch_rx_s_par(pl->n_rx, pl->M_max, pl->words_max, lds_limit, &lds_rx);
+            if (!S_rx) { ctx->err = "receive-antenna combining: the plan's widest allocation does not fit the device's LDS"; return MI_LTE_ERR_UNSUPPORTED; }
+        }
+        const size_t   lds_off = (lds_rx + 7) & ~(size_t)7;
         float          auto_t  = (float)MI_LTE_DEMAP_AUTO_T;
         if (const char *ev = getenv("MI_LTE_DEMAP_AUTO_T")) { // (tuning aid: tools/pusch_llr_sweep.py checks the header's constant with it)
             const float t = (float)atof(ev);
@@ -1046,7 +1194,26 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
                                          (uint32_t)mi_lte_ul_subframe_floats(), pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, \
                                          pl->core.d_e_len, pl->M_max, S_par, recip_up(S_par), static_cast<const PuschShape *>(ctx->d_pusch_shapes), la)
 #define MI_PUSCH_LAUNCH_LLR(T) do { if (pl->llr_noise > 0.0f) MI_PUSCH_LAUNCH_LLR_V(T, PuschLlrNoise, LLR_NOISE_LDS_BYTES, ln); else MI_PUSCH_LAUNCH_LLR_V(T, PuschLlr, LLR_LDS_BYTES, la); } while (0)
+        // More than 64 KB of dynamic LDS has to be asked for, per kernel and device (as bcjr.hip does for k_bcjr_block): once per plan and
+        // instantiation.  Two widths only, the run function's own choice: MI_LTE_PUSCH_THREADS does not reach the combining launch.
+#define MI_PUSCH_LAUNCH_RX_V(T, N, NZ) do { \
+            const PuschLlrRx<N, NZ> lr{ln, pl->ant_stride}; \
+            const uint32_t bit = 1u << ((T == 256 ? 1 : 0) + (N == 4 ? 2 : 0) + (NZ ? 4 : 0)); \
+            if (!(pl->rx_lds_set & bit)) { \
+                MI_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k_pusch_demod<T, true, PuschLlrRx<N, NZ>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit)); \
+                pl->rx_lds_set |= bit; \
+            } \
+            MI_LAUNCH(ctx, "k_pusch_demod_llr_rx", (k_pusch_demod<T, true, PuschLlrRx<N, NZ>>), dim3(pl->core.n_alloc), dim3(T), lds_off + LLR_NOISE_LDS_BYTES, d_subframes, \
+                      (uint32_t)mi_lte_ul_subframe_floats(), pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, \
+                      pl->core.d_e_len, pl->M_max, S_rx, recip_up(S_rx), static_cast<const PuschShape *>(ctx->d_pusch_shapes), lr); } while (0)
+#define MI_PUSCH_LAUNCH_RX(T, N) do { if (pl->llr_noise > 0.0f) MI_PUSCH_LAUNCH_RX_V(T, N, true); else MI_PUSCH_LAUNCH_RX_V(T, N, false); } while (0)
+        if (pl->n_rx > 1) {
+            if (pl->M_max <= 96) { if (pl->n_rx == 2) MI_PUSCH_LAUNCH_RX(192, 2); else MI_PUSCH_LAUNCH_RX(192, 4); }
+            else                 { if (pl->n_rx == 2) MI_PUSCH_LAUNCH_RX(256, 2); else MI_PUSCH_LAUNCH_RX(256, 4); }
+        } else
         if (threads == 64) MI_PUSCH_LAUNCH_LLR(64); else if (threads == 128) MI_PUSCH_LAUNCH_LLR(128); else if (threads == 192) MI_PUSCH_LAUNCH_LLR(192); else MI_PUSCH_LAUNCH_LLR(256);
+#undef MI_PUSCH_LAUNCH_RX
+#undef MI_PUSCH_LAUNCH_RX_V
 #undef MI_PUSCH_LAUNCH_LLR
 #undef MI_PUSCH_LAUNCH_LLR_V
     } else if (threads == 64) MI_PUSCH_LAUNCH(64); else if (threads == 128) MI_PUSCH_LAUNCH(128); else if (threads == 192) MI_PUSCH_LAUNCH(192); else MI_PUSCH_LAUNCH(256);
@@ -1063,7 +1230,7 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
         if ((rc = mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter)) != MI_LTE_OK) return rc;
         const size_t at = ctx->last_kernels.find(','); // (mi_dlsch3_run lists the downlink's demodulator in front of its own kernels)
         ctx->last_kernels.replace(0, at == std::string::npos ? 0 : at,
-                                  std::string(llr ? "k_pusch_demod_llr:1" : "k_pusch_demod:1") +
+                                  std::string(llr && pl->n_rx > 1 ? "k_pusch_demod_llr_rx:1" : llr ? "k_pusch_demod_llr:1" : "k_pusch_demod:1") +
                                       (!pl->uci          ? ""
                                        : pl->uci->cqi_on ? ",k_ulsch_uci_gather:1,k_ulsch_uci_decide:1,k_ulsch_cqi_decode:1"
                                                          : ",k_ulsch_uci_gather:1,k_ulsch_uci_decide:1"));

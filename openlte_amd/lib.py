@@ -464,6 +464,8 @@ def load_library():
     L.mi_lte_pusch_plan_set_llr_tap.argtypes = [vp, u32]
     L.mi_lte_pusch_plan_set_llr_noise.argtypes = [vp, C.c_float]
     L.mi_lte_pusch_plan_llr_noise.argtypes = [vp, C.POINTER(vp)]
+    L.mi_lte_pusch_plan_set_rx_antennas.argtypes = [vp, u32, u32]
+    L.mi_lte_pusch_plan_rx_antennas.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     L.mi_lte_pusch_decode_run_harq.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.mi_lte_pusch_plan_llr_symbols.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32)]
     L.mi_lte_prach_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), C.POINTER(vp)]
@@ -990,6 +992,17 @@ class PuschPlan:
     def llr_noise(self):
         """3GPP mode: float32 [n_alloc], sigma2_a of the last MAXLOG run with the noise gain on (stage tap; zeros before one)."""
         return self._llr_floats(self.ctx.L.mi_lte_pusch_plan_llr_noise, self.n_alloc)
+
+    def set_rx_antennas(self, n_rx, ant_stride=0):
+        """3GPP mode: MAXLOG runs combine n_rx = 2 or 4 receive antennas (maximum-ratio combining); the grid of antenna r of unit u is
+        subframe r * ant_stride + u of the run's d_subframes, ant_stride >= the plan's units.  n_rx = 1: off."""
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_set_rx_antennas(self.h, n_rx, ant_stride))
+
+    def rx_antennas(self):
+        """(n_rx, ant_stride) as the plan holds them: (1, 0) by default"""
+        n, s = C.c_uint32(), C.c_uint32()
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_rx_antennas(self.h, C.byref(n), C.byref(s)))
+        return int(n.value), int(s.value)
 
     def set_llr_tap(self, on=True):
         """3GPP mode: have MAXLOG runs also store the de-mapper's input symbols (llr_symbols); off frees the buffer again."""

@@ -257,6 +257,29 @@ def ul_units_3gpp(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, uci=None, a
     return iq, tx
 
 
+def ul_units_3gpp_rx(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, n_rx, ant_stride=None, seeds=None, payload=None, seed=1, **kw):
+    """n_rx receive-antenna captures of the same transmission, in the antenna-major order mi_lte_pusch_plan_set_rx_antennas reads: unit
+    r * ant_stride + u is antenna r of unit u (ant_stride defaults to the number of units; units past it stay zero).  Every antenna is
+    ul_units_3gpp with the same payload and a seed of its own (seeds[r], by default seed + 1000 r): another gain, phase, delay and noise.
+    payload None: random transport blocks drawn from `seed`.  Further keywords (uci, ack, ri, cqi, gain, max_delay, snr_db, peak) go to
+    ul_units_3gpp.  Returns (iq int8 [n_rx * ant_stride, unit_len, 2], tx uint8 [n_units, n_alloc, max tbs])."""
+    n = len(subfr_num)
+    ant_stride = n if ant_stride is None else int(ant_stride)
+    if ant_stride < n:
+        raise ValueError("ant_stride: at least the number of units")
+    seeds = [seed + 1000 * r for r in range(n_rx)] if seeds is None else list(seeds)
+    if len(seeds) != n_rx:
+        raise ValueError("seeds: one per antenna")
+    max_tbs = max([a.tbs for a in allocs], default=8)
+    if payload is None:
+        payload = np.random.default_rng(seed).integers(0, 2, (n, max(n_alloc, 1), max_tbs), dtype=np.uint8)
+    iq = np.zeros((n_rx * ant_stride, ul_unit_len(cfg.fft_size), 2), np.int8)
+    tx = None
+    for r in range(n_rx):
+        iq[r * ant_stride:r * ant_stride + n], tx = ul_units_3gpp(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, seed=seeds[r], payload=payload, **kw)
+    return iq, tx
+
+
 def ulsch_mux_3gpp(N_prb, Q_m, uci, f, ack=(), ri=(), cqi=(), c_init=0):
     """mi_lte_ulsch_mux_3gpp: (values before scrambling, 0 / 1 / 2 = x / 3 = y; bits after scrambling), each uint8 [12 * 12 N_prb * Q_m] in
     transmit order, of one allocation whose G coded data bits are f."""
