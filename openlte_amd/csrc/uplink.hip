@@ -33,12 +33,13 @@
 #include "phy_dev.hpp"
 #include "ulsch_uci.h"
 #include "demap_llr.h"
+#include "pusch_launch.h"
+
+using namespace pusch_geom; // EST_ROWS, the LLR block's sizes, PUSCH_THREADS and the launch rule
 
 namespace {
 
 constexpr int N_SC_MAX = 1200;
-
-constexpr uint32_t EST_ROWS = 9; // k_pusch_demod: LDS floats kept per subcarrier of the allocation
 
 struct PuschDesc {
     uint32_t subfr, cell;   // of the allocation's unit
@@ -201,9 +202,6 @@ __device__ __forceinline__ void dft_pass(const float2 *__restrict__ in, float2 *
     }
 }
 
-#ifndef PUSCH_THREADS
-#define PUSCH_THREADS 256
-#endif
 #ifndef WPE
 #define WPE 6
 #endif
@@ -229,13 +227,10 @@ struct PuschLlr {
     float2         *x_tap;        // the symbol tap (mi_lte_pusch_plan_set_llr_tap) or NULL
     const uint32_t *x_off;        // [n_alloc]: float2 offset of the allocation's 12 M symbols in x_tap
 };
-constexpr uint32_t LLR_LDS_BYTES = 4 * 12 * sizeof(double) + 12 * sizeof(float);
 struct PuschLlrNoise : PuschLlr {
     float  noise;  // g = noise / sigma2 of the DMRS noise estimate in place of either gain of PuschLlr
     float *s2_out; // [n_alloc]: the sigma2 tap
 };
-constexpr uint32_t LLR_NOISE_LDS_BYTES = LLR_LDS_BYTES + 4 * sizeof(double); // nsum[4] (double) behind rho
-static_assert(LLR_LDS_BYTES % sizeof(double) == 0, "nsum is read as double");
 // Receive-antenna combining (mi_lte_pusch_plan_set_rx_antennas, include/mi_lte.h "PUSCH, 3GPP mode: receive-antenna combining") is one more
 // family, k_pusch_demod<THREADS, true, PuschLlrRx<N_RX, NOISE>> (launched and listed as k_pusch_demod_llr_rx), N_RX = 2 or 4: the grid of
 // antenna r of unit u is subframe r ant_stride + u, the LDS holds N_RX sets of the nine estimate rows in front of the twiddles, the estimate
@@ -704,31 +699,6 @@ struct mi_lte_pusch_plan {
     uint32_t      n_units = 0, n_rx = 1, ant_stride = 0, rx_lds_set = 0;
 };
 
-// Data symbols a workgroup transforms side by side: as many of 12, 6, 3, 2, 1 as keep the two ping-pong buffers within ~40 KiB (all 12 up to 17 PRB)
-static uint32_t pusch_s_par(uint32_t M_max)
-{
-    uint32_t S_par = 12;
-    while (S_par > 1 && (size_t)S_par * M_max * 2 * sizeof(float2) > 40 * 1024) S_par = S_par == 12 ? 6 : S_par == 6 ? 3 : S_par - 1; // 12, or a divisor of 6
-    return S_par;
-}
-
-// Dynamic LDS of the demodulator in front of its LLR block: n_rx sets of estimate rows, the twiddles, the ping-pong buffers, the scrambling words
-static size_t pusch_lds(uint32_t n_rx, uint32_t M_max, uint32_t words_max, uint32_t S_par)
-{
-    return sizeof(float) * EST_ROWS * (size_t)n_rx * M_max + sizeof(float2) * (size_t)M_max * (1 + 2 * S_par) + sizeof(uint32_t) * (words_max + 1);
-}
-
-// S_par of a combining launch (include/mi_lte.h): pusch_s_par's value, stepped further down 3 -> 2 -> 1 until the launch's whole dynamic LDS
-// fits `limit` bytes; 0 when it does not fit at S_par = 1.  *lds: the bytes in front of the LLR block, as pusch_lds gives them.
-static uint32_t pusch_rx_s_par(uint32_t n_rx, uint32_t M_max, uint32_t words_max, size_t limit, size_t *lds)
-{
-    for (uint32_t S_par = pusch_s_par(M_max); S_par >= 1; S_par = S_par == 12 ? 6 : S_par == 6 ? 3 : S_par - 1) {
-        *lds = pusch_lds(n_rx, M_max, words_max, S_par);
-        if (((*lds + 7) & ~(size_t)7) + LLR_NOISE_LDS_BYTES <= limit) return S_par;
-    }
-    return 0;
-}
-
 // UL-SCH rate matching has no soft-buffer limit (36.212 5.2.2.5: N_cb = K_w).  As a DL-SCH soft-buffer configuration: an N_IR no block reaches
 static const mi_lte_dlsch_cfg ULSCH_AS_DLSCH = {MI_LTE_ULSCH_N_SOFT, MI_LTE_ULSCH_M_HARQ};
 
@@ -1038,8 +1008,8 @@ int mi_lte_pusch_plan_set_rx_antennas(mi_lte_pusch_plan *pl, uint32_t n_rx, uint
     if (ant_stride < pl->n_units) return MI_LTE_ERR_INVALID_ARG;
     int limit = 0; // the device's per-workgroup LDS: the combining launch has to fit it at some S_par
     if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, pl->device) != hipSuccess) return MI_LTE_ERR_HIP;
-    size_t lds;
-    if (!pusch_rx_s_par(n_rx, pl->M_max, pl->words_max, (size_t)std::max(limit, 0), &lds)) return MI_LTE_ERR_UNSUPPORTED;
+    PuschLaunch L; // (the noise-referenced gain does not change what fits)
+    if (!pusch_launch_plan(pl->M_max, pl->words_max, /*maxlog=*/true, /*noise=*/false, n_rx, (size_t)std::max(limit, 0), 0, &L)) return MI_LTE_ERR_UNSUPPORTED;
     pl->n_rx = n_rx; pl->ant_stride = ant_stride;
     return MI_LTE_OK;
 }
@@ -1135,6 +1105,37 @@ int mi_lte_pusch_plan_soft_bits(const mi_lte_pusch_plan *pl, uint32_t alloc, con
 
 } // extern "C"
 
+// The workgroup's width as a template argument: f(PuschWidth<64 | 128 | 192 | 256>) for what pusch_launch_plan (pusch_launch.h) chose
+template <uint32_t T> using PuschWidth = std::integral_constant<uint32_t, T>;
+template <typename F> static int pusch_width(uint32_t threads, F f)
+{
+    return threads == 64 ? f(PuschWidth<64>{}) : threads == 128 ? f(PuschWidth<128>{}) : threads == 192 ? f(PuschWidth<192>{}) : f(PuschWidth<256>{});
+}
+
+// The demodulator's launch as L shapes it, k_pusch_demod<T, SPEC, Llr...>: Llr is the kernel's own trailing pack, nothing or the family's
+// argument block (PuschLlr, PuschLlrNoise, PuschLlrRx<N, NZ>).  lds_limit: the device's per-workgroup LDS, read for a combining launch only.
+template <uint32_t T, bool SPEC, typename... Llr>
+static int pusch_launch(PuschWidth<T>, std::bool_constant<SPEC>, mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const PuschLaunch &L, size_t lds_limit,
+                        const float *d_subframes, const Llr &...la_pack)
+{
+    [[maybe_unused]] constexpr uint32_t N  = (RxOf<Llr>::N * ... * 1u);
+    [[maybe_unused]] constexpr bool     NZ = (RxOf<Llr>::NOISE || ...);
+    if constexpr (N > 1) {
+        // More than 64 KB of dynamic LDS has to be asked for, per kernel and device (as bcjr.hip does for k_bcjr_block): once per plan and
+        // instantiation
+        const uint32_t bit = 1u << ((T == 256 ? 1 : 0) + (N == 4 ? 2 : 0) + (NZ ? 4 : 0));
+        if (!(pl->rx_lds_set & bit)) {
+            MI_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k_pusch_demod<T, true, PuschLlrRx<N, NZ>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
+            pl->rx_lds_set |= bit;
+        }
+    }
+    const GoldTables gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
+    MI_LAUNCH(ctx, L.label, (k_pusch_demod<T, SPEC, Llr...>), dim3(pl->core.n_alloc), dim3(T), L.lds_bytes, d_subframes, (uint32_t)mi_lte_ul_subframe_floats(),
+              pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->M_max, L.S_par, recip_up(L.S_par),
+              static_cast<const PuschShape *>(ctx->d_pusch_shapes), la_pack...);
+    return MI_LTE_OK;
+}
+
 // A plan run: the demodulator, then the 3GPP mode's control information and code blocks (ulsch_uci.hip, dlsch3gpp.hip) or the REF dispatch
 // (turbo.hip).  pool / h_bind: a HARQ run (mi_lte_pusch_decode_run_harq), nullptr otherwise.  Every refusal returns before a launch.
 static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *pool, const mi_lte_harq_bind *h_bind, const float *d_subframes,
@@ -1154,71 +1155,48 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
     rc = mi_ctx_gold_tables(ctx);
     if (rc != MI_LTE_OK) return rc;
     if ((rc = pusch_shapes(ctx)) != MI_LTE_OK) return rc;
-    GoldTables   gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
-    const uint32_t S_par = pusch_s_par(pl->M_max);
-    const size_t   lds   = pusch_lds(1, pl->M_max, pl->words_max, S_par);
-    // Workgroup size: the kernel's phases hold 3 M, M, 2 M, 12 M / R and 12 M items (M = 12 N_prb sub-carriers) between barriers, and the
-    // heavy ones (atan2f, sincosf, the divisions) are the short ones -- a workgroup much wider than 3 M leaves whole wavefronts waiting at
-    // every barrier for the one that has the transcendental work (SQ_WAIT_ANY: 67 % of the wave time at 256 threads and M = 72).  Measured on
-    // W5 (16 UEs x 6 PRB): 64 / 128 / 192 / 256 threads = see profiles/r04_variants_pusch_threads.txt; larger allocations keep 256.
-    uint32_t threads = pl->M_max <= 96 ? 192u : PUSCH_THREADS;
+    uint32_t threads_override = 0;
     if (const char *ev = getenv("MI_LTE_PUSCH_THREADS")) { // (tuning aid)
         const int t = atoi(ev);
-        if (t >= 64 && t <= (int)PUSCH_THREADS && t % 64 == 0) threads = (uint32_t)t;
+        if (t >= 64 && t <= (int)PUSCH_THREADS && t % 64 == 0) threads_override = (uint32_t)t;
     }
-#define MI_PUSCH_LAUNCH_V(T, SPEC) MI_LAUNCH(ctx, "k_pusch_demod", (k_pusch_demod<T, SPEC>), dim3(pl->core.n_alloc), dim3(T), lds, d_subframes, (uint32_t)mi_lte_ul_subframe_floats(), \
-                                    pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->M_max, S_par, recip_up(S_par), \
-                                    static_cast<const PuschShape *>(ctx->d_pusch_shapes))
-#define MI_PUSCH_LAUNCH(T) do { if (pl->g3) MI_PUSCH_LAUNCH_V(T, true); else MI_PUSCH_LAUNCH_V(T, false); } while (0)
     const bool llr = pl->g3 && pl->demap == MI_LTE_DEMAP_MAXLOG; // (mi_lte_pusch_plan_set_demapper)
-    if (llr) { // the same launch with the LLR block behind the scrambling words: the only instantiation whose dynamic LDS grows
-        // combining: n_rx sets of estimate rows, and S_par stepped down until the whole launch fits the device's per-workgroup LDS
-        uint32_t S_rx = S_par;
-        size_t   lds_rx = lds, lds_limit = 0;
-        if (pl->n_rx > 1) {
-            int limit = 0;
-            MI_HIP_CHECK(ctx, hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
-            lds_limit = (size_t)std::max(limit, 0);
-            S_rx      = pusch_rx_s_par(pl->n_rx, pl->M_max, pl->words_max, lds_limit, &lds_rx);
-            if (!S_rx) { ctx->err = "receive-antenna combining: the plan's widest allocation does not fit the device's LDS"; return MI_LTE_ERR_UNSUPPORTED; }
-        }
-        const size_t   lds_off = (lds_rx + 7) & ~(size_t)7;
-        float          auto_t  = (float)MI_LTE_DEMAP_AUTO_T;
+    float      auto_t = (float)MI_LTE_DEMAP_AUTO_T;
+    if (llr)
         if (const char *ev = getenv("MI_LTE_DEMAP_AUTO_T")) { // (tuning aid: tools/pusch_llr_sweep.py checks the header's constant with it)
             const float t = (float)atof(ev);
             if (t >= 1.0f && t <= 127.0f) auto_t = t;
         }
-        const PuschLlr      la{pl->demap_gain, auto_t,(uint32_t)(lds_off / sizeof(float)), pl->d_llr_gain, pl->d_llr_rho, pl->d_llr_x, pl->d_x_off};
-        const PuschLlrNoise ln{la, pl->llr_noise, pl->d_llr_s2};
-#define MI_PUSCH_LAUNCH_LLR_V(T, ARG, LDS, la) MI_LAUNCH(ctx, "k_pusch_demod_llr", (k_pusch_demod<T, true, ARG>), dim3(pl->core.n_alloc), dim3(T), lds_off + LDS, d_subframes, \
-                                         (uint32_t)mi_lte_ul_subframe_floats(), pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, \
-                                         pl->core.d_e_len, pl->M_max, S_par, recip_up(S_par), static_cast<const PuschShape *>(ctx->d_pusch_shapes), la)
-#define MI_PUSCH_LAUNCH_LLR(T) do { if (pl->llr_noise > 0.0f) MI_PUSCH_LAUNCH_LLR_V(T, PuschLlrNoise, LLR_NOISE_LDS_BYTES, ln); else MI_PUSCH_LAUNCH_LLR_V(T, PuschLlr, LLR_LDS_BYTES, la); } while (0)
-        // More than 64 KB of dynamic LDS has to be asked for, per kernel and device (as bcjr.hip does for k_bcjr_block): once per plan and
-        // instantiation.  Two widths only, the run function's own choice: MI_LTE_PUSCH_THREADS does not reach the combining launch.
-#define MI_PUSCH_LAUNCH_RX_V(T, N, NZ) do { \
-            const PuschLlrRx<N, NZ> lr{ln, pl->ant_stride}; \
-            const uint32_t bit = 1u << ((T == 256 ? 1 : 0) + (N == 4 ? 2 : 0) + (NZ ? 4 : 0)); \
-            if (!(pl->rx_lds_set & bit)) { \
-                MI_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k_pusch_demod<T, true, PuschLlrRx<N, NZ>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit)); \
-                pl->rx_lds_set |= bit; \
-            } \
-            MI_LAUNCH(ctx, "k_pusch_demod_llr_rx", (k_pusch_demod<T, true, PuschLlrRx<N, NZ>>), dim3(pl->core.n_alloc), dim3(T), lds_off + LLR_NOISE_LDS_BYTES, d_subframes, \
-                      (uint32_t)mi_lte_ul_subframe_floats(), pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, \
-                      pl->core.d_e_len, pl->M_max, S_rx, recip_up(S_rx), static_cast<const PuschShape *>(ctx->d_pusch_shapes), lr); } while (0)
-#define MI_PUSCH_LAUNCH_RX(T, N) do { if (pl->llr_noise > 0.0f) MI_PUSCH_LAUNCH_RX_V(T, N, true); else MI_PUSCH_LAUNCH_RX_V(T, N, false); } while (0)
-        if (pl->n_rx > 1) {
-            if (pl->M_max <= 96) { if (pl->n_rx == 2) MI_PUSCH_LAUNCH_RX(192, 2); else MI_PUSCH_LAUNCH_RX(192, 4); }
-            else                 { if (pl->n_rx == 2) MI_PUSCH_LAUNCH_RX(256, 2); else MI_PUSCH_LAUNCH_RX(256, 4); }
-        } else
-        if (threads == 64) MI_PUSCH_LAUNCH_LLR(64); else if (threads == 128) MI_PUSCH_LAUNCH_LLR(128); else if (threads == 192) MI_PUSCH_LAUNCH_LLR(192); else MI_PUSCH_LAUNCH_LLR(256);
-#undef MI_PUSCH_LAUNCH_RX
-#undef MI_PUSCH_LAUNCH_RX_V
-#undef MI_PUSCH_LAUNCH_LLR
-#undef MI_PUSCH_LAUNCH_LLR_V
-    } else if (threads == 64) MI_PUSCH_LAUNCH(64); else if (threads == 128) MI_PUSCH_LAUNCH(128); else if (threads == 192) MI_PUSCH_LAUNCH(192); else MI_PUSCH_LAUNCH(256);
-#undef MI_PUSCH_LAUNCH
-#undef MI_PUSCH_LAUNCH_V
+    size_t lds_limit = 0; // the device's per-workgroup LDS: a combining launch has to fit it at some S_par
+    if (llr && pl->n_rx > 1) {
+        int limit = 0;
+        MI_HIP_CHECK(ctx, hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+        lds_limit = (size_t)std::max(limit, 0);
+    }
+    PuschLaunch L;
+    if (!pusch_launch_plan(pl->M_max, pl->words_max, llr, pl->llr_noise > 0.0f, pl->n_rx, lds_limit, threads_override, &L)) {
+        ctx->err = "receive-antenna combining: the plan's widest allocation does not fit the device's LDS";
+        return MI_LTE_ERR_UNSUPPORTED;
+    }
+    const PuschLlr      la{pl->demap_gain, auto_t, (uint32_t)(L.lds_off / sizeof(float)), pl->d_llr_gain, pl->d_llr_rho, pl->d_llr_x, pl->d_x_off};
+    const PuschLlrNoise ln{la, pl->llr_noise, pl->d_llr_s2};
+    const auto go = [&](auto width, auto spec, const auto &...la_pack) { return pusch_launch(width, spec, ctx, pl, L, lds_limit, d_subframes, la_pack...); };
+    const std::true_type spec3; // every max-log launch is the 3GPP mode's
+    switch (L.family) {
+    case PuschFamily::PLAIN: rc = pusch_width(L.threads, [&](auto w) { return pl->g3 ? go(w, spec3) : go(w, std::false_type{}); }); break;
+    case PuschFamily::LLR: rc = pusch_width(L.threads, [&](auto w) { return go(w, spec3, la); }); break;
+    case PuschFamily::LLR_NOISE: rc = pusch_width(L.threads, [&](auto w) { return go(w, spec3, ln); }); break;
+    case PuschFamily::LLR_RX: { // two widths only, the rule's own choice: the combining kernels exist at no other
+        const uint32_t stride = pl->ant_stride;
+        const auto rx = [&](auto w) {
+            return L.n_rx == 2 ? (L.noise ? go(w, spec3, PuschLlrRx<2, true>{ln, stride}) : go(w, spec3, PuschLlrRx<2, false>{ln, stride}))
+                               : (L.noise ? go(w, spec3, PuschLlrRx<4, true>{ln, stride}) : go(w, spec3, PuschLlrRx<4, false>{ln, stride}));
+        };
+        rc = L.threads == 192 ? rx(PuschWidth<192>{}) : rx(PuschWidth<256>{});
+        break;
+    }
+    }
+    if (rc != MI_LTE_OK) return rc;
     MI_HIP_CHECK(ctx, hipGetLastError());
     if (pl->g3) { // 3GPP mode: the code blocks of dlsch3gpp.hip, combined into the pool's buffers on a HARQ run
         MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/true);
@@ -1230,7 +1208,7 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
         if ((rc = mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter)) != MI_LTE_OK) return rc;
         const size_t at = ctx->last_kernels.find(','); // (mi_dlsch3_run lists the downlink's demodulator in front of its own kernels)
         ctx->last_kernels.replace(0, at == std::string::npos ? 0 : at,
-                                  std::string(llr && pl->n_rx > 1 ? "k_pusch_demod_llr_rx:1" : llr ? "k_pusch_demod_llr:1" : "k_pusch_demod:1") +
+                                  std::string(L.label) + ":1" +
                                       (!pl->uci          ? ""
                                        : pl->uci->cqi_on ? ",k_ulsch_uci_gather:1,k_ulsch_uci_decide:1,k_ulsch_cqi_decode:1"
                                                          : ",k_ulsch_uci_gather:1,k_ulsch_uci_decide:1"));
@@ -1239,7 +1217,7 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
     // several block sizes (the UEs of a subframe rarely share one): one launch set over all of them, as in the PDSCH chain
     rc = mi_turbo_ref_dispatch(ctx, pl->core.groups.data(), (uint32_t)pl->core.groups.size(), pl->core.io(d_out_bits, d_status, /*ul=*/true), &pl->core.multi);
     if (rc != MI_LTE_OK) return rc;
-    ctx->last_kernels.insert(0, "k_pusch_demod:1,");
+    ctx->last_kernels.insert(0, std::string(L.label) + ":1,");
     return MI_LTE_OK;
 }
 
