@@ -1121,8 +1121,8 @@ int  mi_lte_pdcch_search_run(mi_lte_ctx *ctx, mi_lte_pdcch_search_plan *plan, co
                              const uint32_t *d_n_id_cell, uint32_t n_units, uint32_t *h_cfi, uint32_t *h_n_cce, uint32_t *h_n_found,
                              mi_lte_pdcch_found *h_found /* [n_units][MI_LTE_PDCCH_SEARCH_MAX_FOUND] */);
 int  mi_lte_pdcch_search_soft(const mi_lte_pdcch_search_plan *plan, const int8_t **d_soft, uint32_t *unit_stride); /* valid after a run */
-/* A C-RNTI's DCI format 0 / 1A as this library's transmitter packs them (tx_ctrl.cc, pinned to the reference's dci_0_pack / dci_1a_pack),
- * host arithmetic.  Both: the flag bit (1 = format 1A, 0 = format 0), then one more flag, then the resource indication value in
+/* A C-RNTI's DCI format 0 / 1A as this library's transmitter packs them (tx_ctrl.cc, pinned to the reference's dci_0_pack / dci_1a_pack; packer
+ * and unpacker read one field list, dci.h), host arithmetic (dci.cc).  Both: the flag bit (1 = format 1A, 0 = format 0), then one more flag, then the resource indication value in
  * ceil(log2(N_rb (N_rb + 1) / 2)) bits, decoded over its WHOLE range (36.213 7.1.6.3 / 8.1): with q = floor(RIV / N_rb), r = RIV mod N_rb,
  * length = q + 1 and start = r when q + r < N_rb, otherwise length = N_rb - q + 1 and start = N_rb - 1 - r.
  * Format 1A: localized (0) / distributed (1), RIV, MCS 5 bits, HARQ process 3, NDI 1, RV 2, TPC 2.  MCS 0-9 QPSK, 10-16 16QAM, 17-28 64QAM

@@ -3,11 +3,9 @@
 // liblte_phy_pdsch_channel_decode in every real subframe (LTE_fdd_dl_fs_samp_buf.cc:445-470).
 //
 // Everything that only depends on the cell and on the control-format indicator is index arithmetic and is done once
-// per plan on the host, following the reference step by step: PCFICH resource elements (pcfich_channel_demap :7887-7925),
-// PHICH resource-element groups (phich_channel_demap :8224-8290), the PDCCH REG walk with its PCFICH/PHICH/CRS
-// exclusions (:4590-4700), the cyclic-shift and sub-block-interleaver undo (:4702-4824), the CCEs and the six
-// common-search-space candidates (4 x aggregation 4, 2 x aggregation 8), and the convolutional rate-unmatching index map
-// (rate_unmatch_conv :11597-11755).  The device does the arithmetic:
+// per plan on the host (pdcch_geom.cc: the PCFICH and PHICH positions, the REG walk, the interleaver undo, the CCEs, the six
+// common-search-space candidates and the rate-unmatching index map); what the DCIs mean is dci.cc's.  This file holds the
+// kernels and the code that launches them.  The device does the arithmetic:
 //
 //   k_pdcch_decode : one workgroup per subframe, one wavefront per candidate.  PCFICH: gather, transmit-diversity
 //       combiner, QPSK soft de-map, descramble, CFI by minimum distance (cfi_channel_decode :13648-13706).  Per candidate:
@@ -25,21 +23,19 @@
 // float.  Candidate CCEs past the last CCE of the subframe read stale scratch in the reference; here they count as erasures
 // (what a fresh LIBLTE_PHY_STRUCT gives).
 #include <algorithm>
-#include <cmath>
 #include <cstring>
-#include <map>
 #include <vector>
 
 #include "ctx.hpp"
+#include "dci.h"
+#include "pdcch_geom.h"
+#include "pdcch_search.hpp"
 #include "phy_dev.hpp"
-#include "lte_tables.h"
-#include "synth.hpp"
 #include "tbcc_dev.h"
 
-namespace {
+using namespace pdcch_geom;
 
-constexpr int      N_SC_MAX = 1200;
-constexpr uint32_t N_CAND = 6, RE_MAX = 288, NO_RE = 0xFFFFFFFFu;
+namespace {
 
 struct PdcchDev {
     uint32_t N_rb_dl, N_ant, n_cells, dci_size[2];
@@ -322,26 +318,6 @@ struct SearchUnit { uint32_t cfi, n_cce; };
 struct SearchHit { uint64_t payload; int32_t metric, energy; };
 struct SearchOut { uint32_t cfi, n_cce, n_found, pad; mi_lte_pdcch_found found[MI_LTE_PDCCH_SEARCH_MAX_FOUND]; };
 
-// 36.213 9.1.1: Y_k for k = sf, from Y_(-1) = rnti; and the number of candidates of an aggregation level
-__host__ __device__ inline uint32_t search_space_y(uint32_t rnti, uint32_t sf)
-{
-    uint32_t y = rnti;
-    for (uint32_t k = 0; k <= sf; k++) y = (39827u * y) % 65537u; // (y <= 65536: the product stays below 2^32)
-    return y;
-}
-__host__ __device__ inline uint32_t search_space_m(uint32_t L) { return L <= 2 ? 6u : 2u; }
-
-// the candidates of n_cce CCEs in reporting order: every L = 8, 4, 2, 1 in turn, first CCEs ascending
-__host__ __device__ inline uint32_t search_n_cand(uint32_t n_cce) { return (n_cce >> 3) + (n_cce >> 2) + (n_cce >> 1) + n_cce; }
-__host__ __device__ inline void search_cand(uint32_t n_cce, uint32_t cand, uint32_t &L, uint32_t &cce)
-{
-    const uint32_t n8 = n_cce >> 3, n4 = n_cce >> 2, n2 = n_cce >> 1;
-    if (cand < n8) { L = 8; cce = 8 * cand; }
-    else if (cand < n8 + n4) { L = 4; cce = 4 * (cand - n8); }
-    else if (cand < n8 + n4 + n2) { L = 2; cce = 2 * (cand - n8 - n4); }
-    else { L = 1; cce = cand - n8 - n4 - n2; }
-}
-
 // one workgroup per subframe: CFI, then every CCE de-mapped to int8 soft bits, SEARCH_CHUNK_CCE CCEs at a time through LDS
 __global__ __launch_bounds__(256) void k_pdcch_search_demod(const float *__restrict__ subframes, uint32_t sf_stride, const uint32_t *__restrict__ subfr_num,
                                                             const uint32_t *__restrict__ n_id_cell, PdcchSearchDev P, GoldTables gt,
@@ -536,133 +512,6 @@ __global__ __launch_bounds__(768) void k_pbch_decode(const float *__restrict__ s
     }
 }
 
-// ---- host: index tables ------------------------------------------------------------------------
-
-// positions of the PCFICH / PHICH resource-element groups in symbol 0 (pcfich_channel_demap, phich_channel_demap)
-struct CtrlRegs { uint32_t pcfich_k[4]; float pcfich_n[4]; std::vector<uint32_t> phich_k; };
-
-CtrlRegs ctrl_regs(uint32_t N_rb_dl, uint32_t cell, float phich_res)
-{
-    CtrlRegs r;
-    const uint32_t k_hat = 6 * (cell % (2 * N_rb_dl));
-    for (uint32_t i = 0; i < 4; i++) {
-        r.pcfich_k[i] = (k_hat + (i * N_rb_dl / 2) * 12 / 2) % (N_rb_dl * 12);
-        r.pcfich_n[i] = (r.pcfich_k[i] / 6) - 0.5;
-    }
-    const uint32_t N_group = (uint32_t)ceilf((float)phich_res * ((float)N_rb_dl / (float)8));
-    const uint32_t n_l = N_rb_dl * 2 - 4;
-    for (uint32_t m = 0; m < N_group; m++) {
-        uint32_t n_hat[3];
-        for (uint32_t i = 0; i < 3; i++) n_hat[i] = (cell + m + i * n_l / 3) % n_l;
-        for (uint32_t i = 0; i < 4; i++)
-            for (uint32_t j = 0; j < 3; j++)
-                if (n_hat[j] > r.pcfich_n[i]) n_hat[j]++; // sequential, against the float REG number, as the reference does
-        for (uint32_t i = 0; i < 3; i++) r.phich_k.push_back(n_hat[i] * 6);
-    }
-    return r;
-}
-
-// natural position -> rank in the sub-block interleaver's read-out order, dummies skipped (36.212 5.1.4.2.1; the reference
-// rebuilds this per call, liblte_phy.cc:4717-4812)
-std::vector<uint32_t> cc_interleaver_rank(uint32_t n)
-{
-    uint32_t R = 0;
-    while (n > 32 * R) R++;
-    const uint32_t K_pi = 32 * R, N_dummy = K_pi - n;
-    std::vector<uint32_t> rank(K_pi, 0);
-    uint32_t k = 0;
-    for (uint32_t j = 0; j < 32; j++)     // read column by column ...
-        for (uint32_t i = 0; i < R; i++) { // ... of the column-permuted matrix
-            const uint32_t nat = i * 32 + LTE_SUBBLOCK_COL_PERM_CC[j];
-            if (nat >= N_dummy) rank[nat] = k++;
-        }
-    std::vector<uint32_t> out(n);
-    for (uint32_t i = 0; i < n; i++) out[i] = rank[N_dummy + i];
-    return out;
-}
-
-// the resource elements of every CCE of one (cell, N_symbs) in order, 36 per CCE: perm[36 N_cce ..] (plus the REGs behind the last whole CCE);
-// returns N_cce
-uint32_t cce_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_res, uint32_t N_symbs, std::vector<uint32_t> &perm)
-{
-    perm.clear();
-    const CtrlRegs cr = ctrl_regs(N_rb_dl, cell, phich_res);
-    int64_t n_reg = (int64_t)N_symbs * (N_rb_dl * 3) - N_rb_dl - 4 - (int64_t)cr.phich_k.size();
-    if (N_ant == 4) n_reg -= N_rb_dl;
-    if (n_reg <= 0) return 0;
-    const uint32_t N_reg = (uint32_t)n_reg, N_cce = N_reg / 9;
-    std::vector<uint32_t> reg(4 * (size_t)N_reg, NO_RE); // REG m: its 4 RE indices (l*1200 + k)
-    uint32_t m = 0;
-    for (uint32_t k = 0; k < N_rb_dl * 12; k++)            // Steps 1-10 of 36.211 6.8.5 as the reference walks them
-        for (uint32_t l = 0; l < N_symbs; l++) {
-            if (m >= N_reg) continue;
-            if (l == 0 || (l == 1 && N_ant == 4)) {
-                bool valid = (k % 6) == 0;
-                if (l == 0) {
-                    for (uint32_t i = 0; i < 4; i++) valid &= k != cr.pcfich_k[i];
-                    for (uint32_t kk : cr.phich_k) valid &= k != kk;
-                }
-                if (!valid) continue;
-                uint32_t idx = 0;
-                for (uint32_t i = 0; i < 6; i++)
-                    if ((cell % 3) != (i % 3)) reg[4 * m + idx++] = l * N_SC_MAX + k + i; // skip the CRS positions
-                m++;
-            } else if ((k % 4) == 0) {
-                for (uint32_t i = 0; i < 4; i++) reg[4 * m + i] = l * N_SC_MAX + k + i;
-                m++;
-            }
-        }
-    // undo the cell-specific cyclic shift, then the sub-block interleaver
-    std::vector<uint32_t> shifted(4 * (size_t)N_reg);
-    perm.resize(4 * (size_t)N_reg);
-    for (uint32_t i = 0; i < N_reg; i++) std::copy(&reg[4 * i], &reg[4 * i] + 4, &shifted[4 * ((i + cell) % N_reg)]);
-    const std::vector<uint32_t> rank = cc_interleaver_rank(N_reg);
-    for (uint32_t i = 0; i < N_reg; i++) std::copy(&shifted[4 * rank[i]], &shifted[4 * rank[i]] + 4, &perm[4 * i]);
-    return N_cce;
-}
-
-// RE lists of the six common-search-space candidates for one (cell, N_symbs)
-void candidate_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_res, uint32_t N_symbs, uint32_t *out /*[N_CAND][RE_MAX]*/)
-{
-    std::fill(out, out + N_CAND * RE_MAX, NO_RE);
-    std::vector<uint32_t> perm;
-    const uint32_t N_cce = cce_res(N_rb_dl, N_ant, cell, phich_res, N_symbs, perm);
-    for (uint32_t c = 0; c < N_CAND; c++) {
-        // the reference always tries all six candidates; CCEs past the last one hold whatever its scratch held before --
-        // zeros on a fresh LIBLTE_PHY_STRUCT, which de-map to soft value 0.  Here those elements are marked absent and
-        // contribute 0 (the only state-dependent corner of the reference's decoder)
-        const uint32_t L = c < 4 ? 4 : 8, first = (c < 4 ? c : c - 4) * L;
-        for (uint32_t j = 0; j < L * 36; j++)
-            if (first + j / 36 < N_cce) out[c * RE_MAX + j] = perm[(size_t)(first + j / 36) * 36 + j % 36];
-    }
-}
-
-// where received bit k of E lands in d[3*N_c] (rate_unmatch_conv :11597-11755: three sub-block-interleaved streams back to
-// back, circular read from position 0, dummies skipped)
-void conv_rm_map(uint32_t N_c, uint32_t E, uint16_t *map)
-{
-    uint32_t R = 0;
-    while (N_c > 32 * R) R++;
-    const uint32_t K_pi = 32 * R, K_w = 3 * K_pi, N_dummy = K_pi - N_c;
-    for (uint32_t k = 0, j = 0; k < E; j++) {
-        const uint32_t w = j % K_w, x = w / K_pi, pos = w % K_pi, col = pos / R, row = pos % R;
-        const uint32_t nat = row * 32 + LTE_SUBBLOCK_COL_PERM_CC[col];
-        if (nat >= N_dummy) map[k++] = (uint16_t)((nat - N_dummy) * 3 + x);
-    }
-}
-
-void dci_sizes(uint32_t N_rb_dl, uint32_t *s1a, uint32_t *s1c) // liblte_phy.cc:4835-4857
-{
-    switch (N_rb_dl) {
-    case 6:  *s1a = 21; *s1c = 9;  break;
-    case 15: *s1a = 22; *s1c = 11; break;
-    case 25: *s1a = 25; *s1c = 13; break;
-    case 50: *s1a = 27; *s1c = 13; break;
-    case 75: *s1a = 27; *s1c = 14; break;
-    default: *s1a = 28; *s1c = 15; break;
-    }
-}
-
 } // namespace
 
 struct mi_lte_pdcch_plan {
@@ -689,13 +538,6 @@ struct mi_lte_pdcch_search_plan {
 
 extern "C" {
 
-// the six LTE bandwidths and a PHICH resource N_g in (0, 2] (36.211 6.9: 1/6, 1/2, 1, 2): what bounds the REG tables below (a negative or
-// not-a-number N_g would size them by a wrapped group count)
-static bool standard_ctrl_cfg(uint32_t nrb, float phich_res)
-{
-    return (nrb == 6 || nrb == 15 || nrb == 25 || nrb == 50 || nrb == 75 || nrb == 100) && phich_res > 0.0f && phich_res <= 2.0f;
-}
-
 int mi_lte_pdcch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, float phich_res, uint32_t phich_dur_extended, uint32_t flags,
                              const uint32_t *h_cells, uint32_t n_cells, mi_lte_pdcch_plan **out)
 {
@@ -717,7 +559,7 @@ int mi_lte_pdcch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, float ph
             mi_lte_pdcch_re_tables(nrb, cfg->N_ant, cells[c], phich_res, ns, &pcf[(size_t)c * 16], &cand[((size_t)c * 4 + ns - 1) * N_CAND * RE_MAX]);
     }
     uint32_t sz[2];
-    dci_sizes(nrb, &sz[0], &sz[1]);
+    dci::sizes(nrb, &sz[0], &sz[1]);
     std::vector<uint16_t> rm((size_t)2 * 2 * 576, 0);
     for (uint32_t f = 0; f < 2; f++)
         for (uint32_t e = 0; e < 2; e++) conv_rm_map(sz[f] + 16, e ? 576 : 288, &rm[((size_t)f * 2 + e) * 576]);
@@ -740,124 +582,12 @@ int mi_lte_pdcch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, float ph
     return MI_LTE_OK;
 }
 
-// the index tables on their own (host arithmetic): where the PCFICH and the six candidates live in the subframe grid
-int mi_lte_pdcch_re_tables(uint32_t N_rb_dl, uint32_t N_ant, uint32_t N_id_cell, float phich_res, uint32_t N_symbs, uint32_t *pcfich /*[16]*/,
-                           uint32_t *cand /*[6][288]*/)
-{
-    if (!pcfich || !cand || !standard_ctrl_cfg(N_rb_dl, phich_res) || !(N_ant == 1 || N_ant == 2 || N_ant == 4) || N_id_cell > 503 || N_symbs < 1 || N_symbs > 4)
-        return MI_LTE_ERR_INVALID_ARG;
-    const CtrlRegs cr = ctrl_regs(N_rb_dl, N_id_cell, phich_res);
-    for (uint32_t i = 0; i < 4; i++) {
-        uint32_t idx = 0;
-        for (uint32_t j = 0; j < 6; j++)
-            if ((N_id_cell % 3) != (j % 3)) pcfich[i * 4 + idx++] = cr.pcfich_k[i] + j;
-    }
-    candidate_res(N_rb_dl, N_ant, N_id_cell, phich_res, N_symbs, cand);
-    return MI_LTE_OK;
-}
-
-// PCFICH / PHICH resource-element-group positions as the reference reports them in LIBLTE_PHY_PCFICH_STRUCT::k, n and
-// LIBLTE_PHY_PHICH_STRUCT::k, N_reg (pcfich_channel_demap :7903-7910, phich_channel_demap :8243-8278)
-int mi_lte_ctrl_reg_positions(uint32_t N_rb_dl, uint32_t N_id_cell, float phich_res, uint32_t *pcfich_k /*[4]*/, float *pcfich_n /*[4]*/,
-                              uint32_t *phich_N_reg, uint32_t *phich_k /*[75]*/)
-{
-    if (!pcfich_k || !pcfich_n || !phich_N_reg || !phich_k || !standard_ctrl_cfg(N_rb_dl, phich_res) || N_id_cell > 503) return MI_LTE_ERR_INVALID_ARG;
-    const CtrlRegs cr = ctrl_regs(N_rb_dl, N_id_cell, phich_res);
-    if (cr.phich_k.size() > 75) return MI_LTE_ERR_INVALID_ARG;
-    for (uint32_t i = 0; i < 4; i++) { pcfich_k[i] = cr.pcfich_k[i]; pcfich_n[i] = cr.pcfich_n[i]; }
-    *phich_N_reg = (uint32_t)cr.phich_k.size();
-    std::copy(cr.phich_k.begin(), cr.phich_k.end(), phich_k);
-    return MI_LTE_OK;
-}
-
 void mi_lte_pdcch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pdcch_plan *pl)
 {
     if (!pl) return;
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
     for (void *p : pl->owned) (void)hipFree(p);
     delete pl;
-}
-
-static bool common_rnti(uint32_t rnti) { return rnti == 0xFFFFu || rnti == 0xFFFEu || (rnti >= 1 && rnti <= 0x3Cu); }
-
-// DCI format 1A for SI-/P-/RA-RNTI -> allocation (dci_1a_unpack, liblte_phy.cc:13273-13378; localized VRBs only, like the
-// reference: a distributed assignment leaves prb[][] untouched).  Returns 0, or 4 = LIBLTE_ERROR_INVALID_CONTENTS.
-int mi_lte_dci_1a_unpack(uint32_t payload, uint32_t n_bits, uint32_t rnti, uint32_t N_rb_dl, uint32_t N_ant, mi_lte_pdcch_dci *o)
-{
-    if (!o || n_bits > 32 || N_rb_dl == 0 || N_rb_dl > 110) return MI_LTE_ERR_INVALID_ARG; // (110: LIBLTE_PHY_N_RB_DL_MAX)
-    uint32_t pos = n_bits;
-    auto take = [&](uint32_t n) { pos = pos >= n ? pos - n : 0; return (payload >> pos) & ((1u << n) - 1u); };
-    if (take(1) == 0) return 4;                   // flagged as DCI format 0
-    if (!common_rnti(rnti)) return 0;             // the reference leaves the allocation alone and still reports success
-    const uint32_t distributed = take(1);
-    const uint32_t riv_len = (uint32_t)ceilf(logf(N_rb_dl * (N_rb_dl + 1) / 2) / logf(2));
-    const uint32_t riv = take(riv_len);
-    o->alloc.N_prb = riv / N_rb_dl + 1;
-    const uint32_t rb_start = riv % N_rb_dl;
-    o->mcs = take(5);
-    take(3);                                      // HARQ process
-    take(1);                                      // new-data indicator
-    o->alloc.rv_idx = take(2);
-    const uint32_t tpc = take(2), col = (tpc % 2) == 0 ? 0 : 1; // N_PRB^1A = 2 or 3
-    if (!distributed)
-        for (uint32_t i = 0; i < o->alloc.N_prb && i < 112; i++) o->alloc.prb[0][i] = o->alloc.prb[1][i] = (uint8_t)(rb_start + i);
-    o->alloc.mod_type = 1;                        // QPSK
-    o->alloc.tx_mode  = N_ant == 1 ? 1 : 2;
-    o->alloc.rnti     = rnti;
-    if (o->mcs >= 27) return 4;
-    o->alloc.tbs = LTE_TBS_NPRB_2_3[o->mcs][col];
-    return 0;
-}
-
-// DCI format 1C -> allocation (dci_1c_unpack, liblte_phy.cc:13400-13611): distributed VRBs of 36.211 6.2.3.2 and the
-// format-1C transport-block sizes.  A RIV that matches no (length, start) pair leaves N_prb as the caller set it.
-int mi_lte_dci_1c_unpack(uint32_t payload, uint32_t n_bits, uint32_t rnti, uint32_t N_rb_dl, uint32_t N_ant, mi_lte_pdcch_dci *o)
-{
-    if (!o || n_bits > 32 || N_rb_dl < 6 || N_rb_dl > 110) return MI_LTE_ERR_INVALID_ARG;
-    uint32_t pos = n_bits;
-    auto take = [&](uint32_t n) { pos = pos >= n ? pos - n : 0; return (payload >> pos) & ((1u << n) - 1u); };
-    const uint32_t gap2 = N_rb_dl < 50 ? 0u : take(1);
-    uint32_t N_gap;
-    if (N_rb_dl <= 10) N_gap = (uint32_t)ceilf(N_rb_dl / 2.0);
-    else if (N_rb_dl == 11) N_gap = 4;
-    else if (N_rb_dl <= 19) N_gap = 8;
-    else if (N_rb_dl <= 26) N_gap = 12;
-    else if (N_rb_dl <= 44) N_gap = 18;
-    else if (N_rb_dl <= 49) N_gap = 27;
-    else if (N_rb_dl <= 63) N_gap = gap2 ? 9 : 27;
-    else if (N_rb_dl <= 70) N_gap = gap2 ? 16 : 32;
-    else N_gap = gap2 ? 16 : 48;
-    const uint32_t n_vrb_gap1 = 2 * std::min(N_gap, N_rb_dl - N_gap), n_vrb_gap2 = (N_rb_dl / (2 * N_gap)) * 2 * N_gap;
-    const uint32_t n_vrb = gap2 ? n_vrb_gap2 : n_vrb_gap1, step = N_rb_dl <= 49 ? 2 : 4, n_tilde = gap2 ? 2 * N_gap : n_vrb;
-    if (!common_rnti(rnti)) return 4;
-    const uint32_t q = n_vrb_gap1 / step, riv_len = (uint32_t)ceilf(logf(q * (q + 1) / 2.0) / logf(2));
-    const uint32_t riv = take(riv_len), nd = n_vrb / step;
-    uint32_t rb_start = 0;
-    for (uint32_t len = 1; len <= nd; len++)      // every (length, start) pair is tried and the last match stands
-        for (uint32_t st = 0; st + 1 <= nd; st++) {
-            const uint32_t code = (len - 1) <= nd / 2 ? nd * (len - 1) + st : nd * (nd - len + 1) + (nd - 1 - st);
-            if (riv == code) { o->alloc.N_prb = len * step; rb_start = st * step; }
-        }
-    o->mcs = take(5);
-    const uint32_t P = N_rb_dl <= 10 ? 1 : N_rb_dl <= 26 ? 2 : N_rb_dl <= 63 ? 3 : 4;
-    const uint32_t n_row = (uint32_t)(ceilf(n_tilde / (4.0 * P)) * P), n_null = 4 * n_row - n_tilde;
-    for (uint32_t i = 0, v = rb_start; i < o->alloc.N_prb && i < 112; i++, v++) {
-        const uint32_t vt = v % n_tilde, blk = n_tilde * (v / n_tilde);
-        const uint32_t two_col = 2 * n_row * (vt % 2) + vt / 2 + blk, four_col = n_row * (vt % 4) + vt / 4 + blk;
-        uint32_t even;
-        if (n_null != 0 && vt >= n_tilde - n_null && (vt % 2) == 1) even = two_col - n_row;
-        else if (n_null != 0 && vt >= n_tilde - n_null && (vt % 2) == 0) even = two_col - n_row + n_null / 2;
-        else if (n_null != 0 && vt < n_tilde - n_null && (vt % 4) >= 2) even = four_col - n_null / 2;
-        else even = four_col;
-        const uint32_t odd = (even + n_tilde / 2) % n_tilde + blk;
-        o->alloc.prb[0][i] = (uint8_t)(even < n_tilde / 2 ? even : even + N_gap - n_tilde / 2);
-        o->alloc.prb[1][i] = (uint8_t)(odd < n_tilde / 2 ? odd : odd + N_gap - n_tilde / 2);
-    }
-    o->alloc.mod_type = 1;
-    o->alloc.tx_mode  = N_ant == 1 ? 1 : 2;
-    o->alloc.rnti     = rnti;
-    o->alloc.tbs      = LTE_TBS_DCI_1C[o->mcs & 31]; // a 5-bit field: always in range
-    return 0;
 }
 
 int mi_lte_pdcch_decode_run(mi_lte_ctx *ctx, mi_lte_pdcch_plan *pl, const float *d_subframes, const uint32_t *d_subfr_num,
@@ -960,22 +690,7 @@ int mi_lte_pbch_decode_run(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const floa
     return MI_LTE_OK;
 }
 
-// ---- input synthesis (benchmark and tests): control regions as 36.211 / 36.212 transmit them --------------------------
-// PCFICH + up to four format-1A DCIs at aggregation level 4 in the common search space (what the reference's own
-// transmitter sends, liblte_phy.cc:4113-4330), through a smooth random channel per port + AWGN, directly as device-subframe
-// grids with noisy channel estimates.  Transmit diversity follows 36.211 6.3.4.3 on all ports.
 // ---- the blind search's plan and run (include/mi_lte.h: "PDCCH, 3GPP mode") ----------------------------------------------------
-
-int mi_lte_pdcch_search_space(uint32_t rnti, uint32_t subfr_num, uint32_t N_cce, uint32_t L, uint32_t *first_cce /*[6]*/, uint32_t *n)
-{
-    if (!first_cce || !n || rnti == 0 || rnti > 0xFFFFu || subfr_num > 9 || !(L == 1 || L == 2 || L == 4 || L == 8)) return MI_LTE_ERR_INVALID_ARG;
-    const uint32_t nl = N_cce / L;
-    *n = 0;
-    if (nl == 0) return MI_LTE_OK; // no candidate fits: no modulus to take
-    const uint32_t y = search_space_y(rnti, subfr_num);
-    for (uint32_t m = 0; m < search_space_m(L); m++) first_cce[(*n)++] = L * ((y + m) % nl);
-    return MI_LTE_OK;
-}
 
 int mi_lte_pdcch_search_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, float phich_res, uint32_t phich_dur_extended, uint32_t flags,
                                     const uint32_t *h_cells, uint32_t n_cells, const uint32_t *h_n_bits, uint32_t n_sizes, mi_lte_pdcch_search_plan **out)
@@ -1128,206 +843,5 @@ int mi_lte_pdcch_search_soft(const mi_lte_pdcch_search_plan *pl, const int8_t **
     return MI_LTE_OK;
 }
 
-// A C-RNTI's DCI format 0 / 1A as tx_ctrl.cc packs them (pack_0, pack_1a); the field list is in include/mi_lte.h
-int mi_lte_dci_0_1a_unpack_crnti(uint64_t payload, uint32_t n_bits, uint32_t rnti, uint32_t N_rb, uint32_t N_ant, mi_lte_dci_crnti *o)
-{
-    if (!o || n_bits > 64 || rnti == 0 || rnti > 0xFFFFu || N_rb == 0 || N_rb > 110 || !(N_ant == 1 || N_ant == 2 || N_ant == 4)) return MI_LTE_ERR_INVALID_ARG;
-    const uint32_t riv_len = (uint32_t)ceilf(logf(N_rb * (N_rb + 1) / 2) / logf(2)); // (the float logarithms of the packers)
-    uint32_t pos = n_bits;
-    auto take = [&](uint32_t n) { pos -= n; return (uint32_t)((payload >> pos) & ((1ull << n) - 1ull)); };
-    if (n_bits < 1) return MI_LTE_ERR_INVALID_ARG;
-    memset(o, 0, sizeof(*o));
-    o->format = take(1);
-    if (n_bits < 2 + riv_len + (o->format ? 13u : 12u)) return MI_LTE_ERR_INVALID_ARG;
-    o->flag = take(1);
-    o->riv  = take(riv_len);
-    const uint32_t q = o->riv / N_rb, r = o->riv % N_rb;
-    const bool     riv_ok = o->riv < N_rb * (N_rb + 1) / 2; // (inside that range the two branches below are one-to-one)
-    if (q + r < N_rb) { o->N_prb = q + 1; o->rb_start = r; }
-    else if (riv_ok) { o->N_prb = N_rb - q + 1; o->rb_start = N_rb - 1 - r; }
-    o->mcs = take(5);
-    if (o->format) { o->harq = take(3); o->ndi = take(1); o->rv = take(2); o->tpc = take(2); }
-    else { o->ndi = take(1); o->tpc = take(2); o->cyclic_shift = take(3); o->cqi_request = take(1); }
-    o->alloc.rnti = rnti;
-    if (!riv_ok || o->N_prb == 0 || o->N_prb > N_rb) { o->N_prb = 0; return 4; }
-    if (o->format && o->flag) return 4; // distributed VRBs: no PRB list here
-    o->alloc.N_prb = o->N_prb;
-    for (uint32_t i = 0; i < o->N_prb; i++) o->alloc.prb[0][i] = o->alloc.prb[1][i] = (uint8_t)(o->rb_start + i);
-    if (o->mcs > 28) return 4; // no transport block of its own
-    if (o->format) {
-        const uint32_t i_tbs = o->mcs <= 9 ? o->mcs : o->mcs <= 16 ? o->mcs - 1 : o->mcs - 2;
-        o->alloc.mod_type = o->mcs <= 9 ? 1 : o->mcs <= 16 ? 2 : 3;
-        o->alloc.tbs      = 8u * LTE_TBS_DIV8[i_tbs][o->N_prb - 1];
-        o->alloc.rv_idx   = o->rv;
-        o->alloc.tx_mode  = N_ant == 1 ? 1 : 2;
-    }
-    return 0;
-}
-
 } // extern "C"
 
-// one DCI of a synthetic control region: n_bits payload bits (first bit in bit n_bits - 1) for rnti on CCEs cce .. cce + L - 1
-struct CtrlRec { uint32_t rnti, L, cce, n_bits; uint64_t payload; };
-
-// The body both generators share.  records(u, N_cce, out) lists unit u's DCIs (every one inside the N_cce CCEs, none overlapping) or returns
-// an error; per DCI: CRC16 masked with the RNTI (36.212 5.3.3.2), the tail-biting convolutional code (5.1.3.1), rate matching to 72 L bits
-// (5.1.4.2), scrambling at bit 72 cce of the subframe's sequence, QPSK and transmit diversity onto the CCEs' resource elements.
-template <typename Records>
-static int synth_ctrl_grids(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
-                            const uint32_t *h_cfi, const mi_lte_synth_channel *chan, float *h_grids, Records records)
-{
-    const uint32_t nrb = cfg->N_rb_dl, n_ant = cfg->N_ant;
-    if (!(n_ant == 1 || n_ant == 2 || n_ant == 4)) return MI_LTE_ERR_INVALID_ARG;
-    const size_t plane = 16 * (size_t)N_SC_MAX, nf = (2 + 2 * (size_t)n_ant) * plane;
-    const double r2 = 1.0 / std::sqrt(2.0);
-    synth::Rng   rng(chan->seed);
-    std::vector<double> tr(n_ant * plane), ti(n_ant * plane);
-    std::vector<uint32_t> cand(N_CAND * RE_MAX), perm;
-    std::vector<CtrlRec>  recs;
-    std::vector<uint16_t> map(576);
-    uint32_t pcf[16];
-    for (uint32_t u = 0; u < n_units; u++) {
-        const uint32_t sf = h_subfr_num[u], cell = h_n_id_cell[u], cfi = h_cfi[u], n_symbs = cfi + (nrb <= 10 ? 1 : 0);
-        if (cfi < 1 || cfi > 4 || n_symbs > 4 || cell > 503 || sf > 9) return MI_LTE_ERR_INVALID_ARG;
-        int rc = mi_lte_pdcch_re_tables(nrb, n_ant, cell, phich_res, n_symbs, pcf, cand.data());
-        if (rc != MI_LTE_OK) return rc;
-        const uint32_t N_cce = cce_res(nrb, n_ant, cell, phich_res, n_symbs, perm);
-        std::fill(tr.begin(), tr.end(), 0.0);
-        std::fill(ti.begin(), ti.end(), 0.0);
-        // d[0..n): QPSK symbols of scrambled bits b -> transmit-diversity pre-coding onto the elements pos[]
-        auto place = [&](const uint32_t *pos, const uint8_t *b, uint32_t n) {
-            std::vector<double> dr(n), di(n);
-            for (uint32_t i = 0; i < n; i++) { dr[i] = (1 - 2 * (int)b[2 * i]) * r2; di[i] = (1 - 2 * (int)b[2 * i + 1]) * r2; }
-            auto put = [&](uint32_t port, uint32_t p, double re, double im) { tr[port * plane + p] = re; ti[port * plane + p] = im; };
-            if (n_ant == 1) {
-                for (uint32_t i = 0; i < n; i++) put(0, pos[i], dr[i], di[i]);
-            } else {
-                for (uint32_t i = 0; i + 1 < n; i += 2) { // pairs (x0, x1): port a sends x0, x1; port b sends -x1*, x0*
-                    const uint32_t a = n_ant == 2 ? 0 : ((i & 2) ? 1 : 0), bb = n_ant == 2 ? 1 : ((i & 2) ? 3 : 2);
-                    put(a, pos[i], r2 * dr[i], r2 * di[i]);
-                    put(a, pos[i + 1], r2 * dr[i + 1], r2 * di[i + 1]);
-                    put(bb, pos[i], -r2 * dr[i + 1], r2 * di[i + 1]);
-                    put(bb, pos[i + 1], r2 * dr[i], -r2 * di[i]);
-                }
-            }
-        };
-        { // PCFICH (36.212 5.3.4, 36.211 6.7)
-            uint8_t b[32], c[32];
-            synth::gold((((sf + 1) * (2 * cell + 1)) << 9) + cell, 32, c);
-            for (uint32_t i = 0; i < 32; i++) b[i] = (uint8_t)((cfi == 4 ? 0u : ((i % 3) == cfi - 1 ? 0u : 1u)) ^ c[i]);
-            place(pcf, b, 16);
-        }
-        recs.clear();
-        rc = records(u, N_cce, recs);
-        if (rc != MI_LTE_OK) return rc;
-        std::vector<uint8_t> c(72 * (size_t)N_cce + 1);
-        synth::gold((sf << 9) + cell, 72 * N_cce, c.data());
-        for (const CtrlRec &d : recs) {
-            const uint32_t K = d.n_bits + 16, E = 72 * d.L;
-            std::vector<uint8_t> bits(K, 0);
-            for (uint32_t i = 0; i < d.n_bits; i++) bits[i] = (uint8_t)((d.payload >> (d.n_bits - 1 - i)) & 1u);
-            // CRC16 masked with the RNTI (36.212 5.3.3.2)
-            uint32_t rem = 0;
-            for (uint32_t t = 0; t < K; t++) {
-                rem = (rem << 1) | (t < d.n_bits ? bits[t] : 0u);
-                if (rem & 0x10000u) rem ^= 0x11021u;
-            }
-            rem ^= d.rnti & 0xFFFFu;
-            for (uint32_t i = 0; i < 16; i++) bits[d.n_bits + i] = (uint8_t)((rem >> (15 - i)) & 1u);
-            // tail-biting convolutional code, K = 7, rate 1/3 (36.212 5.1.3.1)
-            std::vector<uint8_t> dd(3 * K);
-            uint32_t             state = 0;
-            for (uint32_t i = 0; i < 6; i++) state |= (uint32_t)bits[K - 1 - i] << (5 - i); // most recent input in bit 5
-            const uint32_t G[3] = {0133, 0171, 0165};
-            for (uint32_t t = 0; t < K; t++) {
-                const uint32_t reg = ((uint32_t)bits[t] << 6) | state;
-                for (uint32_t o = 0; o < 3; o++) dd[3 * t + o] = (uint8_t)(__builtin_popcount(reg & G[o]) & 1);
-                state = reg >> 1;
-            }
-            // rate matching to E = 72 L and scrambling at the first CCE's offset
-            uint8_t e[576];
-            conv_rm_map(K, E, map.data());
-            for (uint32_t k = 0; k < E; k++) e[k] = dd[map[k]] ^ c[72 * (size_t)d.cce + k];
-            place(&perm[36 * (size_t)d.cce], e, E / 2);
-        }
-        // channel + noise -> rx grid and estimates (symbols 0..3 only: the control region)
-        float *g = h_grids + (size_t)u * nf;
-        std::fill(g, g + nf, 0.0f);
-        const double sig = chan->snr_db >= 200 ? 0.0 : std::pow(10.0, -chan->snr_db / 20.0) * r2;
-        std::vector<double> rr(4 * N_SC_MAX, 0.0), ri(4 * N_SC_MAX, 0.0);
-        for (uint32_t p = 0; p < n_ant; p++) {
-            const double amp = chan->gain_min + (chan->gain_max - chan->gain_min) * rng.uniform();
-            const double tau = (2 * rng.uniform() - 1) * 2e-3, ph = (2 * rng.uniform() - 1) * M_PI;
-            for (uint32_t l = 0; l < 4; l++)
-                for (uint32_t k = 0; k < 12 * nrb; k++) {
-                    const double hr = amp * std::cos(ph + 2 * M_PI * tau * k), hi = amp * std::sin(ph + 2 * M_PI * tau * k);
-                    const size_t q = l * N_SC_MAX + k;
-                    rr[q] += hr * tr[p * plane + q] - hi * ti[p * plane + q];
-                    ri[q] += hr * ti[p * plane + q] + hi * tr[p * plane + q];
-                    g[(2 + p) * plane + q]         = (float)(hr + 0.2 * sig * rng.normal());
-                    g[(2 + n_ant + p) * plane + q] = (float)(hi + 0.2 * sig * rng.normal());
-                }
-        }
-        for (uint32_t l = 0; l < 4; l++)
-            for (uint32_t k = 0; k < 12 * nrb; k++) {
-                const size_t q = l * N_SC_MAX + k;
-                g[q]         = (float)(rr[q] + sig * rng.normal());
-                g[plane + q] = (float)(ri[q] + sig * rng.normal());
-            }
-    }
-    return MI_LTE_OK;
-}
-
-extern "C" {
-
-int mi_lte_synth_ctrl_grids(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
-                            const uint32_t *h_cfi, const mi_lte_synth_dci *h_dci /*[n_units][n_dci]*/, uint32_t n_dci,
-                            const mi_lte_synth_channel *chan, float *h_grids)
-{
-    if (!cfg || !h_subfr_num || !h_n_id_cell || !h_cfi || (n_dci && !h_dci) || n_dci > 4 || !chan || !h_grids) return MI_LTE_ERR_INVALID_ARG;
-    const uint32_t nrb = cfg->N_rb_dl;
-    uint32_t sz[2];
-    dci_sizes(nrb, &sz[0], &sz[1]);
-    return synth_ctrl_grids(cfg, phich_res, n_units, h_subfr_num, h_n_id_cell, h_cfi, chan, h_grids, [&](uint32_t u, uint32_t N_cce, std::vector<CtrlRec> &out) {
-        for (uint32_t a = 0; a < n_dci; a++) {
-            const mi_lte_synth_dci &d = h_dci[(size_t)u * n_dci + a];
-            if (d.rnti == 0) continue; // unused slot
-            if (4 * a + 4 > N_cce) continue; // this candidate's CCEs do not all exist: nothing is sent (as the reference)
-            // DCI format 1A for SI-/P-/RA-RNTI (36.212 5.3.3.1.3; the reference's dci_1a_pack :13138-13215)
-            uint64_t payload = 0;
-            uint32_t pos = 0;
-            auto push = [&](uint32_t v, uint32_t n) { payload = (payload << n) | (v & ((1u << n) - 1u)); pos += n; };
-            const uint32_t riv_len = (uint32_t)ceilf(logf(nrb * (nrb + 1) / 2) / logf(2));
-            if (d.N_prb == 0 || d.N_prb - 1 > nrb / 2 || d.rb_start + d.N_prb > nrb || d.mcs > 26) return (int)MI_LTE_ERR_INVALID_ARG;
-            push(1, 1); push(0, 1); push(nrb * (d.N_prb - 1) + d.rb_start, riv_len); push(d.mcs, 5); push(0, 3); push(0, 1); push(d.rv_idx, 2); push(1, 2);
-            if (pos > sz[0]) return (int)MI_LTE_ERR_INVALID_ARG;
-            out.push_back(CtrlRec{d.rnti, 4, 4 * a, sz[0], payload << (sz[0] - pos)});
-        }
-        return (int)MI_LTE_OK;
-    });
-}
-
-// any DCI anywhere (include/mi_lte.h): up to MI_LTE_SYNTH_MAX_REC records per unit, rnti = 0 marks an unused slot
-int mi_lte_synth_ctrl_grids_dci(const mi_lte_dl_cfg *cfg, float phich_res, uint32_t n_units, const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell,
-                                const uint32_t *h_cfi, const mi_lte_synth_dci_rec *h_rec /*[n_units][n_rec]*/, uint32_t n_rec,
-                                const mi_lte_synth_channel *chan, float *h_grids)
-{
-    if (!cfg || !h_subfr_num || !h_n_id_cell || !h_cfi || (n_rec && !h_rec) || n_rec > MI_LTE_SYNTH_MAX_REC || !chan || !h_grids) return MI_LTE_ERR_INVALID_ARG;
-    return synth_ctrl_grids(cfg, phich_res, n_units, h_subfr_num, h_n_id_cell, h_cfi, chan, h_grids, [&](uint32_t u, uint32_t N_cce, std::vector<CtrlRec> &out) {
-        uint8_t used[128] = {0}; // (N_cce <= 121: 100 RB, four symbols)
-        for (uint32_t a = 0; a < n_rec; a++) {
-            const mi_lte_synth_dci_rec &d = h_rec[(size_t)u * n_rec + a];
-            if (d.rnti == 0) continue; // unused slot
-            if (d.rnti > 0xFFFFu || !(d.L == 1 || d.L == 2 || d.L == 4 || d.L == 8) || d.cce % d.L || d.n_bits < 1 || d.n_bits > 64) return (int)MI_LTE_ERR_INVALID_ARG;
-            if (d.cce >= N_cce || d.cce + d.L > N_cce || N_cce > 128) return (int)MI_LTE_ERR_INVALID_ARG; // reaches past the last CCE
-            for (uint32_t i = 0; i < d.L; i++) {
-                if (used[d.cce + i]) return (int)MI_LTE_ERR_INVALID_ARG; // overlaps an earlier record
-                used[d.cce + i] = 1;
-            }
-            out.push_back(CtrlRec{d.rnti, d.L, d.cce, d.n_bits, d.n_bits == 64 ? d.payload : d.payload & ((1ull << d.n_bits) - 1ull)});
-        }
-        return (int)MI_LTE_OK;
-    });
-}
-
-} // extern "C"

@@ -12,71 +12,44 @@
 #include <vector>
 
 #include "../../include/mi_lte.h"
+#include "dci.h"
 #include "lte_tables.h"
+#include "pdcch_geom.h"
 #include "synth.hpp"
 #include "tx_host.h"
 
 using namespace tx;
 
 namespace {
-inline void put_bits(uint8_t *&at, uint32_t value, uint32_t n)
+// a DCI's fields by its format's list (dci.h) as bits into out, n_pad zero bits behind them and one more where 36.212 5.3.3.1.2 calls the size
+// ambiguous; returns the payload size
+template <uint32_t N>
+uint32_t put_dci(const dci::Field (&list)[N], const dci::Fields &f, uint32_t N_rb, uint32_t n_pad, uint8_t *out)
 {
-    for (uint32_t i = 0; i < n; i++) *at++ = (value >> (n - 1 - i)) & 1u;
+    uint64_t       payload;
+    const uint32_t n_fields = dci::pack(list, f, dci::riv_bits(N_rb), &payload);
+    uint32_t       n = n_fields + n_pad;
+    if (dci::ambiguous_size(n)) n++;
+    for (uint32_t i = 0; i < n; i++) out[i] = i < n_fields ? (payload >> (n_fields - 1 - i)) & 1u : 0;
+    return n;
 }
-// resource indication value of a contiguous run (36.213 7.1.6.3 / 8.1.1) and the width of its field, the logarithms in float as the reference takes them
-inline uint32_t riv_bits(uint32_t N_rb) { return (uint32_t)ceilf(logf(N_rb * (N_rb + 1) / 2) / logf(2)); }
-inline uint32_t riv(uint32_t N_rb, uint32_t N_prb, uint32_t first) { return (N_prb - 1) <= N_rb / 2 ? N_rb * (N_prb - 1) + first : N_rb * (N_rb - N_prb + 1) + (N_rb - 1 - first); }
-// 36.212 5.3.3.1.2: payload sizes that are ambiguous get one more bit
-inline bool ambiguous_size(uint32_t n) { return n == 12 || n == 14 || n == 16 || n == 20 || n == 24 || n == 26 || n == 32 || n == 40 || n == 44 || n == 56; }
-
 // 36.212 5.3.3.1.3, localised allocation; an SI / paging / random-access RNTI carries N_PRB^1A = 3 in the TPC field's place and no new-data bit.
 // Returns the payload size and the transport block size the DCI stands for.
 uint32_t pack_1a(const mi_lte_tx_alloc &al, uint32_t N_rb_dl, uint8_t *out, uint32_t *tbs)
 {
-    uint8_t   *at        = out;
-    const bool broadcast = al.rnti == 0xFFFF || al.rnti == 0xFFFE || (al.rnti >= 0x0001 && al.rnti <= 0x003C);
-    put_bits(at, 1, 1); // format 1A
-    put_bits(at, 0, 1); // localised
-    put_bits(at, riv(N_rb_dl, al.N_prb, al.prb[0][0]), riv_bits(N_rb_dl));
-    put_bits(at, al.mcs, 5);
-    put_bits(at, 0, 3);                         // HARQ process
-    put_bits(at, broadcast ? 0 : al.ndi, 1);
-    put_bits(at, al.rv_idx, 2);
-    put_bits(at, broadcast ? 1 : al.tpc, 2);
+    const bool  broadcast = dci::common_rnti(al.rnti);
+    dci::Fields f{};
+    f.format = 1; // (flag 0: localised; HARQ process 0)
+    f.riv = dci::riv_encode(N_rb_dl, al.N_prb, al.prb[0][0]); f.mcs = al.mcs; f.ndi = broadcast ? 0 : al.ndi; f.rv = al.rv_idx; f.tpc = broadcast ? 1 : al.tpc;
     *tbs = 8u * LTE_TBS_DIV8[al.mcs][(broadcast ? 3 : al.N_prb) - 1];
-    if (ambiguous_size((uint32_t)(at - out))) put_bits(at, 0, 1);
-    return (uint32_t)(at - out);
+    return put_dci(dci::FORMAT_1A, f, N_rb_dl, 0, out);
 }
-// 36.212 5.3.3.1.1, no hopping, one cluster
+// 36.212 5.3.3.1.1, no hopping, one cluster; cyclic shift 0, no CSI request, one padding bit
 uint32_t pack_0(const mi_lte_tx_alloc &al, uint32_t N_rb_ul, uint8_t *out)
 {
-    uint8_t *at = out;
-    put_bits(at, 0, 1); // format 0
-    put_bits(at, 0, 1); // no hopping
-    put_bits(at, riv(N_rb_ul, al.N_prb, al.prb[0][0]), riv_bits(N_rb_ul));
-    put_bits(at, al.mcs, 5);
-    put_bits(at, al.ndi, 1);
-    put_bits(at, al.tpc, 2);
-    put_bits(at, 0, 3); // cyclic shift
-    put_bits(at, 0, 1); // CSI request
-    put_bits(at, 0, 1); // padding
-    if (ambiguous_size((uint32_t)(at - out))) put_bits(at, 0, 1);
-    return (uint32_t)(at - out);
-}
-
-// REG order of 36.212 5.1.4.2.1 for n REGs (pdcch_permute_pre_calc, liblte_phy.cc:7970-8067): the sub-block interleaver of the convolutional
-// rate matching applied to the REG numbers
-void reg_permutation(uint32_t n, std::vector<uint32_t> &map)
-{
-    const uint32_t R = (n + 31) / 32, K_pi = 32 * R, N_dummy = K_pi - n;
-    map.clear();
-    for (uint32_t k = 0; k < K_pi && map.size() < n; k++) {
-        const uint32_t col = k / R, row = k % R;
-        uint32_t       j   = (col + 16) % 32; // 36.212 table 5.1.4-2 = the bit-reversed order turned by 16
-        j                  = ((j & 1) << 4) | ((j & 2) << 2) | (j & 4) | ((j & 8) >> 2) | ((j & 16) >> 4);
-        const uint32_t t   = 32 * row + j;
-        if (t >= N_dummy) map.push_back(t - N_dummy);
-    }
+    dci::Fields f{};
+    f.riv = dci::riv_encode(N_rb_ul, al.N_prb, al.prb[0][0]); f.mcs = al.mcs; f.ndi = al.ndi; f.tpc = al.tpc;
+    return put_dci(dci::FORMAT_0, f, N_rb_ul, 1, out);
 }
 } // namespace
 
@@ -105,10 +78,8 @@ extern "C" int mi_lte_pdcch_channel_encode(mi_lte_tx *t, uint32_t N_rb_dl, uint3
         layer_map_dl(d_re, d_im, M_symb, N_ant, 1, x_re, x_im, &M_layer);
         pre_code_dl(x_re, x_im, M_layer, N_ant, y_re, y_im, 576, &M_ap);
         pcfich->N_reg = 4;
-        const uint32_t k_hat = (N_sc_rb_dl / 2) * (N_id_cell % (2 * N_rb_dl));
+        pdcch_geom::pcfich_regs(N_rb_dl, N_id_cell, pcfich->k, pcfich->n);
         for (uint32_t i = 0; i < 4; i++) {
-            pcfich->k[i] = (k_hat + (i * N_rb_dl / 2) * N_sc_rb_dl / 2) % N_sc;
-            pcfich->n[i] = (pcfich->k[i] / 6) - 0.5;
             for (uint32_t p = 0; p < N_ant; p++)
                 for (uint32_t j = 0, idx = 0; j < 6; j++)
                     if (N_id_cell % 3 != j % 3) {
@@ -142,12 +113,8 @@ extern "C" int mi_lte_pdcch_channel_encode(mi_lte_tx *t, uint32_t N_rb_dl, uint3
             layer_map_dl(d_re, d_im, 12, N_ant, 1, x_re, x_im, &M_layer);
             pre_code_dl(x_re, x_im, M_layer, N_ant, y_re, y_im, 576, &M_ap);
             if (phich_dur != 0) continue; // (the extended duration is not mapped by the reference either)
-            const uint32_t n_l = N_rb_dl * 2 - pcfich->N_reg;
-            uint32_t       n_hat[3];
-            for (uint32_t i = 0; i < 3; i++) n_hat[i] = (N_id_cell + m + i * n_l / 3) % n_l;
-            for (uint32_t i = 0; i < pcfich->N_reg; i++) // REG numbers count the REGs the PCFICH left
-                for (uint32_t j = 0; j < 3; j++)
-                    if (n_hat[j] > pcfich->n[i]) n_hat[j]++;
+            uint32_t n_hat[3]; // REG numbers count the REGs the PCFICH left
+            pdcch_geom::phich_group_regs(N_rb_dl, N_id_cell, m, pcfich->n, n_hat);
             // (one element counter for all three REGs AND all ports: port p's values are taken from where the counter stands, liblte_phy.cc:8196-8211)
             for (uint32_t i = 0, y_idx = 0; i < 3; i++) {
                 phich->k[idx + i] = n_hat[i] * 6;
@@ -213,7 +180,7 @@ extern "C" int mi_lte_pdcch_channel_encode(mi_lte_tx *t, uint32_t N_rb_dl, uint3
     std::vector<uint32_t> map;
     bool                  known = false;
     for (uint32_t n = 1; n <= 3; n++) known = known || N_reg == n * (N_rb_dl * 3) - N_rb_dl - 4 - N_group_phich * 3;
-    if (known) reg_permutation(N_reg, map);
+    if (known) pdcch_geom::cc_interleaver_order(N_reg, map);
     else map.assign(N_reg, 0);
     if (N_reg == 787 && N_ant >= 2) {
         // 787 REGs (20 MHz, three symbols, N_g = 1/6) is one more than the table has rows: that row IS the two uint16 work vectors behind the table

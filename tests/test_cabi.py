@@ -142,7 +142,7 @@ def test_transmit_functions_refuse_what_the_reference_has_no_defined_behaviour_f
 
 
 def test_transmit_functions_under_address_and_undefined_behaviour_sanitizers():
-    """tools/asan/run.sh: the host-side transmit sources (tx.cc, tx_ctrl.cc, tx_ul.cc, sched.cc, synth.cc, ul_rs.cc) compiled with g++
+    """tools/asan/run.sh: the host-side transmit sources (tx.cc, tx_ctrl.cc, tx_ul.cc, sched.cc, synth.cc, ul_rs.cc, pdcch_geom.cc; dci.h is header code) compiled with g++
     -fsanitize=address,undefined and driven through every transmit entry point with random inputs, out-of-range ones included (PRB numbers past
     the grid, transport blocks past five code blocks, MCS past the table, control regions without a REG): no report.  CPU build only."""
     import shutil
