@@ -908,6 +908,15 @@ int      mi_lte_prach_detect_launch(mi_lte_ctx *ctx, mi_lte_prach_plan *plan, co
                                     const uint64_t *d_occ_start, uint32_t n_occ);
 int      mi_lte_prach_detect_fetch(mi_lte_ctx *ctx, mi_lte_prach_plan *plan, uint32_t *h_N_det_pre, uint32_t *h_det_pre,
                                    uint32_t *h_det_ta, uint32_t max_occ);
+/* the detector's tap, for tests and not for callers: runs the same three kernels over the batch (the correlation kernel in an instantiation
+ * that also stores every power; the detection entries above store none) and copies out what they computed, forming no verdict --
+ * h_xhat: the kept bins, n_occ x N_zc float pairs (re, im); h_stats: the per-root records the verdict is formed from, [n_occ][n_roots];
+ * h_power: the correlation power profiles, float [n_occ][n_roots][N_zc].  N_zc = 839 (format 4: 139).  Waits for the stream; the plan is
+ * left as it was.  MI_LTE_ERR_INVALID_ARG as mi_lte_prach_detect_run, and for a NULL output. */
+typedef struct { float sum, max_val; uint32_t max_off, pad; } mi_lte_prach_corr_stat;
+int      mi_lte_prach_detect_tap(mi_lte_ctx *ctx, mi_lte_prach_plan *plan, const void *d_samples_a, const void *d_samples_b,
+                                 const uint64_t *d_occ_start, uint32_t n_occ, float *h_xhat, mi_lte_prach_corr_stat *h_stats,
+                                 float *h_power);
 
 /* ---------------------------------------------------------------- PUCCH formats 1 / 1a / 1b
  * mi_lte_pucch_decode_run replaces liblte_phy_pucch_format_1_1a_1b_channel_decode() (liblte/hdr/liblte_phy.h:775-782,

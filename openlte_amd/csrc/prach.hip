@@ -130,11 +130,14 @@ struct CorrOut { float sum, max_val; uint32_t max_off, pad; };
 // the convolution with the fixed sequence conj(c) is a product with its precomputed 2048-point spectrum (plan: d_bspec), the chirp
 // comes from a table with exactly reduced angles (plan: d_chirp).  16x fewer operations than the 839 x 839 direct sums it replaces
 // (2.8 -> 0.3 ms for 1638 occasions x 8 roots).
+// TAP (mi_lte_prach_detect_tap, for tests): every correlation power also goes to pw[occ][root][m]; the detection launches instantiate
+// TAP = false, which neither reads pw nor stores anything more than the per-root record.
 constexpr uint32_t BL = 2048;
 
+template <bool TAP>
 __global__ __launch_bounds__(256) void k_prach_corr(const float2 *__restrict__ x_hat, const float2 *__restrict__ xu_fft, uint32_t n_roots, uint32_t N_ZC,
                                                     const float2 *__restrict__ chirp, const float2 *__restrict__ bspec, const float2 *__restrict__ tw_g,
-                                                    CorrOut *__restrict__ out)
+                                                    CorrOut *__restrict__ out, float *__restrict__ pw)
 {
     extern __shared__ float2 lds[]; // a[BL] | b[BL] | tw[BL/2]
     __shared__ float    r_sum[4], r_max[4];
@@ -167,6 +170,7 @@ __global__ __launch_bounds__(256) void k_prach_corr(const float2 *__restrict__ x
         const float  zr = z.x * (1.0f / BL), zi = -z.y * (1.0f / BL);
         const float  ar = zr * c.x - zi * c.y, ai = zr * c.y + zi * c.x;
         const float  p = ar * ar + ai * ai;
+        if constexpr (TAP) pw[((size_t)occ * n_roots + root) * N_ZC + m] = p;
         sum += p;
         if (p > mx) { mx = p; off = m; }
     }
@@ -354,13 +358,14 @@ uint32_t mi_lte_prach_occasion_samples(const mi_lte_prach_plan *pl) { return pl 
 // The kernels of one batch of occasions and where their per-root maxima go: *h_co = pinned host memory the kernel wrote itself (a few
 // occasions), or d_co in the context's scratch for the caller to copy
 static int prach_launch(mi_lte_ctx *ctx, mi_lte_prach_plan *pl, const void *d_samples_a, const void *d_samples_b, const uint64_t *d_occ_start, uint32_t n_occ,
-                        bool small_results, CorrOut **h_co_out, CorrOut **d_co_out, size_t *co_bytes_out)
+                        bool small_results, CorrOut **h_co_out, CorrOut **d_co_out, size_t *co_bytes_out, float **d_pow_tap = nullptr)
 {
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const uint32_t N_ZC = pl->n_zc, P = pl->phases;
     const size_t xh_bytes = sizeof(float2) * (size_t)n_occ * N_ZC, co_bytes = sizeof(CorrOut) * (size_t)n_occ * pl->n_roots;
     const size_t f_off = (xh_bytes + co_bytes + 64 + 255) & ~(size_t)255, f_bytes = sizeof(float2) * (size_t)n_occ * pl->T_fft; // P x N2 per occasion
-    int rc = mi_ctx_reserve_scratch(ctx, f_off + f_bytes);
+    const size_t pow_bytes = d_pow_tap ? sizeof(float) * (size_t)n_occ * pl->n_roots * N_ZC : 0; // the tap's power profiles, behind F
+    int rc = mi_ctx_reserve_scratch(ctx, f_off + f_bytes + pow_bytes);
     if (rc != MI_LTE_OK) return rc;
     float2  *d_xh = (float2 *)ctx->scratch;
     // the per-root maxima of a few occasions go straight into pinned host memory (no copy command for a per-call caller); a batch's through scratch
@@ -381,8 +386,13 @@ static int prach_launch(mi_lte_ctx *ctx, mi_lte_prach_plan *pl, const void *d_sa
         MI_LAUNCH(ctx, "k_prach_fft", (k_prach_fft<float>), dim3(P, n_occ), dim3(256), (2 * N2 + 1024) * sizeof(float2), s, d_occ_start, pl->T_cp, N2, P, (const float2 *)pl->d_tw, d_F);
     }
     MI_LAUNCH(ctx, "k_prach_bins", k_prach_bins, dim3((N_ZC + 255) / 256, n_occ), dim3(256), 0, (const float2 *)d_F, N2, P, pl->T_fft, pl->start, N_ZC, d_xh);
-    MI_LAUNCH(ctx, "k_prach_corr", k_prach_corr, dim3(pl->n_roots, n_occ), dim3(256), sizeof(float2) * (2 * BL + BL / 2), d_xh, pl->d_xu_fft, pl->n_roots, N_ZC,
-              (const float2 *)pl->d_chirp, (const float2 *)pl->d_bspec, (const float2 *)pl->d_tw, d_co);
+    if (d_pow_tap) {
+        *d_pow_tap = (float *)((char *)ctx->scratch + f_off + f_bytes);
+        MI_LAUNCH(ctx, "k_prach_corr", (k_prach_corr<true>), dim3(pl->n_roots, n_occ), dim3(256), sizeof(float2) * (2 * BL + BL / 2), d_xh, pl->d_xu_fft, pl->n_roots, N_ZC,
+                  (const float2 *)pl->d_chirp, (const float2 *)pl->d_bspec, (const float2 *)pl->d_tw, d_co, *d_pow_tap);
+    } else
+        MI_LAUNCH(ctx, "k_prach_corr", (k_prach_corr<false>), dim3(pl->n_roots, n_occ), dim3(256), sizeof(float2) * (2 * BL + BL / 2), d_xh, pl->d_xu_fft, pl->n_roots, N_ZC,
+                  (const float2 *)pl->d_chirp, (const float2 *)pl->d_bspec, (const float2 *)pl->d_tw, d_co, (float *)nullptr);
     MI_HIP_CHECK(ctx, hipGetLastError());
     ctx->last_kernels = "k_prach_bins:1,k_prach_corr:1";
     *h_co_out = h_co; *d_co_out = d_co; *co_bytes_out = co_bytes;
@@ -433,6 +443,25 @@ int mi_lte_prach_detect_run(mi_lte_ctx *ctx, mi_lte_prach_plan *pl, const void *
     }
     MI_HIP_CHECK(ctx, h_co ? mi_stream_wait(ctx, n_occ) : hipStreamSynchronize(ctx->stream)); // (a copy into pageable memory is done when the runtime says so)
     prach_verdicts(pl, h_co ? h_co : co_copy.data(), n_occ, h_N_det_pre, h_det_pre, h_det_ta);
+    return MI_LTE_OK;
+}
+
+// For tests: the same three kernels (k_prach_corr<true>), and what they computed copied out -- the kept bins, the per-root records the
+// verdict code reads, the whole power profiles.  No verdicts; nothing of the plan changes.
+static_assert(sizeof(mi_lte_prach_corr_stat) == sizeof(CorrOut), "the tap hands the CorrOut records out as they are");
+int mi_lte_prach_detect_tap(mi_lte_ctx *ctx, mi_lte_prach_plan *pl, const void *d_samples_a, const void *d_samples_b, const uint64_t *d_occ_start,
+                            uint32_t n_occ, float *h_xhat, mi_lte_prach_corr_stat *h_stats, float *h_power)
+{
+    if (!ctx || !pl || !d_samples_a || !d_occ_start || n_occ == 0 || !h_xhat || !h_stats || !h_power) return MI_LTE_ERR_INVALID_ARG;
+    CorrOut *h_co = nullptr, *d_co = nullptr;
+    float   *d_pow = nullptr;
+    size_t   co_bytes = 0;
+    int rc = prach_launch(ctx, pl, d_samples_a, d_samples_b, d_occ_start, n_occ, false, &h_co, &d_co, &co_bytes, &d_pow);
+    if (rc != MI_LTE_OK) return rc;
+    MI_D2H(ctx, h_xhat, ctx->scratch, sizeof(float2) * (size_t)n_occ * pl->n_zc);
+    MI_D2H(ctx, h_stats, d_co, co_bytes);
+    MI_D2H(ctx, h_power, d_pow, sizeof(float) * (size_t)n_occ * pl->n_roots * pl->n_zc);
+    MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return MI_LTE_OK;
 }
 

@@ -478,6 +478,7 @@ def load_library():
     L.mi_lte_prach_detect_run.argtypes = [vp, vp, vp, vp, vp, u32, u32p, u32p, u32p]
     L.mi_lte_prach_detect_launch.argtypes = [vp, vp, vp, vp, vp, u32]
     L.mi_lte_prach_detect_fetch.argtypes = [vp, vp, u32p, u32p, u32p, u32]
+    L.mi_lte_prach_detect_tap.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp]
     L.mi_lte_device_copy_rate.argtypes = [vp, C.c_size_t, u32, C.POINTER(C.c_double)]
     L.mi_lte_device_copy_rates.argtypes = [vp, C.POINTER(C.c_double)]
     L.mi_lte_pdcch_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.c_float, u32, u32, u32p, u32, C.POINTER(vp)]
@@ -1036,6 +1037,19 @@ class PrachPlan:
         self.h = h
         self.n_roots = ctx.L.mi_lte_prach_plan_n_roots(h)
         self.occasion_samples = ctx.L.mi_lte_prach_occasion_samples(h)
+        self.n_zc = 139 if prach_cfg.preamble_format == 4 else 839
+
+    STAT = np.dtype([("sum", np.float32), ("max_val", np.float32), ("max_off", np.uint32), ("pad", np.uint32)])  # mi_lte_prach_corr_stat
+
+    def tap_dev(self, d_a, d_b, d_start, n_occ):
+        """For tests (mi_lte_prach_detect_tap): what the three kernels computed for n_occ occasions -- the kept bins complex64 [n_occ, N_zc],
+        the per-root records STAT [n_occ, n_roots], the correlation power profiles float32 [n_occ, n_roots, N_zc]."""
+        xhat = np.zeros((n_occ, self.n_zc), np.complex64)
+        stats = np.zeros((n_occ, self.n_roots), self.STAT)
+        power = np.zeros((n_occ, self.n_roots, self.n_zc), np.float32)
+        self.ctx._check(self.ctx.L.mi_lte_prach_detect_tap(self.ctx.h, self.h, d_a.ptr, d_b.ptr if d_b is not None else None, d_start.ptr, n_occ,
+                                                            xhat.ctypes.data, stats.ctypes.data, power.ctypes.data))
+        return xhat, stats, power
 
     def detect_dev(self, d_a, d_b, d_start, n_occ):
         """(N_det_pre, det_pre, det_ta) uint32 arrays, one entry per occasion."""
