@@ -1152,6 +1152,70 @@ typedef struct {
 } mi_lte_dci_crnti;
 int  mi_lte_dci_0_1a_unpack_crnti(uint64_t payload, uint32_t n_bits, uint32_t rnti, uint32_t N_rb, uint32_t N_ant, mi_lte_dci_crnti *out);
 
+/* ---------------------------------------------------------------- PHICH, 3GPP mode: the HARQ indicators that answer a PUSCH (opt-in)
+ * mi_lte_phich_* decode what phich_channel_map sends (liblte/src/liblte_phy.cc:8076-8215; this library's transmitter: mi_lte_pdcch_channel_encode).
+ * The reference has no PHICH decoder -- phich_channel_demap (liblte_phy.cc:8243-8278) only computes the positions, so that the PDCCH can keep
+ * off them -- so the specification is the authority: 36.211 6.9 and 36.213 9.1.2.  FDD, normal cyclic prefix, normal PHICH duration (symbol 0
+ * only), N_SF = 4; the six standard bandwidths, N_g in (0, 2], cells of 1, 2 and 4 CRS ports, full estimate planes (not MI_LTE_CE_COMPACT).
+ *
+ * Host arithmetic.  mi_lte_phich_n_group: N_group = ceil(N_g N_rb_dl / 8), what the PDCCH tables and N_reg / 3 of mi_lte_ctrl_reg_positions
+ *   count; 0 for a non-standard bandwidth or an N_g outside (0, 2].  mi_lte_phich_resource (36.213 9.1.2, N_SF = 4): the PHICH that answers
+ *   the PUSCH whose first slot starts at resource block I_prb_ra_lowest, sent with DMRS cyclic-shift field n_dmrs:
+ *     n_group = (I_prb_ra_lowest + n_dmrs) mod N_group + I_phich N_group,  n_seq = (floor(I_prb_ra_lowest / N_group) + n_dmrs) mod 8;
+ *   MI_LTE_ERR_INVALID_ARG for N_group = 0, n_dmrs > 7, null pointers.  mi_lte_phich_re_table: the plan's index table for one cell,
+ *   re[12 m + 4 i + j] (below); MI_LTE_ERR_INVALID_ARG where mi_lte_phich_n_group gives 0, for a cell past 503 and for null pointers.
+ *
+ * Positions.  Group m's three REGs are those of phich_channel_demap (:8243-8278): first sub-carrier 6 n_i, n_i counted among the REGs the
+ *   PCFICH left, exactly what mi_lte_ctrl_reg_positions reports and the PDCCH tables exclude.  Quadruplet i = 0 .. 2 occupies, in increasing
+ *   k, the four of REG i's six sub-carriers with k mod 3 != N_id_cell mod 3: RE(4 i + j), j = 0 .. 3, all in symbol 0.  (The reference steps
+ *   over the PCFICH REGs in the order they are listed, not in ascending order, so in some cells a PHICH REG lands on a PCFICH REG; the
+ *   positions are kept as the transmitter writes them.)
+ * Scrambling.  c(0) .. c(11): the first 12 bits of the Gold sequence with c_init = ((subfr_num + 1) (2 N_id_cell + 1) << 9) + N_id_cell
+ *   (phich_channel_map :8076-8215 uses the same); s(e) = 1 - 2 c(e).
+ * Sequences.  w_n(j) = walsh[n mod 4][j] (n < 4 ? 1 : j_imag), n = 0 .. 7, walsh = {++++, +-+-, ++--, +--+} (36.211 table 6.9.1-2).  BPSK
+ *   reference z0 = (1 + j) / sqrt 2; HI = 0 (NACK) is sent as +z0, HI = 1 (ACK) as -z0 (36.212 5.3.5, 36.211 table 7.1.1-1).
+ * Combining.  y(e), h_p(e): the unit's received element and port p's estimate at RE(e), read from the device subframe of
+ *   mi_lte_dl_frontend_batch (y planes, then N_ant real and N_ant imaginary estimate planes, index l 1200 + k).
+ *   1 port:  r(e) = y(e) conj(h_0(e)), P(e) = |h_0(e)|^2.
+ *   2 ports: pairs (a, b) = (4 i, 4 i + 1) and (4 i + 2, 4 i + 3) of the pre-coder of 36.211 6.3.4.3, ports (A, B) = (0, 1):
+ *     r(a) = sqrt 2 (conj(h_A(a)) y(a) + h_B(b) conj(y(b))),  P(a) = |h_A(a)|^2 + |h_B(b)|^2,
+ *     r(b) = sqrt 2 (conj(h_A(b)) y(b) - h_B(a) conj(y(a))),  P(b) = |h_A(b)|^2 + |h_B(a)|^2.
+ *   4 ports: the same with (A, B) = (0, 2) when (i + m) mod 2 = 0 and (1, 3) otherwise, for the whole quadruplet (36.211 6.9.2 -- not the
+ *     PDSCH's alternation inside a group of four).
+ * Despreading, float32, every sum in the order written:
+ *   q_i(n) = sum_{j = 0..3} conj(w_n(j)) s(4 i + j) r(4 i + j);  P_tot = sum_{e = 0..11} P(e);
+ *   rep_i(n) = Re(q_i(n) conj(z0)) / P_tot;  metric(n) = rep_0 + rep_1 + rep_2;  hi(n) = (metric(n) < 0).
+ *   Without noise a present indicator gives -+1 and an absent one 0; sequences n and n + 4 separate in the projection onto z0.
+ *   P_tot = 0 or not finite: metric = rep = power = 0, hi = 0, flags = MI_LTE_PHICH_NO_POWER.  A unit whose cell the plan was not built for
+ *   (or whose subframe number is past 9): the same zeros with flags = MI_LTE_PHICH_UNKNOWN_CELL.  A DTX threshold on metric is the caller's.
+ * mi_lte_phich_plan_create holds, per listed cell and group, the 12 grid indices, and N_group.  MI_LTE_ERR_INVALID_ARG, nothing allocated:
+ *   null pointers, n_cells = 0, a cell past 503, and -- with the context's error text set -- a non-standard bandwidth, a port count other
+ *   than 1 / 2 / 4, N_g outside (0, 2], the extended PHICH duration (refused as mi_lte_pdcch_plan_create refuses it), MI_LTE_CE_COMPACT in
+ *   cfg->sample_format, flags other than 0.
+ * mi_lte_phich_decode_run, the dense form: one launch of k_phich_decode (one workgroup per unit) on the context's stream, which the call does
+ *   not wait for; d_out (device memory) receives [n_units][N_group][8] records, every group and sequence of every unit.  No atomics: two
+ *   runs give the same bytes.  MI_LTE_ERR_INVALID_ARG before any launch: null pointers, n_units = 0. */
+#define MI_LTE_PHICH_NO_POWER     1u
+#define MI_LTE_PHICH_UNKNOWN_CELL 2u
+typedef struct {
+    float    metric;     /* rep[0] + rep[1] + rep[2]: about -1 ACK, +1 NACK, 0 nothing sent */
+    float    power;      /* P_tot                                                            */
+    float    rep[3];     /* the three repetitions: stage taps                                */
+    uint32_t hi;         /* metric < 0: 1 = ACK                                              */
+    uint32_t flags;      /* MI_LTE_PHICH_NO_POWER, MI_LTE_PHICH_UNKNOWN_CELL                 */
+    uint32_t reserved;
+} mi_lte_phich_result;   /* 32 bytes */
+typedef struct mi_lte_phich_plan mi_lte_phich_plan;
+uint32_t mi_lte_phich_n_group(uint32_t N_rb_dl, float phich_res);
+int  mi_lte_phich_resource(uint32_t I_prb_ra_lowest, uint32_t n_dmrs, uint32_t N_group, uint32_t I_phich, uint32_t *n_group, uint32_t *n_seq);
+int  mi_lte_phich_re_table(uint32_t N_rb_dl, uint32_t N_id_cell, float phich_res, uint32_t *N_group, uint32_t *re /* [25][12] */);
+int  mi_lte_phich_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, float phich_res /* N_g: 1/6, 1/2, 1, 2 */, uint32_t phich_dur_extended,
+                              uint32_t flags, const uint32_t *h_cells, uint32_t n_cells, mi_lte_phich_plan **out);
+void mi_lte_phich_plan_destroy(mi_lte_ctx *ctx, mi_lte_phich_plan *plan);
+uint32_t mi_lte_phich_plan_n_group(const mi_lte_phich_plan *plan);
+int  mi_lte_phich_decode_run(mi_lte_ctx *ctx, mi_lte_phich_plan *plan, const float *d_subframes, const uint32_t *d_subfr_num,
+                             const uint32_t *d_n_id_cell, uint32_t n_units, mi_lte_phich_result *d_out /* [n_units][N_group][8] */);
+
 /* ---------------------------------------------------------------- PBCH
  * mi_lte_pbch_decode_run replaces liblte_phy_bch_channel_decode() (liblte/hdr/liblte_phy.h:947-953, implementation
  * liblte/src/liblte_phy.cc:3968-4105 with bch_channel_decode :12581-12650) for a batch of device subframes holding subframe 0

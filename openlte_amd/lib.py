@@ -213,6 +213,49 @@ def pucch2_modulate(tab, fmt, b, ack=None, grid=None):
     return grid
 
 
+class PhichResult(C.Structure):
+    """mi_lte_phich_result (32 bytes): metric = rep[0] + rep[1] + rep[2] (about -1 ACK, +1 NACK, 0 nothing sent), power = P_tot, hi = 1 for
+    metric < 0; rep and power are the decoder's stage taps (mi_lte.h: "PHICH, 3GPP mode")"""
+    _fields_ = [("metric", C.c_float), ("power", C.c_float), ("rep", C.c_float * 3), ("hi", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PHICH_NO_POWER, PHICH_UNKNOWN_CELL, PHICH_N_SEQ = 1, 2, 8
+
+
+class Pcfich(C.Structure):
+    """mi_lte_pcfich: LIBLTE_PHY_PCFICH_STRUCT as mi_lte_pdcch_channel_encode reads (cfi) and writes (N_reg, k, n) it"""
+    _fields_ = [("n", C.c_float * 4), ("k", C.c_uint32 * 4), ("cfi", C.c_uint32), ("N_reg", C.c_uint32)]
+
+
+class Phich(C.Structure):
+    """mi_lte_phich: LIBLTE_PHY_PHICH_STRUCT; present[m][n] / b[m][n]: indicator n of group m is sent / its value (1 = ACK)"""
+    _fields_ = [("z_re", C.c_float * 3), ("z_im", C.c_float * 3), ("k", C.c_uint32 * 75), ("N_reg", C.c_uint32), ("b", (C.c_uint8 * 8) * 25),
+                ("present", (C.c_uint8 * 8) * 25)]
+
+
+def phich_n_group(n_rb_dl, phich_res):
+    """mi_lte_phich_n_group (host arithmetic): ceil(N_g N_rb_dl / 8); 0 for a non-standard bandwidth or an N_g outside (0, 2]."""
+    return int(load_library().mi_lte_phich_n_group(n_rb_dl, float(phich_res)))
+
+
+def phich_resource(i_prb_ra_lowest, n_dmrs, n_group, i_phich=0):
+    """mi_lte_phich_resource (host arithmetic, 36.213 9.1.2 with N_SF = 4): (n_group, n_seq) of the PHICH that answers a PUSCH."""
+    g, s = C.c_uint32(), C.c_uint32()
+    rc = load_library().mi_lte_phich_resource(i_prb_ra_lowest, n_dmrs, n_group, i_phich, C.byref(g), C.byref(s))
+    if rc != 0:
+        raise MiLteError("mi_lte_phich_resource(%d, %d, %d, %d) failed: %d" % (i_prb_ra_lowest, n_dmrs, n_group, i_phich, rc), rc)
+    return g.value, s.value
+
+
+def phich_re_table(n_rb_dl, n_id_cell, phich_res):
+    """mi_lte_phich_re_table (host arithmetic): uint32 [N_group, 12], the sub-carrier in symbol 0 of RE(4 i + j) of every group of a cell."""
+    n, re = C.c_uint32(), np.zeros(25 * 12, np.uint32)
+    rc = load_library().mi_lte_phich_re_table(n_rb_dl, n_id_cell, float(phich_res), C.byref(n), re)
+    if rc != 0:
+        raise MiLteError("mi_lte_phich_re_table(%d, %d, %g) failed: %d" % (n_rb_dl, n_id_cell, phich_res, rc), rc)
+    return re[:12 * n.value].reshape(n.value, 12).copy()
+
+
 HARQ_NONE, HARQ_NEW_DATA = 0xFFFFFFFF, 1
 DEMAP_REF, DEMAP_MAXLOG = 0, 1  # mi_lte_pdsch_plan_set_demapper, mi_lte_pusch_plan_set_demapper (3GPP plans)
 DEMAP_AUTO_T = 16               # MI_LTE_DEMAP_AUTO_T
@@ -489,6 +532,17 @@ def load_library():
     L.mi_lte_pucch2_encode.argtypes = [u32, vp, vp]
     L.mi_lte_pucch2_modulate.argtypes = [C.POINTER(Pucch2Tab), u32, vp, vp, vp, vp]
     L.mi_lte_pucch2_decode_run.argtypes = [vp, u32, vp, u32, C.POINTER(Pucch2Res), u32, C.POINTER(Pucch2Tab), u32, vp]
+    L.mi_lte_pdcch_channel_encode.argtypes = [vp, u32, u32, u32, u32, u32, C.POINTER(Pcfich), C.POINTER(Phich), C.POINTER(TxAlloc), u32, C.POINTER(u32), u32, u32, u32, u32,
+                                              f32p, f32p]
+    L.mi_lte_phich_n_group.argtypes = [u32, C.c_float]
+    L.mi_lte_phich_n_group.restype = u32
+    L.mi_lte_phich_resource.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
+    L.mi_lte_phich_re_table.argtypes = [u32, u32, C.c_float, C.POINTER(u32), u32p]
+    L.mi_lte_phich_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.c_float, u32, u32, u32p, u32, C.POINTER(vp)]
+    L.mi_lte_phich_plan_destroy.argtypes = [vp, vp]
+    L.mi_lte_phich_plan_n_group.argtypes = [vp]
+    L.mi_lte_phich_plan_n_group.restype = u32
+    L.mi_lte_phich_decode_run.argtypes = [vp, vp, vp, vp, vp, u32, vp]
     L.mi_lte_coarse_timing_samples.argtypes = [u32, u32]
     L.mi_lte_coarse_timing_samples.restype = C.c_size_t
     L.mi_lte_coarse_timing_run.argtypes = [vp, C.POINTER(DlCfg), vp, vp, C.c_uint64, u32, C.POINTER(CoarseTiming)]
@@ -1118,6 +1172,43 @@ class PdcchPlan:
             self.h = None
 
 
+class PhichPlan:
+    """mi_lte_phich_plan: the PHICH resource elements of the listed cells (include/mi_lte.h: "PHICH, 3GPP mode"); n_group groups of eight
+    sequences per subframe."""
+
+    def __init__(self, ctx, cfg, cells, phich_res=1.0, phich_dur_extended=0):
+        self.ctx = ctx
+        h = C.c_void_p()
+        cells = np.ascontiguousarray(cells, np.uint32)
+        ctx._check(ctx.L.mi_lte_phich_plan_create(ctx.h, C.byref(cfg), float(phich_res), int(phich_dur_extended), 0, cells, len(cells), C.byref(h)))
+        self.h = h
+        self.n_group = int(ctx.L.mi_lte_phich_plan_n_group(h))
+
+    def out_bytes(self, n_units):
+        return C.sizeof(PhichResult) * n_units * self.n_group * PHICH_N_SEQ
+
+    def decode_dev(self, d_subframes, d_sf, d_cell, n_units, d_out=None):
+        """mi_lte_phich_decode_run: every group and sequence of n_units device subframes.  With d_out (device memory, out_bytes(n_units))
+        the call queues the kernel and returns None; without, it returns the records as a numpy record array [n_units, n_group, 8] with
+        PhichResult's fields."""
+        own = d_out is None
+        if own:
+            d_out = self.ctx.alloc(self.out_bytes(max(n_units, 1)))
+        try:
+            self.ctx._check(self.ctx.L.mi_lte_phich_decode_run(self.ctx.h, self.h, d_subframes.ptr, d_sf.ptr, d_cell.ptr, n_units, d_out.ptr))
+            if not own:
+                return None
+            return d_out.download(np.uint8, self.out_bytes(n_units)).view(np.dtype(PhichResult)).reshape(n_units, self.n_group, PHICH_N_SEQ)
+        finally:
+            if own:
+                d_out.free()
+
+    def close(self):
+        if self.h:
+            self.ctx.L.mi_lte_phich_plan_destroy(self.ctx.h, self.h)
+            self.h = None
+
+
 class PdcchSearchPlan:
     """mi_lte_pdcch_search_plan: the blind search over the whole control region (include/mi_lte.h: "PDCCH, 3GPP mode") for the listed cells
     and DCI sizes; the RNTI set is exactly what set_rntis was given last (empty at first)."""
@@ -1226,6 +1317,24 @@ class Transmitter:
                     t.prb[s][i] = a.prb[s][i]
         re, im = self._g()
         self._ok(self.L.mi_lte_pdsch_channel_encode(self.h, self.n_rb, 12, arr, len(allocs), n_pdcch_symbs, self.cell, self.n_ant, subfr_num, re, im), "mi_lte_pdsch_channel_encode")
+
+    def control(self, subfr_num, cfi, n_group_phich, phich_present=None, phich_b=None, dcis=(), n_rb_ul=None):
+        """mi_lte_pdcch_channel_encode: the PCFICH, n_group_phich PHICH groups (phich_present / phich_b: uint8 [n_group, 8], which indicators
+        are sent and their values, 1 = ACK) and one DCI per TxAlloc of dcis (format 1A for chan_type 0, format 0 for uplink grants) written
+        into the grid.  Returns (Pcfich, Phich, N_pdcch_symbs) as the call leaves them."""
+        pc, ph, n_symbs = Pcfich(), Phich(), C.c_uint32(0)
+        pc.cfi = cfi
+        for name, src in (("present", phich_present), ("b", phich_b)):
+            if src is not None:
+                src = np.asarray(src, np.uint8)
+                for g in range(min(n_group_phich, 25)):
+                    for s in range(8):
+                        getattr(ph, name)[g][s] = int(src[g][s])
+        arr = (TxAlloc * max(len(dcis), 1))(*dcis)
+        re, im = self._g()
+        self._ok(self.L.mi_lte_pdcch_channel_encode(self.h, self.n_rb, self.n_rb if n_rb_ul is None else n_rb_ul, 12, n_group_phich, 4, C.byref(pc), C.byref(ph), arr,
+                                                    len(dcis), C.byref(n_symbs), self.cell, self.n_ant, 0, subfr_num, re, im), "mi_lte_pdcch_channel_encode")
+        return pc, ph, n_symbs.value
 
     def samples(self, ant=0):
         """OFDM modulation of the grid's 14 symbols: (i, q) float32 of one subframe."""
@@ -1505,6 +1614,10 @@ class Context:
 
     def pdcch_plan(self, cfg, cells, phich_res=1.0, per_port_estimates=False):
         return PdcchPlan(self, cfg, cells, phich_res, 0, per_port_estimates)
+
+    def phich_plan(self, cfg, cells, phich_res=1.0):
+        """The PHICH decoder for the listed cells: PhichPlan.decode_dev gives metric, hi and the stage taps of every (group, sequence)."""
+        return PhichPlan(self, cfg, cells, phich_res, 0)
 
     def pdcch_search_plan(self, cfg, cells, sizes, rntis=(), phich_res=1.0, any_cce=False):
         """The blind PDCCH search: every CCE-aligned candidate at L = 8, 4, 2, 1 against each of the DCI `sizes` (bits), hits reported for the
