@@ -848,6 +848,57 @@ int mi_lte_pusch_plan_llr_noise(const mi_lte_pusch_plan *plan, const float **d_s
 int mi_lte_pusch_plan_set_rx_antennas(mi_lte_pusch_plan *plan, uint32_t n_rx, uint32_t ant_stride);
 int mi_lte_pusch_plan_rx_antennas(const mi_lte_pusch_plan *plan, uint32_t *n_rx, uint32_t *ant_stride);
 
+/* ---------------------------------------------------------------- PUSCH, 3GPP mode: MMSE equalisation
+ * The sections above equalise with one zero-forcing tap per sub-carrier.  After it and the 1 / sqrt(M) inverse DFT every sample of symbol s
+ * carries noise sigma^2 / rho_s, rho_s the harmonic mean of the channel power: on a channel that is flat over the allocation that is the
+ * best there is, on one with delay spread a single faded sub-carrier sets the noise of all M samples.  A MAXLOG run with the noise gain on
+ * can equalise with the MMSE tap instead, which weighs every sub-carrier by its own signal-to-noise ratio.  The reference has no
+ * counterpart; this text is the contract and tests/pusch_mmse_model.py restates it in float64.
+ * Inputs (n_rx = 1, 2 or 4).  h_r(s)[i], y_r(s)[i] and P_s[i] = sum_r (Re h_r(s)[i]^2 + Im h_r(s)[i]^2) exactly as the combining section forms
+ *   them (n_rx = 1: P = Re h^2 + Im h^2, the float whose reciprocal is the zero-forcing hn); s2 = sigma2_a, the float of the noise section
+ *   including its mean over the antennas.  The units agree: the DMRS has unit modulus, so the least-squares products, and with them h,
+ *   carry the grid's noise variance.
+ * Equaliser, in float.  q_s[i] = 1.0f / (P_s[i] + s2); z_s[i] = (sum_r y_r(s)[i] conj(h_r(s)[i])) * q_s[i]: the numerator's sums are those of
+ *   the combining section, for n_rx = 1 the two two-product terms of the single-antenna equaliser.  x_s[k] is the pre-decoder's output for z
+ *   times (float)(1 / sqrt(M)).  It is biased -- E x = mu_s d for a sent symbol d -- and it is what mi_lte_pusch_plan_llr_symbols reports.
+ * Residual.  nu_s = (float)((sum_i (double)q_s[i]) * (double)s2 / M): the sum in double, in the rho pass's fixed order (each thread its own
+ *   i, i + THREADS, ..; the xor butterfly within the wavefront; the wavefronts' slots in ascending order; no atomics: two runs give
+ *   identical bytes).  nu_s is the mean-square error of x_s[k] for unit-energy symbols; the useful amplitude is mu_s = 1 - nu_s, and the
+ *   residual interference plus noise around mu_s d has variance nu_s (1 - nu_s).
+ * LLR.  With u = Re x or Im x: the max-log section's llr_axis with w = (1 - (double)nu_s) / (double)nu_s and t = (double)u / (double)nu_s,
+ *   i.e. w times the unbiased symbol u / (1 - nu_s): the natural-unit max-log LLR at the post-equaliser SINR w.  A nu_s that is not finite
+ *   or lies outside the open interval (0, 1) gives w = 0 and t = 0: the symbol's soft bits are 0.
+ * Gain.  An MMSE run needs the noise estimate: it runs only while the demapper is MAXLOG and mi_lte_pusch_plan_set_llr_noise has
+ *   scale > 0.  g_a = (float)scale -- the 1 / sigma^2 is already inside w -- and mi_lte_pusch_plan_llr_gain reports it;
+ *   v = clamp(rint(g_a L), -127, 127) as in the max-log section.  v is therefore `scale` times the natural LLR, the scale of a zero-forcing
+ *   noise-referenced run: HARQ transmissions equalised either way combine.  s2 = 0 or not finite: g_a = 0 and an all-zero allocation, by
+ *   the noise section's rule.
+ * Taps.  mi_lte_pusch_plan_llr_nu holds nu_s.  mi_lte_pusch_plan_llr_rho holds, on an MMSE run, (float)((double)s2 * w_s): the reliability
+ *   on zero forcing's scale (SINR = rho / sigma2), never below zero forcing's rho_s (the harmonic mean of P + s2 less s2 is at least that
+ *   of P).  mi_lte_pusch_plan_llr_noise and _llr_symbols as before.
+ * Consequences.  P the same on every sub-carrier: nu_s = s2 / (P + s2), w = P / s2 and t = x_zf P / s2 -- the zero-forcing noise-referenced
+ *   run's g (rho x, rho) in exact arithmetic.  s2 -> 0: z tends to the zero-forcing z and w s2 to rho_s.  An all-zero grid has s2 = 0 with
+ *   it: q is infinite, nu_s is not a number, w = 0 and every byte 0 (with P = 0 and s2 > 0: q = 1 / s2, nu_s = 1, w = 0).  A dead antenna
+ *   drops out of numerator and P as in the combining section.
+ * Kernel.  k_pusch_demod_llr_mmse, listed under that name: the launch of the noise-on run with the same n_rx -- k_pusch_demod_llr's
+ *   threads, S_par and dynamic LDS for n_rx = 1, k_pusch_demod_llr_rx's, with its S_par stepping and its fit, for n_rx = 2 and 4 -- and one
+ *   more barrier in front of the reliability pass, which needs s2.  A plan that never saw the setter, or is back at MI_LTE_EQ_ZF, launches
+ *   what it launched before with the arguments and LDS it had.
+ * Downstream.  Control information, the CQI decoder, the HARQ pool, the code blocks and the outputs take the bytes as they take any others.
+ * mi_lte_pusch_plan_set_equaliser: MI_LTE_EQ_ZF (the default) or MI_LTE_EQ_MMSE.  Refusals, the plan left as it was:
+ *   MI_LTE_ERR_INVALID_ARG for a NULL plan or an unknown mode; MI_LTE_ERR_UNSUPPORTED on a reference-mode plan, for any mode.  Accepted
+ *   whatever the plan's current demapper and noise setting, but a run or HARQ run with MMSE set while the demapper is MI_LTE_DEMAP_REF or the
+ *   noise scale is 0 launches nothing, returns MI_LTE_ERR_UNSUPPORTED and sets the context's error text; the plan runs again once either
+ *   setting is changed.  (No LDS condition of its own: mi_lte_pusch_plan_set_rx_antennas has refused what does not fit.)
+ * mi_lte_pusch_plan_equaliser: the plan's current mode.
+ * mi_lte_pusch_plan_llr_nu: tap, float [n_alloc][12], nu_s of the last MMSE run; device pointer owned by the plan, allocated when MMSE is
+ *   first set and zero until an MMSE run.  MI_LTE_ERR_INVALID_ARG on a reference-mode plan and while the plan never had MMSE set. */
+#define MI_LTE_EQ_ZF 0u
+#define MI_LTE_EQ_MMSE 1u
+int mi_lte_pusch_plan_set_equaliser(mi_lte_pusch_plan *plan, uint32_t mode);
+int mi_lte_pusch_plan_equaliser(const mi_lte_pusch_plan *plan, uint32_t *mode);
+int mi_lte_pusch_plan_llr_nu(const mi_lte_pusch_plan *plan, const float **d_nu);
+
 /* ---------------------------------------------------------------- PUSCH, 3GPP mode: HARQ soft combining
  * mi_lte_pusch_decode_run on a 3GPP plan with the allocations' soft bits combined into the pool's buffers.  The pool is the type of
  * "PDSCH, 3GPP mode: HARQ soft combining" above, and one pool of a context serves its PDSCH and PUSCH plans alike; the contract is that
@@ -1673,6 +1724,22 @@ int    mi_lte_synth_ul_units_3gpp_payload_i8(const mi_lte_dl_cfg *cfg, const mi_
                                              uint32_t n_alloc, const mi_lte_synth_channel *chan, const mi_lte_ulsch_uci *h_uci,
                                              const uint8_t *h_ack, const uint8_t *h_ri, const uint8_t *h_cqi, uint32_t h_cqi_stride,
                                              const uint8_t *h_payload, uint32_t tbs_stride, int8_t *h_iq);
+/* mi_lte_synth_ul_units_3gpp_payload_i8 (h_uci and its companions optional, as there) through a channel of several paths with integer
+ * delays.  Per unit the draws of gain, phase and delay are the existing ones in the existing order; after them one further phase phi_p is
+ * drawn per path p >= 1 (phi_0 is the existing phase).  The channel output is gain * sum_p a_p exp(i phi_p) t[i - dly - delay[p]], a_p the
+ * amplitudes normalised to sum a_p^2 = 1; AWGN is added as before, and the int8 scale is additionally divided by sum_p a_p so that nothing
+ * clips at chan->peak.  One path therefore writes mi_lte_synth_ul_units_3gpp_payload_i8's bytes, byte for byte.  MI_LTE_ERR_INVALID_ARG for a
+ * NULL paths, n_paths outside 1 .. 4, delay[0] != 0, an amplitude that is negative or not finite, sum amp^2 = 0. */
+typedef struct {
+    uint32_t n_paths;  /* 1 .. 4 */
+    uint32_t delay[4]; /* delay[0] = 0; delay[p] extra integer samples of path p */
+    double   amp[4];   /* relative amplitudes, normalised inside to sum amp^2 = 1 */
+} mi_lte_synth_paths;
+int    mi_lte_synth_ul_units_3gpp_paths_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units,
+                                           const uint32_t *h_subfr_num, const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs,
+                                           uint32_t n_alloc, const mi_lte_synth_channel *chan, const mi_lte_ulsch_uci *h_uci,
+                                           const uint8_t *h_ack, const uint8_t *h_ri, const uint8_t *h_cqi, uint32_t h_cqi_stride,
+                                           const uint8_t *h_payload, uint32_t tbs_stride, const mi_lte_synth_paths *paths, int8_t *h_iq);
 
 /* n_occ PRACH occasions (format 0-3 preambles per 36.211 5.7.2-5.7.3): preamble h_preamble_idx[o] of the cell's 64,
  * delayed by h_delay[o] samples, through a flat channel + AWGN; mi_lte_synth_prach_len() complex int8 samples each. */

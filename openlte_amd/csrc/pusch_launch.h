@@ -48,14 +48,15 @@ inline uint32_t pusch_rx_s_par(uint32_t n_rx, uint32_t M_max, uint32_t words_max
     return 0;
 }
 
-// The families of k_pusch_demod instantiations: <T, SPEC>, <T, true, PuschLlr>, <T, true, PuschLlrNoise>, <T, true, PuschLlrRx<n_rx, noise>>
-enum class PuschFamily { PLAIN, LLR, LLR_NOISE, LLR_RX };
+// The families of k_pusch_demod instantiations: <T, SPEC>, <T, true, PuschLlr>, <T, true, PuschLlrNoise>, <T, true, PuschLlrRx<n_rx, noise>>,
+// <T, true, PuschLlrMmse<n_rx>>
+enum class PuschFamily { PLAIN, LLR, LLR_NOISE, LLR_RX, LLR_MMSE };
 
 struct PuschLaunch {
     PuschFamily family;
     uint32_t    threads;   // the workgroup's width: 64 / 128 / 192 / 256, a combining launch's 192 or 256
-    uint32_t    n_rx;      // antennas combined: 2 or 4 for LLR_RX, 1 otherwise
-    bool        noise;     // the noise-referenced gain (LLR_NOISE, or LLR_RX's NOISE argument)
+    uint32_t    n_rx;      // antennas combined: 2 or 4 for LLR_RX, 1, 2 or 4 for LLR_MMSE, 1 otherwise
+    bool        noise;     // the noise-referenced gain (LLR_NOISE, LLR_RX's NOISE argument; LLR_MMSE always)
     uint32_t    S_par;
     size_t      lds_off;   // bytes in front of the LLR block, rounded up to 8 (PLAIN: unused, 0)
     size_t      lds_bytes; // the launch's dynamic LDS
@@ -66,8 +67,10 @@ struct PuschLaunch {
 // max-log demapper on a 3GPP plan; noise: llr_noise > 0 and n_rx: the antennas, both read for a max-log launch only; lds_limit: the
 // device's per-workgroup LDS, read for a combining launch only; threads_override: a validated MI_LTE_PUSCH_THREADS (0: none), which does
 // not reach a combining launch.  false: a combining launch that does not fit lds_limit at S_par = 1 (*out is not a launch then).
+// mmse: MMSE equalisation (mi_lte_pusch_plan_set_equaliser), read for a max-log launch with the noise gain on only -- the caller refuses an
+// MMSE run without either: the noise-on launch of the same n_rx under LLR_MMSE's family and label.
 inline bool pusch_launch_plan(uint32_t M_max, uint32_t words_max, bool maxlog, bool noise, uint32_t n_rx, size_t lds_limit, uint32_t threads_override,
-                              PuschLaunch *out)
+                              PuschLaunch *out, bool mmse = false)
 {
     // Workgroup size: the kernel's phases hold 3 M, M, 2 M, 12 M / R and 12 M items (M = 12 N_prb sub-carriers) between barriers, and the
     // heavy ones (atan2f, sincosf, the divisions) are the short ones -- a workgroup much wider than 3 M leaves whole wavefronts waiting at
@@ -82,12 +85,14 @@ inline bool pusch_launch_plan(uint32_t M_max, uint32_t words_max, bool maxlog, b
     if (n_rx <= 1) { // the same launch with the LLR block behind the scrambling words
         const size_t off = pusch_round8(pusch_lds(1, M_max, words_max, S_par));
         *out = {noise ? PuschFamily::LLR_NOISE : PuschFamily::LLR, threads, 1, noise, S_par, off, off + (noise ? LLR_NOISE_LDS_BYTES : LLR_LDS_BYTES), "k_pusch_demod_llr"};
+        if (mmse && noise) { out->family = PuschFamily::LLR_MMSE; out->label = "k_pusch_demod_llr_mmse"; } // LLR_NOISE's launch in every other field
         return true;
     }
     // combining: n_rx sets of estimate rows, S_par stepped down until the whole launch fits, the LLR block always the noise launch's
     const uint32_t S_rx = pusch_rx_s_par(n_rx, M_max, words_max, lds_limit);
     const size_t   off  = pusch_round8(pusch_lds(n_rx, M_max, words_max, S_rx ? S_rx : 1));
     *out = {PuschFamily::LLR_RX, M_max <= 96 ? 192u : 256u, n_rx, noise, S_rx, off, off + LLR_NOISE_LDS_BYTES, "k_pusch_demod_llr_rx"};
+    if (mmse && noise) { out->family = PuschFamily::LLR_MMSE; out->label = "k_pusch_demod_llr_mmse"; } // LLR_RX's launch in every other field, and its refusal
     return S_rx != 0;
 }
 

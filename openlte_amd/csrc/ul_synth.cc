@@ -96,9 +96,24 @@ struct UlUci { const mi_lte_ulsch_uci *uci; const uint8_t *ack, *ri, *cqi; uint3
 static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units, const uint32_t *h_subfr_num,
                           const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
                           const mi_lte_synth_channel *chan, int8_t *h_iq, uint8_t *h_tx_bits, uint32_t tbs_stride, bool spec, const UlUci *uu = nullptr,
-                          const uint8_t *h_payload = nullptr)
+                          const uint8_t *h_payload = nullptr, const mi_lte_synth_paths *paths = nullptr)
 {
     if (!cfg || !ul || !h_subfr_num || !h_n_id_cell || !h_allocs || !chan || !h_iq) return MI_LTE_ERR_INVALID_ARG;
+    // multipath (mi_lte_synth_ul_units_3gpp_paths_i8): the amplitudes normalised to sum a^2 = 1, and sum a, which the int8 scale is divided by
+    uint32_t n_paths = 1, p_dly[4] = {0, 0, 0, 0};
+    double   p_amp[4] = {1.0, 0.0, 0.0, 0.0}, a_sum = 1.0;
+    if (paths) {
+        if (paths->n_paths < 1 || paths->n_paths > 4 || paths->delay[0] != 0) return MI_LTE_ERR_INVALID_ARG;
+        double e = 0.0;
+        for (uint32_t p = 0; p < paths->n_paths; p++) {
+            if (!(paths->amp[p] >= 0.0) || !std::isfinite(paths->amp[p])) return MI_LTE_ERR_INVALID_ARG;
+            e += paths->amp[p] * paths->amp[p];
+        }
+        if (!(e > 0.0) || !std::isfinite(e)) return MI_LTE_ERR_INVALID_ARG;
+        n_paths = paths->n_paths;
+        a_sum   = 0.0;
+        for (uint32_t p = 0; p < n_paths; p++) { p_dly[p] = paths->delay[p]; p_amp[p] = n_paths == 1 ? 1.0 : paths->amp[p] / std::sqrt(e); a_sum += p_amp[p]; }
+    }
     if (uu && (!spec || !uu->uci || !uu->ack || !uu->ri)) return MI_LTE_ERR_INVALID_ARG;
     if (!synth::valid_grid(cfg->fft_size, cfg->N_rb_dl)) return MI_LTE_ERR_INVALID_ARG;
     auto valid = [&](const mi_lte_pdsch_alloc &al) {
@@ -236,6 +251,8 @@ static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uin
         const double   gain = chan->gain_min + (chan->gain_max - chan->gain_min) * rng.uniform();
         const double   ph   = 2.0 * M_PI * rng.uniform() - M_PI;
         const uint32_t dly  = (uint32_t)(rng.uniform() * (chan->max_delay + 0.999));
+        double p_ph[4] = {ph, 0.0, 0.0, 0.0}; // one further phase per path behind the first, drawn behind the existing three
+        for (uint32_t p = 1; p < n_paths; p++) p_ph[p] = 2.0 * M_PI * rng.uniform() - M_PI;
         double p_sig = 0, peak = 0;
         for (size_t i = 0; i < unit_len; i++) {
             p_sig += t_re[i] * t_re[i] + t_im[i] * t_im[i];
@@ -244,13 +261,21 @@ static int synth_ul_units(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uin
         p_sig /= (double)unit_len;
         const double scale = (peak > 0 ? chan->peak / peak : 1.0);
         const double sigma = chan->snr_db >= 200 ? 0.0 : std::sqrt(p_sig / std::pow(10.0, chan->snr_db / 10.0) / 2.0);
-        const double hr = gain * std::cos(ph), hi = gain * std::sin(ph);
+        const double hr = gain * p_amp[0] * std::cos(ph), hi = gain * p_amp[0] * std::sin(ph); // (p_amp[0] = 1.0 for one path: the same doubles)
         int8_t *o = h_iq + (size_t)u * unit_len * 2;
         for (size_t i = 0; i < unit_len; i++) {
             double sr = 0, si = 0;
             if (i >= dly) { sr = t_re[i - dly]; si = t_im[i - dly]; }
-            const double yr = hr * sr - hi * si + sigma * rng.normal(), yi = hr * si + hi * sr + sigma * rng.normal();
-            const long qr = std::lround(yr * scale / std::max(1.0, chan->gain_max)), qi = std::lround(yi * scale / std::max(1.0, chan->gain_max));
+            double cr = hr * sr - hi * si, ci = hr * si + hi * sr; // the first path: the flat channel's two terms
+            for (uint32_t p = 1; p < n_paths; p++) {
+                const size_t d = (size_t)dly + p_dly[p];
+                if (i < d) continue;
+                const double gr = gain * p_amp[p] * std::cos(p_ph[p]), gi = gain * p_amp[p] * std::sin(p_ph[p]);
+                cr += gr * t_re[i - d] - gi * t_im[i - d];
+                ci += gr * t_im[i - d] + gi * t_re[i - d];
+            }
+            const double yr = cr + sigma * rng.normal(), yi = ci + sigma * rng.normal();
+            const long qr = std::lround(yr * scale / std::max(1.0, chan->gain_max) / a_sum), qi = std::lround(yi * scale / std::max(1.0, chan->gain_max) / a_sum);
             o[2 * i]     = (int8_t)std::max(-127L, std::min(127L, qr));
             o[2 * i + 1] = (int8_t)std::max(-127L, std::min(127L, qi));
         }
@@ -292,6 +317,17 @@ int mi_lte_synth_ul_units_3gpp_payload_i8(const mi_lte_dl_cfg *cfg, const mi_lte
     const UlUci uu = {h_uci, h_ack, h_ri, h_cqi, h_cqi_stride};
     if (!h_payload) return MI_LTE_ERR_INVALID_ARG;
     return synth_ul_units(cfg, ul, n_units, h_subfr_num, h_n_id_cell, h_allocs, n_alloc, chan, h_iq, nullptr, tbs_stride, true, h_uci ? &uu : nullptr, h_payload);
+}
+
+int mi_lte_synth_ul_units_3gpp_paths_i8(const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, uint32_t n_units, const uint32_t *h_subfr_num,
+                                        const uint32_t *h_n_id_cell, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
+                                        const mi_lte_synth_channel *chan, const mi_lte_ulsch_uci *h_uci, const uint8_t *h_ack, const uint8_t *h_ri,
+                                        const uint8_t *h_cqi, uint32_t h_cqi_stride, const uint8_t *h_payload, uint32_t tbs_stride,
+                                        const mi_lte_synth_paths *paths, int8_t *h_iq)
+{
+    const UlUci uu = {h_uci, h_ack, h_ri, h_cqi, h_cqi_stride};
+    if (!h_payload || !paths) return MI_LTE_ERR_INVALID_ARG;
+    return synth_ul_units(cfg, ul, n_units, h_subfr_num, h_n_id_cell, h_allocs, n_alloc, chan, h_iq, nullptr, tbs_stride, true, h_uci ? &uu : nullptr, h_payload, paths);
 }
 
 // ---- PRACH (36.211 5.7.2-5.7.3): preamble v of root u is x_u((n + C_v) mod 839); its 839-point DFT sits on the PRACH

@@ -244,6 +244,21 @@ struct PuschLlrRx : PuschLlrNoise {
 };
 template <typename T> struct RxOf { static constexpr uint32_t N = 1; static constexpr bool NOISE = false; };
 template <uint32_t N_, bool NOISE_> struct RxOf<PuschLlrRx<N_, NOISE_>> { static constexpr uint32_t N = N_; static constexpr bool NOISE = NOISE_; };
+// MMSE equalisation (mi_lte_pusch_plan_set_equaliser, include/mi_lte.h "PUSCH, 3GPP mode: MMSE equalisation") is the last family,
+// k_pusch_demod<THREADS, true, PuschLlrMmse<N_RX>> (launched and listed as k_pusch_demod_llr_mmse), N_RX = 1, 2 or 4: the noise pass's sums
+// are reduced behind a barrier of its own, so that sigma2 exists before the reliability pass; that pass sums q = 1 / (P + sigma2) in place of
+// hn = 1 / P and its twelve finishing threads form nu_s = sigma2 mean(q), w_s = (1 - nu_s) / nu_s and the two taps; the equaliser item
+// multiplies by q; the de-mapper takes t = x / nu_s and w_s, and the gain is the noise setter's scale.  The LDS is the noise launch's:
+// nu_s lies in rho's twelve floats and w_s in wsum's first twelve doubles, which their finishing threads have read by then.  The argument
+// block is PuschLlrNoise's plus the nu tap and, for N_RX > 1, the antenna stride.  Every other instantiation has MMSE = false and each
+// `if constexpr (MMSE)` drops out of it.
+template <uint32_t N>
+struct PuschLlrMmse : PuschLlrNoise {
+    float   *nu_out;     // [n_alloc][12]: the nu tap
+    uint32_t ant_stride; // as PuschLlrRx's; unused for N = 1
+};
+template <typename T> struct MmseOf { static constexpr bool ON = false; static constexpr uint32_t N = 1; };
+template <uint32_t N_> struct MmseOf<PuschLlrMmse<N_>> { static constexpr bool ON = true; static constexpr uint32_t N = N_; };
 
 // h(s) of data symbol sp (0 .. 5) of a slot and hn = 1 / |h|^2 as the one-tap equaliser uses it, from the slot's DMRS estimate: magnitude and
 // slope, u = exp(i ang_b), f1 .. f3 = exp(i n f_ang) for n = 1, 2, 3 (liblte_phy.cc:13770-13780: symbols 0-2 / 3-5 of a slot lie -3..-1 /
@@ -263,6 +278,7 @@ __device__ __forceinline__ PuschNoLlr llr_args() { return PuschNoLlr{}; }
 __device__ __forceinline__ const PuschLlr &llr_args(const PuschLlr &la) { return la; }
 __device__ __forceinline__ const PuschLlrNoise &llr_args(const PuschLlrNoise &la) { return la; }
 template <uint32_t N, bool NOISE_> __device__ __forceinline__ const PuschLlrRx<N, NOISE_> &llr_args(const PuschLlrRx<N, NOISE_> &la) { return la; }
+template <uint32_t N> __device__ __forceinline__ const PuschLlrMmse<N> &llr_args(const PuschLlrMmse<N> &la) { return la; }
 #ifndef WPE_LLR
 #define WPE_LLR 4
 #endif
@@ -270,15 +286,16 @@ template <uint32_t N, bool NOISE_> __device__ __forceinline__ const PuschLlrRx<N
 template <uint32_t THREADS, bool SPEC = false, typename... LlrArgs>
 // (four antennas: the equaliser item carries four sets of estimates and grid values for six symbols, and the LDS of such a launch keeps the
 // occupancy under 4 from 10 PRB on anyway -- 3 waves per SIMD, 168 registers, in place of a spill)
-__attribute__((amdgpu_waves_per_eu((RxOf<LlrArgs>::N * ... * 1u) == 4 ? 3 : sizeof...(LlrArgs) ? WPE_LLR : WPE, 8)))
+__attribute__((amdgpu_waves_per_eu((RxOf<LlrArgs>::N * ... * 1u) * (MmseOf<LlrArgs>::N * ... * 1u) == 4 ? 3 : sizeof...(LlrArgs) ? WPE_LLR : WPE, 8)))
 __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict__ subframes, uint32_t sf_stride,
                                                      const mi_lte_pdsch_alloc *__restrict__ allocs, const PuschDesc *__restrict__ desc,
                                                      const float *__restrict__ dmrs_pool, GoldTables gt, int8_t *__restrict__ e_base,
                                                      const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len, uint32_t M_max,
                                                      uint32_t S_par, float r_S_par, const PuschShape *__restrict__ shapes, LlrArgs... la_pack)
 {
-    constexpr bool LLR = sizeof...(LlrArgs) == 1, NOISE = (std::is_same<LlrArgs, PuschLlrNoise>::value || ...) || (RxOf<LlrArgs>::NOISE || ...);
-    constexpr uint32_t N_RX = (RxOf<LlrArgs>::N * ... * 1u); // receive antennas combined (PuschLlrRx); 1 everywhere else
+    constexpr bool MMSE = (MmseOf<LlrArgs>::ON || ...); // MMSE equalisation (PuschLlrMmse); false everywhere else
+    constexpr bool LLR = sizeof...(LlrArgs) == 1, NOISE = (std::is_same<LlrArgs, PuschLlrNoise>::value || ...) || (RxOf<LlrArgs>::NOISE || ...) || MMSE;
+    constexpr uint32_t N_RX = (RxOf<LlrArgs>::N * ... * 1u) * (MmseOf<LlrArgs>::N * ... * 1u); // receive antennas combined (PuschLlrRx, PuschLlrMmse); 1 everywhere else
     static_assert(sizeof...(LlrArgs) <= 1 && (!LLR || SPEC), "the max-log de-mapper belongs to the 3GPP mode");
     [[maybe_unused]] const auto la = llr_args(la_pack...);
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -364,6 +381,8 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
     // then the wavefronts' LDS slots in ascending order.  No atomics: two runs give the same bytes.
     [[maybe_unused]] const float *rho = nullptr;
     [[maybe_unused]] double       gd  = 0.0;
+    [[maybe_unused]] float         s2_m = 0.0f;     // MMSE: sigma2, in every thread, from the reliability pass on
+    [[maybe_unused]] const double *w_m  = nullptr; // MMSE: w_s of the twelve symbols
     if constexpr (LLR) {
         double *wsum  = reinterpret_cast<double *>(sm + la.lds_off); // [THREADS / 64][12]
         float  *rho_w = reinterpret_cast<float *>(wsum + 4 * 12);
@@ -393,6 +412,13 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
             for (int o = 32; o; o >>= 1) part += __shfl_xor(part, o);
             if ((threadIdx.x & 63u) == 0) nsum[threadIdx.x >> 6] = part;
         }
+        if constexpr (MMSE) { // sigma2 before the reliability pass, which adds it to every P: the noise section's sum and quotient, in every thread
+            __syncthreads();
+            double S = nsum[0];
+            for (uint32_t w = 1; w < THREADS / 64; w++) S += nsum[w];
+            if constexpr (N_RX > 1) s2_m = (float)(S / (120.0 * (double)N_prb * (double)N_RX));
+            else s2_m = (float)(S / (120.0 * (double)N_prb));
+        }
         for (uint32_t b = 0; b < 2; b++) { // slot: six data symbols per pass, so a thread carries six partial sums
             double part[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             for (uint32_t i = threadIdx.x; i < M; i += THREADS) {
@@ -412,7 +438,10 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
                         }
                     }
 #pragma unroll
-                    for (uint32_t sp = 0; sp < 6; sp++) part[sp] += (double)(1.0f / P[sp]);
+                    for (uint32_t sp = 0; sp < 6; sp++) {
+                        if constexpr (MMSE) part[sp] += (double)(1.0f / (P[sp] + s2_m));
+                        else part[sp] += (double)(1.0f / P[sp]);
+                    }
                     continue;
                 }
                 const float    mag = est[b * M_max + i], f_mag = est[2 * M_max + i];
@@ -422,7 +451,8 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
                 for (uint32_t sp = 0; sp < 6; sp++) {
                     float h_re, h_im, hn;
                     slot_h(mag, f_mag, u, f1, f2, f3, sp, h_re, h_im, hn);
-                    part[sp] += (double)hn;
+                    if constexpr (MMSE) part[sp] += (double)(1.0f / ((h_re * h_re + h_im * h_im) + s2_m));
+                    else part[sp] += (double)hn;
                 }
             }
 #pragma unroll
@@ -435,16 +465,30 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
         if (threadIdx.x < 12) {
             double sum = wsum[threadIdx.x];
             for (uint32_t w = 1; w < THREADS / 64; w++) sum += wsum[w * 12 + threadIdx.x];
+            if constexpr (MMSE) { // nu_s, w_s and the taps; rho's float holds nu_s (0: no information) and wsum's column head, read above, w_s
+                const float  nu = (float)(sum * (double)s2_m / (double)M);
+                const bool   ok = nu > 0.0f && nu < 1.0f; // (false for a NaN)
+                const double w  = ok ? (1.0 - (double)nu) / (double)nu : 0.0;
+                rho_w[threadIdx.x] = ok ? nu : 0.0f;
+                wsum[threadIdx.x]  = w;
+                la.nu_out[a_idx * 12 + threadIdx.x]  = nu;
+                la.rho_out[a_idx * 12 + threadIdx.x] = (float)((double)s2_m * w);
+            } else {
             const float r = (float)((double)M / sum);
             // an infinite or NaN hn makes the sum infinite or NaN; a zero sum the quotient: rho_s = 0 in each case
             const float r_ok = (fabs(sum) <= 1.7976931348623157e308 && fabsf(r) <= 3.4028234e38f) ? r : 0.0f;
             rho_w[threadIdx.x] = r_ok;
             la.rho_out[a_idx * 12 + threadIdx.x] = r_ok;
+            }
         }
         __syncthreads();
         rho = rho_w;
         gd  = (double)la.gain;
-        if constexpr (NOISE) { // every thread forms the same sum in the same order
+        if constexpr (MMSE) { // g_a = scale: the 1 / sigma2 is inside w_s.  sigma2 0 or not finite: every soft bit 0
+            w_m = wsum;
+            gd  = (s2_m > 0.0f && s2_m <= 3.4028234e38f) ? (double)la.noise : 0.0;
+            if (threadIdx.x == 0) la.s2_out[a_idx] = s2_m;
+        } else if constexpr (NOISE) { // every thread forms the same sum in the same order
             double S = nsum[0];
             for (uint32_t w = 1; w < THREADS / 64; w++) S += nsum[w];
             float s2;
@@ -499,7 +543,7 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
 #pragma unroll
                 for (uint32_t sp = 0; sp < 6; sp++) {
                     if (sp < sp0 || sp >= sp1) continue; // uniform
-                    const float hn = 1.0f / P[sp];
+                    const float hn = MMSE ? 1.0f / (P[sp] + s2_m) : 1.0f / P[sp];
                     dst[sp * M_max] = make_float2(c_re[sp] * hn, c_im[sp] * hn);
                 }
                 continue;
@@ -518,6 +562,7 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
                 float          h_re, h_im, hn;
                 slot_h(mag, f_mag, u, f1, f2, f3, sp, h_re, h_im, hn);
                 const float  zr = z_re[l * N_SC_MAX], zi = z_im[l * N_SC_MAX];
+                if constexpr (MMSE) hn = 1.0f / ((h_re * h_re + h_im * h_im) + s2_m); // q in place of hn
                 dst[sp * M_max] = make_float2((zr * h_re + zi * h_im) * hn, (zi * h_re - zr * h_im) * hn);
             }
         }
@@ -552,10 +597,16 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
             if constexpr (LLR) { // t = rho_s x, w = rho_s; bit 2k on the real axis, 2k + 1 on the imaginary
                 const float xr = scale * x.x, xi = scale * x.y;
                 if (la.x_tap) la.x_tap[la.x_off[a_idx] + __umul24(s, M) + k] = make_float2(xr, xi);
-                const double w = (double)rho[s];
                 double       li[3] = {0.0, 0.0, 0.0}, lq[3] = {0.0, 0.0, 0.0};
+                if constexpr (MMSE) { // t = u / nu_s, w = (1 - nu_s) / nu_s; both 0 where nu_s carries no information
+                    const double nu = (double)rho[s], w = w_m[s];
+                    llr_axis<(MOD < 1 ? 1u : MOD)>(nu > 0.0 ? (double)xr / nu : 0.0, w, li);
+                    llr_axis<(MOD < 1 ? 1u : MOD)>(nu > 0.0 ? (double)xi / nu : 0.0, w, lq);
+                } else {
+                const double w = (double)rho[s];
                 llr_axis<(MOD < 1 ? 1u : MOD)>(w * (double)xr, w, li);
                 llr_axis<(MOD < 1 ? 1u : MOD)>(w * (double)xi, w, lq);
+                }
 #pragma unroll
                 for (uint32_t q = 0; q < QM; q += 2) { b[q] = (int8_t)llr_byte(gd, li[q >> 1]); b[q + 1] = (int8_t)llr_byte(gd, lq[q >> 1]); }
             } else
@@ -697,6 +748,10 @@ struct mi_lte_pusch_plan {
     // mi_lte_pusch_plan_set_rx_antennas: antennas a MAXLOG run combines (1: off) and the subframes between two antennas' grids of one unit;
     // the instantiations of k_pusch_demod_llr_rx whose dynamic-LDS attribute is set on the plan's device (one bit each)
     uint32_t      n_units = 0, n_rx = 1, ant_stride = 0, rx_lds_set = 0;
+    // mi_lte_pusch_plan_set_equaliser: the equaliser of a MAXLOG run with the noise gain on, and the last MMSE run's nu [n_alloc][12]
+    // (nothing of it exists until MMSE is first set)
+    uint32_t      eq = MI_LTE_EQ_ZF;
+    float        *d_llr_nu = nullptr;
 };
 
 // UL-SCH rate matching has no soft-buffer limit (36.212 5.2.2.5: N_cb = K_w).  As a DL-SCH soft-buffer configuration: an N_IR no block reaches
@@ -1021,6 +1076,35 @@ int mi_lte_pusch_plan_rx_antennas(const mi_lte_pusch_plan *pl, uint32_t *n_rx, u
     return MI_LTE_OK;
 }
 
+int mi_lte_pusch_plan_set_equaliser(mi_lte_pusch_plan *pl, uint32_t mode)
+{
+    if (!pl || mode > MI_LTE_EQ_MMSE) return MI_LTE_ERR_INVALID_ARG;
+    if (!pl->g3) return MI_LTE_ERR_UNSUPPORTED; // a reference-mode plan keeps the reference's equaliser
+    if (mode == MI_LTE_EQ_MMSE && !pl->d_llr_nu) { // the nu tap, zeros until an MMSE run
+        const size_t bytes = sizeof(float) * 12 * (size_t)pl->core.n_alloc;
+        float       *nu = nullptr;
+        if (hipSetDevice(pl->device) != hipSuccess || hipMalloc((void **)&nu, bytes) != hipSuccess) return MI_LTE_ERR_HIP;
+        if (hipMemset(nu, 0, bytes) != hipSuccess) { (void)hipFree(nu); return MI_LTE_ERR_HIP; }
+        pl->d_llr_nu = nu;
+    }
+    pl->eq = mode;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_equaliser(const mi_lte_pusch_plan *pl, uint32_t *mode)
+{
+    if (!pl || !mode) return MI_LTE_ERR_INVALID_ARG;
+    *mode = pl->eq;
+    return MI_LTE_OK;
+}
+
+int mi_lte_pusch_plan_llr_nu(const mi_lte_pusch_plan *pl, const float **d_nu)
+{
+    if (!pl || !d_nu || !pl->d_llr_nu) return MI_LTE_ERR_INVALID_ARG;
+    *d_nu = pl->d_llr_nu;
+    return MI_LTE_OK;
+}
+
 int mi_lte_pusch_plan_set_llr_tap(mi_lte_pusch_plan *pl, uint32_t on)
 {
     if (!pl || !pl->g3) return MI_LTE_ERR_INVALID_ARG;
@@ -1088,6 +1172,7 @@ void mi_lte_pusch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl)
     (void)hipFree(pl->d_llr_gain);
     (void)hipFree(pl->d_llr_x);
     (void)hipFree(pl->d_x_off);
+    (void)hipFree(pl->d_llr_nu);
     mi_dlsch3_free(pl->g3);
     mi_ulsch_uci_free(pl->uci);
     delete pl;
@@ -1113,19 +1198,19 @@ template <typename F> static int pusch_width(uint32_t threads, F f)
 }
 
 // The demodulator's launch as L shapes it, k_pusch_demod<T, SPEC, Llr...>: Llr is the kernel's own trailing pack, nothing or the family's
-// argument block (PuschLlr, PuschLlrNoise, PuschLlrRx<N, NZ>).  lds_limit: the device's per-workgroup LDS, read for a combining launch only.
+// argument block (PuschLlr, PuschLlrNoise, PuschLlrRx<N, NZ>, PuschLlrMmse<N>).  lds_limit: the device's per-workgroup LDS, read for a combining launch only.
 template <uint32_t T, bool SPEC, typename... Llr>
 static int pusch_launch(PuschWidth<T>, std::bool_constant<SPEC>, mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const PuschLaunch &L, size_t lds_limit,
                         const float *d_subframes, const Llr &...la_pack)
 {
-    [[maybe_unused]] constexpr uint32_t N  = (RxOf<Llr>::N * ... * 1u);
-    [[maybe_unused]] constexpr bool     NZ = (RxOf<Llr>::NOISE || ...);
+    [[maybe_unused]] constexpr uint32_t N  = (RxOf<Llr>::N * ... * 1u) * (MmseOf<Llr>::N * ... * 1u);
+    [[maybe_unused]] constexpr bool     NZ = (RxOf<Llr>::NOISE || ...), MM = (MmseOf<Llr>::ON || ...);
     if constexpr (N > 1) {
         // More than 64 KB of dynamic LDS has to be asked for, per kernel and device (as bcjr.hip does for k_bcjr_block): once per plan and
         // instantiation
-        const uint32_t bit = 1u << ((T == 256 ? 1 : 0) + (N == 4 ? 2 : 0) + (NZ ? 4 : 0));
+        const uint32_t bit = 1u << ((T == 256 ? 1 : 0) + (N == 4 ? 2 : 0) + (NZ ? 4 : 0) + (MM ? 8 : 0));
         if (!(pl->rx_lds_set & bit)) {
-            MI_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k_pusch_demod<T, true, PuschLlrRx<N, NZ>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
+            MI_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k_pusch_demod<T, true, Llr...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
             pl->rx_lds_set |= bit;
         }
     }
@@ -1151,6 +1236,11 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
         ctx->err = "receive-antenna combining needs the max-log demapper (mi_lte_pusch_plan_set_demapper, MI_LTE_DEMAP_MAXLOG)";
         return MI_LTE_ERR_UNSUPPORTED;
     }
+    const bool mmse = pl->eq == MI_LTE_EQ_MMSE;
+    if (mmse && (pl->demap != MI_LTE_DEMAP_MAXLOG || !(pl->llr_noise > 0.0f))) { // (mi_lte_pusch_plan_set_equaliser: changing either setting makes the plan runnable again)
+        ctx->err = "MMSE equalisation needs the max-log demapper and the noise-referenced gain (mi_lte_pusch_plan_set_demapper, mi_lte_pusch_plan_set_llr_noise)";
+        return MI_LTE_ERR_UNSUPPORTED;
+    }
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     rc = mi_ctx_gold_tables(ctx);
     if (rc != MI_LTE_OK) return rc;
@@ -1174,7 +1264,7 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
         lds_limit = (size_t)std::max(limit, 0);
     }
     PuschLaunch L;
-    if (!pusch_launch_plan(pl->M_max, pl->words_max, llr, pl->llr_noise > 0.0f, pl->n_rx, lds_limit, threads_override, &L)) {
+    if (!pusch_launch_plan(pl->M_max, pl->words_max, llr, pl->llr_noise > 0.0f, pl->n_rx, lds_limit, threads_override, &L, mmse)) {
         ctx->err = "receive-antenna combining: the plan's widest allocation does not fit the device's LDS";
         return MI_LTE_ERR_UNSUPPORTED;
     }
@@ -1193,6 +1283,13 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
                                : (L.noise ? go(w, spec3, PuschLlrRx<4, true>{ln, stride}) : go(w, spec3, PuschLlrRx<4, false>{ln, stride}));
         };
         rc = L.threads == 192 ? rx(PuschWidth<192>{}) : rx(PuschWidth<256>{});
+        break;
+    }
+    case PuschFamily::LLR_MMSE: { // one antenna at the four widths, two and four at the combining launch's two
+        const uint32_t stride = pl->ant_stride;
+        const auto rx = [&](auto w) { return L.n_rx == 2 ? go(w, spec3, PuschLlrMmse<2>{ln, pl->d_llr_nu, stride}) : go(w, spec3, PuschLlrMmse<4>{ln, pl->d_llr_nu, stride}); };
+        if (L.n_rx <= 1) rc = pusch_width(L.threads, [&](auto w) { return go(w, spec3, PuschLlrMmse<1>{ln, pl->d_llr_nu, 0u}); });
+        else rc = L.threads == 192 ? rx(PuschWidth<192>{}) : rx(PuschWidth<256>{});
         break;
     }
     }

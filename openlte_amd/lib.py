@@ -257,6 +257,7 @@ def phich_re_table(n_rb_dl, n_id_cell, phich_res):
 
 
 HARQ_NONE, HARQ_NEW_DATA = 0xFFFFFFFF, 1
+EQ_ZF, EQ_MMSE = 0, 1  # mi_lte_pusch_plan_set_equaliser (3GPP plans)
 DEMAP_REF, DEMAP_MAXLOG = 0, 1  # mi_lte_pdsch_plan_set_demapper, mi_lte_pusch_plan_set_demapper (3GPP plans)
 DEMAP_AUTO_T = 16               # MI_LTE_DEMAP_AUTO_T
 
@@ -509,6 +510,9 @@ def load_library():
     L.mi_lte_pusch_plan_llr_noise.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_pusch_plan_set_rx_antennas.argtypes = [vp, u32, u32]
     L.mi_lte_pusch_plan_rx_antennas.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    L.mi_lte_pusch_plan_set_equaliser.argtypes = [vp, u32]
+    L.mi_lte_pusch_plan_equaliser.argtypes = [vp, C.POINTER(u32)]
+    L.mi_lte_pusch_plan_llr_nu.argtypes = [vp, C.POINTER(vp)]
     L.mi_lte_pusch_decode_run_harq.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.mi_lte_pusch_plan_llr_symbols.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32)]
     L.mi_lte_prach_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.POINTER(PrachCfg), C.POINTER(vp)]
@@ -1058,6 +1062,21 @@ class PuschPlan:
         n, s = C.c_uint32(), C.c_uint32()
         self.ctx._check(self.ctx.L.mi_lte_pusch_plan_rx_antennas(self.h, C.byref(n), C.byref(s)))
         return int(n.value), int(s.value)
+
+    def set_equaliser(self, mode):
+        """3GPP mode: EQ_ZF (default, one zero-forcing tap per sub-carrier) or EQ_MMSE (the tap 1 / (P + sigma2) and LLRs at the
+        post-equaliser SINR); an MMSE run needs set_demapper(DEMAP_MAXLOG) and set_llr_noise(scale > 0)."""
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_set_equaliser(self.h, mode))
+
+    def equaliser(self):
+        """EQ_ZF or EQ_MMSE as the plan holds it"""
+        m = C.c_uint32()
+        self.ctx._check(self.ctx.L.mi_lte_pusch_plan_equaliser(self.h, C.byref(m)))
+        return int(m.value)
+
+    def llr_nu(self):
+        """3GPP mode, once EQ_MMSE was set: float32 [n_alloc, 12], the residual nu_s of the last MMSE run (stage tap; zeros before one)."""
+        return self._llr_floats(self.ctx.L.mi_lte_pusch_plan_llr_nu, (self.n_alloc, 12))
 
     def set_llr_tap(self, on=True):
         """3GPP mode: have MAXLOG runs also store the de-mapper's input symbols (llr_symbols); off frees the buffer again."""

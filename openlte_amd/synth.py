@@ -20,6 +20,11 @@ class SynthChannel(C.Structure):
                 ("peak", C.c_double), ("seed", C.c_uint64)]
 
 
+class SynthPaths(C.Structure):
+    """mi_lte_synth_paths"""
+    _fields_ = [("n_paths", C.c_uint32), ("delay", C.c_uint32 * 4), ("amp", C.c_double * 4)]
+
+
 def _lib():
     L = load_library()
     if not getattr(L, "_synth_bound", False):
@@ -49,6 +54,9 @@ def _lib():
         L.mi_lte_synth_ul_units_3gpp_payload_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(UlCfg), C.c_uint32, _u32p, _u32p, C.c_void_p, C.c_uint32,
                                                             C.POINTER(SynthChannel), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                             C.c_void_p, C.c_uint32, _i8p]
+        L.mi_lte_synth_ul_units_3gpp_paths_i8.argtypes = [C.POINTER(DlCfg), C.POINTER(UlCfg), C.c_uint32, _u32p, _u32p, C.c_void_p, C.c_uint32,
+                                                          C.POINTER(SynthChannel), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                          C.c_void_p, C.c_uint32, C.POINTER(SynthPaths), _i8p]
         L.mi_lte_ulsch_mux_3gpp.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(UlschUci), _u8p, _u8p, _u8p, _u8p, C.c_uint32, _u8p, _u8p]
         L.mi_lte_synth_prach_len.argtypes = [C.c_uint32, C.c_uint32]
         L.mi_lte_synth_prach_len.restype = C.c_size_t
@@ -212,12 +220,15 @@ def ul_units(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, gain=(0.5, 1.5),
 
 
 def ul_units_3gpp(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, uci=None, ack=None, ri=None, cqi=None, gain=(0.5, 1.5), max_delay=4,
-                  snr_db=30.0, peak=100.0, seed=1, payload=None):
+                  snr_db=30.0, peak=100.0, seed=1, payload=None, paths=None):
     """ul_units with the 3GPP UL-SCH transmitter (mi_lte_synth_ul_units_3gpp_i8): any tbs of Table 7.1.7.2.1-1, the exact interleaver.
     uci: one UlschUci per allocation (unit-major, as allocs) -- mi_lte_synth_ul_units_3gpp_uci_i8, with the control values the caller's:
     ack[k], ri[k] the allocation's information bits (sequences of O_ack / O_ri bits) and cqi[k] its Q_cqi coded CQI bits.
     payload: the transport blocks to send, uint8 [n_units, n_alloc, >= max tbs] one bit per byte (mi_lte_synth_ul_units_3gpp_payload_i8:
-    a HARQ retransmission is the same payload with another rv and seed); returned as tx."""
+    a HARQ retransmission is the same payload with another rv and seed); returned as tx.
+    paths: (delays, amps), a channel of 1 .. 4 paths (mi_lte_synth_ul_units_3gpp_paths_i8): delays[0] = 0, the further ones extra integer
+    samples; amps relative, normalised inside.  Every path behind the first draws a phase of its own from the seed.  Without a payload one
+    is drawn from numpy's generator seeded with `seed`."""
     n, na = len(subfr_num), len(allocs)
     max_tbs = max([a.tbs for a in allocs], default=8)
     arr = (PdschAlloc * max(na, 1))(*allocs)
@@ -238,10 +249,23 @@ def ul_units_3gpp(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, uci=None, a
                     dst[k, :min(cnt, dst.shape[1])] = np.asarray(src[k], np.uint8)[:dst.shape[1]]  # (O > 2 is the library's to refuse)
         u_arr = (UlschUci * max(na, 1))(*uci)
         ctrl = (C.cast(u_arr, C.c_void_p), h_ack, h_ri, h_cqi, stride)
+    if paths is not None and payload is None:
+        payload = np.random.default_rng(seed).integers(0, 2, (n, max(n_alloc, 1), max_tbs), dtype=np.uint8)
     if payload is not None:
         pl = np.ascontiguousarray(payload, np.uint8)
         if pl.ndim != 3 or pl.shape[0] != n or pl.shape[1] != max(n_alloc, 1):
             raise ValueError("payload: uint8 [n_units, n_alloc, >= max tbs]")
+        if paths is not None:
+            delays, amps = paths
+            if len(delays) != len(amps) or len(delays) > 4:
+                raise ValueError("paths: (delays, amps), at most four of each")
+            sp = SynthPaths(len(delays), (C.c_uint32 * 4)(*[int(d) for d in delays]), (C.c_double * 4)(*[float(a) for a in amps]))
+            rc = _lib().mi_lte_synth_ul_units_3gpp_paths_i8(C.byref(cfg), C.byref(ulcfg), n, sf, cell, C.cast(arr, C.c_void_p), n_alloc, C.byref(ch),
+                                                            *[None if v is None else v if isinstance(v, (int, C.c_void_p)) else v.ctypes.data for v in ctrl],
+                                                            pl.ctypes.data, pl.shape[2], C.byref(sp), iq)
+            if rc != 0:
+                raise MiLteError("mi_lte_synth_ul_units_3gpp_paths_i8 failed: %d" % rc, rc)
+            return iq, pl[:, :, :max_tbs].copy()
         rc = _lib().mi_lte_synth_ul_units_3gpp_payload_i8(C.byref(cfg), C.byref(ulcfg), n, sf, cell, C.cast(arr, C.c_void_p), n_alloc, C.byref(ch),
                                                           *[None if v is None else v if isinstance(v, (int, C.c_void_p)) else v.ctypes.data for v in ctrl],
                                                           pl.ctypes.data, pl.shape[2], iq)
@@ -261,7 +285,7 @@ def ul_units_3gpp_rx(cfg, ulcfg, subfr_num, n_id_cell, allocs, n_alloc, n_rx, an
     """n_rx receive-antenna captures of the same transmission, in the antenna-major order mi_lte_pusch_plan_set_rx_antennas reads: unit
     r * ant_stride + u is antenna r of unit u (ant_stride defaults to the number of units; units past it stay zero).  Every antenna is
     ul_units_3gpp with the same payload and a seed of its own (seeds[r], by default seed + 1000 r): another gain, phase, delay and noise.
-    payload None: random transport blocks drawn from `seed`.  Further keywords (uci, ack, ri, cqi, gain, max_delay, snr_db, peak) go to
+    payload None: random transport blocks drawn from `seed`.  Further keywords (uci, ack, ri, cqi, gain, max_delay, snr_db, peak, paths) go to
     ul_units_3gpp.  Returns (iq int8 [n_rx * ant_stride, unit_len, 2], tx uint8 [n_units, n_alloc, max tbs])."""
     n = len(subfr_num)
     ant_stride = n if ant_stride is None else int(ant_stride)

@@ -4,8 +4,10 @@
 // with one line each,
 //   fits family threads S_par lds_off lds_bytes label
 // fits: 1, or 0 for a combining launch that does not fit lds_limit at S_par = 1; family: plain / llr / llr_noise / llr_rx.
-//   pusch_launch_driver [query file]
+// With --mmse in front, every query has an eighth field, mmse (mi_lte_pusch_plan_set_equaliser), and the family may be llr_mmse.
+//   pusch_launch_driver [--mmse] [query file]
 #include <cstdio>
+#include <cstring>
 
 #include "../../openlte_amd/csrc/pusch_launch.h"
 
@@ -13,15 +15,23 @@ using namespace pusch_geom;
 
 int main(int argc, char **argv)
 {
+    const bool eight = argc > 1 && !strcmp(argv[1], "--mmse");
+    if (eight) { argc--; argv++; }
     FILE *fp = argc > 1 ? fopen(argv[1], "r") : stdin;
     if (!fp) { printf("pusch launch driver: cannot read %s\n", argv[1]); return 1; }
-    static const char *const family[] = {"plain", "llr", "llr_noise", "llr_rx"};
-    unsigned           M_max, words_max, maxlog, noise, n_rx, threads;
+    static const char *const family[] = {"plain", "llr", "llr_noise", "llr_rx", "llr_mmse"};
+    unsigned           M_max, words_max, maxlog, noise, n_rx, threads, mmse;
     unsigned long long limit;
     long               n = 0;
-    while (fscanf(fp, "%u %u %u %u %u %llu %u", &M_max, &words_max, &maxlog, &noise, &n_rx, &limit, &threads) == 7) {
+    while (!eight && fscanf(fp, "%u %u %u %u %u %llu %u", &M_max, &words_max, &maxlog, &noise, &n_rx, &limit, &threads) == 7) {
         PuschLaunch L;
         const bool  fits = pusch_launch_plan(M_max, words_max, maxlog != 0, noise != 0, n_rx, (size_t)limit, threads, &L);
+        printf("%d %s %u %u %zu %zu %s\n", fits ? 1 : 0, family[(int)L.family], L.threads, L.S_par, L.lds_off, L.lds_bytes, L.label);
+        n++;
+    }
+    while (eight && fscanf(fp, "%u %u %u %u %u %llu %u %u", &M_max, &words_max, &maxlog, &noise, &n_rx, &limit, &threads, &mmse) == 8) {
+        PuschLaunch L;
+        const bool  fits = pusch_launch_plan(M_max, words_max, maxlog != 0, noise != 0, n_rx, (size_t)limit, threads, &L, mmse != 0);
         printf("%d %s %u %u %zu %zu %s\n", fits ? 1 : 0, family[(int)L.family], L.threads, L.S_par, L.lds_off, L.lds_bytes, L.label);
         n++;
     }
