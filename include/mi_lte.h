@@ -1305,6 +1305,25 @@ int    mi_lte_find_sss_run(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void
                            uint32_t N_id_2, uint32_t *symb_starts /* [7] in/out */, float pss_thresh, uint32_t *N_id_1,
                            uint32_t *frame_start_idx, uint32_t *found);
 
+/* For tests and not for callers: what the kernels of the three searches wrote, copied out.  Each tap runs the same device part as
+ * its _run (one function in sync.hip serves both), waits for the stream and forms no verdict; it returns
+ * MI_LTE_ERR_INVALID_ARG where its _run does and for a NULL output.  n_slot = 15360 fft_size / 2048, N_sc = 12 N_rb_dl.
+ *   mi_lte_coarse_timing_tap  h_corr: float pairs (re, im) [N_slots][n_slot], k_cp_corr's sums; h_acc: float [n_slot], k_cp_accum's.
+ *   mi_lte_find_pss_tap       h_rows: float [84][2][1200], the 12 x 7 symbols' spectra as k_sync_fft wrote them (real parts, then
+ *       imaginary parts; the first N_sc columns of each are written, the rest is left as it was); h_corr: float pairs [84][9], row
+ *       r against PSS k at sub-carrier shift sft - 1 in column 3 k + sft; h_fine_rows: float [80][2][1200] and h_fine_corr: float pairs
+ *       [80] of the fine-timing pass.  That pass depends on the first one's verdict, which the tap does NOT form: the caller passes
+ *       N_id_2 (0..2), pss_symb (0..83) and shift (-1, 0, +1) -- from h_corr of an earlier call, or as mi_lte_find_pss_run gave them.
+ *   mi_lte_find_sss_tap       h_row: float [2][1200] (first N_sc columns written), the symbol at symb_starts[5]; h_corr: float
+ *       pairs [336], N_id_1 i against subframe 0's sequence in column 2 i and subframe 5's in column 2 i + 1. */
+int    mi_lte_coarse_timing_tap(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d_samples_a, const void *d_samples_b,
+                                uint64_t start, uint32_t N_slots, float *h_corr, float *h_acc);
+int    mi_lte_find_pss_tap(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d_samples_a, const void *d_samples_b, uint64_t start,
+                           const uint32_t *symb_starts /* [7] */, uint32_t N_id_2, uint32_t pss_symb, int32_t shift, float *h_rows,
+                           float *h_corr, float *h_fine_rows, float *h_fine_corr);
+int    mi_lte_find_sss_tap(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d_samples_a, const void *d_samples_b, uint64_t start,
+                           uint32_t N_id_2, const uint32_t *symb_starts /* [7]; [5] is read */, float *h_row, float *h_corr);
+
 /* The scanner's caller-side steps between the searches, for a capture that stays in HBM:
  *   mi_lte_iq_i8_to_planar  int8 I,Q pairs -> planar fp32 i_samps / q_samps (LTE_fdd_dl_fs_samp_buf.cc:657-694);
  *   mi_lte_freq_shift_run   LTE_fdd_dl_fs_samp_buf::freq_shift (:696-713) in place: sample i (buffer index first_index + k for

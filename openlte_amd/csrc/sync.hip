@@ -184,9 +184,10 @@ template <typename F> int with_samples(const mi_lte_dl_cfg *cfg, const void *a, 
     return MI_LTE_ERR_INVALID_ARG;
 }
 
-// FFT rows at the given window starts, then correlations with n_seq sequences: h_out[r][q] (float2)
+// FFT rows at the given window starts, then correlations with n_seq sequences: h_out[r][q] (float2).  h_rows (the taps): the rows
+// k_seq_corr read, [n_rows][2][1200] with the first 12 N_rb_dl columns of each written -- what k_sync_fft wrote; the rest is not touched.
 int fft_and_corr(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *a, const void *b, const std::vector<uint64_t> &win, const std::vector<float2> &seq,
-                 const std::vector<uint32_t> &z0, std::vector<float2> &h_out)
+                 const std::vector<uint32_t> &z0, std::vector<float2> &h_out, float *h_rows = nullptr)
 {
     const uint32_t n_rows = (uint32_t)win.size(), n_seq = (uint32_t)z0.size();
     // carve the per-call tables out of the context's scratch (no allocation on the search path)
@@ -208,8 +209,94 @@ int fft_and_corr(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *a, const
     MI_HIP_CHECK(ctx, hipGetLastError());
     h_out.resize((size_t)n_rows * n_seq);
     MI_D2H(ctx, h_out.data(), d_out.p, h_out.size() * 8);
+    std::vector<float> rows;
+    if (h_rows) {
+        rows.resize((size_t)n_rows * 2 * N_SC_MAX);
+        MI_D2H(ctx, rows.data(), d_rows.p, rows.size() * 4);
+    }
     MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t r = 0; h_rows && r < (size_t)2 * n_rows; r++) memcpy(h_rows + r * N_SC_MAX, &rows[r * N_SC_MAX], 4 * (size_t)cfg->N_rb_dl * 12);
     return MI_LTE_OK;
+}
+
+// ---- the device part of each search, shared by its _run entry and its tap (mi_lte_*_tap, for tests), so that a tap shows what the _run judged
+
+// coarse timing: the scratch carved, k_cp_corr and k_cp_accum queued
+struct CoarseDev { float2 *corr; float *acc; uint32_t *pos; float2 *pk; };
+int coarse_launch(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d_samples_a, const void *d_samples_b, uint64_t start, uint32_t N_slots, const Geom &g,
+                  CoarseDev *d)
+{
+    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t n_corr = (size_t)N_slots * g.n_slot;
+    int rc = mi_ctx_reserve_scratch(ctx, n_corr * 8 + (size_t)g.n_slot * 4 + 8 * 4 + (size_t)5 * N_slots * 8);
+    if (rc != MI_LTE_OK) return rc;
+    float2   *d_corr = (float2 *)ctx->scratch;
+    float    *d_acc  = (float *)(d_corr + n_corr);
+    uint32_t *d_pos  = (uint32_t *)(d_acc + g.n_slot);
+    float2   *d_pk   = (float2 *)(d_pos + 8);
+    rc = with_samples(cfg, d_samples_a, d_samples_b, [&](auto src) {
+        MI_LAUNCH(ctx, "k_cp_corr", (k_cp_corr<decltype(src)>), dim3((g.n_slot + CP_BLK - 1) / CP_BLK, N_slots), dim3(256), 0, src, start, g.n_slot, g.N, g.cpe, d_corr);
+        return MI_LTE_OK;
+    });
+    if (rc != MI_LTE_OK) return rc;
+    MI_LAUNCH(ctx, "k_cp_accum", k_cp_accum, dim3((g.n_slot + 255) / 256), dim3(256), 0, (const float2 *)d_corr, g.n_slot, N_slots, d_acc);
+    MI_HIP_CHECK(ctx, hipGetLastError());
+    *d = CoarseDev{d_corr, d_acc, d_pos, d_pk};
+    return MI_LTE_OK;
+}
+
+// PSS search, first pass: 84 symbols (12 slots x 7) against nine sequences -- PSS k at sub-carrier shift -1, 0, +1 (:5347-5366); c[r][3 k + sft]
+int pss_search_pass(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d_samples_a, const void *d_samples_b, uint64_t start, const Geom &g,
+                    const uint32_t *symb_starts, std::vector<float2> &seq, std::vector<uint32_t> &z0, std::vector<float2> &c, float *h_rows = nullptr)
+{
+    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    seq.resize(9 * 62);
+    z0.resize(9);
+    for (uint32_t k = 0; k < 3; k++) {
+        float2 pss[62];
+        gen_pss(k, pss);
+        for (uint32_t sft = 0; sft < 3; sft++) {
+            std::copy(pss, pss + 62, &seq[(k * 3 + sft) * 62]);
+            z0[k * 3 + sft] = g.n_sc / 2 - 31 + sft - 1;
+        }
+    }
+    std::vector<uint64_t> win(84);
+    for (uint32_t i = 0; i < 12; i++)
+        for (uint32_t j = 0; j < 7; j++) win[i * 7 + j] = start + symb_starts[j] + (uint64_t)g.n_slot * i + g.cp0 - 1;
+    return fft_and_corr(ctx, cfg, d_samples_a, d_samples_b, win, seq, z0, c, h_rows);
+}
+
+// PSS search, second pass: 80 sample offsets around symbol pss_symb against the first pass's sequence (N_id_2, shift) (:5441-5480); c[i + 40]
+int pss_fine_pass(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d_samples_a, const void *d_samples_b, uint64_t start, const Geom &g,
+                  const uint32_t *symb_starts, uint32_t N_id_2, uint32_t pss_symb, int32_t shift, const std::vector<float2> &seq, const std::vector<uint32_t> &z0,
+                  std::vector<float2> &c, float *h_rows = nullptr)
+{
+    const uint32_t N_s = pss_symb / 7, N_symb = pss_symb % 7;
+    std::vector<uint64_t> win2(80);
+    for (int32_t i = -40; i < 40; i++) {
+        int32_t idx = (int32_t)(symb_starts[N_symb] + g.n_slot * N_s);
+        if (i < 0) { if (idx >= -i) idx += i; } else idx += i;
+        win2[i + 40] = start + (uint64_t)(uint32_t)idx + g.cp0 - 1;
+    }
+    std::vector<float2>   seq1(seq.begin() + (N_id_2 * 3 + (shift + 1)) * 62, seq.begin() + (N_id_2 * 3 + (shift + 1) + 1) * 62);
+    std::vector<uint32_t> z1(1, z0[N_id_2 * 3 + (shift + 1)]);
+    return fft_and_corr(ctx, cfg, d_samples_a, d_samples_b, win2, seq1, z1, c, h_rows);
+}
+
+// SSS search: the symbol at symb5 against the 168 x 2 sequences of N_id_2; c[2 N_id_1 + h], h = 0 subframe 0's, 1 subframe 5's
+int sss_pass(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d_samples_a, const void *d_samples_b, uint64_t start, const Geom &g, uint32_t N_id_2,
+             uint32_t symb5, std::vector<float2> &c, float *h_rows = nullptr)
+{
+    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    std::vector<float2>   seq((size_t)336 * 62);
+    std::vector<uint32_t> z0(336, g.n_sc / 2 - 31);
+    for (uint32_t i = 0; i < 168; i++) {
+        float s0[62], s5[62];
+        gen_sss(i, N_id_2, s0, s5);
+        for (uint32_t t = 0; t < 62; t++) { seq[(size_t)(2 * i) * 62 + t] = make_float2(s0[t], 0.0f); seq[(size_t)(2 * i + 1) * 62 + t] = make_float2(s5[t], 0.0f); }
+    }
+    std::vector<uint64_t> win(1, start + symb5 + g.cp0 - 1);
+    return fft_and_corr(ctx, cfg, d_samples_a, d_samples_b, win, seq, z0, c, h_rows);
 }
 
 // The scanner's carrier-frequency correction (LTE_fdd_dl_file_scan/src/LTE_fdd_dl_fs_samp_buf.cc:696-713), in place on planar float
@@ -266,21 +353,12 @@ int mi_lte_coarse_timing_run(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const vo
     Geom g;
     int  rc = geom(cfg, &g);
     if (rc != MI_LTE_OK) return rc;
-    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const size_t n_corr = (size_t)N_slots * g.n_slot;
-    rc = mi_ctx_reserve_scratch(ctx, n_corr * 8 + (size_t)g.n_slot * 4 + 8 * 4 + (size_t)5 * N_slots * 8);
+    CoarseDev dv;
+    rc = coarse_launch(ctx, cfg, d_samples_a, d_samples_b, start, N_slots, g, &dv);
     if (rc != MI_LTE_OK) return rc;
-    float2   *d_corr = (float2 *)ctx->scratch;
-    float    *d_acc  = (float *)(d_corr + n_corr);
-    uint32_t *d_pos  = (uint32_t *)(d_acc + g.n_slot);
-    float2   *d_pk   = (float2 *)(d_pos + 8);
-    rc = with_samples(cfg, d_samples_a, d_samples_b, [&](auto src) {
-        MI_LAUNCH(ctx, "k_cp_corr", (k_cp_corr<decltype(src)>), dim3((g.n_slot + CP_BLK - 1) / CP_BLK, N_slots), dim3(256), 0, src, start, g.n_slot, g.N, g.cpe, d_corr);
-        return MI_LTE_OK;
-    });
-    if (rc != MI_LTE_OK) return rc;
-    MI_LAUNCH(ctx, "k_cp_accum", k_cp_accum, dim3((g.n_slot + 255) / 256), dim3(256), 0, (const float2 *)d_corr, g.n_slot, N_slots, d_acc);
-    MI_HIP_CHECK(ctx, hipGetLastError());
+    float2   *d_corr = dv.corr, *d_pk = dv.pk;
+    float    *d_acc  = dv.acc;
+    uint32_t *d_pos  = dv.pos;
     // ---- the reference's decisions on the n_slot accumulated values (:5746-5805)
     std::vector<float> c(2 * 15360 + 1, 0.0f); // dl_timing_abs_corr[LIBLTE_PHY_N_SAMPS_PER_SLOT_30_72MHZ*2] (liblte_phy.h:475)
     MI_D2H(ctx, c.data(), d_acc, (size_t)g.n_slot * 4);
@@ -347,23 +425,9 @@ int mi_lte_find_pss_run(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d
     Geom g;
     int  rc = geom(cfg, &g);
     if (rc != MI_LTE_OK) return rc;
-    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    // nine sequences: PSS k at sub-carrier shift -1, 0, +1 (:5347-5366)
-    std::vector<float2>   seq(9 * 62);
-    std::vector<uint32_t> z0(9);
-    for (uint32_t k = 0; k < 3; k++) {
-        float2 pss[62];
-        gen_pss(k, pss);
-        for (uint32_t sft = 0; sft < 3; sft++) {
-            std::copy(pss, pss + 62, &seq[(k * 3 + sft) * 62]);
-            z0[k * 3 + sft] = g.n_sc / 2 - 31 + sft - 1;
-        }
-    }
-    std::vector<uint64_t> win(84);
-    for (uint32_t i = 0; i < 12; i++)
-        for (uint32_t j = 0; j < 7; j++) win[i * 7 + j] = start + symb_starts[j] + (uint64_t)g.n_slot * i + g.cp0 - 1;
-    std::vector<float2> c;
-    rc = fft_and_corr(ctx, cfg, d_samples_a, d_samples_b, win, seq, z0, c);
+    std::vector<float2>   seq, c;
+    std::vector<uint32_t> z0;
+    rc = pss_search_pass(ctx, cfg, d_samples_a, d_samples_b, start, g, symb_starts, seq, z0, c);
     if (rc != MI_LTE_OK) return rc;
     float   corr_max = 0;
     int32_t shift    = 0;
@@ -376,15 +440,7 @@ int mi_lte_find_pss_run(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d
     *freq_offset = 15000.0f * shift;
     // fine timing: 80 offsets around the PSS symbol (:5441-5480)
     const uint32_t N_s = *pss_symb / 7, N_symb = *pss_symb % 7;
-    std::vector<uint64_t> win2(80);
-    for (int32_t i = -40; i < 40; i++) {
-        int32_t idx = (int32_t)(symb_starts[N_symb] + g.n_slot * N_s);
-        if (i < 0) { if (idx >= -i) idx += i; } else idx += i;
-        win2[i + 40] = start + (uint64_t)(uint32_t)idx + g.cp0 - 1;
-    }
-    std::vector<float2>   seq1(seq.begin() + (*N_id_2 * 3 + (shift + 1)) * 62, seq.begin() + (*N_id_2 * 3 + (shift + 1) + 1) * 62);
-    std::vector<uint32_t> z1(1, z0[*N_id_2 * 3 + (shift + 1)]);
-    rc = fft_and_corr(ctx, cfg, d_samples_a, d_samples_b, win2, seq1, z1, c);
+    rc = pss_fine_pass(ctx, cfg, d_samples_a, d_samples_b, start, g, symb_starts, *N_id_2, *pss_symb, shift, seq, z0, c);
     if (rc != MI_LTE_OK) return rc;
     corr_max      = 0;
     int8_t timing = 0;
@@ -409,17 +465,8 @@ int mi_lte_find_sss_run(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d
     Geom g;
     int  rc = geom(cfg, &g);
     if (rc != MI_LTE_OK) return rc;
-    MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    std::vector<float2>   seq((size_t)336 * 62);
-    std::vector<uint32_t> z0(336, g.n_sc / 2 - 31);
-    for (uint32_t i = 0; i < 168; i++) {
-        float s0[62], s5[62];
-        gen_sss(i, N_id_2, s0, s5);
-        for (uint32_t t = 0; t < 62; t++) { seq[(size_t)(2 * i) * 62 + t] = make_float2(s0[t], 0.0f); seq[(size_t)(2 * i + 1) * 62 + t] = make_float2(s5[t], 0.0f); }
-    }
-    std::vector<uint64_t> win(1, start + symb_starts[5] + g.cp0 - 1);
-    std::vector<float2>   c;
-    rc = fft_and_corr(ctx, cfg, d_samples_a, d_samples_b, win, seq, z0, c);
+    std::vector<float2> c;
+    rc = sss_pass(ctx, cfg, d_samples_a, d_samples_b, start, g, N_id_2, symb_starts[5], c);
     if (rc != MI_LTE_OK) return rc;
     const float    sss_thresh = pss_thresh * 0.9;
     const uint32_t to_sss     = (g.N + g.cpe) * 4 + g.N + g.cp0; // from the frame (or half-frame) start to the SSS symbol
@@ -435,6 +482,61 @@ int mi_lte_find_sss_run(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d
                 break;
             }
     ctx->last_kernels = "k_sync_fft:1,k_seq_corr:1";
+    return MI_LTE_OK;
+}
+
+// ---- for tests and not for callers: what the kernels of each search wrote, copied out.  Every tap runs the device part of its _run
+// (above), waits for the stream and forms no verdict.
+
+int mi_lte_coarse_timing_tap(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d_samples_a, const void *d_samples_b, uint64_t start,
+                             uint32_t N_slots, float *h_corr, float *h_acc)
+{
+    if (!ctx || !cfg || !d_samples_a || !h_corr || !h_acc || N_slots == 0) return MI_LTE_ERR_INVALID_ARG;
+    Geom g;
+    int  rc = geom(cfg, &g);
+    if (rc != MI_LTE_OK) return rc;
+    CoarseDev dv;
+    rc = coarse_launch(ctx, cfg, d_samples_a, d_samples_b, start, N_slots, g, &dv);
+    if (rc != MI_LTE_OK) return rc;
+    MI_D2H(ctx, h_corr, dv.corr, (size_t)N_slots * g.n_slot * 8);
+    MI_D2H(ctx, h_acc, dv.acc, (size_t)g.n_slot * 4);
+    MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return MI_LTE_OK;
+}
+
+// The second pass depends on the first's verdict: the tap takes it from the caller (N_id_2, pss_symb, shift = -1, 0, +1), who forms it from
+// h_corr of an earlier call or passes what mi_lte_find_pss_run returned.
+int mi_lte_find_pss_tap(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d_samples_a, const void *d_samples_b, uint64_t start,
+                        const uint32_t *symb_starts /*[7]*/, uint32_t N_id_2, uint32_t pss_symb, int32_t shift, float *h_rows, float *h_corr,
+                        float *h_fine_rows, float *h_fine_corr)
+{
+    if (!ctx || !cfg || !d_samples_a || !symb_starts || !h_rows || !h_corr || !h_fine_rows || !h_fine_corr || N_id_2 > 2 || pss_symb >= 84 || shift < -1 || shift > 1)
+        return MI_LTE_ERR_INVALID_ARG;
+    Geom g;
+    int  rc = geom(cfg, &g);
+    if (rc != MI_LTE_OK) return rc;
+    std::vector<float2>   seq, c;
+    std::vector<uint32_t> z0;
+    rc = pss_search_pass(ctx, cfg, d_samples_a, d_samples_b, start, g, symb_starts, seq, z0, c, h_rows);
+    if (rc != MI_LTE_OK) return rc;
+    memcpy(h_corr, c.data(), c.size() * 8);
+    rc = pss_fine_pass(ctx, cfg, d_samples_a, d_samples_b, start, g, symb_starts, N_id_2, pss_symb, shift, seq, z0, c, h_fine_rows);
+    if (rc != MI_LTE_OK) return rc;
+    memcpy(h_fine_corr, c.data(), c.size() * 8);
+    return MI_LTE_OK;
+}
+
+int mi_lte_find_sss_tap(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const void *d_samples_a, const void *d_samples_b, uint64_t start,
+                        uint32_t N_id_2, const uint32_t *symb_starts /*[7]; [5] is read*/, float *h_row, float *h_corr)
+{
+    if (!ctx || !cfg || !d_samples_a || !symb_starts || !h_row || !h_corr || N_id_2 > 2) return MI_LTE_ERR_INVALID_ARG;
+    Geom g;
+    int  rc = geom(cfg, &g);
+    if (rc != MI_LTE_OK) return rc;
+    std::vector<float2> c;
+    rc = sss_pass(ctx, cfg, d_samples_a, d_samples_b, start, g, N_id_2, symb_starts[5], c, h_row);
+    if (rc != MI_LTE_OK) return rc;
+    memcpy(h_corr, c.data(), c.size() * 8);
     return MI_LTE_OK;
 }
 

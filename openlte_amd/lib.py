@@ -552,6 +552,9 @@ def load_library():
     L.mi_lte_coarse_timing_run.argtypes = [vp, C.POINTER(DlCfg), vp, vp, C.c_uint64, u32, C.POINTER(CoarseTiming)]
     L.mi_lte_find_pss_run.argtypes = [vp, C.POINTER(DlCfg), vp, vp, C.c_uint64, u32p, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.mi_lte_find_sss_run.argtypes = [vp, C.POINTER(DlCfg), vp, vp, C.c_uint64, u32, u32p, C.c_float, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.mi_lte_coarse_timing_tap.argtypes = [vp, C.POINTER(DlCfg), vp, vp, C.c_uint64, u32, vp, vp]
+    L.mi_lte_find_pss_tap.argtypes = [vp, C.POINTER(DlCfg), vp, vp, C.c_uint64, vp, u32, u32, C.c_int32, vp, vp, vp, vp]
+    L.mi_lte_find_sss_tap.argtypes = [vp, C.POINTER(DlCfg), vp, vp, C.c_uint64, u32, vp, vp, vp]
     L.mi_lte_pbch_decode_run.argtypes = [vp, C.POINTER(DlCfg), vp, vp, u32, u32p, u32p, u32p]
     L.mi_lte_pdcch_re_tables.argtypes = [u32, u32, u32, C.c_float, u32, u32p, u32p]
     L.mi_lte_dci_1a_unpack.argtypes = [u32, u32, u32, u32, u32, C.POINTER(PdcchDci)]
@@ -1624,6 +1627,40 @@ class Context:
         self._check(self.L.mi_lte_find_sss_run(self.h, C.byref(cfg), d_a.ptr, d_b.ptr if d_b is not None else None, start, n_id_2, ss, pss_thresh,
                                                C.byref(n1), C.byref(fs), C.byref(found)))
         return bool(found.value), n1.value, fs.value, ss
+
+    # ---- taps of the three searches, for tests and not for callers (mi_lte_*_tap): what the kernels wrote, no verdicts.  `out`: the output
+    # arrays to write into (float32, C-contiguous, of the documented shapes) where a test wants to see what a call leaves untouched.
+
+    def coarse_timing_tap_dev(self, cfg, d_a, d_b, n_slots, start=0, out=None):
+        """(corr complex64 [n_slots, n_slot] of k_cp_corr, acc float32 [n_slot] of k_cp_accum)"""
+        n_slot = 15360 * cfg.fft_size // 2048
+        corr, acc = out if out is not None else (np.zeros((n_slots, n_slot, 2), np.float32), np.zeros(n_slot, np.float32))
+        assert corr.dtype == acc.dtype == np.float32 and corr.shape == (n_slots, n_slot, 2) and acc.shape == (n_slot,)
+        assert corr.flags.c_contiguous and acc.flags.c_contiguous
+        self._check(self.L.mi_lte_coarse_timing_tap(self.h, C.byref(cfg), d_a.ptr, d_b.ptr if d_b is not None else None, start, n_slots,
+                                                    corr.ctypes.data, acc.ctypes.data))
+        return corr.view(np.complex64)[..., 0], acc
+
+    def find_pss_tap_dev(self, cfg, d_a, d_b, symb_starts, n_id_2, pss_symb, shift, start=0, out=None):
+        """(rows float32 [84, 2, 1200], corr complex64 [84, 9], fine rows float32 [80, 2, 1200], fine corr complex64 [80]); the second pass runs
+        for the caller's (n_id_2, pss_symb, shift): the tap forms no verdict of its own."""
+        ss = np.ascontiguousarray(symb_starts, np.uint32)
+        rows, corr, frows, fcorr = out if out is not None else (np.zeros((84, 2, 1200), np.float32), np.zeros((84, 9, 2), np.float32),
+                                                                np.zeros((80, 2, 1200), np.float32), np.zeros((80, 2), np.float32))
+        assert all(a.dtype == np.float32 and a.flags.c_contiguous for a in (rows, corr, frows, fcorr))
+        assert (rows.shape, corr.shape, frows.shape, fcorr.shape) == ((84, 2, 1200), (84, 9, 2), (80, 2, 1200), (80, 2))
+        self._check(self.L.mi_lte_find_pss_tap(self.h, C.byref(cfg), d_a.ptr, d_b.ptr if d_b is not None else None, start, ss.ctypes.data, n_id_2, pss_symb,
+                                               shift, rows.ctypes.data, corr.ctypes.data, frows.ctypes.data, fcorr.ctypes.data))
+        return rows, corr.view(np.complex64)[..., 0], frows, fcorr.view(np.complex64)[..., 0]
+
+    def find_sss_tap_dev(self, cfg, d_a, d_b, n_id_2, symb_starts, start=0, out=None):
+        """(row float32 [2, 1200], corr complex64 [336]: N_id_1 i at 2 i (subframe 0's sequence) and 2 i + 1 (subframe 5's))"""
+        ss = np.ascontiguousarray(symb_starts, np.uint32)
+        row, corr = out if out is not None else (np.zeros((2, 1200), np.float32), np.zeros((336, 2), np.float32))
+        assert row.dtype == corr.dtype == np.float32 and row.shape == (2, 1200) and corr.shape == (336, 2) and row.flags.c_contiguous and corr.flags.c_contiguous
+        self._check(self.L.mi_lte_find_sss_tap(self.h, C.byref(cfg), d_a.ptr, d_b.ptr if d_b is not None else None, start, n_id_2, ss.ctypes.data,
+                                               row.ctypes.data, corr.ctypes.data))
+        return row, corr.view(np.complex64)[..., 0]
 
     def pbch_decode_dev(self, cfg, d_subframes, d_cell, n_units):
         """(N_ant[n] (0 = not decoded), offset[n], mib[n] = the 24 BCH bits, first bit in bit 23); cfg.N_ant must be 4."""

@@ -39,10 +39,14 @@ def window_start(fft, sym):
 def symbol_rows(x, fft, n_rb, n_sym=16):
     """complex128 [n_sym, 12 n_rb]: x is the unit's complex samples from its start.  Guard band dropped, DC skipped, spectrum un-shifted:
     columns 0 .. half - 1 are bins N - half .. N - 1, columns half .. are bins 1 .. half."""
+    return rows_at(x, fft, n_rb, [window_start(fft, s) for s in range(n_sym)])
+
+
+def rows_at(x, fft, n_rb, starts):
+    """complex128 [len(starts), 12 n_rb]: the same rows of the FFT windows that open at the given sample indices of x"""
     half = 6 * n_rb
-    out = np.zeros((n_sym, 2 * half), np.complex128)
-    for s in range(n_sym):
-        w = window_start(fft, s)
+    out = np.zeros((len(starts), 2 * half), np.complex128)
+    for s, w in enumerate(starts):
         X = np.fft.fft(np.asarray(x[w:w + fft], np.complex128))
         out[s, :half], out[s, half:] = X[fft - half:], X[1:half + 1]
     return out

@@ -500,7 +500,9 @@ SYNC_CASES = {
     # name: (fft, N_rb_dl, cell, frames, delay samples prepended, frequency offset Hz, snr_db)
     "1p4MHz_clean": (128, 6, 17, 18, 0, 0.0, 300.0),
     "1p4MHz_offset": (128, 6, 301, 18, 1234, 700.0, 12.0),
+    "3MHz": (256, 15, 222, 18, 777, 400.0, 10.0),          # 1920 windows per slot: a k_cp_corr tail block of 896
     "5MHz_noisy": (512, 25, 150, 18, 40000, -300.0, 6.0),
+    "10MHz": (1024, 50, 409, 12, 54321, -200.0, 12.0),     # 7680 windows per slot: a tail block of 512
     "20MHz": (2048, 100, 77, 10, 100001, 150.0, 15.0),
 }
 
