@@ -1134,7 +1134,7 @@ int  mi_lte_dci_1c_unpack(uint32_t payload, uint32_t n_bits, uint32_t rnti, uint
  * caller lists (SI-, P- and RA-RNTIs included only when listed); mi_lte_pdcch_search_plan_set_rntis replaces it, n_rnti = 0 empties it.
  * Refused like mi_lte_pdcch_plan_create (MI_LTE_ERR_UNSUPPORTED): a non-standard bandwidth, a port count other than 1 / 2 / 4, N_g outside
  * (0, 2], the extended PHICH duration.  MI_LTE_ERR_INVALID_ARG: n_sizes = 0 or > MI_LTE_PDCCH_SEARCH_MAX_SIZES, a size outside 8 .. 64, a
- * size listed twice, a cell past 503, an RNTI of 0 or above 0xFFFF.  Every refusal comes before any launch.
+ * size listed twice, a cell past 503, an RNTI of 0 or above 0xFFFF, a flag other than the two below.  Every refusal comes before any launch.
  *
  * mi_lte_pdcch_search_run, everything queued on the context's stream, one wait (before the compacted results are read), no allocation
  * after the first run at a given n_units:
@@ -1142,12 +1142,44 @@ int  mi_lte_dci_1c_unpack(uint32_t payload, uint32_t n_bits, uint32_t rnti, uint
  *      Every CCE's 36 resource elements through the transmit-diversity combiner with each port's own estimate (the arithmetic of
  *      MI_LTE_PDCCH_PER_PORT_ESTIMATES), the QPSK de-mapper and the descrambler (c_init = (subfr_num << 9) + cell, CCE c at bit 72 c):
  *      int8 soft bits soft[unit][72 cce + k], positive = bit 0.  A cell the plan was not built for, a subframe number past 9, cfi = 0 or
- *      N_symbs > 4: h_cfi = 0, h_n_cce = 0, no hit.
+ *      N_symbs > 4: h_cfi = 0, h_n_cce = 0, no hit, and nothing of the unit's soft bits is written; a run writes soft[unit][0 .. 72 h_n_cce)
+ *      and nothing past it.
+ *      The de-mapper's arithmetic (float32; the same for the PCFICH's 16 elements and for a CCE's 36; tests/pdcch_ctrl_model.py restates
+ *      it in float64).  The elements are taken in groups of N_ant in the order of the table; y(e) is the received element, h_p(e) port
+ *      p's estimate at it.
+ *        1 port:  x(e) = conj(h_0(e)) y(e) / |h_0(e)|^2.
+ *        2 ports: the pair (a, b) = (2 g, 2 g + 1) of the pre-coder of 36.211 6.3.4.3 with ports (A, B) = (0, 1).  Both estimates are
+ *          read at the pair's FIRST element a, also for x(b):  P_A = |h_A(a)|^2, P_B = |h_B(a)|^2, hn = sqrt(P_A^2 + P_B^2),
+ *            x(a) = (conj(h_A(a)) y(a) + h_B(a) conj(y(b))) / hn,   x(b) = (conj(h_A(a)) y(b) - h_B(a) conj(y(a))) / hn.
+ *          (hn is the reference's normaliser, not P_A + P_B: without noise |x| = (P_A + P_B) / (sqrt 2 hn), 1 for equal ports and
+ *          1 / sqrt 2 for one port in a fade.)
+ *        4 ports: per group of four elements 4 g .. 4 g + 3 the same on two pairs: elements (0, 1) of the group with ports (0, 2) and the
+ *          estimates at element 0; elements (2, 3) with ports (1, 3) and the estimates at element 2 (36.211 6.3.4.3; a group is one
+ *          resource-element group, so the pairs alternate inside every quadruplet).
+ *        QPSK soft value: (s_re, s_im) = the signs of x's components, its quadrant (a component that is exactly zero goes where atan2 puts
+ *          the angle: [0, pi/2) is +, +; [pi/2, pi) is -, +; [-pi/2, 0) is +, -); dist = |x - (s_re + j s_im) / sqrt 2|,
+ *          m = trunc(127 (1 - min(dist, 1 - 1/120))), so 1 <= m <= 127; the symbol's two bits are s_re m and s_im m.
+ *        Descrambling: bit n of the region (n = 72 cce + k; the PCFICH: n = 0 .. 31 of its own sequence) is negated where c(n) = 1.
+ *        An element marked absent in a table (0xFFFFFFFF; the search's tables have none) gives 0 on both bits.
+ *        Zero estimates (hn = 0, or |h_0|^2 = 0) make x 0 / 0: not a number, whatever y is.  Both bits of every element of the pair (of the
+ *          element, with 1 port) are then 0 -- the one way the de-mapper yields a 0; for the PCFICH a 0 counts as bit 0.  A finite x
+ *          however large (a received sample of 1e30) saturates at m = 1 with its quadrant's signs.
+ *      PCFICH decision: the 32 descrambled soft bits, bit = (soft < 0), against the four code words of 36.212 table 5.3.4-1 (CFI 4: all
+ *      zero); the smallest Hamming distance wins, the lower CFI on a tie; 4 or more errors: cfi = 0.
+ *      Positions: the plan's tables are those of mi_lte_pdcch_re_tables carried on to every CCE (mi_lte_pdcch_cce_tables gives them on the
+ *      host): REGs as 36.211 6.2.4 counts them, the walk of 6.8.5 (k' outer, l' inner), the quadruplet interleaver of 36.212 5.1.4.2.1 and
+ *      the cyclic shift by N_id_cell.  In two respects they are the reference's and not 36.211's, by default: (i) the PHICH groups the walk
+ *      steps over are those of the PHICH section below -- numbered past the PCFICH's four REGs in the order 6.7.4 lists them, which is not
+ *      ascending once they wrap round the band's edge, so that a PHICH REG can be a wrong one or a PCFICH REG; (ii) with four ports N_reg
+ *      loses N_rb groups to symbol 1's CRS even where N_symbs = 1.  Either moves every CCE of the cells and sizes concerned (about a third
+ *      of all (cell, N_g, N_symbs, ports)); this library's transmitter and PHICH decoder share (i).  MI_LTE_PDCCH_SEARCH_36211_REGS builds
+ *      the plan's tables as 36.211 6.9.3 and 6.8.1 write both -- what a standard eNodeB sends.
  *   2. k_pdcch_search_decode, one wavefront per (unit, candidate, size).  Candidates: every L in {8, 4, 2, 1} and every first CCE with
  *      cce mod L = 0 and cce + L <= N_cce.  With N = n_bits + 16, a pair with N >= 72 L is skipped (no redundancy left).  Per pair:
  *      a. rate un-matching in int32: d[map[r]] = sum over j of soft[r + 3 N j] (r < 3 N, r + 3 N j < 72 L); positions never sent are 0.
- *      b. energy = sum |d|; energy = 0 is no hit whatever the CRC says.  (Step 1's de-mapper never yields a 0: its smallest magnitude is 1, so
- *         a noiseless empty region reads +-1 in the scrambler's pattern and is turned away by the CRC and the RNTI set like any noise.)
+ *      b. energy = sum |d|; energy = 0 is no hit whatever the CRC says.  (With estimates that are not zero step 1's de-mapper never yields a
+ *         0: its smallest magnitude is 1, so a noiseless empty region reads +-1 in the scrambler's pattern and is turned away by the CRC and
+ *         the RNTI set like any noise.  Zero estimates do yield 0, step 1.)
  *      c. the tail-biting decoder of the CQI section, step 2b (the same device code), over the N steps: maximum-correlation Viterbi, all
  *         64 metrics 0 at the start, three laps, the even predecessor on a tie, end state the first maximum in state order, traceback
  *         over all 3 N steps, the bits of the middle lap; metric = the decided word re-encoded and correlated with d.
@@ -1165,6 +1197,7 @@ int  mi_lte_dci_1c_unpack(uint32_t payload, uint32_t n_bits, uint32_t rnti, uint
 #define MI_LTE_PDCCH_SEARCH_MAX_SIZES 4
 #define MI_LTE_PDCCH_SEARCH_MAX_FOUND 16
 #define MI_LTE_PDCCH_SEARCH_ANY_CCE   1u   /* report a hit wherever it lies, not only inside its RNTI's search spaces */
+#define MI_LTE_PDCCH_SEARCH_36211_REGS 2u  /* the plan's tables with the PHICH groups and N_reg of 36.211 (step 1, Positions), not the reference's */
 typedef struct {
     uint32_t rnti, L, cce, n_bits;   /* cce = first CCE */
     uint64_t payload;                /* first DCI bit in bit n_bits-1 */
@@ -1181,6 +1214,10 @@ int  mi_lte_pdcch_search_run(mi_lte_ctx *ctx, mi_lte_pdcch_search_plan *plan, co
                              const uint32_t *d_n_id_cell, uint32_t n_units, uint32_t *h_cfi, uint32_t *h_n_cce, uint32_t *h_n_found,
                              mi_lte_pdcch_found *h_found /* [n_units][MI_LTE_PDCCH_SEARCH_MAX_FOUND] */);
 int  mi_lte_pdcch_search_soft(const mi_lte_pdcch_search_plan *plan, const int8_t **d_soft, uint32_t *unit_stride); /* valid after a run */
+/* a search plan's table for one (cell, N_symbs) on its own (host arithmetic): *n_cce, and the grid indices l*1200 + k of the first min(*n_cce, n_max)
+ * CCEs' 36 resource elements in order.  flags: 0 or MI_LTE_PDCCH_SEARCH_36211_REGS.  MI_LTE_ERR_INVALID_ARG as mi_lte_pdcch_re_tables. */
+int  mi_lte_pdcch_cce_tables(uint32_t N_rb_dl, uint32_t N_ant, uint32_t N_id_cell, float phich_res, uint32_t N_symbs, uint32_t flags,
+                             uint32_t *n_cce, uint32_t *cce_re /* [36 n_max] */, uint32_t n_max);
 /* A C-RNTI's DCI format 0 / 1A as this library's transmitter packs them (tx_ctrl.cc, pinned to the reference's dci_0_pack / dci_1a_pack; packer
  * and unpacker read one field list, dci.h), host arithmetic (dci.cc).  Both: the flag bit (1 = format 1A, 0 = format 0), then one more flag, then the resource indication value in
  * ceil(log2(N_rb (N_rb + 1) / 2)) bits, decoded over its WHOLE range (36.213 7.1.6.3 / 8.1): with q = floor(RIV / N_rb), r = RIV mod N_rb,

@@ -701,7 +701,7 @@ int mi_lte_pdcch_search_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, f
         ctx->err = "PDCCH search plan: standard bandwidths, 1/2/4 ports, PHICH resource in (0, 2], normal PHICH duration";
         return MI_LTE_ERR_UNSUPPORTED;
     }
-    if (n_sizes == 0 || n_sizes > MI_LTE_PDCCH_SEARCH_MAX_SIZES || (flags & ~MI_LTE_PDCCH_SEARCH_ANY_CCE)) return MI_LTE_ERR_INVALID_ARG;
+    if (n_sizes == 0 || n_sizes > MI_LTE_PDCCH_SEARCH_MAX_SIZES || (flags & ~(MI_LTE_PDCCH_SEARCH_ANY_CCE | MI_LTE_PDCCH_SEARCH_36211_REGS))) return MI_LTE_ERR_INVALID_ARG;
     for (uint32_t i = 0; i < n_sizes; i++) {
         if (h_n_bits[i] < 8 || h_n_bits[i] > 64) return MI_LTE_ERR_INVALID_ARG;
         for (uint32_t j = 0; j < i; j++)
@@ -721,7 +721,7 @@ int mi_lte_pdcch_search_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, f
         const int rc = mi_lte_pdcch_re_tables(nrb, cfg->N_ant, cells[c], phich_res, 1, &pcf[(size_t)c * 16], cand.data());
         if (rc != MI_LTE_OK) return rc;
         for (uint32_t ns = 1; ns <= 4; ns++) {
-            ncce[(size_t)c * 4 + ns - 1] = cce_res(nrb, cfg->N_ant, cells[c], phich_res, ns, perm[(size_t)c * 4 + ns - 1]);
+            ncce[(size_t)c * 4 + ns - 1] = cce_res(nrb, cfg->N_ant, cells[c], phich_res, ns, perm[(size_t)c * 4 + ns - 1], (flags & MI_LTE_PDCCH_SEARCH_36211_REGS) != 0);
             max_cce = std::max(max_cce, ncce[(size_t)c * 4 + ns - 1]);
         }
     }

@@ -29,14 +29,22 @@ void phich_group_regs(uint32_t N_rb_dl, uint32_t cell, uint32_t m, const float p
             if (n_hat[j] > pcfich_n[i]) n_hat[j]++; // sequential, against the float REG number, as the reference does
 }
 
-CtrlRegs ctrl_regs(uint32_t N_rb_dl, uint32_t cell, float phich_res)
+CtrlRegs ctrl_regs(uint32_t N_rb_dl, uint32_t cell, float phich_res, bool regs_36211)
 {
     CtrlRegs r;
     pcfich_regs(N_rb_dl, cell, r.pcfich_k, r.pcfich_n);
     const uint32_t N_group = (uint32_t)ceilf((float)phich_res * ((float)N_rb_dl / (float)8));
+    std::vector<uint32_t> free_reg; // 36.211 6.9.3: the REGs of symbol 0 the PCFICH left, numbered from the lowest frequency up
+    for (uint32_t n = 0; regs_36211 && n < 2 * N_rb_dl; n++)
+        if (std::find(r.pcfich_k, r.pcfich_k + 4, 6 * n) == r.pcfich_k + 4) free_reg.push_back(n);
     for (uint32_t m = 0; m < N_group; m++) {
         uint32_t n_hat[3];
-        phich_group_regs(N_rb_dl, cell, m, r.pcfich_n, n_hat);
+        if (regs_36211) {
+            const uint32_t n_l = (uint32_t)free_reg.size();
+            for (uint32_t i = 0; i < 3; i++) n_hat[i] = free_reg[(cell + m + i * n_l / 3) % n_l];
+        } else {
+            phich_group_regs(N_rb_dl, cell, m, r.pcfich_n, n_hat);
+        }
         for (uint32_t i = 0; i < 3; i++) r.phich_k.push_back(n_hat[i] * 6);
     }
     return r;
@@ -54,12 +62,12 @@ void cc_interleaver_order(uint32_t n, std::vector<uint32_t> &order)
         }
 }
 
-uint32_t cce_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_res, uint32_t N_symbs, std::vector<uint32_t> &perm)
+uint32_t cce_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_res, uint32_t N_symbs, std::vector<uint32_t> &perm, bool regs_36211)
 {
     perm.clear();
-    const CtrlRegs cr = ctrl_regs(N_rb_dl, cell, phich_res);
+    const CtrlRegs cr = ctrl_regs(N_rb_dl, cell, phich_res, regs_36211);
     int64_t n_reg = (int64_t)N_symbs * (N_rb_dl * 3) - N_rb_dl - 4 - (int64_t)cr.phich_k.size();
-    if (N_ant == 4) n_reg -= N_rb_dl;
+    if (N_ant == 4 && (N_symbs > 1 || !regs_36211)) n_reg -= N_rb_dl; // (the reference takes symbol 1's CRS off a region that has no symbol 1)
     if (n_reg <= 0) return 0;
     const uint32_t N_reg = (uint32_t)n_reg, N_cce = N_reg / 9;
     std::vector<uint32_t> reg(4 * (size_t)N_reg, NO_RE); // REG m: its 4 RE indices (l*1200 + k)
@@ -140,6 +148,19 @@ int mi_lte_pdcch_re_tables(uint32_t N_rb_dl, uint32_t N_ant, uint32_t N_id_cell,
             if ((N_id_cell % 3) != (j % 3)) pcfich[i * 4 + idx++] = k[i] + j;
     }
     candidate_res(N_rb_dl, N_ant, N_id_cell, phich_res, N_symbs, cand);
+    return MI_LTE_OK;
+}
+
+// every CCE's resource elements (include/mi_lte.h: "PDCCH, 3GPP mode"): what a search plan holds for one (cell, N_symbs)
+int mi_lte_pdcch_cce_tables(uint32_t N_rb_dl, uint32_t N_ant, uint32_t N_id_cell, float phich_res, uint32_t N_symbs, uint32_t flags, uint32_t *n_cce,
+                            uint32_t *cce_re /*[36 n_max]*/, uint32_t n_max)
+{
+    if (!n_cce || (n_max && !cce_re) || !standard_ctrl_cfg(N_rb_dl, phich_res) || !(N_ant == 1 || N_ant == 2 || N_ant == 4) || N_id_cell > 503 || N_symbs < 1 ||
+        N_symbs > 4 || (flags & ~MI_LTE_PDCCH_SEARCH_36211_REGS))
+        return MI_LTE_ERR_INVALID_ARG;
+    std::vector<uint32_t> perm;
+    *n_cce = cce_res(N_rb_dl, N_ant, N_id_cell, phich_res, N_symbs, perm, (flags & MI_LTE_PDCCH_SEARCH_36211_REGS) != 0);
+    std::copy(perm.begin(), perm.begin() + 36 * (size_t)std::min(*n_cce, n_max), cce_re);
     return MI_LTE_OK;
 }
 

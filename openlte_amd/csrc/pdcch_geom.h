@@ -24,13 +24,15 @@ void pcfich_regs(uint32_t N_rb_dl, uint32_t cell, uint32_t k[4], float n[4]);
 void phich_group_regs(uint32_t N_rb_dl, uint32_t cell, uint32_t m, const float pcfich_n[4], uint32_t n_hat[3]);
 // both for a cell whose group count follows from N_g
 struct CtrlRegs { uint32_t pcfich_k[4]; float pcfich_n[4]; std::vector<uint32_t> phich_k; };
-CtrlRegs ctrl_regs(uint32_t N_rb_dl, uint32_t cell, float phich_res);
+// (regs_36211: the PHICH groups numbered as 36.211 6.9.3 writes it, over the REGs the PCFICH left in ascending order -- MI_LTE_PDCCH_SEARCH_36211_REGS)
+CtrlRegs ctrl_regs(uint32_t N_rb_dl, uint32_t cell, float phich_res, bool regs_36211 = false);
 
 // read-out order of the sub-block interleaver over n positions, dummies skipped (36.212 5.1.4.2.1): order[k] = natural position read k-th
 void cc_interleaver_order(uint32_t n, std::vector<uint32_t> &order);
 // the resource elements of every CCE of one (cell, N_symbs) in order, 36 per CCE: perm[36 N_cce ..] (plus the REGs behind the last whole CCE);
-// returns N_cce
-uint32_t cce_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_res, uint32_t N_symbs, std::vector<uint32_t> &perm);
+// returns N_cce.  regs_36211: ctrl_regs' numbering, and N_reg counted as 36.211 6.8.1 does (four ports lose N_rb groups to symbol 1's CRS only
+// where the region has a symbol 1)
+uint32_t cce_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_res, uint32_t N_symbs, std::vector<uint32_t> &perm, bool regs_36211 = false);
 // RE lists of the six common-search-space candidates for one (cell, N_symbs)
 void candidate_res(uint32_t N_rb_dl, uint32_t N_ant, uint32_t cell, float phich_res, uint32_t N_symbs, uint32_t *out /*[N_CAND][RE_MAX]*/);
 // where received bit k of E lands in d[3*N_c] (rate_unmatch_conv :11597-11755)

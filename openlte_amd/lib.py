@@ -342,7 +342,7 @@ class DciCrnti(C.Structure):
                [("alloc", PdschAlloc)]
 
 
-PDCCH_SEARCH_MAX_SIZES, PDCCH_SEARCH_MAX_FOUND, PDCCH_SEARCH_ANY_CCE = 4, 16, 1
+PDCCH_SEARCH_MAX_SIZES, PDCCH_SEARCH_MAX_FOUND, PDCCH_SEARCH_ANY_CCE, PDCCH_SEARCH_36211_REGS = 4, 16, 1, 2
 
 
 class CoarseTiming(C.Structure):
@@ -560,6 +560,7 @@ def load_library():
     L.mi_lte_dci_1a_unpack.argtypes = [u32, u32, u32, u32, u32, C.POINTER(PdcchDci)]
     L.mi_lte_dci_1c_unpack.argtypes = [u32, u32, u32, u32, u32, C.POINTER(PdcchDci)]
     L.mi_lte_pdcch_search_space.argtypes = [u32, u32, u32, u32, u32p, C.POINTER(u32)]
+    L.mi_lte_pdcch_cce_tables.argtypes = [u32, u32, u32, C.c_float, u32, u32, C.POINTER(u32), u32p, u32]
     L.mi_lte_pdcch_search_plan_create.argtypes = [vp, C.POINTER(DlCfg), C.c_float, u32, u32, u32p, u32, u32p, u32, C.POINTER(vp)]
     L.mi_lte_pdcch_search_plan_set_rntis.argtypes = [vp, vp, u32p, u32]
     L.mi_lte_pdcch_search_plan_destroy.argtypes = [vp, vp]
@@ -1235,12 +1236,13 @@ class PdcchSearchPlan:
     """mi_lte_pdcch_search_plan: the blind search over the whole control region (include/mi_lte.h: "PDCCH, 3GPP mode") for the listed cells
     and DCI sizes; the RNTI set is exactly what set_rntis was given last (empty at first)."""
 
-    def __init__(self, ctx, cfg, cells, sizes, rntis=(), phich_res=1.0, any_cce=False, phich_dur_extended=0):
+    def __init__(self, ctx, cfg, cells, sizes, rntis=(), phich_res=1.0, any_cce=False, phich_dur_extended=0, regs_36211=False):
         self.ctx, self.cfg = ctx, cfg
         h = C.c_void_p()
         cells, sizes = np.ascontiguousarray(cells, np.uint32), np.ascontiguousarray(sizes, np.uint32)
         ctx._check(ctx.L.mi_lte_pdcch_search_plan_create(ctx.h, C.byref(cfg), float(phich_res), int(phich_dur_extended),
-                                                         PDCCH_SEARCH_ANY_CCE if any_cce else 0, cells, len(cells), sizes, len(sizes), C.byref(h)))
+                                                         (PDCCH_SEARCH_ANY_CCE if any_cce else 0) | (PDCCH_SEARCH_36211_REGS if regs_36211 else 0), cells,
+                                                         len(cells), sizes, len(sizes), C.byref(h)))
         self.h = h
         if len(rntis):
             try:
@@ -1389,6 +1391,15 @@ def dci_unpack(fmt, payload, n_bits, rnti, n_rb_dl, n_ant):
     L = load_library()
     f = L.mi_lte_dci_1a_unpack if fmt == 0 else L.mi_lte_dci_1c_unpack
     return f(int(payload), int(n_bits), int(rnti), int(n_rb_dl), int(n_ant), C.byref(d)), d
+
+
+def pdcch_cce_tables(n_rb_dl, n_ant, cell, phich_res, n_symbs, regs_36211=False):
+    """mi_lte_pdcch_cce_tables: (N_cce, uint32 [N_cce, 36] grid indices of every CCE's resource elements) as a search plan holds them."""
+    n, out = C.c_uint32(), np.zeros(36 * 128, np.uint32)
+    rc = load_library().mi_lte_pdcch_cce_tables(n_rb_dl, n_ant, cell, float(phich_res), n_symbs, PDCCH_SEARCH_36211_REGS if regs_36211 else 0, C.byref(n), out, 128)
+    if rc != 0:
+        raise MiLteError("mi_lte_pdcch_cce_tables failed: %d" % rc, rc)
+    return n.value, out[:36 * n.value].reshape(-1, 36).copy()
 
 
 def pdcch_search_space(rnti, subfr_num, n_cce, L):
@@ -1675,10 +1686,11 @@ class Context:
         """The PHICH decoder for the listed cells: PhichPlan.decode_dev gives metric, hi and the stage taps of every (group, sequence)."""
         return PhichPlan(self, cfg, cells, phich_res, 0)
 
-    def pdcch_search_plan(self, cfg, cells, sizes, rntis=(), phich_res=1.0, any_cce=False):
+    def pdcch_search_plan(self, cfg, cells, sizes, rntis=(), phich_res=1.0, any_cce=False, regs_36211=False):
         """The blind PDCCH search: every CCE-aligned candidate at L = 8, 4, 2, 1 against each of the DCI `sizes` (bits), hits reported for the
-        RNTIs listed -- inside their own or the common search space, or anywhere with any_cce."""
-        return PdcchSearchPlan(self, cfg, cells, sizes, rntis, phich_res, any_cce)
+        RNTIs listed -- inside their own or the common search space, or anywhere with any_cce.  regs_36211: the tables of
+        MI_LTE_PDCCH_SEARCH_36211_REGS (a standard eNodeB's positions, not the reference's)."""
+        return PdcchSearchPlan(self, cfg, cells, sizes, rntis, phich_res, any_cce, regs_36211=regs_36211)
 
     def pusch_plan(self, cfg, ulcfg, unit_subfr_num, unit_n_id_cell, allocs, uci=None):
         """A reference-mode PUSCH plan.  It has no control information: a `uci` is refused (MiLteError, -4)."""
