@@ -48,9 +48,19 @@ inline uint32_t pusch_rx_s_par(uint32_t n_rx, uint32_t M_max, uint32_t words_max
     return 0;
 }
 
-// The families of k_pusch_demod instantiations: <T, SPEC>, <T, true, PuschLlr>, <T, true, PuschLlrNoise>, <T, true, PuschLlrRx<n_rx, noise>>,
-// <T, true, PuschLlrMmse<n_rx>>
+// The families of k_pusch_demod instantiations, one per argument block of uplink.hip (PuschNoLlr, PuschLlr, PuschLlrNoise,
+// PuschLlrRx<n_rx, noise>, PuschLlrMmse<n_rx>); pusch_variant_compiled says which of them exist at which width
 enum class PuschFamily { PLAIN, LLR, LLR_NOISE, LLR_RX, LLR_MMSE };
+
+// Whether k_pusch_demod is compiled for a family at a workgroup width and antenna count: the single-antenna variants at the four widths, the
+// combining ones (two or four antennas) at 192 and 256 only.  uplink.hip instantiates by it, and pusch_launch_plan below plans nothing else
+// (tests/test_pusch_launch_cpu.py, tests/test_pusch_mmse_launch_cpu.py).
+constexpr bool pusch_variant_compiled(PuschFamily family, uint32_t threads, uint32_t n_rx)
+{
+    const bool single    = n_rx == 1 && (threads == 64 || threads == 128 || threads == 192 || threads == 256);
+    const bool combining = (n_rx == 2 || n_rx == 4) && (threads == 192 || threads == 256);
+    return family == PuschFamily::LLR_RX ? combining : family == PuschFamily::LLR_MMSE ? single || combining : single;
+}
 
 struct PuschLaunch {
     PuschFamily family;

@@ -210,17 +210,33 @@ __device__ __forceinline__ void dft_pass(const float2 *__restrict__ in, float2 *
 // compiler knows) -- and the index products are 24-bit multiplies (v_mul_lo_u32 / v_mad_u64_u32 issue at a quarter of the rate)
 // SPEC = the 3GPP mode's demodulator (mi_lte_pusch_plan_create_3gpp): the pre-decoder's output scaled by 1 / sqrt(M) as 36.211 5.3.3 has it,
 // where the reference -- and SPEC = false -- multiplies by sqrt(M).  One factor; everything else is the same code.
-// LLR = the 3GPP mode's opt-in max-log demapper (MI_LTE_DEMAP_MAXLOG, include/mi_lte.h "PUSCH, 3GPP mode: max-log soft-decision demapping"):
-// a pass of its own over the LDS-resident estimates forms the twelve rho_s = M / sum_k hn_k(s) and the allocation's gain before the
-// symbol-group loop, and the de-mapper writes clamp(rint(g L)) with llr_axis / llr_byte (demap_llr.h) in place of demap_symbol.  It is the
-// instantiation with one more kernel argument, k_pusch_demod<THREADS, true, PuschLlr> (launched and listed as k_pusch_demod_llr); without
-// that argument every `if constexpr (LLR)` drops out and k_pusch_demod<THREADS, SPEC> has the signature and the code it had.
-// The noise-referenced gain (mi_lte_pusch_plan_set_llr_noise) is a further instantiation, k_pusch_demod<THREADS, true, PuschLlrNoise> (launched
-// and listed as k_pusch_demod_llr too): one more pass over the LDS-resident estimates in front of the rho pass, the second differences of
-// the two DMRS least-squares rows, gives sigma2_a, and g_a = noise / sigma2_a.  Its two arguments and its LDS slots are PuschLlrNoise's alone:
-// with the setter off the launch is PuschLlr's, with the code, the argument block and the LDS it had.
-struct PuschNoLlr {};
+// LA = the variant: the kernel's last argument is one of the blocks below, whose constants say what the kernel does with it.  A constant
+// that is off drops its `if constexpr` sections out, and with N_RX = 1 each antenna loop has one trip.
+//   block                 launched as              what it adds; its LDS behind the scrambling words
+//   PuschNoLlr            k_pusch_demod            nothing (demap_symbol's soft bits); none
+//   PuschLlr              k_pusch_demod_llr        LLR, the max-log de-mapper (MI_LTE_DEMAP_MAXLOG): a pass over the LDS-resident estimates forms the
+//                                                  twelve rho_s = M / sum_k hn_k(s) and the gain before the symbol-group loop (the automatic gain needs
+//                                                  them all); the de-mapper writes clamp(rint(g L)) (demap_llr.h).  wsum[4][12] (double) | rho[12] (float)
+//   PuschLlrNoise         k_pusch_demod_llr        NOISE (mi_lte_pusch_plan_set_llr_noise): a pass in front of the rho pass, the second differences of
+//                                                  the two DMRS rows, gives sigma2, and g = noise / sigma2.  PuschLlr's | nsum[4] (double)
+//   PuschLlrRx<N, NOISE>  k_pusch_demod_llr_rx     N_RX = 2 or 4 (mi_lte_pusch_plan_set_rx_antennas): antenna r of unit u is subframe r ant_stride + u,
+//                                                  every pass loops over the antennas and the equaliser forms z = (sum_r y_r conj(h_r)) / sum_r |h_r|^2.
+//                                                  NOISE = false leaves noise and s2_out unused.  PuschLlrNoise's, behind N_RX sets of estimate rows
+//   PuschLlrMmse<N>       k_pusch_demod_llr_mmse   MMSE and NOISE, N_RX = 1, 2 or 4 (mi_lte_pusch_plan_set_equaliser): sigma2 is reduced behind a barrier
+//                                                  of its own; the rho pass sums q = 1 / (P + sigma2) in place of hn = 1 / P and finishes with nu_s =
+//                                                  sigma2 mean(q), w_s = (1 - nu_s) / nu_s; the equaliser multiplies by q, the de-mapper takes t = x / nu_s
+//                                                  and w_s, the gain is the noise setter's scale.  PuschLlrNoise's: nu_s in rho's floats, w_s in wsum's
+//                                                  first twelve doubles, which their finishing threads have read by then
+// Every sum of these passes is in double and in a fixed order (thread, xor butterfly in the wavefront, the wavefronts' LDS slots ascending;
+// antennas ascending) and there are no atomics: two runs give the same bytes.  The blocks stay separate types, fields in this order: a
+// superset struct would move ant_stride and nu_out in the kernel argument segment.
+struct PuschNoLlr {
+    static constexpr PuschFamily FAMILY = PuschFamily::PLAIN;
+    static constexpr bool LLR = false, NOISE = false, MMSE = false; static constexpr uint32_t N_RX = 1;
+};
 struct PuschLlr {
+    static constexpr PuschFamily FAMILY = PuschFamily::LLR;
+    static constexpr bool LLR = true, NOISE = false, MMSE = false; static constexpr uint32_t N_RX = 1;
     float           gain, auto_t; // gain > 0: fixed; 0: automatic, g = auto_t / (4 A^2 mean rho)
     uint32_t        lds_off;      // float offset in the dynamic LDS of wsum[4][12] (double) | rho[12] (float)
     float          *g_out, *rho_out; // [n_alloc], [n_alloc][12]: the taps
@@ -228,37 +244,24 @@ struct PuschLlr {
     const uint32_t *x_off;        // [n_alloc]: float2 offset of the allocation's 12 M symbols in x_tap
 };
 struct PuschLlrNoise : PuschLlr {
+    static constexpr PuschFamily FAMILY = PuschFamily::LLR_NOISE;
+    static constexpr bool NOISE = true;
     float  noise;  // g = noise / sigma2 of the DMRS noise estimate in place of either gain of PuschLlr
     float *s2_out; // [n_alloc]: the sigma2 tap
 };
-// Receive-antenna combining (mi_lte_pusch_plan_set_rx_antennas, include/mi_lte.h "PUSCH, 3GPP mode: receive-antenna combining") is one more
-// family, k_pusch_demod<THREADS, true, PuschLlrRx<N_RX, NOISE>> (launched and listed as k_pusch_demod_llr_rx), N_RX = 2 or 4: the grid of
-// antenna r of unit u is subframe r ant_stride + u, the LDS holds N_RX sets of the nine estimate rows in front of the twiddles, the estimate
-// phase, the noise pass and the rho pass loop over the antennas, and the equaliser's (sub-carrier, slot) item forms
-// z = (sum_r y_r conj(h_r)) / sum_r |h_r|^2.  The transform, the de-mapper and every buffer are the single-antenna ones.  The argument block
-// and the LDS slots are PuschLlrNoise's (NOISE = false leaves noise and s2_out unused) plus the stride.  With N_RX = 1 -- every other
-// instantiation -- each antenna loop has one trip and each `if constexpr (N_RX > 1)` drops out.
 template <uint32_t N, bool NOISE_>
 struct PuschLlrRx : PuschLlrNoise {
+    static constexpr PuschFamily FAMILY = PuschFamily::LLR_RX;
+    static constexpr bool NOISE = NOISE_; static constexpr uint32_t N_RX = N;
     uint32_t ant_stride; // subframes between the grids of antennas r and r + 1 of one unit
 };
-template <typename T> struct RxOf { static constexpr uint32_t N = 1; static constexpr bool NOISE = false; };
-template <uint32_t N_, bool NOISE_> struct RxOf<PuschLlrRx<N_, NOISE_>> { static constexpr uint32_t N = N_; static constexpr bool NOISE = NOISE_; };
-// MMSE equalisation (mi_lte_pusch_plan_set_equaliser, include/mi_lte.h "PUSCH, 3GPP mode: MMSE equalisation") is the last family,
-// k_pusch_demod<THREADS, true, PuschLlrMmse<N_RX>> (launched and listed as k_pusch_demod_llr_mmse), N_RX = 1, 2 or 4: the noise pass's sums
-// are reduced behind a barrier of its own, so that sigma2 exists before the reliability pass; that pass sums q = 1 / (P + sigma2) in place of
-// hn = 1 / P and its twelve finishing threads form nu_s = sigma2 mean(q), w_s = (1 - nu_s) / nu_s and the two taps; the equaliser item
-// multiplies by q; the de-mapper takes t = x / nu_s and w_s, and the gain is the noise setter's scale.  The LDS is the noise launch's:
-// nu_s lies in rho's twelve floats and w_s in wsum's first twelve doubles, which their finishing threads have read by then.  The argument
-// block is PuschLlrNoise's plus the nu tap and, for N_RX > 1, the antenna stride.  Every other instantiation has MMSE = false and each
-// `if constexpr (MMSE)` drops out of it.
 template <uint32_t N>
 struct PuschLlrMmse : PuschLlrNoise {
+    static constexpr PuschFamily FAMILY = PuschFamily::LLR_MMSE;
+    static constexpr bool MMSE = true; static constexpr uint32_t N_RX = N;
     float   *nu_out;     // [n_alloc][12]: the nu tap
     uint32_t ant_stride; // as PuschLlrRx's; unused for N = 1
 };
-template <typename T> struct MmseOf { static constexpr bool ON = false; static constexpr uint32_t N = 1; };
-template <uint32_t N_> struct MmseOf<PuschLlrMmse<N_>> { static constexpr bool ON = true; static constexpr uint32_t N = N_; };
 
 // h(s) of data symbol sp (0 .. 5) of a slot and hn = 1 / |h|^2 as the one-tap equaliser uses it, from the slot's DMRS estimate: magnitude and
 // slope, u = exp(i ang_b), f1 .. f3 = exp(i n f_ang) for n = 1, 2, 3 (liblte_phy.cc:13770-13780: symbols 0-2 / 3-5 of a slot lie -3..-1 /
@@ -274,30 +277,34 @@ __device__ __forceinline__ void slot_h(float mag, float f_mag, float2 u, float2 
     hn = 1.0f / (h_re * h_re + h_im * h_im);
 }
 
-__device__ __forceinline__ PuschNoLlr llr_args() { return PuschNoLlr{}; }
-__device__ __forceinline__ const PuschLlr &llr_args(const PuschLlr &la) { return la; }
-__device__ __forceinline__ const PuschLlrNoise &llr_args(const PuschLlrNoise &la) { return la; }
-template <uint32_t N, bool NOISE_> __device__ __forceinline__ const PuschLlrRx<N, NOISE_> &llr_args(const PuschLlrRx<N, NOISE_> &la) { return la; }
-template <uint32_t N> __device__ __forceinline__ const PuschLlrMmse<N> &llr_args(const PuschLlrMmse<N> &la) { return la; }
+// sigma2 of the noise pass from its wavefronts' sums: S = nsum[0] + nsum[1] + .. in this order, over the 120 N_prb second differences an
+// antenna contributes (2 slots x 10 N_prb terms of 6 sigma^2 each) and, combining, the antennas' mean: MRC assumes equal noise power per
+// antenna.  Every thread forms the same sum in the same order.
+template <uint32_t THREADS, uint32_t N_RX>
+__device__ __forceinline__ float noise_sigma2(const double *nsum, uint32_t N_prb)
+{
+    double S = nsum[0];
+    for (uint32_t w = 1; w < THREADS / 64; w++) S += nsum[w];
+    if constexpr (N_RX > 1) return (float)(S / (120.0 * (double)N_prb * (double)N_RX));
+    else return (float)(S / (120.0 * (double)N_prb));
+}
+
 #ifndef WPE_LLR
 #define WPE_LLR 4
 #endif
 
-template <uint32_t THREADS, bool SPEC = false, typename... LlrArgs>
+template <uint32_t THREADS, bool SPEC = false, typename LA = PuschNoLlr>
 // (four antennas: the equaliser item carries four sets of estimates and grid values for six symbols, and the LDS of such a launch keeps the
 // occupancy under 4 from 10 PRB on anyway -- 3 waves per SIMD, 168 registers, in place of a spill)
-__attribute__((amdgpu_waves_per_eu((RxOf<LlrArgs>::N * ... * 1u) * (MmseOf<LlrArgs>::N * ... * 1u) == 4 ? 3 : sizeof...(LlrArgs) ? WPE_LLR : WPE, 8)))
+__attribute__((amdgpu_waves_per_eu(LA::N_RX == 4 ? 3 : LA::LLR ? WPE_LLR : WPE, 8)))
 __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict__ subframes, uint32_t sf_stride,
                                                      const mi_lte_pdsch_alloc *__restrict__ allocs, const PuschDesc *__restrict__ desc,
                                                      const float *__restrict__ dmrs_pool, GoldTables gt, int8_t *__restrict__ e_base,
                                                      const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len, uint32_t M_max,
-                                                     uint32_t S_par, float r_S_par, const PuschShape *__restrict__ shapes, LlrArgs... la_pack)
+                                                     uint32_t S_par, float r_S_par, const PuschShape *__restrict__ shapes, [[maybe_unused]] const LA la)
 {
-    constexpr bool MMSE = (MmseOf<LlrArgs>::ON || ...); // MMSE equalisation (PuschLlrMmse); false everywhere else
-    constexpr bool LLR = sizeof...(LlrArgs) == 1, NOISE = (std::is_same<LlrArgs, PuschLlrNoise>::value || ...) || (RxOf<LlrArgs>::NOISE || ...) || MMSE;
-    constexpr uint32_t N_RX = (RxOf<LlrArgs>::N * ... * 1u) * (MmseOf<LlrArgs>::N * ... * 1u); // receive antennas combined (PuschLlrRx, PuschLlrMmse); 1 everywhere else
-    static_assert(sizeof...(LlrArgs) <= 1 && (!LLR || SPEC), "the max-log de-mapper belongs to the 3GPP mode");
-    [[maybe_unused]] const auto la = llr_args(la_pack...);
+    constexpr bool LLR = LA::LLR, NOISE = LA::NOISE, MMSE = LA::MMSE; constexpr uint32_t N_RX = LA::N_RX; // the variant, as its block declares it
+    static_assert(!LLR || SPEC, "the max-log de-mapper belongs to the 3GPP mode");
     extern __shared__ __attribute__((aligned(16))) float sm[];
     // LDS: est[N_RX][9][M_max] (mag0 mag1 dmag | unit vectors of ang0, ang1, dang; one set per antenna) | tw[M_max] | buf A[S_par][M_max] |
     // buf B[S_par][M_max] (float2) | scrambling words
@@ -414,14 +421,13 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
         }
         if constexpr (MMSE) { // sigma2 before the reliability pass, which adds it to every P: the noise section's sum and quotient, in every thread
             __syncthreads();
-            double S = nsum[0];
-            for (uint32_t w = 1; w < THREADS / 64; w++) S += nsum[w];
-            if constexpr (N_RX > 1) s2_m = (float)(S / (120.0 * (double)N_prb * (double)N_RX));
-            else s2_m = (float)(S / (120.0 * (double)N_prb));
+            s2_m = noise_sigma2<THREADS, N_RX>(nsum, N_prb);
         }
         for (uint32_t b = 0; b < 2; b++) { // slot: six data symbols per pass, so a thread carries six partial sums
             double part[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             for (uint32_t i = threadIdx.x; i < M; i += THREADS) {
+                // (Here and in the equaliser item the combining form stays a branch of its own, not the single-antenna loop with more trips: it
+                // sums from 0.0f, and 0.0f + x is not x for x = -0, so one merged loop would change the sign of zeros the symbol tap can show)
                 if constexpr (N_RX > 1) { // hn = 1 / P, P = sum_r |h_r|^2 in float with r ascending: the float the combining equaliser multiplies with
                     float P[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -489,11 +495,7 @@ __global__ __launch_bounds__(THREADS) void k_pusch_demod(const float *__restrict
             gd  = (s2_m > 0.0f && s2_m <= 3.4028234e38f) ? (double)la.noise : 0.0;
             if (threadIdx.x == 0) la.s2_out[a_idx] = s2_m;
         } else if constexpr (NOISE) { // every thread forms the same sum in the same order
-            double S = nsum[0];
-            for (uint32_t w = 1; w < THREADS / 64; w++) S += nsum[w];
-            float s2;
-            if constexpr (N_RX > 1) s2 = (float)(S / (120.0 * (double)N_prb * (double)N_RX)); // the antennas' mean: MRC assumes equal noise power per antenna
-            else s2 = (float)(S / (120.0 * (double)N_prb));
+            const float s2 = noise_sigma2<THREADS, N_RX>(nsum, N_prb);
             const float gf = (float)((double)la.noise / (double)s2);
             // sigma2 0 or not finite, or a gain past float: every soft bit 0
             gd = (s2 > 0.0f && s2 <= 3.4028234e38f && fabsf(gf) <= 3.4028234e38f) ? (double)gf : 0.0;
@@ -1190,35 +1192,34 @@ int mi_lte_pusch_plan_soft_bits(const mi_lte_pusch_plan *pl, uint32_t alloc, con
 
 } // extern "C"
 
-// The workgroup's width as a template argument: f(PuschWidth<64 | 128 | 192 | 256>) for what pusch_launch_plan (pusch_launch.h) chose
+// The workgroup's width as a template argument: f(PuschWidth<64 | 128 | 192 | 256>{}) for what pusch_launch_plan (pusch_launch.h) chose
 template <uint32_t T> using PuschWidth = std::integral_constant<uint32_t, T>;
 template <typename F> static int pusch_width(uint32_t threads, F f)
 {
     return threads == 64 ? f(PuschWidth<64>{}) : threads == 128 ? f(PuschWidth<128>{}) : threads == 192 ? f(PuschWidth<192>{}) : f(PuschWidth<256>{});
 }
 
-// The demodulator's launch as L shapes it, k_pusch_demod<T, SPEC, Llr...>: Llr is the kernel's own trailing pack, nothing or the family's
-// argument block (PuschLlr, PuschLlrNoise, PuschLlrRx<N, NZ>, PuschLlrMmse<N>).  lds_limit: the device's per-workgroup LDS, read for a combining launch only.
-template <uint32_t T, bool SPEC, typename... Llr>
-static int pusch_launch(PuschWidth<T>, std::bool_constant<SPEC>, mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const PuschLaunch &L, size_t lds_limit,
-                        const float *d_subframes, const Llr &...la_pack)
+// The demodulator's launch as L shapes it, k_pusch_demod<T, SPEC, LA> with L's argument block `la`.  The kernel is instantiated only where
+// pusch_variant_compiled (pusch_launch.h) says the variant exists, and without SPEC for the plain block alone; pusch_launch_plan plans
+// nothing else, so the other branch is never reached.  lds_limit: the device's per-workgroup LDS, read for a combining launch only.
+template <uint32_t T, bool SPEC, typename LA>
+static int pusch_launch(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, const PuschLaunch &L, size_t lds_limit, const float *d_subframes, const LA &la)
 {
-    [[maybe_unused]] constexpr uint32_t N  = (RxOf<Llr>::N * ... * 1u) * (MmseOf<Llr>::N * ... * 1u);
-    [[maybe_unused]] constexpr bool     NZ = (RxOf<Llr>::NOISE || ...), MM = (MmseOf<Llr>::ON || ...);
-    if constexpr (N > 1) {
-        // More than 64 KB of dynamic LDS has to be asked for, per kernel and device (as bcjr.hip does for k_bcjr_block): once per plan and
-        // instantiation
-        const uint32_t bit = 1u << ((T == 256 ? 1 : 0) + (N == 4 ? 2 : 0) + (NZ ? 4 : 0) + (MM ? 8 : 0));
-        if (!(pl->rx_lds_set & bit)) {
-            MI_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k_pusch_demod<T, true, Llr...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
-            pl->rx_lds_set |= bit;
+    if constexpr (pusch_variant_compiled(LA::FAMILY, T, LA::N_RX) && (SPEC || !LA::LLR)) {
+        if constexpr (LA::N_RX > 1) {
+            // More than 64 KB of dynamic LDS has to be asked for, per kernel and device (as for k_bcjr_block, bcjr.hip): once per plan and instantiation
+            const uint32_t bit = 1u << ((T == 256 ? 1 : 0) + (LA::N_RX == 4 ? 2 : 0) + (LA::NOISE ? 4 : 0) + (LA::MMSE ? 8 : 0));
+            if (!(pl->rx_lds_set & bit)) {
+                MI_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k_pusch_demod<T, SPEC, LA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
+                pl->rx_lds_set |= bit;
+            }
         }
-    }
-    const GoldTables gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
-    MI_LAUNCH(ctx, L.label, (k_pusch_demod<T, SPEC, Llr...>), dim3(pl->core.n_alloc), dim3(T), L.lds_bytes, d_subframes, (uint32_t)mi_lte_ul_subframe_floats(),
-              pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->M_max, L.S_par, recip_up(L.S_par),
-              static_cast<const PuschShape *>(ctx->d_pusch_shapes), la_pack...);
-    return MI_LTE_OK;
+        const GoldTables gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
+        MI_LAUNCH(ctx, L.label, (k_pusch_demod<T, SPEC, LA>), dim3(pl->core.n_alloc), dim3(T), L.lds_bytes, d_subframes, (uint32_t)mi_lte_ul_subframe_floats(),
+                  pl->core.d_allocs, pl->d_desc, pl->d_dmrs, gt, pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->M_max, L.S_par, recip_up(L.S_par),
+                  static_cast<const PuschShape *>(ctx->d_pusch_shapes), la);
+        return MI_LTE_OK;
+    } else { ctx->err = "k_pusch_demod: no such variant at this workgroup width"; return MI_LTE_ERR_UNSUPPORTED; }
 }
 
 // A plan run: the demodulator, then the 3GPP mode's control information and code blocks (ulsch_uci.hip, dlsch3gpp.hip) or the REF dispatch
@@ -1270,28 +1271,25 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
     }
     const PuschLlr      la{pl->demap_gain, auto_t, (uint32_t)(L.lds_off / sizeof(float)), pl->d_llr_gain, pl->d_llr_rho, pl->d_llr_x, pl->d_x_off};
     const PuschLlrNoise ln{la, pl->llr_noise, pl->d_llr_s2};
-    const auto go = [&](auto width, auto spec, const auto &...la_pack) { return pusch_launch(width, spec, ctx, pl, L, lds_limit, d_subframes, la_pack...); };
-    const std::true_type spec3; // every max-log launch is the 3GPP mode's
-    switch (L.family) {
-    case PuschFamily::PLAIN: rc = pusch_width(L.threads, [&](auto w) { return pl->g3 ? go(w, spec3) : go(w, std::false_type{}); }); break;
-    case PuschFamily::LLR: rc = pusch_width(L.threads, [&](auto w) { return go(w, spec3, la); }); break;
-    case PuschFamily::LLR_NOISE: rc = pusch_width(L.threads, [&](auto w) { return go(w, spec3, ln); }); break;
-    case PuschFamily::LLR_RX: { // two widths only, the rule's own choice: the combining kernels exist at no other
-        const uint32_t stride = pl->ant_stride;
-        const auto rx = [&](auto w) {
-            return L.n_rx == 2 ? (L.noise ? go(w, spec3, PuschLlrRx<2, true>{ln, stride}) : go(w, spec3, PuschLlrRx<2, false>{ln, stride}))
-                               : (L.noise ? go(w, spec3, PuschLlrRx<4, true>{ln, stride}) : go(w, spec3, PuschLlrRx<4, false>{ln, stride}));
-        };
-        rc = L.threads == 192 ? rx(PuschWidth<192>{}) : rx(PuschWidth<256>{});
+    // width and block to the one launch; SPEC is the plan's mode (every max-log launch is the 3GPP mode's)
+    const auto go = [&](const auto &block) {
+        return pusch_width(L.threads, [&](auto w) {
+            return pl->g3 ? pusch_launch<decltype(w)::value, true>(ctx, pl, L, lds_limit, d_subframes, block)
+                          : pusch_launch<decltype(w)::value, false>(ctx, pl, L, lds_limit, d_subframes, block);
+        });
+    };
+    switch (L.family) { // L's family, antennas and noise gain as the kernel's argument block
+    case PuschFamily::PLAIN: rc = go(PuschNoLlr{}); break;
+    case PuschFamily::LLR: rc = go(la); break;
+    case PuschFamily::LLR_NOISE: rc = go(ln); break;
+    case PuschFamily::LLR_RX:
+        rc = L.n_rx == 2 ? (L.noise ? go(PuschLlrRx<2, true>{ln, pl->ant_stride}) : go(PuschLlrRx<2, false>{ln, pl->ant_stride}))
+                         : (L.noise ? go(PuschLlrRx<4, true>{ln, pl->ant_stride}) : go(PuschLlrRx<4, false>{ln, pl->ant_stride}));
         break;
-    }
-    case PuschFamily::LLR_MMSE: { // one antenna at the four widths, two and four at the combining launch's two
-        const uint32_t stride = pl->ant_stride;
-        const auto rx = [&](auto w) { return L.n_rx == 2 ? go(w, spec3, PuschLlrMmse<2>{ln, pl->d_llr_nu, stride}) : go(w, spec3, PuschLlrMmse<4>{ln, pl->d_llr_nu, stride}); };
-        if (L.n_rx <= 1) rc = pusch_width(L.threads, [&](auto w) { return go(w, spec3, PuschLlrMmse<1>{ln, pl->d_llr_nu, 0u}); });
-        else rc = L.threads == 192 ? rx(PuschWidth<192>{}) : rx(PuschWidth<256>{});
+    case PuschFamily::LLR_MMSE:
+        rc = L.n_rx <= 1 ? go(PuschLlrMmse<1>{ln, pl->d_llr_nu, 0u})
+                         : L.n_rx == 2 ? go(PuschLlrMmse<2>{ln, pl->d_llr_nu, pl->ant_stride}) : go(PuschLlrMmse<4>{ln, pl->d_llr_nu, pl->ant_stride});
         break;
-    }
     }
     if (rc != MI_LTE_OK) return rc;
     MI_HIP_CHECK(ctx, hipGetLastError());

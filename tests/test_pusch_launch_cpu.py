@@ -26,7 +26,7 @@ def test_launch_rule_equals_the_python_restatements(tmp_path):
     equals what the Python models give: the override or pc.threads for one antenna, rxm.threads whatever the override for a combining
     launch; pc.s_par for one antenna, rxm.s_par for combining, "does not fit" exactly where that is 0; rxm.lds_bytes for the combining and
     the single-antenna noise launch, 32 bytes less for the single-antenna max-log launch, 36 M + 8 M (1 + 2 S) + 4 W for the plain one.
-    No sanitizer report."""
+    Every launch that fits is one pusch_variant_compiled says is compiled.  No sanitizer report."""
     qs = queries()
     assert len(qs) == 74 * 3 * len(LIMITS) * len(OVERRIDES) * sum(len(f) for f in FAMILIES.values()) and len(set(qs)) == len(qs)
     path = str(tmp_path / "queries.txt")
@@ -40,8 +40,9 @@ def test_launch_rule_equals_the_python_restatements(tmp_path):
     refused = set()
     for (n_rx, n, q, maxlog, noise, limit, over), line in zip(qs, lines):
         M, W, what = 12 * n, rxm.words(n, q), (n_rx, n, q, maxlog, noise, limit, over, line)
-        fits, family, threads, S, lds_off, lds_bytes, label = line.split()
+        fits, family, threads, S, lds_off, lds_bytes, label, compiled = line.split()
         fits, threads, S, lds_off, lds_bytes = int(fits), int(threads), int(S), int(lds_off), int(lds_bytes)
+        assert compiled == "1" or not fits, what  # a launch that fits is a k_pusch_demod instantiation that exists (pusch_variant_compiled)
         if n_rx == 1:
             assert fits == 1 and threads == (over or pc.threads(M)) and S == pc.s_par(M), what
             if not maxlog:

@@ -28,7 +28,8 @@ def ask(tmp_path, name, script, lines):
 def test_mmse_launch_equals_the_python_restatement(tmp_path):
     """All 74 planned sizes (each alone as M_max) x Q_m x n_rx 1 / 2 / 4 x both LDS limits x the width overrides, MAXLOG with the noise gain
     on and mmse = 1: fits, family llr_mmse, width, S_par, the bytes in front of the LLR block, the dynamic LDS and the label are
-    pusch_mmse_model.launch's; the refusal is the combining launch's."""
+    pusch_mmse_model.launch's; the refusal is the combining launch's.  Every launch that fits is one pusch_variant_compiled says is
+    compiled."""
     qs = [(n_rx, n, q, limit, over) for n_rx in (1, 2, 4) for n in pc.planned_sizes() for q in (2, 4, 6) for limit in LIMITS for over in OVERRIDES]
     assert len(qs) == 74 * 3 * 3 * len(LIMITS) * len(OVERRIDES)
     out = ask(tmp_path, "mmse.txt", "run_pusch_launch_mmse.sh",
@@ -36,8 +37,9 @@ def test_mmse_launch_equals_the_python_restatement(tmp_path):
     refused = set()
     for (n_rx, n, q, limit, over), line in zip(qs, out):
         M, W, what = 12 * n, rxm.words(n, q), (n_rx, n, q, limit, over, line)
-        fits, family, threads, S, lds_off, lds_bytes, label = line.split()
+        fits, family, threads, S, lds_off, lds_bytes, label, compiled = line.split()
         want = mm.launch(n_rx, M, W, limit, over)
+        assert compiled == "1" or not want[0], what  # a launch that fits is a k_pusch_demod instantiation that exists (pusch_variant_compiled)
         assert (int(fits), family, int(threads), int(S), label) == (want[0], want[1], want[2], want[3], want[6]), what
         if want[0]:
             assert (int(lds_off), int(lds_bytes)) == (want[4], want[5]) and (n_rx == 1 or want[5] <= limit), what
@@ -64,4 +66,5 @@ def test_mmse_off_is_the_seven_field_answer(tmp_path):
             n_mmse += 1
         else:
             assert o == b, (b, o)
+        assert o.split()[7] == "1" or o.split()[0] == "0", o  # whatever fits is compiled, with mmse on as with it off
     assert n_mmse > 100

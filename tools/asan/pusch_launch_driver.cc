@@ -2,8 +2,9 @@
 // queries, one per line of the file named on the command line (or of stdin),
 //   M_max words_max maxlog noise n_rx lds_limit threads_override
 // with one line each,
-//   fits family threads S_par lds_off lds_bytes label
-// fits: 1, or 0 for a combining launch that does not fit lds_limit at S_par = 1; family: plain / llr / llr_noise / llr_rx.
+//   fits family threads S_par lds_off lds_bytes label compiled
+// fits: 1, or 0 for a combining launch that does not fit lds_limit at S_par = 1; family: plain / llr / llr_noise / llr_rx; compiled:
+// pusch_variant_compiled for the launch just planned -- whether k_pusch_demod exists for its family, width and antenna count.
 // With --mmse in front, every query has an eighth field, mmse (mi_lte_pusch_plan_set_equaliser), and the family may be llr_mmse.
 //   pusch_launch_driver [--mmse] [query file]
 #include <cstdio>
@@ -26,13 +27,15 @@ int main(int argc, char **argv)
     while (!eight && fscanf(fp, "%u %u %u %u %u %llu %u", &M_max, &words_max, &maxlog, &noise, &n_rx, &limit, &threads) == 7) {
         PuschLaunch L;
         const bool  fits = pusch_launch_plan(M_max, words_max, maxlog != 0, noise != 0, n_rx, (size_t)limit, threads, &L);
-        printf("%d %s %u %u %zu %zu %s\n", fits ? 1 : 0, family[(int)L.family], L.threads, L.S_par, L.lds_off, L.lds_bytes, L.label);
+        printf("%d %s %u %u %zu %zu %s %d\n", fits ? 1 : 0, family[(int)L.family], L.threads, L.S_par, L.lds_off, L.lds_bytes, L.label,
+               pusch_variant_compiled(L.family, L.threads, L.n_rx) ? 1 : 0);
         n++;
     }
     while (eight && fscanf(fp, "%u %u %u %u %u %llu %u %u", &M_max, &words_max, &maxlog, &noise, &n_rx, &limit, &threads, &mmse) == 8) {
         PuschLaunch L;
         const bool  fits = pusch_launch_plan(M_max, words_max, maxlog != 0, noise != 0, n_rx, (size_t)limit, threads, &L, mmse != 0);
-        printf("%d %s %u %u %zu %zu %s\n", fits ? 1 : 0, family[(int)L.family], L.threads, L.S_par, L.lds_off, L.lds_bytes, L.label);
+        printf("%d %s %u %u %zu %zu %s %d\n", fits ? 1 : 0, family[(int)L.family], L.threads, L.S_par, L.lds_off, L.lds_bytes, L.label,
+               pusch_variant_compiled(L.family, L.threads, L.n_rx) ? 1 : 0);
         n++;
     }
     if (fp != stdin) fclose(fp);
