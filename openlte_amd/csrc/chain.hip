@@ -15,6 +15,9 @@
 #include "demap_llr.h"
 #include "soft_pack.h"
 #include "gold_run.h"
+#include "pdsch_launch.h"
+
+using namespace pdsch_geom;
 
 namespace {
 
@@ -87,8 +90,7 @@ __device__ __forceinline__ void pair_table_scan(uint2 *tab, const mi_lte_pdsch_a
     if (ln == 63) tab[n_pairs] = make_uint2(incl, 0u); // total
 }
 
-// k_pdsch_demod's `flags`: the packed hand-over (soft_pack.h), and the scrambling words word by word from the tables as before gold_run.h
-enum : uint32_t { DEMOD_PACK = 1u, DEMOD_GOLD_TABLE = 2u };
+// (k_pdsch_demod's `flags`, DEMOD_PACK and DEMOD_GOLD_TABLE: pdsch_launch.h)
 // words per run of the scrambling sequence's recurrence (gold_run.h; 2 / 4 / 8 measured: profiles/r11_variants_demod_prologue.txt)
 #ifndef GOLD_RUN_R
 #define GOLD_RUN_R 2
@@ -108,18 +110,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
                                                      const mi_lte_pdsch_alloc *__restrict__ allocs,
                                                      const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell,
                                                      GoldTables gt, int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off,
-                                                     uint32_t *__restrict__ e_len, uint32_t max_pairs, uint32_t max_words,
+                                                     uint32_t *__restrict__ e_len, uint32_t max_pairs, uint32_t words_al,
                                                      uint32_t e_lds_cap, uint32_t flags)
 {
     const uint32_t pack = flags & DEMOD_PACK;
     extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // tab[max_pairs+1] (offset, mask | position) | cw[...] | soft bits (packed hand-over: one mask byte per symbol)
     __shared__ uint2 qam_lut[64]; // hard-decision mask -> six soft bits (16QAM / 64QAM)
+    static_assert(sizeof(qam_lut) == REF_STATIC_LDS, "pdsch_launch.h counts the static LDS");
     const uint32_t a_idx = blockIdx.x;
     const mi_lte_pdsch_alloc &al = allocs[a_idx];
     const uint32_t unit = al.unit, sf = subfr_num[unit], cell = n_id_cell[unit], N_ant = ONE_PORT ? 1u : g.N_ant, N_prb = al.N_prb;
     const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : al.mod_type == 1 ? 2 : 1;
     uint2    *tab = reinterpret_cast<uint2 *>(smu);
-    uint32_t *cw  = smu + ((2 * (max_pairs + 1) + 3u) & ~3u); // cw and e_lds stay 16-byte aligned
+    uint32_t *cw  = smu + pairs_words(max_pairs); // cw and e_lds stay 16-byte aligned
     uint32_t first_sc, last_sc;
     sync_window(g.N_rb_dl, first_sc, last_sc);
 
@@ -166,10 +169,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
         return (t.y >> 12) + (uint32_t)__builtin_ctz(m);
     };
     // soft bits are assembled in LDS when they fit and leave with 16-byte stores
-    int8_t    *e_lds  = reinterpret_cast<int8_t *>(cw + max_words);
+    int8_t    *e_lds  = reinterpret_cast<int8_t *>(cw + words_al);
     const bool via_lds = N_bits <= e_lds_cap;
     // the packed hand-over (soft_pack.h): a 16QAM / 64QAM allocation leaves as one bit per soft bit.  Its symbols' masks are collected in LDS,
-    // one byte per symbol (at most 15 600 of them: the host sizes the block for it), and packed after the barrier below
+    // one byte per symbol (at most 17 160 of them: the host sizes the block for it), and packed after the barrier below
     const bool pk = pack && al.mod_type >= 2;
     auto run = [&](auto modc, auto pkc) {
     constexpr uint32_t MOD = decltype(modc)::value, QM = MOD == 3 ? 6 : MOD == 2 ? 4 : MOD == 1 ? 2 : 1;
@@ -420,32 +423,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPACT ? D
 // gain > 0: g = gain.  gain == 0: a first sweep over the allocation's estimate planes sums w (per thread, then inside each wave, then over the
 // waves' LDS slots, always in that order and in double: a run is reproducible) and g = T / (4 A^2 wbar) (T = auto_t: MI_LTE_DEMAP_AUTO_T),
 // rounded to float -- the value llr_gain[allocation] reports is the value the soft bits were scaled with.
-// The noise-referenced gain (mi_lte_pdsch_plan_set_llr_noise) is a further instantiation, k_pdsch_demod_llr<N_ANT, PdschLlrNoise> (launched and
-// listed under the same names): one more argument, no wbar sweep, g = scale / sigma2[unit] of the CRS noise estimate k_dl_crs_noise left
-// (dl_noise.hip).  Without that argument every `if constexpr (NOISE)` drops out and k_pdsch_demod_llr<N_ANT> has the arguments, the LDS and the
-// code it had.
+// The last argument is the variant's block.  PdschLlrGain (empty): the two gains above.  PdschLlrNoise, the noise-referenced gain
+// (mi_lte_pdsch_plan_set_llr_noise; launched and listed under the same names): no wbar sweep, g = scale / sigma2[unit] of the CRS noise
+// estimate k_dl_crs_noise left (dl_noise.hip).  With PdschLlrGain every `if constexpr (Args::NOISE)` drops out and the kernel has the
+// arguments, the LDS and the code it had before the noise-referenced gain.
+struct PdschLlrGain {
+    static constexpr bool NOISE = false;
+};
 struct PdschLlrNoise {
+    static constexpr bool NOISE = true;
     const float *sigma2; // [n_units]: k_dl_crs_noise's estimates of this run
     float        scale;  // g = scale / sigma2[unit] in place of either gain
 };
-template <uint32_t N_ANT, typename... Noise>
+template <uint32_t N_ANT, typename Args>
 __global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict__ subframes, DemodGeom g, const mi_lte_pdsch_alloc *__restrict__ allocs,
                                                          const uint32_t *__restrict__ subfr_num, const uint32_t *__restrict__ n_id_cell, GoldTables gt,
                                                          int8_t *__restrict__ e_base, const uint32_t *__restrict__ e_off, uint32_t *__restrict__ e_len,
-                                                         uint32_t max_pairs, uint32_t max_words, uint32_t e_lds_cap, float gain, float auto_t,
-                                                         float *__restrict__ llr_gain, uint32_t gold_table, Noise... noise)
+                                                         uint32_t max_pairs, uint32_t words_al, uint32_t e_lds_cap, float gain, float auto_t,
+                                                         float *__restrict__ llr_gain, uint32_t gold_table, Args args)
 {
     static_assert(N_ANT == 1 || N_ANT == 2 || N_ANT == 4, "one port, or transmit diversity on two or four");
-    static_assert(sizeof...(Noise) <= 1 && (std::is_same<Noise, PdschLlrNoise>::value && ...), "at most the noise-referenced gain's argument");
-    constexpr bool NOISE = sizeof...(Noise) == 1;
+    static_assert(std::is_same<Args, PdschLlrGain>::value || std::is_same<Args, PdschLlrNoise>::value, "the variant's argument block");
+    constexpr bool NOISE = Args::NOISE;
     extern __shared__ __attribute__((aligned(16))) uint32_t smu[]; // tab[max_pairs+1] (offset, mask | position) | cw[...] | soft bits
     __shared__ double w_wave[4];
+    static_assert(sizeof(w_wave) == LLR_STATIC_LDS, "pdsch_launch.h counts the static LDS");
     const uint32_t a_idx = blockIdx.x;
     const mi_lte_pdsch_alloc &al = allocs[a_idx];
     const uint32_t unit = al.unit, sf = subfr_num[unit], cell = n_id_cell[unit], N_prb = al.N_prb;
     const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : 2; // (a 3GPP plan holds no BPSK allocation)
     uint2    *tab = reinterpret_cast<uint2 *>(smu);
-    uint32_t *cw  = smu + ((2 * (max_pairs + 1) + 3u) & ~3u);
+    uint32_t *cw  = smu + pairs_words(max_pairs);
     uint32_t first_sc, last_sc;
     sync_window(g.N_rb_dl, first_sc, last_sc);
     const uint32_t cfi = al.n_pdcch_symbs ? al.n_pdcch_symbs : g.cfi;
@@ -511,7 +519,7 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict
     auto ldf = [](const char *p, uint32_t off) __attribute__((always_inline)) { return *reinterpret_cast<const float *>(p + off); };
     double gd = (double)gain;
     if constexpr (NOISE) { // every thread forms the same quotient
-        const float s2 = (noise.sigma2[unit], ...), gf = (float)((double)(noise.scale, ...) / (double)s2);
+        const float s2 = args.sigma2[unit], gf = (float)((double)args.scale / (double)s2);
         gd = (s2 > 0.0f && s2 <= 3.4028234e38f && fabsf(gf) <= 3.4028234e38f) ? (double)gf : 0.0; // sigma2 0 or not finite, or a gain past float: every soft bit 0
     } else if (gain == 0.0f) { // wbar: the mean of w over the allocation's symbols
         double part = 0.0;
@@ -544,7 +552,7 @@ __global__ __launch_bounds__(256) void k_pdsch_demod_llr(const float *__restrict
     if (threadIdx.x == 0) llr_gain[a_idx] = (float)gd;
 
     int8_t    *e      = e_base + (size_t)e_off[a_idx] * 64;
-    int8_t    *e_lds  = reinterpret_cast<int8_t *>(cw + max_words);
+    int8_t    *e_lds  = reinterpret_cast<int8_t *>(cw + words_al);
     const bool via_lds = N_bits <= e_lds_cap;
     auto run = [&](auto modc, auto *dst) __attribute__((always_inline)) {
         constexpr uint32_t MOD = decltype(modc)::value, QM = MOD == 3 ? 6 : MOD == 2 ? 4 : 2;
@@ -643,7 +651,8 @@ struct mi_lte_pdsch_plan {
     int8_t       *d_bcjr_soft = nullptr;                  // [max n_cb][3(K+4)] int8 channel values of the group being decoded
     uint8_t      *d_bcjr_bits = nullptr;                  // [max n_cb][K] its hard decisions
     size_t        bcjr_soft_cap = 0, bcjr_bits_cap = 0;
-    uint32_t      cfi = 0, max_pairs = 0, max_words = 0, max_tbs = 0;
+    uint32_t      cfi = 0, max_tbs = 0;
+    PdschDemodSizes sizes; // what the demodulator's launch is sized by (pdsch_launch.h)
     bool          dynamic = false, wide = false; // wide: the output stride of the largest single-code-block transport block, whatever is held
     bool          mapped = false; // the descriptor arrays ARE the pinned staging block, mapped into the device (mi_pdsch_plan_create_mapped)
     // pinned staging for re-assignments: allocs | e_off | cb_alloc, copied with one command each on the context's stream
@@ -658,10 +667,8 @@ struct mi_lte_pdsch_plan {
     // floats); n_units = 1 + the largest unit an allocation names
     float       llr_noise = 0.0f, *d_llr_s2 = nullptr;
     uint32_t    n_units = 0;
-    // the packed hand-over (soft_pack.h): what the demodulator's LDS block must hold -- the soft bits of the longest allocation that stays
-    // bytes (BPSK / QPSK, in words) and the symbols of the longest 16QAM / 64QAM one -- and the stage tap's debt: the context of the last run and whether
-    // its 16QAM / 64QAM slots still hold bits (mi_lte_pdsch_plan_soft_bits expands them once; a re-assignment voids them)
-    uint32_t            max_words_lo = 0, max_symb_hi = 0;
+    // the packed hand-over (soft_pack.h): the stage tap's debt -- the context of the last run and whether its 16QAM / 64QAM slots still
+    // hold bits (mi_lte_pdsch_plan_soft_bits expands them once; a re-assignment voids them)
     mutable mi_lte_ctx *tap_ctx = nullptr;
     mutable bool        tap_packed = false;
 };
@@ -684,7 +691,8 @@ static int plan_layout(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t N_pdcch_
     const mi_lte_dl_cfg *cfg = &pl->cfg;
     pl->cfi          = N_pdcch_symbs;
     pl->core.n_alloc = n_alloc;
-    pl->max_pairs = pl->max_words = pl->max_tbs = pl->max_words_lo = pl->max_symb_hi = 0;
+    pl->max_tbs = 0;
+    pl->sizes   = PdschDemodSizes{};
     pl->tap_packed = false; // (the slots move: what a last run left in them is no allocation's any more)
     pl->core.groups.clear();
     for (uint32_t a = 0; a < n_alloc; a++) {
@@ -704,15 +712,9 @@ static int plan_layout(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t N_pdcch_
                 }
         row[a]      = (uint8_t)r;
         pl->max_tbs = std::max(pl->max_tbs, al.tbs);
-        const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : al.mod_type == 1 ? 2 : 1;
-        const uint32_t pairs = (14 - cfi) * al.N_prb, e_max = pairs * 12 * Qm;
-        pl->max_pairs = std::max(pl->max_pairs, 14 * al.N_prb); // the demodulator's pair table spans all 14 symbols
-        pl->max_words = std::max(pl->max_words, (e_max + 31) / 32);
-        if (al.mod_type >= 2) pl->max_symb_hi = std::max(pl->max_symb_hi, pairs * 12);
-        else pl->max_words_lo = std::max(pl->max_words_lo, (e_max + 31) / 32);
-        e_bits[a]     = e_max;
+        e_bits[a]   = pl->sizes.add(al.N_prb, cfi, al.mod_type);
     }
-    if (pl->max_words > 4095) { // the demodulator reads one word past the allocation's last scrambling word
+    if (pl->sizes.max_words > MAX_WORDS) { // the demodulator reads one word past the allocation's last scrambling word
         ctx->err = "allocation larger than the scrambling table";
         return MI_LTE_ERR_UNSUPPORTED;
     }
@@ -1016,8 +1018,8 @@ int mi_lte_pdsch_plan_soft_bits(const mi_lte_pdsch_plan *pl, uint32_t alloc, con
     if (pl->tap_packed) { // the last run handed its 16QAM / 64QAM soft bits over as bits: the first tap after it turns them into bytes, once
         mi_lte_ctx *ctx = pl->tap_ctx;
         MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-        hipLaunchKernelGGL(k_soft_expand, dim3(pl->core.n_alloc), dim3(256), sizeof(uint32_t) * (pl->max_words + 4u), ctx->stream, pl->core.d_allocs, pl->core.d_e,
-                           pl->core.d_e_off, pl->core.d_e_len, pl->max_words);
+        hipLaunchKernelGGL(k_soft_expand, dim3(pl->core.n_alloc), dim3(256), sizeof(uint32_t) * (pl->sizes.max_words + 4u), ctx->stream, pl->core.d_allocs, pl->core.d_e,
+                           pl->core.d_e_off, pl->core.d_e_len, pl->sizes.max_words);
         MI_HIP_CHECK(ctx, hipGetLastError());
         pl->tap_packed = false;
     }
@@ -1110,59 +1112,95 @@ void mi_chain_ctx_release(const mi_lte_ctx *ctx)
 int mi_dl_crs_noise(mi_lte_ctx *ctx, uint32_t N_rb_dl, uint32_t N_ant, const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell,
                     uint32_t n_units, float *d_sigma2);
 
-// the plan's demodulator: every allocation's descrambled soft bits and their count
-// pack: 16QAM / 64QAM allocations leave as bits (soft_pack.h; pdsch_run decides per run)
-static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell, bool pack)
+template <PdschFamily F> using Family = std::integral_constant<PdschFamily, F>; // the planned family as a template argument
+
+// What a demodulator launch reads besides the plan and the planned launch
+struct PdschDemodIn {
+    const float    *d_subframes;
+    const uint32_t *d_subfr_num, *d_n_id_cell;
+    float           auto_t; // the automatic gain's target (max-log)
+};
+
+// The demodulator's launch as L shapes it: family F on N_ANT ports.  The kernel is instantiated only where pdsch_variant_compiled
+// (pdsch_launch.h) says the variant exists; pdsch_launch_plan plans nothing else, so the other branch is never reached.
+template <PdschFamily F, uint32_t N_ANT>
+static int pdsch_launch(mi_lte_ctx *ctx, const mi_lte_pdsch_plan *pl, const PdschLaunch &L, const PdschDemodIn &in)
+{
+    if constexpr (pdsch_variant_compiled(F, N_ANT)) {
+        const DemodGeom  g{pl->cfg.N_rb_dl, pl->cfg.N_ant, pl->cfi, (uint32_t)mi_lte_subframe_floats(pl->cfg.N_ant)};
+        const GoldTables gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
+        const auto go = [&](auto kernel, auto... tail) { // the arguments every variant shares, then its own
+            MI_LAUNCH(ctx, L.label, kernel, dim3(pl->core.n_alloc), dim3(L.threads), L.lds_bytes, in.d_subframes, g, pl->core.d_allocs, in.d_subfr_num,
+                      in.d_n_id_cell, gt, pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->sizes.max_pairs, L.words_al, L.e_cap, tail...);
+        };
+        const uint32_t gold_table = (L.flags & DEMOD_GOLD_TABLE) ? 1u : 0u;
+        if constexpr (F == PdschFamily::LLR) go(k_pdsch_demod_llr<N_ANT, PdschLlrGain>, pl->demap_gain, in.auto_t, pl->d_llr_gain, gold_table, PdschLlrGain{});
+        else if constexpr (F == PdschFamily::LLR_NOISE)
+            go(k_pdsch_demod_llr<N_ANT, PdschLlrNoise>, pl->demap_gain, in.auto_t, pl->d_llr_gain, gold_table, PdschLlrNoise{pl->d_llr_s2, pl->llr_noise});
+        else go(k_pdsch_demod<F != PdschFamily::REF_PORTS, F == PdschFamily::REF_ONE_PORT_COMPACT>, L.flags);
+        return MI_LTE_OK;
+    } else { ctx->err = "k_pdsch_demod: no such variant at this port count"; return MI_LTE_ERR_UNSUPPORTED; }
+}
+
+// the plan's demodulator: every allocation's descrambled soft bits and their count, launched as pdsch_launch_plan (pdsch_launch.h) shapes it;
+// *L: that launch.  pack: 16QAM / 64QAM allocations leave as bits (soft_pack.h; pdsch_run decides per run)
+static int pdsch_demod(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const float *d_subframes, const uint32_t *d_subfr_num, const uint32_t *d_n_id_cell, bool pack,
+                       PdschLaunch *L)
 {
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     int rc = mi_ctx_gold_tables(ctx);
     if (rc != MI_LTE_OK) return rc;
-    DemodGeom  g{pl->cfg.N_rb_dl, pl->cfg.N_ant, pl->cfi, (uint32_t)mi_lte_subframe_floats(pl->cfg.N_ant)};
-    GoldTables gt{ctx->d_gold_x1, ctx->d_gold_x2b, ctx->gold_words};
-    const bool gold_table = gold_table_of(ctx);
-    // LDS: pair table | scrambling words | (when it fits in 32 KiB) the allocation's soft bits
-    // A packed run: only the allocations that stay bytes count for e_cap, and a packed allocation's symbol masks (one byte each, at most 15 600: 100
-    // resource blocks, 13 symbols) ALWAYS go through the block -- a long QPSK allocation next to them still finds its own rule (e_cap = 0: direct)
-    const uint32_t words_al = (pl->max_words + 1u + 3u) & ~3u, e_bytes = ((pack ? pl->max_words_lo : pl->max_words) * 32 + 63u) & ~63u;
-    const uint32_t e_cap = (e_bytes <= 32 * 1024) ? e_bytes : 0;
-    const uint32_t pairs_al = ((2 * (pl->max_pairs + 1) + 3u) & ~3u);
-    const size_t lds = sizeof(uint32_t) * ((size_t)pairs_al + words_al) + std::max(e_cap, pack ? (pl->max_symb_hi + 15u) & ~15u : 0u);
-    uint32_t threads = 256;
-    if (const char *ev = getenv("MI_LTE_PDSCH_THREADS")) { // (tuning aid)
-        const int t = atoi(ev);
-        if (t >= 64 && t <= 256 && t % 64 == 0) threads = (uint32_t)t;
-    }
-    auto launch = [&](auto kernel) {
-        MI_LAUNCH(ctx, "k_pdsch_demod", kernel, dim3(pl->core.n_alloc), dim3(threads), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt,
-                  pl->core.d_e, pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, (pack ? DEMOD_PACK : 0u) | (gold_table ? DEMOD_GOLD_TABLE : 0u));
-    };
-    if (pl->demap == MI_LTE_DEMAP_MAXLOG) { // (a 3GPP plan on full estimate planes: mi_lte_pdsch_plan_set_demapper)
-        float auto_t = (float)MI_LTE_DEMAP_AUTO_T;
-        if (const char *ev = getenv("MI_LTE_DEMAP_AUTO_T")) { // (tuning aid: tools/demap_llr_sweep.py chooses the header's constant with it)
-            const float t = (float)atof(ev);
-            if (t >= 1.0f && t <= 127.0f) auto_t = t;
+    const char *ev = getenv("MI_LTE_PDSCH_THREADS"); // (tuning aid)
+    const bool  maxlog = pl->demap == MI_LTE_DEMAP_MAXLOG; // (a 3GPP plan on full estimate planes: mi_lte_pdsch_plan_set_demapper)
+    pdsch_launch_plan(pl->sizes, pl->cfg.N_ant, (pl->cfg.sample_format & MI_LTE_CE_COMPACT) != 0, maxlog, pl->llr_noise > 0.0f, pack, gold_table_of(ctx),
+                      ev ? atoi(ev) : 0, L);
+    PdschDemodIn in{d_subframes, d_subfr_num, d_n_id_cell, (float)MI_LTE_DEMAP_AUTO_T};
+    if (maxlog)
+        if (const char *ev_t = getenv("MI_LTE_DEMAP_AUTO_T")) { // (tuning aid: tools/demap_llr_sweep.py chooses the header's constant with it)
+            const float t = (float)atof(ev_t);
+            if (t >= 1.0f && t <= 127.0f) in.auto_t = t;
         }
-        auto launch_llr = [&](const char *name, auto kernel) {
-            MI_LAUNCH(ctx, name, kernel, dim3(pl->core.n_alloc), dim3(256), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt, pl->core.d_e,
-                      pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain, gold_table ? 1u : 0u);
-        };
-        if (pl->llr_noise > 0.0f) { // the noise-referenced gain: the CRS noise estimate of the plan's units, then the instantiation that divides by it
-            if ((rc = mi_dl_crs_noise(ctx, g.N_rb_dl, g.N_ant, d_subframes, d_subfr_num, d_n_id_cell, pl->n_units, pl->d_llr_s2)) != MI_LTE_OK) return rc;
-            const PdschLlrNoise nz{pl->d_llr_s2, pl->llr_noise};
-            auto launch_llr_noise = [&](const char *name, auto kernel) {
-                MI_LAUNCH(ctx, name, kernel, dim3(pl->core.n_alloc), dim3(256), lds, d_subframes, g, pl->core.d_allocs, d_subfr_num, d_n_id_cell, gt, pl->core.d_e,
-                          pl->core.d_e_off, pl->core.d_e_len, pl->max_pairs, words_al, e_cap, pl->demap_gain, auto_t, pl->d_llr_gain, gold_table ? 1u : 0u, nz);
-            };
-            if (g.N_ant == 1) launch_llr_noise("k_pdsch_demod_llr", k_pdsch_demod_llr<1, PdschLlrNoise>);
-            else if (g.N_ant == 2) launch_llr_noise("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<2, PdschLlrNoise>);
-            else launch_llr_noise("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<4, PdschLlrNoise>);
-        } else if (g.N_ant == 1) launch_llr("k_pdsch_demod_llr", k_pdsch_demod_llr<1>);
-        else if (g.N_ant == 2) launch_llr("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<2>); // (a transmit-diversity plan: its own profiling label)
-        else launch_llr("k_pdsch_demod_llr_txd", k_pdsch_demod_llr<4>);
-    } else if (g.N_ant == 1 && (pl->cfg.sample_format & MI_LTE_CE_COMPACT)) launch(k_pdsch_demod<true, true>);
-    else if (g.N_ant == 1) launch(k_pdsch_demod<true>);
-    else launch(k_pdsch_demod<false>);
+    // the noise-referenced gain: the CRS noise estimate of the plan's units, then the instantiation that divides by it
+    if (L->noise_first && (rc = mi_dl_crs_noise(ctx, pl->cfg.N_rb_dl, pl->cfg.N_ant, d_subframes, d_subfr_num, d_n_id_cell, pl->n_units, pl->d_llr_s2)) != MI_LTE_OK)
+        return rc;
+    const auto ports = [&](auto f) { // L's family on L's ports
+        constexpr PdschFamily F = decltype(f)::value;
+        return L->n_ant == 1 ? pdsch_launch<F, 1>(ctx, pl, *L, in) : L->n_ant == 2 ? pdsch_launch<F, 2>(ctx, pl, *L, in) : pdsch_launch<F, 4>(ctx, pl, *L, in);
+    };
+    switch (L->family) {
+    case PdschFamily::REF_ONE_PORT: rc = ports(Family<PdschFamily::REF_ONE_PORT>{}); break;
+    case PdschFamily::REF_ONE_PORT_COMPACT: rc = ports(Family<PdschFamily::REF_ONE_PORT_COMPACT>{}); break;
+    case PdschFamily::REF_PORTS: rc = ports(Family<PdschFamily::REF_PORTS>{}); break;
+    case PdschFamily::LLR: rc = ports(Family<PdschFamily::LLR>{}); break;
+    case PdschFamily::LLR_NOISE: rc = ports(Family<PdschFamily::LLR_NOISE>{}); break;
+    }
+    if (rc != MI_LTE_OK) return rc;
     MI_HIP_CHECK(ctx, hipGetLastError());
+    return MI_LTE_OK;
+}
+
+// The reference-mode plans' BCJR decoders (mi_lte_pdsch_plan_set_decoder): the code blocks size by size
+static int pdsch_bcjr_decode(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, const MiDecodeIO &io)
+{
+    int    rc;
+    size_t soft = 0, bits = 0;
+    for (auto &gr : pl->core.groups) { soft = std::max(soft, (size_t)gr.n_cb * 3 * (gr.K + 4)); bits = std::max(bits, (size_t)gr.n_cb * gr.K); }
+    if (soft > pl->bcjr_soft_cap || bits > pl->bcjr_bits_cap) { // first run, or a re-assigned plan that needs more
+        MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (pl->d_bcjr_soft) (void)hipFree(pl->d_bcjr_soft);
+        if (pl->d_bcjr_bits) (void)hipFree(pl->d_bcjr_bits);
+        pl->d_bcjr_soft = nullptr; pl->d_bcjr_bits = nullptr;
+        MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_bcjr_soft, soft));
+        MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_bcjr_bits, bits));
+        pl->bcjr_soft_cap = soft; pl->bcjr_bits_cap = bits;
+    }
+    for (auto &gr : pl->core.groups) {
+        rc = mi_turbo_bcjr_group(ctx, gr, io, pl->d_bcjr_soft, pl->d_bcjr_bits, pl->decoder, pl->n_iter, pl->qpp_spec);
+        if (rc != MI_LTE_OK) return rc;
+    }
+    // (what mi_turbo_bcjr_group launched: the one-block-per-wavefront decoder takes the interleaved int8 block, the batch kernels their granule arrays)
+    ctx->last_kernels = pl->decoder == MI_LTE_TURBO_BCJR_BLOCK ? "k_rm_to_i8,k_bcjr_block,k_crc_finish per block size"
+                                                               : "k_cb_desc,k_rm_bcjr_prep,k_bcjr_half,k_bcjr_final,k_crc_finish per block size";
     return MI_LTE_OK;
 }
 
@@ -1183,41 +1221,16 @@ static int pdsch_run(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, mi_lte_harq_pool *p
     // Nor does a run one of whose block-size groups would be gathered straight from global memory (mi_turbo_ref_reads_packed).
     bool pack = ctx->soft_packed && !pl->g3 && !mi_is_bcjr(pl->decoder) && pl->demap == MI_LTE_DEMAP_REF;
     for (const MiKGroup &gr : pl->core.groups) pack = pack && turbo_geom::mi_turbo_ref_reads_packed(gr.K, gr.e_max);
-    if ((rc = pdsch_demod(ctx, pl, d_subframes, d_subfr_num, d_n_id_cell, pack)) != MI_LTE_OK) return rc;
+    PdschLaunch L;
+    if ((rc = pdsch_demod(ctx, pl, d_subframes, d_subfr_num, d_n_id_cell, pack, &L)) != MI_LTE_OK) return rc;
     pl->tap_ctx = ctx; pl->tap_packed = pack; // what the slots hold from here on (mi_lte_pdsch_plan_soft_bits)
     const MiDecodeIO io = pl->core.io(d_out_bits, d_status, /*ul=*/false, pack);
-    if (pl->g3) {
-        rc = mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter);
-        if (rc == MI_LTE_OK && pl->demap == MI_LTE_DEMAP_MAXLOG) {
-            ctx->last_kernels.replace(0, strlen("k_pdsch_demod"), pl->cfg.N_ant == 1 ? "k_pdsch_demod_llr" : "k_pdsch_demod_llr_txd");
-            if (pl->llr_noise > 0.0f) ctx->last_kernels.insert(0, "k_dl_crs_noise:1,");
-        }
-        return rc;
-    }
-    if (!mi_is_bcjr(pl->decoder)) {
-        rc = mi_turbo_ref_dispatch(ctx, pl->core.groups.data(), (uint32_t)pl->core.groups.size(), io, &pl->core.multi);
-        if (rc != MI_LTE_OK) return rc;
-        ctx->last_kernels.insert(0, "k_pdsch_demod:1,");
-        return MI_LTE_OK;
-    }
-    size_t soft = 0, bits = 0;
-    for (auto &gr : pl->core.groups) { soft = std::max(soft, (size_t)gr.n_cb * 3 * (gr.K + 4)); bits = std::max(bits, (size_t)gr.n_cb * gr.K); }
-    if (soft > pl->bcjr_soft_cap || bits > pl->bcjr_bits_cap) { // first run, or a re-assigned plan that needs more
-        MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (pl->d_bcjr_soft) (void)hipFree(pl->d_bcjr_soft);
-        if (pl->d_bcjr_bits) (void)hipFree(pl->d_bcjr_bits);
-        pl->d_bcjr_soft = nullptr; pl->d_bcjr_bits = nullptr;
-        MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_bcjr_soft, soft));
-        MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_bcjr_bits, bits));
-        pl->bcjr_soft_cap = soft; pl->bcjr_bits_cap = bits;
-    }
-    for (auto &gr : pl->core.groups) {
-        rc = mi_turbo_bcjr_group(ctx, gr, io, pl->d_bcjr_soft, pl->d_bcjr_bits, pl->decoder, pl->n_iter, pl->qpp_spec);
-        if (rc != MI_LTE_OK) return rc;
-    }
-    // (what mi_turbo_bcjr_group launched: the one-block-per-wavefront decoder takes the interleaved int8 block, the batch kernels their granule arrays)
-    ctx->last_kernels = pl->decoder == MI_LTE_TURBO_BCJR_BLOCK ? "k_pdsch_demod:1,k_rm_to_i8,k_bcjr_block,k_crc_finish per block size"
-                                                               : "k_pdsch_demod:1,k_cb_desc,k_rm_bcjr_prep,k_bcjr_half,k_bcjr_final,k_crc_finish per block size";
+    // every decode path lists its own kernels; the demodulator's entry, as it was launched, goes in front of them
+    rc = pl->g3                     ? mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter)
+         : !mi_is_bcjr(pl->decoder) ? mi_turbo_ref_dispatch(ctx, pl->core.groups.data(), (uint32_t)pl->core.groups.size(), io, &pl->core.multi)
+                                    : pdsch_bcjr_decode(ctx, pl, io);
+    if (rc != MI_LTE_OK) return rc;
+    ctx->last_kernels = std::string(L.noise_first ? "k_dl_crs_noise:1," : "") + L.label + ":1," + ctx->last_kernels;
     return MI_LTE_OK;
 }
 

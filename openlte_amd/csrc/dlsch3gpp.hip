@@ -545,8 +545,9 @@ int mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lt
         MI_LAUNCH(ctx, "k_harq_commit", k_harq_commit, dim3((g->n_alloc + 255) / 256), dim3(256), 0, (const mi_lte_harq_bind *)p->d_bind, g->n_alloc,
                   (const int32_t *)io.d_status, p->d_state);
     MI_HIP_CHECK(ctx, hipGetLastError());
-    ctx->last_kernels = p ? "k_pdsch_demod:1,k_dl3_desc:1,k_harq_bind:1,k_harq_rm:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1,k_harq_commit:1"
-                          : "k_pdsch_demod:1,k_dl3_desc:1,k_dl3_rm_i8:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1";
+    // (its own kernels: the caller lists its demodulator in front)
+    ctx->last_kernels = p ? "k_dl3_desc:1,k_harq_bind:1,k_harq_rm:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1,k_harq_commit:1"
+                          : "k_dl3_desc:1,k_dl3_rm_i8:1,k_bcjr_* per block size,k_dl3_cb_finish:1,k_dl3_tb_finish:1";
     return MI_LTE_OK;
 }
 

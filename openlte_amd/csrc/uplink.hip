@@ -1301,12 +1301,11 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
             io.d_e = pl->uci->d_e; io.d_e_len = pl->uci->d_e_len;
         }
         if ((rc = mi_dlsch3_run(ctx, pl->g3, pool, h_bind, io, pl->decoder, pl->n_iter)) != MI_LTE_OK) return rc;
-        const size_t at = ctx->last_kernels.find(','); // (mi_dlsch3_run lists the downlink's demodulator in front of its own kernels)
-        ctx->last_kernels.replace(0, at == std::string::npos ? 0 : at,
-                                  std::string(L.label) + ":1" +
-                                      (!pl->uci          ? ""
-                                       : pl->uci->cqi_on ? ",k_ulsch_uci_gather:1,k_ulsch_uci_decide:1,k_ulsch_cqi_decode:1"
-                                                         : ",k_ulsch_uci_gather:1,k_ulsch_uci_decide:1"));
+        ctx->last_kernels = std::string(L.label) + ":1," + // (mi_dlsch3_run lists its own kernels)
+                            (!pl->uci          ? ""
+                             : pl->uci->cqi_on ? "k_ulsch_uci_gather:1,k_ulsch_uci_decide:1,k_ulsch_cqi_decode:1,"
+                                               : "k_ulsch_uci_gather:1,k_ulsch_uci_decide:1,") +
+                            ctx->last_kernels;
         return MI_LTE_OK;
     }
     // several block sizes (the UEs of a subframe rarely share one): one launch set over all of them, as in the PDSCH chain
