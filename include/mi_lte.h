@@ -803,7 +803,7 @@ int mi_lte_pusch_plan_llr_noise(const mi_lte_pusch_plan *plan, const float **d_s
 /* ---------------------------------------------------------------- PUSCH, 3GPP mode: receive-antenna combining
  * A MAXLOG run of a 3GPP plan can combine n_rx = 2 or 4 receive antennas by maximum-ratio combining in front of the transform pre-decoder:
  * one channel estimate per antenna, one combined symbol per sub-carrier, then the single-antenna chain.  The reference has no counterpart
- * (liblte_phy_pusch_channel_decode estimates and equalises one antenna); this text is the contract and tests/pusch_rxdiv_model.py restates
+ * (liblte_phy_pusch_channel_decode estimates and equalises one antenna); this text is the contract and tests/pusch_demod_model.py restates
  * it in float64.
  * Layout of d_subframes on a run of a plan with n_rx > 1 (antenna-major).  The grid of receive antenna r = 0 .. n_rx - 1 of unit u is
  *   subframe index r * ant_stride + u, each grid in the mi_lte_ul_subframe_floats() layout; ant_stride >= the plan's n_units.  One
@@ -853,7 +853,7 @@ int mi_lte_pusch_plan_rx_antennas(const mi_lte_pusch_plan *plan, uint32_t *n_rx,
  * carries noise sigma^2 / rho_s, rho_s the harmonic mean of the channel power: on a channel that is flat over the allocation that is the
  * best there is, on one with delay spread a single faded sub-carrier sets the noise of all M samples.  A MAXLOG run with the noise gain on
  * can equalise with the MMSE tap instead, which weighs every sub-carrier by its own signal-to-noise ratio.  The reference has no
- * counterpart; this text is the contract and tests/pusch_mmse_model.py restates it in float64.
+ * counterpart; this text is the contract and tests/pusch_demod_model.py restates it in float64.
  * Inputs (n_rx = 1, 2 or 4).  h_r(s)[i], y_r(s)[i] and P_s[i] = sum_r (Re h_r(s)[i]^2 + Im h_r(s)[i]^2) exactly as the combining section forms
  *   them (n_rx = 1: P = Re h^2 + Im h^2, the float whose reciprocal is the zero-forcing hn); s2 = sigma2_a, the float of the noise section
  *   including its mean over the antennas.  The units agree: the DMRS has unit modulus, so the least-squares products, and with them h,

@@ -1,8 +1,8 @@
 // The launch of k_pusch_demod (uplink.hip) as a pure host rule: the constants the kernel's LDS layout and the launch share, and one function
 // from a plan's sizes and settings to everything the run function launches with.  No HIP, no context, no environment: uplink.hip launches by
 // it, mi_lte_pusch_plan_set_rx_antennas refuses by it, and tools/asan/pusch_launch_driver.cc prints it for tests/test_pusch_launch_cpu.py,
-// which holds it against the Python restatements the GPU tests choose their sizes by (tests/pusch_predecode_cases.py,
-// tests/pusch_rxdiv_model.py).  (A .h, not a .hpp: the .hpp files are part of every .hip file's build id.)
+// which holds it against the Python restatement the GPU tests choose their sizes by (tests/pusch_demod_model.py, launch()).  (A .h, not a
+// .hpp: the .hpp files are part of every .hip file's build id.)
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -54,7 +54,7 @@ enum class PuschFamily { PLAIN, LLR, LLR_NOISE, LLR_RX, LLR_MMSE };
 
 // Whether k_pusch_demod is compiled for a family at a workgroup width and antenna count: the single-antenna variants at the four widths, the
 // combining ones (two or four antennas) at 192 and 256 only.  uplink.hip instantiates by it, and pusch_launch_plan below plans nothing else
-// (tests/test_pusch_launch_cpu.py, tests/test_pusch_mmse_launch_cpu.py).
+// (tests/test_pusch_launch_cpu.py).
 constexpr bool pusch_variant_compiled(PuschFamily family, uint32_t threads, uint32_t n_rx)
 {
     const bool single    = n_rx == 1 && (threads == 64 || threads == 128 || threads == 192 || threads == 256);
@@ -73,14 +73,19 @@ struct PuschLaunch {
     const char *label;     // what the launch is profiled and listed as
 };
 
-// The launch of a plan whose widest allocation has M_max sub-carriers and whose longest has words_max scrambling words.  maxlog: the
-// max-log demapper on a 3GPP plan; noise: llr_noise > 0 and n_rx: the antennas, both read for a max-log launch only; lds_limit: the
+// The plan's settings a launch is chosen by.  maxlog: the max-log demapper on a 3GPP plan; the rest is read for a max-log launch only --
+// noise: llr_noise > 0; mmse: MMSE equalisation (mi_lte_pusch_plan_set_equaliser), read with the noise gain on only (the caller refuses an
+// MMSE run without either); n_rx: the antennas.
+struct PuschSettings {
+    bool     maxlog, noise, mmse;
+    uint32_t n_rx;
+};
+
+// The launch of a plan whose widest allocation has M_max sub-carriers and whose longest has words_max scrambling words.  lds_limit: the
 // device's per-workgroup LDS, read for a combining launch only; threads_override: a validated MI_LTE_PUSCH_THREADS (0: none), which does
 // not reach a combining launch.  false: a combining launch that does not fit lds_limit at S_par = 1 (*out is not a launch then).
-// mmse: MMSE equalisation (mi_lte_pusch_plan_set_equaliser), read for a max-log launch with the noise gain on only -- the caller refuses an
-// MMSE run without either: the noise-on launch of the same n_rx under LLR_MMSE's family and label.
-inline bool pusch_launch_plan(uint32_t M_max, uint32_t words_max, bool maxlog, bool noise, uint32_t n_rx, size_t lds_limit, uint32_t threads_override,
-                              PuschLaunch *out, bool mmse = false)
+// An MMSE launch is the noise-on launch of the same n_rx under LLR_MMSE's family and label.
+inline bool pusch_launch_plan(uint32_t M_max, uint32_t words_max, const PuschSettings &s, size_t lds_limit, uint32_t threads_override, PuschLaunch *out)
 {
     // Workgroup size: the kernel's phases hold 3 M, M, 2 M, 12 M / R and 12 M items (M = 12 N_prb sub-carriers) between barriers, and the
     // heavy ones (atan2f, sincosf, the divisions) are the short ones -- a workgroup much wider than 3 M leaves whole wavefronts waiting at
@@ -88,21 +93,21 @@ inline bool pusch_launch_plan(uint32_t M_max, uint32_t words_max, bool maxlog, b
     // W5 (16 UEs x 6 PRB): 64 / 128 / 192 / 256 threads = see profiles/r04_variants_pusch_threads.txt; larger allocations keep 256.
     const uint32_t threads = threads_override ? threads_override : M_max <= 96 ? 192u : (uint32_t)PUSCH_THREADS;
     const uint32_t S_par   = pusch_s_par(M_max);
-    if (!maxlog) {
+    if (!s.maxlog) {
         *out = {PuschFamily::PLAIN, threads, 1, false, S_par, 0, pusch_lds(1, M_max, words_max, S_par), "k_pusch_demod"};
         return true;
     }
-    if (n_rx <= 1) { // the same launch with the LLR block behind the scrambling words
+    if (s.n_rx <= 1) { // the same launch with the LLR block behind the scrambling words
         const size_t off = pusch_round8(pusch_lds(1, M_max, words_max, S_par));
-        *out = {noise ? PuschFamily::LLR_NOISE : PuschFamily::LLR, threads, 1, noise, S_par, off, off + (noise ? LLR_NOISE_LDS_BYTES : LLR_LDS_BYTES), "k_pusch_demod_llr"};
-        if (mmse && noise) { out->family = PuschFamily::LLR_MMSE; out->label = "k_pusch_demod_llr_mmse"; } // LLR_NOISE's launch in every other field
+        *out = {s.noise ? PuschFamily::LLR_NOISE : PuschFamily::LLR, threads, 1, s.noise, S_par, off, off + (s.noise ? LLR_NOISE_LDS_BYTES : LLR_LDS_BYTES), "k_pusch_demod_llr"};
+        if (s.mmse && s.noise) { out->family = PuschFamily::LLR_MMSE; out->label = "k_pusch_demod_llr_mmse"; } // LLR_NOISE's launch in every other field
         return true;
     }
     // combining: n_rx sets of estimate rows, S_par stepped down until the whole launch fits, the LLR block always the noise launch's
-    const uint32_t S_rx = pusch_rx_s_par(n_rx, M_max, words_max, lds_limit);
-    const size_t   off  = pusch_round8(pusch_lds(n_rx, M_max, words_max, S_rx ? S_rx : 1));
-    *out = {PuschFamily::LLR_RX, M_max <= 96 ? 192u : 256u, n_rx, noise, S_rx, off, off + LLR_NOISE_LDS_BYTES, "k_pusch_demod_llr_rx"};
-    if (mmse && noise) { out->family = PuschFamily::LLR_MMSE; out->label = "k_pusch_demod_llr_mmse"; } // LLR_RX's launch in every other field, and its refusal
+    const uint32_t S_rx = pusch_rx_s_par(s.n_rx, M_max, words_max, lds_limit);
+    const size_t   off  = pusch_round8(pusch_lds(s.n_rx, M_max, words_max, S_rx ? S_rx : 1));
+    *out = {PuschFamily::LLR_RX, M_max <= 96 ? 192u : 256u, s.n_rx, s.noise, S_rx, off, off + LLR_NOISE_LDS_BYTES, "k_pusch_demod_llr_rx"};
+    if (s.mmse && s.noise) { out->family = PuschFamily::LLR_MMSE; out->label = "k_pusch_demod_llr_mmse"; } // LLR_RX's launch in every other field, and its refusal
     return S_rx != 0;
 }
 

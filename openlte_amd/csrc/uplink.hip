@@ -1066,7 +1066,7 @@ int mi_lte_pusch_plan_set_rx_antennas(mi_lte_pusch_plan *pl, uint32_t n_rx, uint
     int limit = 0; // the device's per-workgroup LDS: the combining launch has to fit it at some S_par
     if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, pl->device) != hipSuccess) return MI_LTE_ERR_HIP;
     PuschLaunch L; // (the noise-referenced gain does not change what fits)
-    if (!pusch_launch_plan(pl->M_max, pl->words_max, /*maxlog=*/true, /*noise=*/false, n_rx, (size_t)std::max(limit, 0), 0, &L)) return MI_LTE_ERR_UNSUPPORTED;
+    if (!pusch_launch_plan(pl->M_max, pl->words_max, {/*maxlog=*/true, /*noise=*/false, /*mmse=*/false, n_rx}, (size_t)std::max(limit, 0), 0, &L)) return MI_LTE_ERR_UNSUPPORTED;
     pl->n_rx = n_rx; pl->ant_stride = ant_stride;
     return MI_LTE_OK;
 }
@@ -1265,7 +1265,7 @@ static int pusch_run(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl, mi_lte_harq_pool *p
         lds_limit = (size_t)std::max(limit, 0);
     }
     PuschLaunch L;
-    if (!pusch_launch_plan(pl->M_max, pl->words_max, llr, pl->llr_noise > 0.0f, pl->n_rx, lds_limit, threads_override, &L, mmse)) {
+    if (!pusch_launch_plan(pl->M_max, pl->words_max, {llr, pl->llr_noise > 0.0f, mmse, pl->n_rx}, lds_limit, threads_override, &L)) {
         ctx->err = "receive-antenna combining: the plan's widest allocation does not fit the device's LDS";
         return MI_LTE_ERR_UNSUPPORTED;
     }

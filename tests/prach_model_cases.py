@@ -16,7 +16,7 @@ import numpy as np
 
 import prach_model as pm
 
-TOL_L2, TOL_EL = 1e-5, 1e-4  # the project's FFT-stage figures (pusch_predecode_cases.TOL_SYMB and 10 x it): the hard gates
+TOL_L2, TOL_EL = 1e-5, 1e-4  # the project's FFT-stage figures (pusch_demod_cases.TOL_SYMB and 10 x it): the hard gates
 GATE_FACTOR = 8.0            # tight gate = GATE_FACTOR x the float32 restatement's worst error on these inputs (as the pre-decoder's tests)
 LEAD = 13
 N_RB = {128: 6, 256: 15, 512: 25, 1024: 50, 2048: 100}

@@ -1,11 +1,11 @@
 """CPU: the claims behind the 3GPP PUSCH plans' max-log demapper (include/mi_lte.h, "PUSCH, 3GPP mode: max-log soft-decision demapping") and
-its float64 model tests/pusch_llr_model.py: the noise variance after zero forcing and the 1 / sqrt(M) inverse DFT is sigma^2 / rho_s; the
+its float64 model tests/pusch_demod_model.py: the noise variance after zero forcing and the 1 / sqrt(M) inverse DFT is sigma^2 / rho_s; the
 piecewise-linear LLR with w = rho_s is the brute-force max-log LLR over the whole constellation; the automatic gain's degenerate cases."""
 import numpy as np
 import pytest
 
 import demap_llr_model as dm
-import pusch_llr_model as pm
+import pusch_demod_model as pm
 
 
 def selective_channel(rng, M, taps=4):

@@ -1,5 +1,5 @@
 """GPU: the 3GPP PUSCH plans' max-log soft-decision demapper (mi_lte_pusch_plan_set_demapper, k_pusch_demod_llr).  Its bytes against the
-float64 model of include/mi_lte.h's text on the tapped symbols and reliabilities (tests/pusch_llr_model.py, the exact layer), the
+float64 model of include/mi_lte.h's text on the tapped symbols and reliabilities (tests/pusch_demod_model.py, the exact layer), the
 reliabilities rho_s against the model's restatement of the polar interpolation (the tolerance layer); a plan that never opts in, or opts out
 again, is the plan it was; everything after the soft-bit buffer -- rate un-matching, the BCJR model, the control-information gather, sums
 and decisions, the CQI decoder -- does with the graded bytes what it does with the default demapper's; and what the soft decisions buy: at an
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import demap_llr_model as dm
-import pusch_llr_model as pm
+import pusch_demod_model as pm
 from test_ulsch3gpp_gpu import QM, Units, check_blocks_exact, grant
 from test_ulsch_cqi_cpu import ZERO, model as cqi_model
 from test_ulsch_uci_gpu import UciUnits, check_gather_and_sums, exact_grants

@@ -1,5 +1,5 @@
 """CPU: the claims behind the 3GPP PUSCH plans' MMSE equalisation (include/mi_lte.h, "PUSCH, 3GPP mode: MMSE equalisation") and its float64
-model tests/pusch_mmse_model.py -- the flat-channel identity with the zero-forcing noise-referenced run, w_s >= rho_s / sigma2, the limit
+model tests/pusch_demod_model.py -- the flat-channel identity with the zero-forcing noise-referenced run, w_s >= rho_s / sigma2, the limit
 s2 -> 0, the error variance nu_s / (1 - nu_s) of the unbiased symbol, the degenerate inputs, the conditions the GPU tests' caps rest on --
 and the multipath generator mi_lte_synth_ul_units_3gpp_paths_i8."""
 import ctypes as C
@@ -8,10 +8,9 @@ import numpy as np
 import pytest
 
 import demap_llr_model as dm
-import pusch_llr_model as pm
-import pusch_mmse_model as mm
-import pusch_noise_model as nm
-import pusch_rxdiv_model as rxm
+import pusch_demod_model as nm
+import pusch_demod_model as pm
+from pusch_demod_cases import mmse_view as mm, rx_view as rxm
 
 ALL_KEYS = tuple(k for n_rx in (1, 2, 4) for k in mm.gpu_keys(n_rx))
 FLAT_KEYS = {n_rx: tuple((n, n_rx, 6, mod) for n, mod in ((1, 1), (6, 2), (10, 3))) for n_rx in (1, 2, 4)}

@@ -1,5 +1,5 @@
 """GPU: MMSE equalisation on the 3GPP PUSCH plans (mi_lte_pusch_plan_set_equaliser, k_pusch_demod_llr_mmse) against the float64 model of
-include/mi_lte.h's text (tests/pusch_mmse_model.py): the tapped symbols, nu_s, the rho tap, sigma2 and the gain on two-path planes of one,
+include/mi_lte.h's text (tests/pusch_demod_model.py): the tapped symbols, nu_s, the rho tap, sigma2 and the gain on two-path planes of one,
 two and four antennas at the sizes where the launch changes shape; the bytes by the model's de-mapper on the run's own taps; flat planes
 against the zero-forcing noise-referenced run; a plan that never saw the setter, or went to MMSE and back, is the plan it was; the
 degenerate grids and every refusal of the contract; transport blocks, control information and HARQ through the multipath generator; and
@@ -7,7 +7,7 @@ what the equaliser buys at the point profiles/pusch_mmse_sweep.txt names.
 
 Gates of the tapped symbols, per data symbol (test_pusch_rxdiv_gpu's rule).  Hard: rel-L2 < 1e-5 and elementwise < 1e-4 of the symbol's
 RMS.  Tight: 8 x the error of the float32 restatement of the estimate, the equaliser and the transform on each row's own cases
-(pusch_mmse_model.float32_floor: 2.1e-7 .. 2.3e-7 rel-L2), capped at the hard gate.  Scalars (nu_s, the rho tap, sigma2): 1e-4.
+(pusch_demod_cases.float32_floor: 2.1e-7 .. 2.3e-7 rel-L2), capped at the hard gate.  Scalars (nu_s, the rho tap, sigma2): 1e-4.
 
 Sizes.  A plan takes N_prb divisible by 2, 3 or 5 only (and 1), so no 17 or 71 PRB: the S_par steps there are held from the planned sizes on
 either side, 16 | 18 and 70 | 72 (test_sizes_sit_on_the_steps).
@@ -24,10 +24,9 @@ import numpy as np
 import pytest
 
 import demap_llr_model as dm
-import pusch_llr_model as pm
-import pusch_mmse_model as mm
-import pusch_predecode_cases as pc
-import pusch_rxdiv_model as rxm
+import pusch_demod_cases as pc
+import pusch_demod_model as pm
+from pusch_demod_cases import mmse_view as mm, rx_view as rxm
 from test_pusch_harq_gpu import decode
 from test_pusch_mmse_cpu import FLAT_KEYS
 from test_pusch_rxdiv_gpu import Run, RxUnits
@@ -102,7 +101,7 @@ def test_sizes_sit_on_the_steps():
 @pytest.mark.parametrize("n_rx", [1, 2, 4])
 def test_taps_and_bytes_against_the_model(ctx, n_rx):
     """Taps: x against the model by the tight gate, nu_s, the rho tap (float)(s2 w_s) and sigma2 to 1e-4, the gain exactly (float)scale.
-    Bytes: every byte against pusch_mmse_model.demap on the run's own (x, nu_s) -- none differs outside the guard band, at most one step
+    Bytes: every byte against pusch_demod_model.demap_mmse on the run's own (x, nu_s) -- none differs outside the guard band, at most one step
     inside it, the band under 1 % of the soft bits (test_pusch_llr_gpu's comparison).  A second run gives the same bytes and taps."""
     all_keys = mm.gpu_keys(n_rx)
     gates = mm.gates(all_keys)
@@ -150,7 +149,7 @@ def test_taps_and_bytes_against_the_model(ctx, n_rx):
 
 @pytest.mark.parametrize("n_rx", [1, 2, 4])
 def test_flat_planes_give_zero_forcings_bytes(ctx, n_rx):
-    """P the same on every sub-carrier (pusch_mmse_model.flat_case; QPSK on 1 PRB, 16QAM on 6, 64QAM on 10): the MMSE bytes against the
+    """P the same on every sub-carrier (pusch_demod_cases.flat_case; QPSK on 1 PRB, 16QAM on 6, 64QAM on 10): the MMSE bytes against the
     zero-forcing noise-referenced run of the same plan -- no byte differs by more than 1, at most 0.5 % differ.  The cap is a condition:
     test_pusch_mmse_cpu shows that the two float64 models differ in no byte on these planes."""
     import openlte_amd as m

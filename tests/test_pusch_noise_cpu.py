@@ -1,4 +1,4 @@
-"""CPU: the DMRS noise estimate of the 3GPP PUSCH plans as include/mi_lte.h states it (tests/pusch_noise_model.py, the float64
+"""CPU: the DMRS noise estimate of the 3GPP PUSCH plans as include/mi_lte.h states it (tests/pusch_demod_model.py, the float64
 restatement the GPU test holds the kernel to): unbiased on a channel with a timing offset, the spread the header quotes, the edges; and the
 uplink payload transmitter (mi_lte_synth_ul_units_3gpp_payload_i8) against the seeded generators it extends.  No GPU."""
 import ctypes as C
@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import pusch_noise_model as nm
+import pusch_demod_model as nm
 from test_ulsch_uci_cpu import uci, units_case
 
 ERR_INVALID = -1

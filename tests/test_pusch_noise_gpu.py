@@ -1,6 +1,6 @@
 """GPU: the DMRS noise estimate of k_pusch_demod_llr and the noise-referenced gain built on it (mi_lte_pusch_plan_set_llr_noise,
-mi_lte_pusch_plan_llr_noise).  sigma2_a against the float64 restatement of include/mi_lte.h's text (tests/pusch_noise_model.py) on the
-front end's planes; the gain exactly (float)(scale / tap); the bytes by test_pusch_llr_gpu's rules with the tapped gain in pusch_llr_model's
+mi_lte_pusch_plan_llr_noise).  sigma2_a against the float64 restatement of include/mi_lte.h's text (tests/pusch_demod_model.py) on the
+front end's planes; the gain exactly (float)(scale / tap); the bytes by test_pusch_llr_gpu's rules with the tapped gain in pusch_demod_model's
 demap(); a plan that turns the setter on and off again is the plan it was; the estimate moves by 10 dB when the noise does; control
 information and the CQI decoder take the bytes as they take any other; the edges and refusals of the header."""
 import ctypes as C
@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 import demap_llr_model as dm
-import pusch_llr_model as pm
-import pusch_noise_model as nm
+import pusch_demod_model as nm
+import pusch_demod_model as pm
 from test_pusch_llr_gpu import CASES, SNRS, c_init, outputs, same_outputs, units_of
 from test_ulsch3gpp_gpu import FFT, QM, ULC, grant
 from test_ulsch_cqi_cpu import ZERO, model as cqi_model

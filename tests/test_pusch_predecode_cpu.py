@@ -1,12 +1,12 @@
 """CPU: what test_pusch_predecode_gpu.py rests on, with no kernel in the loop.  The builder's cases keep the float64 model of the DMRS
-estimate (pusch_llr_model.h_polar) well conditioned; the 74 planned transform sizes reach every radix in every position the kernel has code
+estimate (pusch_demod_model.h_polar) well conditioned; the 74 planned transform sizes reach every radix in every position the kernel has code
 for, every prime of the generic pass, and all four symbol-group shapes; the model's transform has the sign, the scale and the conjugate of
 36.211 5.3.3 on a hand-made case; and a float32 restatement of the kernel's Stockham plan, against numpy's float64 FFT on the tests' own
 inputs, gives the error a float32 transform of these sizes costs -- the figure the GPU tests' tight gate is a multiple of."""
 import numpy as np
 
-import pusch_llr_model as pm
-import pusch_predecode_cases as pc
+import pusch_demod_cases as pc
+import pusch_demod_model as pm
 
 
 def test_planned_sizes_are_the_plans_envelope():

@@ -1,12 +1,12 @@
 """GPU: the front half of k_pusch_demod -- the DMRS least-squares estimate, the one-tap equaliser (slot_h) and the transform pre-decoder
 (dft_pass_r<R> / dft_pass, twelve backward DFTs of size M = 12 N_prb) -- against a float64 model whose transform is numpy's FFT
-(pusch_llr_model.equalise_predecode), through the 3GPP plans' symbol tap (mi_lte_pusch_plan_set_llr_tap).  Every one of the 74 planned sizes,
+(pusch_demod_model.equalise_predecode), through the 3GPP plans' symbol tap (mi_lte_pusch_plan_set_llr_tap).  Every one of the 74 planned sizes,
 so every radix in every position, the generic prime pass at every prime from 7 to 47 and twice at 98 PRB; every symbol-group shape
 (S_par 12 / 6 / 3 / 2), each size in a plan of its own and as a member of a wider plan (row stride M_max != M); the four workgroup widths.
 
 Gates, per data symbol.  Hard: rel-L2 < 1e-5, largest elementwise error < 1e-4 of the symbol's RMS (the project's FFT-stage figures).
 Tight: 8 x the error of a float32 restatement of the same Stockham plan against numpy's float64 FFT on these tests' own inputs
-(pusch_predecode_cases.float32_floor, recomputed here: worst rel-L2 1.62e-7 at 94 PRB, worst elementwise 9.73e-7 of RMS at 74 PRB), so
+(pusch_demod_cases.float32_floor, recomputed here: worst rel-L2 1.62e-7 at 94 PRB, worst elementwise 9.73e-7 of RMS at 74 PRB), so
 1.3e-6 and 7.8e-6.
 
 Measured on an MI355X (worst rel-L2 at N_prb / worst elementwise error over RMS at N_prb):
@@ -28,8 +28,8 @@ one, an error of 3e-2 at 14 PRB, passed all of test_uplink_gpu, test_ulsch3gpp_g
 import numpy as np
 import pytest
 
-import pusch_llr_model as pm
-import pusch_predecode_cases as pc
+import pusch_demod_cases as pc
+import pusch_demod_model as pm
 
 pytestmark = pytest.mark.gpu
 

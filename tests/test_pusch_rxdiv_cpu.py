@@ -1,5 +1,5 @@
 """CPU: the claims behind the 3GPP PUSCH plans' receive-antenna combining (include/mi_lte.h, "PUSCH, 3GPP mode: receive-antenna combining")
-and its float64 model tests/pusch_rxdiv_model.py: one antenna is the single-antenna models to the last bit; the same grid on every antenna
+and its float64 model tests/pusch_demod_model.py: one antenna is the single-antenna models to the last bit; the same grid on every antenna
 is the single-antenna symbol with n_rx times the reliability and the same noise estimate; with independent noise per antenna the combined
 symbol's noise variance is sigma^2 / rho_s and the noise estimate is unbiased with 1 / sqrt(n_rx) of the single-antenna spread; the
 restatement of the launch's LDS and S_par rule gives today's values for one antenna and the limits the header names for two and four; the
@@ -7,17 +7,17 @@ float32 restatement of the combiner stays inside the hard gate; the synthetic an
 import numpy as np
 import pytest
 
-import pusch_llr_model as pm
-import pusch_noise_model as nm
-import pusch_predecode_cases as pc
-import pusch_rxdiv_model as rxm
+import pusch_demod_cases as pc
+import pusch_demod_model as nm
+import pusch_demod_model as pm
+from pusch_demod_cases import rx_view as rxm
 from test_pusch_llr_cpu import selective_channel
 from test_pusch_noise_cpu import channel
 
 
 @pytest.mark.parametrize("n_prb", [1, 6, 25])
 def test_one_antenna_is_the_single_antenna_models(n_prb):
-    """a list of one antenna: every function equals its pusch_llr_model / pusch_noise_model counterpart exactly"""
+    """a list of one antenna: every function equals what it gives for the bare unit's planes exactly"""
     c = pc.case(n_prb, 0)
     one = [c.planes]
     assert np.array_equal(rxm.h_polar(one, c.al, c.dmrs)[0], pm.h_polar(c.planes, c.al, c.dmrs))
@@ -103,7 +103,7 @@ def test_noise_estimate_mean_and_spread(n_rx):
 
 
 def test_lds_and_s_par_rule():
-    """One antenna: the restatement gives today's S_par (pusch_predecode_cases.s_par) and the noise-referenced launch's LDS at every planned
+    """One antenna: the restatement gives today's S_par (pusch_demod_model.s_par) and the noise-referenced launch's LDS at every planned
     size and modulation.  Two antennas: every planned size fits 160 KiB at today's S_par, 144 224 bytes at 99 PRB of 64QAM.  Four: the
     steps and limits the header names -- with 64QAM S_par 3 up to 65 PRB, 2 up to 70, 1 up to 76, refused from 78; with QPSK 3 up to 66,
     2 up to 72, 1 up to 78, refused from 80 -- and 25 PRB fits by a wide margin."""

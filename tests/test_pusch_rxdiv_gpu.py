@@ -1,13 +1,13 @@
 """GPU: receive-antenna combining on the 3GPP PUSCH plans (mi_lte_pusch_plan_set_rx_antennas, k_pusch_demod_llr_rx) against the float64
-model of include/mi_lte.h's text (tests/pusch_rxdiv_model.py): the tapped symbols, rho_s, sigma2 and the gain on synthetic planes of two and
-four antennas at the sizes where the launch changes shape; the bytes by pusch_llr_model.demap on the run's own taps; the same grid on
+model of include/mi_lte.h's text (tests/pusch_demod_model.py): the tapped symbols, rho_s, sigma2 and the gain on synthetic planes of two and
+four antennas at the sizes where the launch changes shape; the bytes by pusch_demod_model.demap on the run's own taps; the same grid on
 every antenna and an all-zero antenna against the single-antenna run; a plan that never saw the setter, or went to 2 and back to 1, is the
 plan it was; transport blocks, control information and HARQ through the transmit chain; every refusal of the contract; and what a second
 antenna buys at a point profiles/pusch_rxdiv_sweep.txt names.
 
-Gates of the tapped symbols, per data symbol.  Hard: rel-L2 < 1e-5 and elementwise < 1e-4 of the symbol's RMS (pusch_predecode_cases).
+Gates of the tapped symbols, per data symbol.  Hard: rel-L2 < 1e-5 and elementwise < 1e-4 of the symbol's RMS (pusch_demod_cases).
 Tight: 8 x the error of the float32 restatement of the estimate, the combiner and the transform on each test's own inputs
-(pusch_rxdiv_model.float32_floor; 1.8e-7 .. 2.0e-7 rel-L2 on these cases), capped at the hard gate.
+(pusch_demod_cases.float32_floor; 1.8e-7 .. 2.0e-7 rel-L2 on these cases), capped at the hard gate.
 
 Measured on an MI355X (worst rel-L2 / worst elementwise error over RMS per plan set of test_taps_against_the_model; tight gates
 1.4e-6 .. 1.6e-6 / 3.1e-6 .. 6.9e-6):
@@ -31,10 +31,10 @@ import numpy as np
 import pytest
 
 import demap_llr_model as dm
-import pusch_llr_model as pm
-import pusch_noise_model as nm
-import pusch_predecode_cases as pc
-import pusch_rxdiv_model as rxm
+import pusch_demod_cases as pc
+import pusch_demod_model as nm
+import pusch_demod_model as pm
+from pusch_demod_cases import rx_view as rxm
 from test_pusch_harq_gpu import decode
 from test_ulsch3gpp_gpu import FFT, QM, ULC, grant
 from test_ulsch_cqi_cpu import CRC_OK, NO_CRC, pack_bits
@@ -59,7 +59,7 @@ def own_choice_of_width(monkeypatch):
 
 
 class Run:
-    """One 3GPP plan over the cases (pusch_rxdiv_model.case), one unit and one allocation each, on n_rx antennas with the symbol tap on.
+    """One 3GPP plan over the cases (pusch_demod_cases.rx_case), one unit and one allocation each, on n_rx antennas with the symbol tap on.
     d_subframes is antenna-major with ant_stride = units + spare; the spare units of every antenna are NaN, so a read of one poisons the
     result.  planes: [unit][antenna], by default the cases' own."""
 
@@ -189,7 +189,7 @@ def test_s_par_steps_are_the_ones_tested():
 @pytest.mark.parametrize("n_rx", [2, 4])
 def test_bytes_against_the_exact_layer(ctx, n_rx):
     """Gate 2.  QPSK on 1 PRB, 16QAM on 6, 64QAM on 10 in one plan, under the automatic gain, a fixed one and the noise-referenced one:
-    no byte differs from pusch_llr_model.demap(taps, rho tap, gain tap) outside the guard band, at most one step inside it, the band
+    no byte differs from pusch_demod_model.demap(taps, rho tap, gain tap) outside the guard band, at most one step inside it, the band
     under 1 % of the soft bits (test_pusch_llr_gpu's cap); the bytes are graded; a second run gives the same bytes."""
     import openlte_amd as m
     sizes, mods = (1, 6, 10), (1, 2, 3)
