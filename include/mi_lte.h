@@ -580,7 +580,12 @@ int mi_lte_ul_dmrs_pusch(const mi_lte_ul_cfg *ul, uint32_t N_id_cell, uint32_t N
  * alloc.unit selects the subframe unit; the unit's subframe number and cell id are host arrays here because
  * the reference signals are generated on the host per (cell, subframe, N_prb).  N_prb must be one the
  * reference has an FFTW plan for: N_prb < N_rb_ul and divisible by 2, 3 or 5 (liblte_phy.cc:2360-2377);
- * single antenna, one code block per transport block. */
+ * single antenna, one code block per transport block.
+ * Refusals of mi_lte_pusch_plan_create (and of its 3GPP forms below), all before anything is allocated on the device:
+ * MI_LTE_ERR_INVALID_ARG for cfg->N_rb_dl outside 6..100 (what mi_lte_ul_frontend_batch accepts) and for a resource block outside the
+ * carrier; MI_LTE_ERR_UNSUPPORTED for an allocation outside the envelope -- tbs above 6120 (more than one code block; sizes near 2^32
+ * included: tbs + 24 is not formed before the bound is checked), an N_prb without a transform plan, mod_type above 3, a unit index past
+ * n_units. */
 typedef struct mi_lte_pusch_plan mi_lte_pusch_plan;
 int      mi_lte_pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul,
                                   const uint32_t *h_unit_subfr_num, const uint32_t *h_unit_n_id_cell, uint32_t n_units,

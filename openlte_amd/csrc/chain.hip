@@ -697,7 +697,7 @@ static int plan_layout(mi_lte_ctx *ctx, mi_lte_pdsch_plan *pl, uint32_t N_pdcch_
     pl->core.groups.clear();
     for (uint32_t a = 0; a < n_alloc; a++) {
         const mi_lte_pdsch_alloc &al = h_allocs[a];
-        const int      r   = cb_alloc ? mi_qpp_row_at_least(al.tbs + 24) : 0;
+        const int      r   = cb_alloc ? mi_tb_row(al.tbs) : 0;
         const uint32_t cfi = al.n_pdcch_symbs ? al.n_pdcch_symbs : N_pdcch_symbs;
         if (r < 0 || al.N_prb == 0 || al.N_prb > cfg->N_rb_dl || al.mod_type > 3 || cfi < 1 || cfi > 4) {
             // multi-code-block transport blocks: the reference's own C > 1 path is broken

@@ -18,12 +18,11 @@
 #include <cstring>
 #include <vector>
 
+#include "dlsch3_layout.h"
 #include "plan_core.hpp"
 
 namespace {
 
-constexpr uint32_t G_CRC24A = 0x1864CFBu; // 36.212 5.1.1, x^24 included
-constexpr uint32_t G_CRC24B = 0x1800063u;
 constexpr uint32_t DL3_E_CAP = 48 * 1024; // LDS a code block stages its soft bits in (larger E_r: read from global memory)
 
 __device__ inline uint32_t k_mimo(uint32_t tx_mode) { return (tx_mode == 3 || tx_mode == 4 || tx_mode == 8 || tx_mode == 9) ? 2u : 1u; }
@@ -37,26 +36,8 @@ __device__ inline void soft_buffer(uint32_t K, uint32_t C, uint32_t tx_mode, uin
     N_cb = N_ir / C < K_w ? N_ir / C : K_w;
     k0   = R * (2 * ((N_cb + 8 * R - 1) / (8 * R)) * rv + 2);
 }
-// x * w mod g for a remainder w < 2^24
-__host__ __device__ inline uint32_t mulx(uint32_t w, uint32_t g) { w <<= 1; return (w & 0x1000000u) ? w ^ g : w; }
-// a * b mod g (Horner over the bits of b)
-__host__ __device__ inline uint32_t mulmod(uint32_t a, uint32_t b, uint32_t g)
-{
-    uint32_t s = 0;
-    for (int i = 23; i >= 0; i--) s = mulx(s, g) ^ (((b >> i) & 1u) ? a : 0u);
-    return s;
-}
-// x^s mod g by squaring
-inline uint32_t xpow(uint32_t s, uint32_t g)
-{
-    uint32_t r = 1, p = 2; // p = x^(2^i)
-    for (; s; s >>= 1, p = mulmod(p, p, g))
-        if (s & 1u) r = mulmod(r, p, g);
-    return r;
-}
 
-// Everything the per-code-block kernels need: the static part from the plan (alloc .. bits_off8), the rest from k_dl3_desc
-struct Dl3Slot { uint32_t alloc, r, C, K, xs, soft_off4, bits_off8, pad; };
+// Everything the per-code-block kernels need: the static part from the plan (Dl3Slot, dlsch3_layout.h), the rest from k_dl3_desc
 struct Dl3Desc {
     uint32_t alloc, r, C, K;
     uint32_t E, off, N_cb, k0;
@@ -317,13 +298,9 @@ __global__ __launch_bounds__(256) void k_harq_commit(const mi_lte_harq_bind *__r
 // ------------------------------------------------------------------------------------------------
 // host side
 
-struct MiDlsch3 {
+struct MiDlsch3 : MiDlsch3Layout { // (the layout's `slots` are dropped once they are on the device)
     mi_lte_dlsch_cfg cfg{};
     uint32_t n_alloc = 0, n_slot = 0, n_l = 1; // n_l: N_L of the code-block concatenation (36.212 5.1.4.1.2)
-    std::vector<MiKGroup> groups;              // a block size's slots, contiguous; ...
-    std::vector<size_t>   g_soft, g_bits;      // ... and where they start in d_soft / d_bits (bytes, on 256)
-    std::vector<uint32_t> a_slot, a_nc, a_K, a_tbs; // per allocation: first slot, C, K, tbs
-    std::vector<size_t>   a_soft;              // per allocation: byte offset of its first block in d_soft
     Dl3Slot  *d_slot = nullptr;
     Dl3Desc  *d_desc = nullptr;
     int8_t   *d_soft = nullptr;
@@ -342,42 +319,17 @@ void mi_dlsch3_free(MiDlsch3 *g)
     delete g;
 }
 
-// The plan's code-block slots: grouped by block size (ascending), inside a size allocation after allocation, block after block.
-// mi_lte_pdsch_plan_create_3gpp has checked every allocation against mi_lte_dlsch_layout.
-int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out, uint32_t n_l)
+// The device half of a laid-out plan (mi_dlsch3_layout): the slots' arrays and tables.
+int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, MiDlsch3Layout &&lay, uint32_t n_alloc, MiDlsch3 **out, uint32_t n_l)
 {
     auto *g   = new MiDlsch3();
-    g->n_l     = n_l;
     auto guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_dlsch3_free(g); });
+    static_cast<MiDlsch3Layout &>(*g) = std::move(lay);
+    g->n_l     = n_l;
     g->cfg     = *cfg;
     g->n_alloc = n_alloc;
-    g->a_slot.resize(n_alloc); g->a_nc.resize(n_alloc); g->a_K.resize(n_alloc); g->a_tbs.resize(n_alloc); g->a_soft.resize(n_alloc);
-    std::vector<uint8_t> row(n_alloc);
-    for (uint32_t a = 0; a < n_alloc; a++) {
-        mi_lte_dlsch_layout_t lay;
-        const int rc = mi_lte_dlsch_layout(h_allocs[a].tbs, 0, 2, h_allocs[a].tx_mode, h_allocs[a].rv_idx & 3u, cfg, &lay);
-        if (rc != MI_LTE_OK) { ctx->err = "transport block size outside the 3GPP mode (F != 0 or tbs > 75376)"; return rc; }
-        g->a_nc[a] = lay.C; g->a_K[a] = lay.K; g->a_tbs[a] = h_allocs[a].tbs;
-        row[a] = (uint8_t)mi_qpp_row_at_least(lay.K);
-    }
-    std::vector<uint32_t> slot_alloc;
-    mi_plan_group(row.data(), g->a_nc.data(), nullptr, n_alloc, g->groups, slot_alloc);
-    g->n_slot = (uint32_t)slot_alloc.size();
-    std::vector<Dl3Slot> slots(g->n_slot);
-    size_t soft = 0, bits = 0;
-    for (const MiKGroup &gr : g->groups) { // a size's arrays start on 256 bytes
-        soft = (soft + 255) & ~(size_t)255; bits = (bits + 255) & ~(size_t)255;
-        g->g_soft.push_back(soft); g->g_bits.push_back(bits);
-        for (uint32_t s = gr.cb_base, r = 0; s < gr.cb_base + gr.n_cb; s++, soft += 3 * (size_t)(gr.K + 4), bits += gr.K) {
-            const uint32_t a = slot_alloc[s], C = g->a_nc[a], B = h_allocs[a].tbs + 24;
-            r = (s > gr.cb_base && slot_alloc[s - 1] == a) ? r + 1 : 0; // an allocation's blocks are adjacent
-            if (r == 0) { g->a_slot[a] = s; g->a_soft[a] = soft; }
-            // x^s mod gCRC24A, s = B - (r + 1)(K - 24) for C > 1 (0 for C = 1): the transport-block bits behind the block's payload
-            const uint32_t xs = xpow(C == 1 ? 0u : B - (r + 1) * (gr.K - 24), G_CRC24A);
-            slots[s] = {a, r, C, gr.K, xs, (uint32_t)(soft / 4), (uint32_t)(bits / 8), 0};
-        }
-        if (soft / 4 > 0xFFFFFFFFull || bits / 8 > 0xFFFFFFFFull) { ctx->err = "3GPP plan too large"; return MI_LTE_ERR_UNSUPPORTED; }
-    }
+    g->n_slot  = (uint32_t)g->slots.size();
+    const size_t soft = g->soft_bytes, bits = g->bits_bytes;
     std::vector<uint32_t> tab(2 * 6144);
     for (uint32_t e = 0, wa = 1, wb = 1; e < 6144; e++, wa = mulx(wa, G_CRC24A), wb = mulx(wb, G_CRC24B)) { tab[e] = wa; tab[6144 + e] = wb; }
     MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_slot, sizeof(Dl3Slot) * g->n_slot));
@@ -393,14 +345,25 @@ int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_
     MI_HIP_CHECK(ctx, hipMalloc((void **)&g->d_slot_buf, sizeof(uint32_t) * g->n_slot));
     MI_HIP_CHECK(ctx, hipMemsetAsync(g->d_soft, 0, std::max<size_t>(soft, 256), ctx->stream)); // (the taps read defined bytes before a first run)
     MI_HIP_CHECK(ctx, hipMemsetAsync(g->d_cb_ok, 0, sizeof(uint32_t) * n_alloc, ctx->stream));
-    MI_H2D(ctx, g->d_slot, slots.data(), sizeof(Dl3Slot) * g->n_slot);
+    MI_H2D(ctx, g->d_slot, g->slots.data(), sizeof(Dl3Slot) * g->n_slot);
     MI_H2D(ctx, g->d_tab, tab.data(), sizeof(uint32_t) * tab.size());
     MI_H2D(ctx, g->d_a_slot, g->a_slot.data(), sizeof(uint32_t) * n_alloc);
     MI_H2D(ctx, g->d_a_nc, g->a_nc.data(), sizeof(uint32_t) * n_alloc);
     MI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<Dl3Slot>().swap(g->slots);
     guard.armed = false;
     *out = g;
     return MI_LTE_OK;
+}
+
+// mi_lte_pdsch_plan_create_3gpp has checked every allocation against mi_lte_dlsch_layout.
+int mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out, uint32_t n_l)
+{
+    MiDlsch3Layout lay;
+    const char    *err = nullptr;
+    const int      rc  = mi_dlsch3_layout(cfg, h_allocs, n_alloc, &lay, &err);
+    if (rc != MI_LTE_OK) { ctx->err = err; return rc; }
+    return mi_dlsch3_create(ctx, cfg, std::move(lay), n_alloc, out, n_l);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "pusch_plan.h"
 
 namespace {
 constexpr size_t ROW = 16 * 1200; // floats per plane of a subframe struct (LIBLTE_PHY_SUBFRAME_STRUCT rows, liblte_phy.h:226-239)
@@ -837,11 +838,8 @@ int mi_lte_ul_subframe_decode_host(mi_lte_ctx *ctx, uint32_t fft_size, uint32_t 
     uint32_t           slot[MI_LTE_UL_SUBFRAME_MAX_ALLOC], n_al = 0;
     for (uint32_t k = 0; k < n_alloc; k++) {
         status[k] = 1; N_out_bits[k] = 0;
-        const mi_lte_pdsch_alloc &a = allocs[k];
-        const bool planned = a.N_prb > 0 && a.N_prb < N_rb_ul && (a.N_prb % 2 == 0 || a.N_prb % 3 == 0 || a.N_prb % 5 == 0);
-        if (!planned || a.tbs + 24 > 6144 || a.tbs + 24 < a.tbs || a.mod_type > 3 || !prbs_on_carrier(a, N_rb_ul)) continue;
-        al[n_al] = a; al[n_al].unit = 0; al[n_al].n_pdcch_symbs = 0;
-        slot[n_al++] = k;
+        al[n_al] = allocs[k]; al[n_al].unit = 0; al[n_al].n_pdcch_symbs = 0;
+        if (pusch_alloc_check(al[n_al], N_rb_ul, 1, /*spec=*/false, nullptr, nullptr, nullptr, nullptr) == MI_LTE_OK) slot[n_al++] = k;
     }
     mi_lte_pusch_plan *plan = nullptr;
     if (n_al) { // the plan carries subframe number, cell, reference signals and the list: all of them are its key (a grant pattern that recurs is planned once)

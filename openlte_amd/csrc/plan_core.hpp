@@ -1,23 +1,11 @@
-// What every plan (PDSCH: chain.hip, PUSCH: uplink.hip, 3GPP transport-block mode: dlsch3gpp.hip) does on the host before a decode: code-block size
-// lookup, soft-bit layout, code-block slots grouped by size, the device arrays and their hand-over to the decoder.  Nothing here knows which channel calls it.
+// What every plan (PDSCH: chain.hip, PUSCH: uplink.hip, 3GPP transport-block mode: dlsch3gpp.hip) holds on the device and hands to the decoder; the
+// arithmetic that lays it out -- code-block size lookup, soft-bit layout, slots grouped by size -- is plan_arith.h's.  Nothing here knows which channel calls it.
 #pragma once
 
 #include "ctx.hpp"
+#include "plan_arith.h"
 
-// Row of LTE_QPP_ROWS (lte_tables.h) of the first code-block size >= B, -1 when B > 6144.
-int mi_qpp_row_at_least(uint32_t B);
-
-// Bytes between two allocations' decoded transport blocks: room for the largest, a multiple of 64 (one bit per byte, or eight when packed)
-inline uint32_t mi_out_stride(uint32_t tbs, bool packed) { return packed ? (((tbs + 7) / 8 + 63) & ~63u) : ((tbs + 63) & ~63u); }
-inline bool     mi_is_bcjr(uint32_t mode) { return mode == MI_LTE_TURBO_BCJR || mode == MI_LTE_TURBO_BCJR_BLOCK || mode == MI_LTE_TURBO_BCJR_EARLY; }
-
-// Soft-bit layout: allocation a's e_bits[a] soft bits start h_e_off[a] 64-byte units into the plan's buffer (each padded to 64 bytes).  Returns the buffer's bytes.
-size_t mi_plan_soft_layout(const uint32_t *e_bits, uint32_t n_alloc, std::vector<uint32_t> &h_e_off);
-
-// Grouping: allocation a has n_cb[a] code blocks (nullptr: one each) of size row[a] (mi_qpp_row_at_least).  Groups in ascending block
-// size; inside a size the allocations in their own order, an allocation's blocks adjacent.  slot_alloc receives the allocation of every
-// code-block slot; a group's e_max is its longest allocation's e_bits (nullptr: 0).  A counting sort over the 188 sizes.
-void mi_plan_group(const uint8_t *row, const uint32_t *n_cb, const uint32_t *e_bits, uint32_t n_alloc, std::vector<MiKGroup> &groups, std::vector<uint32_t> &slot_alloc);
+inline bool mi_is_bcjr(uint32_t mode) { return mode == MI_LTE_TURBO_BCJR || mode == MI_LTE_TURBO_BCJR_BLOCK || mode == MI_LTE_TURBO_BCJR_EARLY; }
 
 // What a plan hands to a decoder entry point (turbo.hip: mi_turbo_ref_dispatch, mi_turbo_bcjr_group; dlsch3gpp.hip: mi_dlsch3_run)
 struct MiDecodeIO {
@@ -58,6 +46,8 @@ int   mi_turbo_bcjr_group(mi_lte_ctx *ctx, const MiKGroup &gr, const MiDecodeIO 
 
 // the 3GPP transport-block mode's part of a plan (dlsch3gpp.hip)
 struct MiDlsch3;
+struct MiDlsch3Layout; // dlsch3_layout.h: the first form commits a layout the caller has made, the second lays the slots out itself
+int             mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, MiDlsch3Layout &&lay, uint32_t n_alloc, MiDlsch3 **out, uint32_t n_l = 1);
 int             mi_dlsch3_create(mi_lte_ctx *ctx, const mi_lte_dlsch_cfg *cfg, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc, MiDlsch3 **out, uint32_t n_l = 1);
 void            mi_dlsch3_free(MiDlsch3 *g);
 int             mi_dlsch3_run(mi_lte_ctx *ctx, MiDlsch3 *g, mi_lte_harq_pool *p, const mi_lte_harq_bind *h_bind, const MiDecodeIO &io, uint32_t decoder, uint32_t n_iter);

@@ -8,6 +8,7 @@
 
 #include "../../include/mi_lte.h"
 #include "lte_tables.h"
+#include "pusch_plan.h"
 
 namespace {
 
@@ -150,7 +151,7 @@ int mi_lte_get_tbs_mcs_and_n_prb_for_ul(uint32_t N_bits, uint32_t N_rb_ul, uint3
     for (uint32_t i = 0; i < 27; i++)
         for (uint32_t j = 0; j < 11; j++) {
             const uint32_t n = j + 1; // SC-FDMA widths have the factors 2, 3, 5 only (36.211 5.3.3); the reference's test is "a multiple of one of them"
-            if (N_bits <= tbs_at(i, j) && (n % 2 == 0 || n % 3 == 0 || n % 5 == 0)) {
+            if (N_bits <= tbs_at(i, j) && pusch_nprb_planned(n, ~0u, false)) { // (whatever the bandwidth)
                 *tbs   = tbs_at(i, j);
                 *N_prb = n;
                 *mcs   = (uint8_t)(i <= 10 ? i : i <= 19 ? i + 1 : i + 2); // 36.213 table 8.6.1-1: MCS 11 and 21 repeat I_TBS 10 and 19

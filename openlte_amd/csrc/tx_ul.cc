@@ -9,6 +9,7 @@
 
 #include "../../include/mi_lte.h"
 #include "prach_sets.hpp"
+#include "pusch_plan.h"
 #include "synth.hpp"
 #include "tx_host.h"
 
@@ -71,7 +72,7 @@ int mi_lte_pusch_channel_encode(mi_lte_tx_ul *t, const mi_lte_ul_cfg *ul, uint32
     // N_prb below N_rb_ul with a factor 2, 3 or 5 (liblte_phy.cc:2360-2378)
     const uint32_t N_prb = al->N_prb;
     if (N_ant != 1 || al->N_layers != 1 || al->N_codewords != 1 || subfr_num > 9) return 1;
-    if (N_prb == 0 || N_prb >= N_rb_ul || !(N_prb % 2 == 0 || N_prb % 3 == 0 || N_prb % 5 == 0) || N_sc_rb_ul != 12 || 12 * N_prb > MI_LTE_TX_GRID_SC) return 1;
+    if (!pusch_nprb_planned(N_prb, N_rb_ul, false) || N_sc_rb_ul != 12 || 12 * N_prb > MI_LTE_TX_GRID_SC) return 1;
     if (!al->msg[0] && al->msg_bits[0]) return 1;
     const uint32_t Q_m = al->mod_type == MI_LTE_MOD_BPSK ? 1 : al->mod_type == MI_LTE_MOD_QPSK ? 2 : al->mod_type == MI_LTE_MOD_16QAM ? 4 : 6;
     const uint32_t M_sc = 12 * N_prb, G = M_sc * 12, tbs = al->tbs;

@@ -22,10 +22,10 @@ struct MiUlschUci {
     std::vector<mi_lte_cqi_desc> h_cqi_desc;
 };
 
-// h_c_init: the scrambling sequence's c_init per allocation; h_e_off / e_bytes: the plan's soft-bit layout (plan_core.hpp).  Every descriptor
-// has passed mi_lte_ulsch_uci_G.
+// h_c_init: the scrambling sequence's c_init per allocation; h_G: what mi_lte_ulsch_uci_G gave for every descriptor; e_bytes: the plan's soft-bit
+// buffer, in which every gathered run fits its allocation's slot (pusch_plan_layout has made and checked all three).
 int  mi_ulsch_uci_create(mi_lte_ctx *ctx, const mi_lte_pdsch_alloc *h_allocs, const mi_lte_ulsch_uci *h_uci, const uint32_t *h_c_init,
-                         const uint32_t *h_e_off, uint32_t n_alloc, size_t e_bytes, MiUlschUci **out);
+                         const uint32_t *h_G, uint32_t n_alloc, size_t e_bytes, MiUlschUci **out);
 void mi_ulsch_uci_free(MiUlschUci *u);
 // k_ulsch_uci_gather and k_ulsch_uci_decide over the demodulator's soft bits d_e (allocation a at d_e + 64 d_e_off[a])
 int  mi_ulsch_uci_run(mi_lte_ctx *ctx, MiUlschUci *u, const int8_t *d_e, const uint32_t *d_e_off);

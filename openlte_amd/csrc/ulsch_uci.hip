@@ -10,8 +10,8 @@
 //                       one partial RI row 12 - Qp_ri mod 4, full RI rows 8 -- no scan, no LDS.
 //   k_ulsch_uci_decide  one workgroup per allocation: the int32 sums of the ACK and RI symbols' soft bits 0 and 1 (wave reduction, then LDS;
 //                       integer sums are order-free, so the result is exact), the decisions, one result record per allocation.
-// The host part: the descriptor checks (mi_lte_ulsch_uci_G), the Q' arithmetic, and the forward map the transmitter is driven by
-// (mi_lte_ulsch_uci_map) -- written from the placement rules, where the kernels use their inverse.
+// The host arithmetic -- the descriptor checks (mi_lte_ulsch_uci_G), the Q' arithmetic, and the forward map the transmitter is driven by
+// (mi_lte_ulsch_uci_map), written from the placement rules where the kernels use their inverse -- is ulsch_host.cc's.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -175,24 +175,19 @@ __global__ __launch_bounds__(DECIDE_THREADS) void k_ulsch_uci_decide(const UciDe
 } // namespace
 
 int mi_ulsch_uci_create(mi_lte_ctx *ctx, const mi_lte_pdsch_alloc *h_allocs, const mi_lte_ulsch_uci *h_uci, const uint32_t *h_c_init,
-                        const uint32_t *h_e_off, uint32_t n_alloc, size_t e_bytes, MiUlschUci **out)
+                        const uint32_t *h_G, uint32_t n_alloc, size_t e_bytes, MiUlschUci **out)
 {
     auto *u    = new MiUlschUci();
     auto guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_ulsch_uci_free(u); });
     u->n_alloc = n_alloc;
-    u->h_G.resize(n_alloc); u->h_Q_cqi.resize(n_alloc);
+    u->h_G.assign(h_G, h_G + n_alloc); u->h_Q_cqi.resize(n_alloc);
     std::vector<UciDesc> desc(n_alloc);
     for (uint32_t a = 0; a < n_alloc; a++) {
         const mi_lte_pdsch_alloc &al = h_allocs[a];
         const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : 2;
-        uint32_t       G  = 0;
-        const int      rc = mi_lte_ulsch_uci_G(al.N_prb, Qm, &h_uci[a], &G);
-        if (rc != MI_LTE_OK) { ctx->err = "control information descriptor refused (mi_lte_ulsch_uci_G)"; return rc; }
-        desc[a] = {12 * al.N_prb, Qm, h_uci[a].Qp_ack, h_uci[a].Qp_ri, h_uci[a].O_ack, h_uci[a].O_ri, h_uci[a].Q_cqi, G, h_c_init[a], {0, 0, 0}};
-        u->h_G[a] = G; u->h_Q_cqi[a] = h_uci[a].Q_cqi;
-        u->tiles = std::max(u->tiles, (G + h_uci[a].Q_cqi + GATHER_TILE - 1) / GATHER_TILE);
-        // the run replaces the allocation's 12 * 12 N_prb * Q_m soft bits in a slot of the same size at the same offset
-        if ((size_t)h_e_off[a] * 64 + ((size_t)G + h_uci[a].Q_cqi + 3) / 4 * 4 > e_bytes) { ctx->err = "soft-bit layout too small for the allocation"; return MI_LTE_ERR_INVALID_ARG; }
+        desc[a] = {12 * al.N_prb, Qm, h_uci[a].Qp_ack, h_uci[a].Qp_ri, h_uci[a].O_ack, h_uci[a].O_ri, h_uci[a].Q_cqi, h_G[a], h_c_init[a], {0, 0, 0}};
+        u->h_Q_cqi[a] = h_uci[a].Q_cqi;
+        u->tiles = std::max(u->tiles, (h_G[a] + h_uci[a].Q_cqi + GATHER_TILE - 1) / GATHER_TILE);
     }
     MI_HIP_CHECK(ctx, hipMalloc(&u->d_desc, sizeof(UciDesc) * n_alloc));
     MI_HIP_CHECK(ctx, hipMalloc((void **)&u->d_e, std::max<size_t>(e_bytes, 64)));
@@ -232,65 +227,3 @@ int mi_ulsch_uci_run(mi_lte_ctx *ctx, MiUlschUci *u, const int8_t *d_e, const ui
     MI_HIP_CHECK(ctx, hipGetLastError());
     return MI_LTE_OK;
 }
-
-// ------------------------------------------------------------------------------------------------
-// host arithmetic (no device, no context)
-
-extern "C" {
-
-int mi_lte_ulsch_uci_qprime(uint32_t kind, uint32_t O, uint32_t beta_x8, uint32_t M_sc_initial, uint32_t N_symb_initial, uint32_t sum_K_r,
-                            uint32_t N_prb, uint32_t Qp_ri, uint32_t *Qp)
-{
-    if (!Qp || kind > MI_LTE_UCI_CQI || sum_K_r == 0 || N_prb == 0 || N_prb > 110) return MI_LTE_ERR_INVALID_ARG;
-    // (factors inside what 36.212 / 36.213 allow, generously: the product below then stays under 2^56)
-    if (O > 0xFFFFu || beta_x8 > 0xFFFFu || M_sc_initial > 1320 || N_symb_initial > 14) return MI_LTE_ERR_INVALID_ARG;
-    const uint64_t M = 12ull * N_prb;
-    if (kind == MI_LTE_UCI_CQI && Qp_ri > 4 * M) return MI_LTE_ERR_INVALID_ARG;
-    const uint64_t cap = kind == MI_LTE_UCI_CQI ? 12 * M - Qp_ri : 4 * M;
-    const uint64_t Oe  = kind == MI_LTE_UCI_CQI && O > 11 ? (uint64_t)O + 8 : O; // the CQI's CRC (36.212 5.2.2.6)
-    const uint64_t num = Oe * M_sc_initial * N_symb_initial * beta_x8, den = 8ull * sum_K_r;
-    const uint64_t q   = (num + den - 1) / den;
-    *Qp = (uint32_t)(q < cap ? q : cap);
-    return MI_LTE_OK;
-}
-
-int mi_lte_ulsch_uci_G(uint32_t N_prb, uint32_t Q_m, const mi_lte_ulsch_uci *uci, uint32_t *G)
-{
-    if (!uci || !G || N_prb == 0 || N_prb > 110 || !(Q_m == 2 || Q_m == 4 || Q_m == 6)) return MI_LTE_ERR_INVALID_ARG;
-    const uint32_t M = 12 * N_prb;
-    if (uci->O_ack > 2 || uci->O_ri > 2 || uci->Qp_ack > 4 * M || uci->Qp_ri > 4 * M) return MI_LTE_ERR_INVALID_ARG;
-    if ((uci->O_ack == 0) != (uci->Qp_ack == 0) || (uci->O_ri == 0) != (uci->Qp_ri == 0) || uci->Q_cqi % Q_m) return MI_LTE_ERR_INVALID_ARG;
-    const int64_t g = (int64_t)Q_m * (12 * (int64_t)M - uci->Qp_ri) - (int64_t)uci->Q_cqi;
-    if (g <= 0) return MI_LTE_ERR_INVALID_ARG;
-    *G = (uint32_t)g;
-    return MI_LTE_OK;
-}
-
-int mi_lte_ulsch_uci_map(uint32_t N_prb, uint32_t Q_m, const mi_lte_ulsch_uci *uci, uint8_t *kind, uint32_t *index)
-{
-    uint32_t  G;
-    const int rc = mi_lte_ulsch_uci_G(N_prb, Q_m, uci, &G);
-    if (rc != MI_LTE_OK) return rc;
-    if (!kind || !index) return MI_LTE_ERR_INVALID_ARG;
-    const uint32_t M = 12 * N_prb, n_cqi = uci->Q_cqi / Q_m;
-    static const uint32_t ri_col[4] = {1, 10, 7, 4}, ack_col[4] = {2, 9, 8, 3};
-    memset(kind, MI_LTE_UCI_CELL_DATA, 12 * (size_t)M);
-    for (uint32_t i = 0; i < uci->Qp_ri; i++) { // 1. rank indication, from the last row upwards
-        const uint32_t cell = (M - 1 - i / 4) * 12 + ri_col[i % 4];
-        kind[cell] = MI_LTE_UCI_CELL_RI; index[2 * cell] = i; index[2 * cell + 1] = 0xFFFFFFFFu;
-    }
-    for (uint32_t cell = 0, t = 0; cell < 12 * M; cell++) { // 2. CQI, then data, row by row around the RI cells
-        if (kind[cell] == MI_LTE_UCI_CELL_RI) continue;
-        kind[cell] = t < n_cqi ? MI_LTE_UCI_CELL_CQI : MI_LTE_UCI_CELL_DATA;
-        index[2 * cell] = t < n_cqi ? t : t - n_cqi; index[2 * cell + 1] = 0xFFFFFFFFu;
-        t++;
-    }
-    for (uint32_t i = 0; i < uci->Qp_ack; i++) { // 3. HARQ-ACK over what step 2 wrote
-        const uint32_t cell = (M - 1 - i / 4) * 12 + ack_col[i % 4];
-        index[2 * cell + 1] = index[2 * cell]; index[2 * cell] = i;
-        kind[cell] = kind[cell] == MI_LTE_UCI_CELL_CQI ? MI_LTE_UCI_CELL_ACK_CQI : MI_LTE_UCI_CELL_ACK_DATA;
-    }
-    return MI_LTE_OK;
-}
-
-} // extern "C"

@@ -23,8 +23,6 @@
 // The DFT sizes are not powers of two and FFTW's operation order is unspecified, so like the downlink FFT
 // this stage is tolerance-checked; everything from the int8 soft bits on is integer-exact.
 #include <algorithm>
-#include <map>
-#include <tuple>
 
 #include <type_traits>
 
@@ -34,17 +32,13 @@
 #include "ulsch_uci.h"
 #include "demap_llr.h"
 #include "pusch_launch.h"
+#include "pusch_plan.h"
 
 using namespace pusch_geom; // EST_ROWS, the LLR block's sizes, PUSCH_THREADS and the launch rule
 
 namespace {
 
 constexpr int N_SC_MAX = 1200;
-
-struct PuschDesc {
-    uint32_t subfr, cell;   // of the allocation's unit
-    uint32_t dmrs_off;      // float offset of dmrs_0_re | dmrs_0_im | dmrs_1_re | dmrs_1_im (M each) in the DMRS pool
-};
 
 // The transform pre-decoding of an allocation of N_prb resource blocks, M = 12 N_prb: the radices of its Stockham passes in the order they
 // run (9, 3, 5, 8, 4, 2, then the primes that are left) with each pass's sizes, sqrt(M) as the reference forms it (liblte_phy.cc:6644: integer
@@ -756,9 +750,6 @@ struct mi_lte_pusch_plan {
     float        *d_llr_nu = nullptr;
 };
 
-// UL-SCH rate matching has no soft-buffer limit (36.212 5.2.2.5: N_cb = K_w).  As a DL-SCH soft-buffer configuration: an N_IR no block reaches
-static const mi_lte_dlsch_cfg ULSCH_AS_DLSCH = {MI_LTE_ULSCH_N_SOFT, MI_LTE_ULSCH_M_HARQ};
-
 // the float next above or equal to 1 / d (see quot)
 static float recip_up(uint32_t d)
 {
@@ -805,10 +796,8 @@ static int pusch_shapes(mi_lte_ctx *ctx)
     return MI_LTE_OK;
 }
 
-// h_dmrs (optional): caller-supplied reference signals, 4 x 12*N_prb floats per allocation back to back -- the
-// per-call host form passes the arrays liblte_phy_ul_init left in the caller's LIBLTE_PHY_STRUCT.
-// spec: a plan in the 3GPP transport-block mode -- the transport block's conditions are mi_lte_ulsch_layout's, its code blocks dlsch3gpp.hip's
-// h_uci (optional, spec only): one control-information descriptor per allocation
+// The arguments are pusch_plan_layout's (pusch_plan.h), which makes everything the plan holds but its device memory: every refusal that is
+// no HIP error comes from there, before the first allocation on the device.
 extern "C" void mi_lte_pusch_plan_destroy(mi_lte_ctx *ctx, mi_lte_pusch_plan *pl);
 static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
                              const uint32_t *h_unit_n_id_cell, uint32_t n_units, const mi_lte_pdsch_alloc *h_allocs, uint32_t n_alloc,
@@ -816,115 +805,47 @@ static int pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
 {
     if (!ctx || !cfg || (!ul && !h_dmrs) || !h_unit_subfr_num || !h_unit_n_id_cell || !h_allocs || !out || n_alloc == 0 || n_units == 0)
         return MI_LTE_ERR_INVALID_ARG;
-    if (h_uci && !spec) { ctx->err = "control information on PUSCH needs a plan in the 3GPP transport-block mode"; return MI_LTE_ERR_UNSUPPORTED; }
+    PuschPlanLayout L;
+    const char     *err = nullptr;
+    const int       rc  = pusch_plan_layout(cfg, ul, h_dmrs, h_unit_subfr_num, h_unit_n_id_cell, n_units, h_allocs, n_alloc, spec, h_uci, &L, &err);
+    if (rc != MI_LTE_OK) {
+        if (err) ctx->err = err;
+        return rc;
+    }
     MI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     auto *pl    = new mi_lte_pusch_plan();
     auto  guard = on_fail([&] { (void)hipStreamSynchronize(ctx->stream); mi_lte_pusch_plan_destroy(nullptr, pl); });
     pl->cfg     = *cfg;
     pl->device  = ctx->device;
-    pl->core.n_alloc = n_alloc;
     pl->n_units = n_units;
-    std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> dmrs_at; // (cell, subframe, N_prb) -> float offset
-    std::vector<float>     dmrs;
-    std::vector<PuschDesc> desc(n_alloc);
-    std::vector<uint8_t>   row(n_alloc);
-    std::vector<uint32_t>  c_init(n_alloc);
-    uint32_t max_tbs = 0;
-    pl->h_e_len.resize(n_alloc);
-    for (uint32_t a = 0; a < n_alloc; a++) {
-        const mi_lte_pdsch_alloc &al = h_allocs[a];
-        const int r = spec ? 0 : mi_qpp_row_at_least(al.tbs + 24);
-        // N_prb the reference has a transform pre-decoding plan for (liblte_phy.cc:2360-2377)
-        // (the 3GPP mode also takes the single resource block: M = 12 is a size of 36.211 5.3.3, and a grant that small is where control
-        // information fills whole rows; the reference's test leaves it out only because 1 is no multiple of 2, 3 or 5)
-        const bool planned = al.N_prb > 0 && al.N_prb < cfg->N_rb_dl && (al.N_prb % 2 == 0 || al.N_prb % 3 == 0 || al.N_prb % 5 == 0 || (spec && al.N_prb == 1));
-        if (r < 0 || !planned || al.mod_type > 3 || al.unit >= n_units) {
-            ctx->err = "PUSCH allocation outside the envelope (one code block; N_prb < N_rb_ul and divisible by 2, 3 or 5) or malformed";
-            return MI_LTE_ERR_UNSUPPORTED;
-        }
-        if (spec) {
-            mi_lte_dlsch_layout_t lay;
-            const int rc = al.mod_type == 0 ? MI_LTE_ERR_UNSUPPORTED : mi_lte_ulsch_layout(al.tbs, 0, 2, al.rv_idx & 3u, &lay);
-            if (rc != MI_LTE_OK) { ctx->err = "PUSCH allocation outside the 3GPP transport-block mode (BPSK, F != 0 or tbs > 75376)"; return rc; }
-        }
-        if (h_uci) { // the descriptor's own conditions, then the transport block over the G that the control information leaves (36.212 5.2.2.7)
-            const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : 2;
-            uint32_t       G  = 0;
-            int rc = mi_lte_ulsch_uci_G(al.N_prb, Qm, &h_uci[a], &G);
-            if (rc != MI_LTE_OK) {
-                ctx->err = "control information refused: O > 2, Q' > 4 M, O without Q' or Q' without O, Q_cqi not a multiple of Q_m, or no room left for data";
-                return rc;
-            }
-            mi_lte_dlsch_layout_t lay;
-            if ((rc = mi_lte_ulsch_layout(al.tbs, G, Qm, al.rv_idx & 3u, &lay)) != MI_LTE_OK) {
-                ctx->err = "the transport block does not fit the bits that control information leaves (mi_lte_ulsch_layout)";
-                return rc;
-            }
-            if (G / Qm < lay.C) { ctx->err = "control information leaves a code block without a symbol"; return MI_LTE_ERR_INVALID_ARG; }
-        }
-        for (uint32_t sl = 0; sl < 2; sl++) // a resource block past the carrier would be read out of the neighbouring symbol row
-            for (uint32_t i = 0; i < al.N_prb; i++)
-                if (al.prb[sl][i] >= cfg->N_rb_dl) {
-                    ctx->err = "PUSCH allocation names a resource block outside the carrier";
-                    return MI_LTE_ERR_INVALID_ARG;
-                }
-        const uint32_t sf = h_unit_subfr_num[al.unit] % 10, cell = h_unit_n_id_cell[al.unit], M = 12 * al.N_prb;
-        if (h_dmrs) {
-            const uint32_t at = (uint32_t)dmrs.size();
-            dmrs.insert(dmrs.end(), h_dmrs, h_dmrs + 4 * (size_t)M);
-            h_dmrs += 4 * (size_t)M;
-            desc[a] = {sf, cell, at};
-        } else {
-            auto key = std::make_tuple(cell, sf, al.N_prb);
-            auto it  = dmrs_at.find(key);
-            if (it == dmrs_at.end()) {
-                const uint32_t at = (uint32_t)dmrs.size();
-                dmrs.resize(dmrs.size() + 4 * (size_t)M);
-                int rc = mi_lte_ul_dmrs_pusch(ul, cell, sf, al.N_prb, &dmrs[at], &dmrs[at + M], &dmrs[at + 2 * M], &dmrs[at + 3 * M]);
-                if (rc != MI_LTE_OK) return rc;
-                it = dmrs_at.emplace(key, at).first;
-            }
-            desc[a] = {sf, cell, it->second};
-        }
-        c_init[a] = (al.rnti << 14) | (sf << 9) | cell; // (k_pusch_demod's)
-        row[a] = (uint8_t)r;
-        max_tbs = std::max(max_tbs, al.tbs);
-        const uint32_t Qm = al.mod_type == 3 ? 6 : al.mod_type == 2 ? 4 : al.mod_type == 1 ? 2 : 1, E = 12 * M * Qm;
-        pl->M_max     = std::max(pl->M_max, M);
-        pl->words_max = std::max(pl->words_max, (E + 31) / 32 + 1);
-        pl->h_e_len[a] = E;
-    }
-    if (pl->words_max > 4096) { ctx->err = "allocation larger than the scrambling table"; return MI_LTE_ERR_UNSUPPORTED; }
-    pl->core.e_bytes    = mi_plan_soft_layout(pl->h_e_len.data(), n_alloc, pl->core.h_e_off);
-    pl->core.out_stride = mi_out_stride(max_tbs, false);
-    pl->max_tbs         = max_tbs;
-    std::vector<uint32_t> cb_alloc(n_alloc, 0u);
-    if (!spec) mi_plan_group(row.data(), nullptr, pl->h_e_len.data(), n_alloc, pl->core.groups, cb_alloc);
+    pl->M_max   = L.M_max; pl->words_max = L.words_max; pl->max_tbs = L.max_tbs;
+    pl->core.n_alloc    = n_alloc;
+    pl->core.e_bytes    = L.e_bytes;
+    pl->core.out_stride = L.out_stride;
+    pl->core.groups     = std::move(L.groups);
+    pl->core.h_e_off    = std::move(L.e_off);
+    pl->h_e_len         = std::move(L.e_len);
+    pl->h_x_off         = std::move(L.x_off);
     MI_HIP_CHECK(ctx, pl->core.allocate(n_alloc, pl->core.e_bytes));
     if (spec) {
-        const int rc = mi_dlsch3_create(ctx, &ULSCH_AS_DLSCH, h_allocs, n_alloc, &pl->g3);
-        if (rc != MI_LTE_OK) return rc;
+        const int rc3 = mi_dlsch3_create(ctx, &ULSCH_AS_DLSCH, std::move(L.g3), n_alloc, &pl->g3);
+        if (rc3 != MI_LTE_OK) return rc3;
         MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_llr_gain, sizeof(float) * 14 * (size_t)n_alloc)); // gain [n_alloc] | rho [n_alloc][12] | sigma2 [n_alloc]
         MI_HIP_CHECK(ctx, hipMemsetAsync(pl->d_llr_gain, 0, sizeof(float) * 14 * (size_t)n_alloc, ctx->stream));
         pl->d_llr_rho = pl->d_llr_gain + n_alloc;
         pl->d_llr_s2  = pl->d_llr_gain + 13 * (size_t)n_alloc;
-        pl->h_x_off.resize(n_alloc + 1);
-        uint64_t at = 0;
-        for (uint32_t a = 0; a < n_alloc; a++) { pl->h_x_off[a] = (uint32_t)at; at += 144ull * h_allocs[a].N_prb; }
-        if (at > 0xFFFFFFFFull) { ctx->err = "plan larger than the symbol tap's 32-bit offsets"; return MI_LTE_ERR_UNSUPPORTED; }
-        pl->h_x_off[n_alloc] = (uint32_t)at;
     }
     if (h_uci) {
-        const int rc = mi_ulsch_uci_create(ctx, h_allocs, h_uci, c_init.data(), pl->core.h_e_off.data(), n_alloc, pl->core.e_bytes, &pl->uci);
-        if (rc != MI_LTE_OK) return rc;
+        const int rcu = mi_ulsch_uci_create(ctx, h_allocs, h_uci, L.c_init.data(), L.G.data(), n_alloc, pl->core.e_bytes, &pl->uci);
+        if (rcu != MI_LTE_OK) return rcu;
     }
     MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_desc, sizeof(PuschDesc) * n_alloc));
-    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_dmrs, sizeof(float) * std::max<size_t>(dmrs.size(), 1)));
+    MI_HIP_CHECK(ctx, hipMalloc((void **)&pl->d_dmrs, sizeof(float) * std::max<size_t>(L.dmrs.size(), 1)));
     MI_H2D(ctx, pl->core.d_allocs, h_allocs, sizeof(mi_lte_pdsch_alloc) * n_alloc);
-    MI_H2D(ctx, pl->d_desc, desc.data(), sizeof(PuschDesc) * n_alloc);
-    MI_H2D(ctx, pl->d_dmrs, dmrs.data(), sizeof(float) * dmrs.size());
+    MI_H2D(ctx, pl->d_desc, L.desc.data(), sizeof(PuschDesc) * n_alloc);
+    MI_H2D(ctx, pl->d_dmrs, L.dmrs.data(), sizeof(float) * L.dmrs.size());
     MI_H2D(ctx, pl->core.d_e_off, pl->core.h_e_off.data(), sizeof(uint32_t) * n_alloc);
-    MI_H2D(ctx, pl->core.d_cb_alloc, cb_alloc.data(), sizeof(uint32_t) * n_alloc);
+    MI_H2D(ctx, pl->core.d_cb_alloc, L.cb_alloc.data(), sizeof(uint32_t) * n_alloc);
     MI_HIP_CHECK(ctx, mi_stream_wait_polling(ctx));
     guard.armed = false;
     *out = pl;
@@ -946,11 +867,6 @@ int mi_lte_pusch_plan_create(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi
 {
     if (!ul) return MI_LTE_ERR_INVALID_ARG;
     return mi_pusch_plan_create_impl(ctx, cfg, ul, h_unit_subfr_num, h_unit_n_id_cell, n_units, h_allocs, n_alloc, nullptr, out);
-}
-
-int mi_lte_ulsch_layout(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t rv, mi_lte_dlsch_layout_t *out)
-{
-    return mi_lte_dlsch_layout(tbs, G, Q_m, 1, rv, &ULSCH_AS_DLSCH, out);
 }
 
 int mi_lte_pusch_plan_create_3gpp(mi_lte_ctx *ctx, const mi_lte_dl_cfg *cfg, const mi_lte_ul_cfg *ul, const uint32_t *h_unit_subfr_num,
