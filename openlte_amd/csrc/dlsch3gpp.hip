@@ -20,23 +20,13 @@
 
 #include "dlsch3_layout.h"
 #include "plan_core.hpp"
+#include "rm_geom.h"
 
 namespace {
 
 constexpr uint32_t DL3_E_CAP = 48 * 1024; // LDS a code block stages its soft bits in (larger E_r: read from global memory)
 
-__device__ inline uint32_t k_mimo(uint32_t tx_mode) { return (tx_mode == 3 || tx_mode == 4 || tx_mode == 8 || tx_mode == 9) ? 2u : 1u; }
 __device__ inline uint32_t q_m(uint32_t mod_type) { return mod_type == 3 ? 6u : mod_type == 2 ? 4u : mod_type == 1 ? 2u : 1u; }
-// 36.212 5.1.4.1.2: soft-buffer size per code block and the redundancy version's start, K_C = 1 (the host's copy: mi_lte_dlsch_layout, synth.cc)
-__device__ inline void soft_buffer(uint32_t K, uint32_t C, uint32_t tx_mode, uint32_t rv, uint32_t N_soft, uint32_t M_dl_harq,
-                                            uint32_t &N_cb, uint32_t &k0)
-{
-    const uint32_t R = (K + 4 + 31) / 32, K_w = 96 * R;
-    const uint32_t N_ir = N_soft / (k_mimo(tx_mode) * (M_dl_harq < 8 ? M_dl_harq : 8));
-    N_cb = N_ir / C < K_w ? N_ir / C : K_w;
-    k0   = R * (2 * ((N_cb + 8 * R - 1) / (8 * R)) * rv + 2);
-}
-
 // Everything the per-code-block kernels need: the static part from the plan (Dl3Slot, dlsch3_layout.h), the rest from k_dl3_desc
 struct Dl3Desc {
     uint32_t alloc, r, C, K;
@@ -57,55 +47,20 @@ __global__ __launch_bounds__(256) void k_dl3_desc(const Dl3Slot *__restrict__ sl
     d.alloc = sl.alloc; d.r = r; d.C = C; d.K = sl.K;
     d.E   = Qm * (r + gam < C ? lo : lo + 1);                    // r <= C - gamma - 1: floor(G' / C), else ceil
     d.off = Qm * (r * lo + (r > C - gam ? r - (C - gam) : 0u)); // blocks C - gamma .. r - 1 have one symbol more
-    soft_buffer(sl.K, C, al.tx_mode, al.rv_idx & 3u, N_soft, M_dl_harq, d.N_cb, d.k0);
+    const RmSoftBuf sb = rm_soft_buffer(sl.K + 4, C, al.tx_mode, N_soft, M_dl_harq, true, al.rv_idx & 3u); // (as the host lays the block out: mi_lte_dlsch_layout, synth.cc)
+    d.N_cb = sb.N_cb; d.k0 = sb.k0;
     d.tbs = al.tbs; d.xs = sl.xs; d.soft_off4 = sl.soft_off4; d.bits_off8 = sl.bits_off8;
     out[s] = d;
 }
-
-// Circular-buffer geometry of a block (36.212 5.1.4.1.1-2): the sub-block-interleaved streams column by column, and for every d element
-// its position p and the number of non-NULL positions below it.  Only row 0 of a stream's R x 32 matrix holds NULLs (the N_d head-padding
-// bits), so the count is a popcount over the columns.  The same geometry as turbo.hip's RmGeom, with N_cb and k0 given.
-struct Rm3 {
-    uint32_t R, K_pi, N_d, N_cb, k0m, Nnn, cnt_k0, mask0, mask2;
-    __device__ static uint32_t lowmask(uint32_t n) { return n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u); }
-    __device__ uint32_t nulls_below(uint32_t p) const
-    {
-        if (p <= K_pi) return __popc(mask0 & lowmask((p + R - 1) / R));
-        const uint32_t q = p - K_pi, a = (q + 1) >> 1, b = q >> 1;
-        return __popc(mask0) + __popc(mask0 & lowmask((a + R - 1) / R)) + __popc(mask2 & lowmask((b + R - 1) / R)) + ((b > K_pi - 1) ? 1u : 0u);
-    }
-    __device__ void init(uint32_t D, uint32_t N_cb_, uint32_t k0)
-    {
-        R = (D + 31) / 32; K_pi = 32 * R; N_d = K_pi - D; N_cb = N_cb_; k0m = k0 % N_cb;
-        mask0 = mask2 = 0;
-        for (uint32_t c = 0; c < 32; c++) {
-            const uint32_t P = __brev(c) >> 27; // inter-column permutation = 5-bit reversal (36.212 table 5.1.4-1)
-            if (P < N_d) mask0 |= 1u << c;
-            if (P + 1 < N_d) mask2 |= 1u << c;
-        }
-        Nnn    = N_cb - nulls_below(N_cb);
-        cnt_k0 = k0m - nulls_below(k0m);
-    }
-    // d[i*3+x] -> its position p and the non-NULL count below it
-    __device__ void pos_cnt(uint32_t i, int x, uint32_t &p, uint32_t &cn) const
-    {
-        const uint32_t n = i + N_d - (x == 2 ? 1u : 0u), c = __brev(n & 31) >> 27, r = n >> 5, ii = c * R + r, cc = c + (r > 0 ? 1u : 0u);
-        uint32_t nulls;
-        if (x == 0)      { p = ii;              nulls = __popc(mask0 & lowmask(cc)); }
-        else if (x == 1) { p = K_pi + 2 * ii;     nulls = __popc(mask0) + __popc(mask0 & lowmask(cc)) + __popc(mask2 & lowmask(cc)); }
-        else             { p = K_pi + 2 * ii + 1; nulls = __popc(mask0) + __popc(mask0 & lowmask(c + 1)) + __popc(mask2 & lowmask(cc)); }
-        cn = p - nulls;
-    }
-};
 
 __device__ __forceinline__ int sat16(int v) { return max(-32768, min(32767, v)); }
 __device__ __forceinline__ int clamp127(int v) { return max(-127, min(127, v)); }
 
 // Rate un-matching of one code block into the decoder's int8 layout d[i*3+x], tail included, the part k_dl3_rm_i8 and k_harq_rm share:
 // stage() puts the block's E_r soft bits in LDS (aligned dwords) when they fit; sum(t) is what position p of d[t] in the circular buffer
-// receives, e[rank(p) + t Nnn], t = 0, 1, .. (rank = non-NULL positions between k0 and p in walk order), summed; 0 where no soft bit reaches.
+// receives, e[rank(p) + t Nnn], t = 0, 1, .. (rank = non-NULL positions between k0 and p in walk order: rm_geom.h), summed; 0 where no soft bit reaches.
 struct Dl3Gather {
-    Rm3           rm;
+    RmGeom        rm;
     const int8_t *es;
     uint32_t      E, n; // E_r; the block's 3 (K + 4) positions
     __device__ void stage(const Dl3Desc &d, const int8_t *e_base, const uint32_t *e_off, int8_t *e_lds, uint32_t e_cap)
@@ -126,11 +81,8 @@ struct Dl3Gather {
     __device__ int sum(uint32_t t) const
     {
         const uint32_t i = t / 3;
-        uint32_t       p, cn;
-        rm.pos_cnt(i, (int)(t - 3 * i), p, cn);
-        int v = 0;
-        if (p < rm.N_cb)
-            for (uint32_t k = p >= rm.k0m ? cn - rm.cnt_k0 : rm.Nnn - rm.cnt_k0 + cn; k < E; k += rm.Nnn) v += es[k];
+        int            v = 0;
+        for (uint32_t k = rm.rank(i, t - 3 * i); k < E; k += rm.Nnn) v += es[k];
         return v;
     }
 };

@@ -13,6 +13,7 @@
 
 #include "../../include/mi_lte.h"
 #include "lte_tables.h"
+#include "rm_geom.h"
 #include "synth.hpp"
 
 namespace synth {
@@ -238,10 +239,9 @@ int mi_lte_dlsch_layout_nl(uint32_t tbs, uint32_t G, uint32_t Q_m, uint32_t N_L,
     if (C * K != Bp) return MI_LTE_ERR_UNSUPPORTED; // filler bits, or blocks of two sizes
     memset(out, 0, sizeof(*out));
     out->C = C; out->K = K; out->B = B;
-    const uint32_t R = (K + 4 + 31) / 32, K_w = 96 * R, K_mimo = (tx_mode == 3 || tx_mode == 4 || tx_mode == 8 || tx_mode == 9) ? 2 : 1;
-    const uint32_t N_ir = dlsch->N_soft / (K_mimo * std::min(dlsch->M_dl_harq, 8u));
-    out->N_cb = std::min(N_ir / C, K_w);
-    out->k0   = R * (2 * ((out->N_cb + 8 * R - 1) / (8 * R)) * rv + 2);
+    const RmSoftBuf sb = rm_soft_buffer(K + 4, C, tx_mode, dlsch->N_soft, dlsch->M_dl_harq, true, rv);
+    out->N_cb = sb.N_cb;
+    out->k0   = sb.k0;
     if (out->N_cb < 2) return MI_LTE_ERR_INVALID_ARG; // (position 1 of the buffer is the first that is never NULL)
     const uint32_t Gp = G / (N_L * Q_m), gam = Gp % C, lo = Gp / C;
     for (uint32_t r = 0, off = 0; r < C; r++) {
@@ -417,8 +417,7 @@ static int synth_dl_units(const mi_lte_dl_cfg *cfg, uint32_t n_units, const uint
             synth::crc24a(b.data(), al.tbs, b.data() + al.tbs);
             if (h_tx_bits) memcpy(h_tx_bits + ((size_t)u * n_alloc + a) * tbs_stride, b.data(), al.tbs);
             synth::turbo_encode(b.data(), K, true, d.data());
-            const uint32_t K_mimo = (al.tx_mode == 3 || al.tx_mode == 4 || al.tx_mode == 8 || al.tx_mode == 9) ? 2 : 1;
-            synth::rate_match(d.data(), K + 4, 250368 / (K_mimo * 8), al.rv_idx, E, e.data());
+            synth::rate_match(d.data(), K + 4, 250368 / (rm_k_mimo(al.tx_mode) * 8), al.rv_idx, E, e.data());
             synth::gold((al.rnti << 14) | (sf << 9) | cell, E, c.data());
             for (uint32_t i = 0; i < E; i++) e[i] ^= c[i];
             const uint32_t     M = E / Qm;

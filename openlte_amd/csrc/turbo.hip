@@ -27,6 +27,7 @@
 #include "plan_core.hpp"
 #include "turbo_swar.h"
 #include "soft_pack.h"
+#include "rm_geom.h"
 
 using namespace turbo_geom;
 
@@ -234,78 +235,8 @@ template <typename T> struct SrcDirect {
 };
 
 // (b) from rate-matched, descrambled soft bits e[0..E) of a PDSCH allocation: turbo rate
-// un-matching (liblte_phy_rate_unmatch_turbo, liblte_phy.cc:11246-11490) fused in as a gather.
-// The circular buffer w[0..3*K_pi) holds, column-major, the sub-block-interleaved streams; the only
-// NULL positions the reference's receiver honours are the N_d = 32R - D head-padding slots of each
-// stream.  Walking w from k0 and consuming one e per non-NULL position means position p
-// receives e[rank(p) + t*Nnn], t = 0,1,.. (repeats are soft-combined by addition, :11402-11416), with
-// rank(p) = number of non-NULL positions between k0 and p in walk order.  Head padding sits in row 0,
-// so "NULLs below p" is a popcount over the 32 columns.
-struct RmGeom {
-    uint32_t R, K_pi, N_d, N_cb, k0m, Nnn, cnt_k0, mask0, mask2;
-    __device__ __forceinline__ static uint32_t lowmask(uint32_t n) { return n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u); }
-    __device__ __forceinline__ uint32_t nulls_below(uint32_t p) const
-    {
-        if (p <= K_pi) return __popc(mask0 & lowmask((p + R - 1) / R));
-        const uint32_t q = p - K_pi, a = (q + 1) >> 1, b = q >> 1;
-        return __popc(mask0) + __popc(mask0 & lowmask((a + R - 1) / R)) + __popc(mask2 & lowmask((b + R - 1) / R)) +
-               ((b > K_pi - 1) ? 1u : 0u);
-    }
-    __device__ __forceinline__ uint32_t cnt(uint32_t p) const { return p - nulls_below(p); }
-    // geometry per liblte_phy.cc:11283-11287 (R), :11371-11399 (K_w, N_ir, N_cb, k0) with the constants
-    // liblte_phy_pdsch_channel_decode passes (M_dl_harq = 8, N_soft = 250368, :3843-3844), C = 1
-    __device__ __forceinline__ void init(uint32_t D, uint32_t tx_mode, uint32_t rv, uint32_t N_soft = 250368,
-                                         uint32_t M_dl_harq = 8, uint32_t C = 1, bool limited = true)
-    {
-        R    = (D + 31) / 32;
-        K_pi = 32 * R;
-        N_d  = K_pi - D;
-        const uint32_t K_w = 3 * K_pi, K_mimo = (tx_mode == 3 || tx_mode == 4 || tx_mode == 8 || tx_mode == 9) ? 2 : 1;
-        const uint32_t N_ir = N_soft / (K_mimo * (M_dl_harq < 8 ? M_dl_harq : 8));
-        N_cb = (limited && N_ir / C < K_w) ? N_ir / C : K_w; // DLSCH/PCH only (liblte_phy.cc:11387-11398)
-        const uint32_t k0 = R * (2 * ((N_cb + 8 * R - 1) / (8 * R)) * rv + 2);
-        k0m  = k0 % N_cb;
-        mask0 = mask2 = 0;
-        for (uint32_t c = 0; c < 32; c++) {
-            const uint32_t P = __brev(c) >> 27; // inter-column permutation = 5-bit reversal (36.212 table 5.1.4-1)
-            if (P < N_d) mask0 |= 1u << c;
-            if (P + 1 < N_d) mask2 |= 1u << c;
-        }
-        Nnn    = cnt(N_cb);
-        cnt_k0 = cnt(k0m);
-    }
-    // circular-buffer position of d[i*3+x]
-    __device__ __forceinline__ uint32_t pos(uint32_t i, int x) const
-    {
-        const uint32_t n = i + N_d;
-        if (x == 2) {
-            const uint32_t m = n - 1, ii = (__brev(m & 31) >> 27) * R + (m >> 5);
-            return K_pi + 2 * ii + 1;
-        }
-        const uint32_t ii = (__brev(n & 31) >> 27) * R + (n >> 5);
-        return x == 0 ? ii : K_pi + 2 * ii;
-    }
-    // the same position together with its non-NULL count below it, without integer division: the
-    // element sits in column c, row r of its stream's R x 32 matrix, and only row 0 holds NULLs, so
-    // "NULL slots below" is a popcount over the columns up to c (+1 if r > 0)
-    __device__ __forceinline__ void pos_cnt(uint32_t i, int x, uint32_t &p, uint32_t &cn) const
-    {
-        const uint32_t n = i + N_d - (x == 2 ? 1u : 0u), c = __brev(n & 31) >> 27, r = n >> 5, ii = c * R + r;
-        const uint32_t cc = c + (r > 0 ? 1u : 0u);
-        uint32_t nulls;
-        if (x == 0) {
-            p     = ii;
-            nulls = __popc(mask0 & lowmask(cc));
-        } else if (x == 1) {
-            p     = K_pi + 2 * ii;
-            nulls = __popc(mask0) + __popc(mask0 & lowmask(cc)) + __popc(mask2 & lowmask(cc));
-        } else {
-            p     = K_pi + 2 * ii + 1;
-            nulls = __popc(mask0) + __popc(mask0 & lowmask(c + 1)) + __popc(mask2 & lowmask(cc));
-        }
-        cn = p - nulls;
-    }
-};
+// un-matching (liblte_phy_rate_unmatch_turbo, liblte_phy.cc:11246-11490) fused in as a gather over
+// the circular buffer's geometry (rm_geom.h: RmGeom, and rm_combo, the index of a size's rank tables).
 
 // Everything the per-code-block kernels need to know about their block, gathered once per decode by k_cb_desc: read through the
 // allocation tables it is a chain of three dependent L2 round trips at the start of every workgroup (slot -> allocation -> its fields ->
@@ -350,8 +281,8 @@ struct SrcRateUnmatch {
     static constexpr bool kIntegerValued = true; // sums of int8 soft bits
     uint32_t e_cap; // bytes of LDS available for staging e (0 = gather from global)
     GroupDesc       g;
-    const uint16_t *tabs; // [12][3K] rank of every d element in the order e is consumed: DL per (rv, K_mimo), then UL per rv
-    const uint32_t *nnn;  // [12]     non-NULL slots per lap of the circular buffer
+    const uint16_t *tabs; // [RM_N_COMBOS][3K] rank of every d element in the order e is consumed: DL per (rv, K_mimo), then UL per rv
+    const uint32_t *nnn;  // [RM_N_COMBOS]     non-NULL slots per lap of the circular buffer
     const uint16_t *tab;
     const int8_t   *e;
     uint32_t        E, Nnn, K_;
@@ -1634,19 +1565,23 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     }
 }
 
-// one thread per code block of the group: the descriptor the per-code-block kernels read (CbDesc)
+// the descriptor the per-code-block kernels read, of code-block slot cb; nnn: its size's non-NULL counts per lap [RM_N_COMBOS]
+__device__ __forceinline__ CbDesc cb_desc(const GroupDesc &g, uint32_t cb, const uint32_t *nnn)
+{
+    const uint32_t a = g.cb_alloc[cb];
+    CbDesc d;
+    d.alloc = a; d.e_off = g.e_off[a]; d.E = g.e_len[a]; d.combo = rm_combo(g.ul, g.allocs[a].rv_idx, g.allocs[a].tx_mode); d.Nnn = nnn[d.combo];
+    d.hard  = (g.allocs[a].mod_type >= 2 && d.E <= d.Nnn) ? 1u : 0u; // the de-mapper's 16QAM / 64QAM soft bits are all +-127 (liblte_phy.cc:9573-9659), and no position is summed
+    d.tbs   = g.allocs[a].tbs; d.pk = (g.soft_pk && g.allocs[a].mod_type >= 2) ? 1u : 0u;
+    return d;
+}
+
+// one thread per code block of the group
 __global__ __launch_bounds__(256) void k_cb_desc(GroupDesc g, uint32_t n_cb, const uint32_t *__restrict__ nnn, CbDesc *__restrict__ out)
 {
     const uint32_t cb = blockIdx.x * blockDim.x + threadIdx.x;
     if (cb >= n_cb) return;
-    const uint32_t a = g.cb_alloc[cb], txm = g.allocs[a].tx_mode;
-    const uint32_t combo = g.ul ? 8u + (g.allocs[a].rv_idx & 3u)
-                                : ((g.allocs[a].rv_idx & 3u) << 1) | ((txm == 3 || txm == 4 || txm == 8 || txm == 9) ? 1u : 0u);
-    CbDesc d;
-    d.alloc = a; d.e_off = g.e_off[a]; d.E = g.e_len[a]; d.combo = combo; d.Nnn = nnn[combo];
-    d.hard  = (g.allocs[a].mod_type >= 2 && d.E <= d.Nnn) ? 1u : 0u; // the de-mapper's 16QAM / 64QAM soft bits are all +-127 (liblte_phy.cc:9573-9659), and no position is summed
-    d.tbs   = g.allocs[a].tbs; d.pk = (g.soft_pk && g.allocs[a].mod_type >= 2) ? 1u : 0u;
-    out[cb] = d;
+    out[cb] = cb_desc(g, cb, nnn);
 }
 
 // the same for a merged decode: one thread per code-block slot of the whole batch, the slot's size found by bisection of the table
@@ -1659,33 +1594,18 @@ __global__ __launch_bounds__(256) void k_cb_desc_multi(GroupDesc g, uint32_t n_c
         const uint32_t mid = (lo + hi) >> 1;
         if (segs[mid].cb_base <= cb) lo = mid; else hi = mid;
     }
-    const uint32_t a = g.cb_alloc[cb], txm = g.allocs[a].tx_mode;
-    const uint32_t combo = g.ul ? 8u + (g.allocs[a].rv_idx & 3u)
-                                : ((g.allocs[a].rv_idx & 3u) << 1) | ((txm == 3 || txm == 4 || txm == 8 || txm == 9) ? 1u : 0u);
-    CbDesc d;
-    d.alloc = a; d.e_off = g.e_off[a]; d.E = g.e_len[a]; d.combo = combo; d.Nnn = segs[lo].nnn[combo];
-    d.hard  = (g.allocs[a].mod_type >= 2 && d.E <= d.Nnn) ? 1u : 0u;
-    d.tbs   = g.allocs[a].tbs; d.pk = (g.soft_pk && g.allocs[a].mod_type >= 2) ? 1u : 0u;
-    out[cb] = d;
+    out[cb] = cb_desc(g, cb, (const uint32_t *)segs[lo].nnn);
 }
 
-// rank tables for the fused rate un-matching: one launch per block size, cached in the context.
-// combo 0..7 = rv*2 + (K_mimo == 2) with M_dl_harq = 8, N_soft = 250368, C = 1 as liblte_phy_pdsch_channel_decode passes them;
-// combo 8..11 = UL-SCH, rv = combo - 8: ulsch_channel_decode passes chan_type ULSCH, so N_cb = K_w (liblte_phy.cc:12437-12449).
+// rank tables for the fused rate un-matching: one launch per block size, cached in the context; one table per combination (rm_geom.h: rm_combo)
 __global__ __launch_bounds__(256) void k_rm_rank_table(uint32_t K, uint16_t *__restrict__ tabs, uint32_t *__restrict__ nnn)
 {
     const uint32_t combo = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
-    RmGeom rm;
-    if (combo < 8) rm.init(K + 4, (combo & 1) ? 3 : 1, combo >> 1);
-    else           rm.init(K + 4, 1, combo - 8, 1, 1, 1, false);
+    const RmGeom rm = rm_combo_geom(combo, K + 4);
     if (t == 0) nnn[combo] = rm.Nnn;
     if (t >= 3 * K) return;
     const uint32_t x = t / K, i = t - x * K;
-    uint32_t p, c;
-    rm.pos_cnt(i, (int)x, p, c);
-    uint32_t k = 0xFFFFu;
-    if (p < rm.N_cb) k = (p >= rm.k0m) ? c - rm.cnt_k0 : rm.Nnn - rm.cnt_k0 + c;
-    tabs[(size_t)combo * 3 * K + t] = (uint16_t)k;
+    tabs[(size_t)combo * 3 * K + t] = (uint16_t)rm.rank(i, x); // (RM_NO_RANK: 0xFFFF)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1698,27 +1618,31 @@ struct RmParams { uint32_t D, E, C, tx_mode, N_soft, M_dl_harq, limited, rv; };
 __global__ __launch_bounds__(256) void k_rate_unmatch_f32(const float *__restrict__ e, RmParams pr, uint32_t n_cb,
                                                           float *__restrict__ d)
 {
-    RmGeom rm;
-    rm.init(pr.D, pr.tx_mode, pr.rv, pr.N_soft, pr.M_dl_harq, pr.C, pr.limited != 0);
+    const RmGeom rm = rm_geom(pr.D, pr.C, pr.tx_mode, pr.N_soft, pr.M_dl_harq, pr.limited != 0, pr.rv);
     const uint32_t cb = blockIdx.y;
     const float   *eb = e + (size_t)cb * pr.E;
     float         *db = d + (size_t)cb * 3 * pr.D;
     for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < 3 * pr.D; t += gridDim.x * blockDim.x) {
         const uint32_t i = t / 3;
-        const int      x = (int)(t - 3 * i);
-        const uint32_t p = rm.pos(i, x);
+        uint32_t       k = rm.rank(i, t - 3 * i);
         float          v = (float)RX_NULL_AS_INT;
-        if (p < rm.N_cb) {
-            const uint32_t c = rm.cnt(p);
-            uint32_t       k = (p >= rm.k0m) ? c - rm.cnt_k0 : rm.Nnn - rm.cnt_k0 + c;
-            if (k < pr.E) {
-                v = eb[k];
-                for (k += rm.Nnn; k < pr.E; k += rm.Nnn)
-                    if (eb[k] != (float)RX_NULL_AS_INT) v += eb[k];
-            }
+        if (k < pr.E) {
+            v = eb[k];
+            for (k += rm.Nnn; k < pr.E; k += rm.Nnn)
+                if (eb[k] != (float)RX_NULL_AS_INT) v += eb[k];
         }
         db[t] = v;
     }
+}
+
+// Termination value u = 0..11 of a code block, d[K + u / 3][u % 3], from the allocation's soft bits e[0..E): the rank tables stop at K, so
+// the geometry is built from the block's combination for these twelve.  Sum over the laps, saturated to +-127.
+__device__ __forceinline__ int rm_tail_value(uint32_t K, uint32_t combo, uint32_t u, const int8_t *e, uint32_t E)
+{
+    const RmGeom rm = rm_combo_geom(combo, K + 4);
+    int          v  = 0;
+    for (uint32_t k = rm.rank(K + u / 3, u % 3); k < E; k += rm.Nnn) v += e[k];
+    return max(-127, min(127, v));
 }
 
 // ---- BCJR mode of the PDSCH / PUSCH chains (MI_LTE_TURBO_BCJR): the max-log-MAP decoder (bcjr.hip) takes int8 channel values
@@ -1732,13 +1656,7 @@ __global__ __launch_bounds__(256) void k_rm_to_i8(GroupDesc g, uint32_t K, uint3
     // "never filled" both read 0 without a predicate), then four trellis positions per thread: their three rank words come in as
     // 8-byte loads, the twelve values leave as three dwords
     extern __shared__ __attribute__((aligned(16))) int8_t e_lds[];
-    __shared__ RmGeom rm_s;
-    const uint32_t cb = blockIdx.x, D = K + 4, a = g.cb_alloc[cb], txm = g.allocs[a].tx_mode, rv = g.allocs[a].rv_idx & 3u;
-    if (threadIdx.x == 0) { // the geometry is the same for the whole code block; only the 12 tail values need it (the tables stop at K)
-        if (g.ul) rm_s.init(D, 1, rv, 1, 1, 1, false);
-        else      rm_s.init(D, txm, rv);
-    }
-    const uint32_t combo = g.ul ? 8u + rv : (rv << 1) | ((txm == 3 || txm == 4 || txm == 8 || txm == 9) ? 1u : 0u);
+    const uint32_t cb = blockIdx.x, D = K + 4, a = g.cb_alloc[cb], combo = rm_combo(g.ul, g.allocs[a].rv_idx, g.allocs[a].tx_mode);
     const uint16_t *tab = tabs + (size_t)combo * 3 * K;
     const uint32_t Nnn = nnn[combo], E = g.e_len[a];
     const int8_t  *e = g.e_base + (size_t)g.e_off[a] * 64;
@@ -1778,18 +1696,7 @@ __global__ __launch_bounds__(256) void k_rm_to_i8(GroupDesc g, uint32_t K, uint3
         uint32_t *dst = reinterpret_cast<uint32_t *>(db + 3 * (size_t)i0);
         dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
     }
-    if (threadIdx.x < 12) { // the termination values d[K..K+3][x]
-        const uint32_t t = 3 * K + threadIdx.x, i = t / 3;
-        const int      x = (int)(t - 3 * i);
-        const RmGeom  &rm = rm_s;
-        const uint32_t p = rm.pos(i, x);
-        uint32_t       k = 0xFFFFu;
-        if (p < rm.N_cb) { const uint32_t c = rm.cnt(p); k = (p >= rm.k0m) ? c - rm.cnt_k0 : rm.Nnn - rm.cnt_k0 + c; }
-        int v = 0;
-        if (k != 0xFFFFu)
-            for (; k < E; k += Nnn) v += e[k];
-        db[t] = (int8_t)max(-127, min(127, v));
-    }
+    if (threadIdx.x < 12) db[3 * K + threadIdx.x] = (int8_t)rm_tail_value(K, combo, threadIdx.x, e, E);
 }
 
 // The BCJR chain's first stage in one kernel: turbo rate un-matching (the REF path's rank-table gather, sums of repeats saturated to +-127) straight
@@ -1827,20 +1734,8 @@ __global__ __launch_bounds__(384) void k_rm_bcjr_prep(SrcRateUnmatch src, uint32
         *reinterpret_cast<uint4 *>(s1_lds + 16 * u) = Q[0];
     }
     if (u < 12) { // the termination values d[K..K+3][x] (the rank tables stop at K): element 3K + u -> x[u] of k_bcjr_prep's record
-        const uint32_t a = src.g.desc[cb].alloc, txm = src.g.allocs[a].tx_mode, rv = src.g.allocs[a].rv_idx & 3u;
-        RmGeom rm;
-        if (src.g.ul) rm.init(K + 4, 1, rv, 1, 1, 1, false);
-        else          rm.init(K + 4, txm, rv);
-        const uint32_t i = K + u / 3;
-        const int      x = (int)(u % 3);
-        const uint32_t p = rm.pos(i, x);
-        int            t = 0;
-        if (p < rm.N_cb) {
-            const uint32_t c = rm.cnt(p);
-            for (uint32_t k = (p >= rm.k0m) ? c - rm.cnt_k0 : rm.Nnn - rm.cnt_k0 + c; k < src.E; k += src.Nnn) t += src.e[k];
-        }
         const uint32_t slot = u < 6 ? ((u & 1u) ? 3 + (u >> 1) : (u >> 1)) : ((u & 1u) ? 9 + ((u - 7) >> 1) : 6 + ((u - 6) >> 1)); // t1s t1p t2s t2p
-        B.tail[((size_t)cb << 4) + slot] = (int8_t)max(-127, min(127, t));
+        B.tail[((size_t)cb << 4) + slot] = (int8_t)rm_tail_value(K, src.g.desc[cb].combo, u, src.e, src.E);
     }
     __syncthreads();
     if (nv >= 0) { // S2[i] = S1[pi[i]]
@@ -2021,11 +1916,11 @@ static int rm_rank_tables(mi_lte_ctx *ctx, uint32_t K, RmTables *out)
     auto it = ctx->rm_tables.find(K);
     if (it == ctx->rm_tables.end()) {
         RmTables t;
-        MI_HIP_CHECK(ctx, hipMalloc((void **)&t.d_tabs, sizeof(uint16_t) * 12 * 3 * K));
-        MI_HIP_CHECK(ctx, hipMalloc((void **)&t.d_nnn, sizeof(uint32_t) * 12));
+        MI_HIP_CHECK(ctx, hipMalloc((void **)&t.d_tabs, sizeof(uint16_t) * RM_N_COMBOS * 3 * K));
+        MI_HIP_CHECK(ctx, hipMalloc((void **)&t.d_nnn, sizeof(uint32_t) * RM_N_COMBOS));
         ctx->owned.push_back(t.d_tabs);
         ctx->owned.push_back(t.d_nnn);
-        MI_LAUNCH(ctx, "k_rm_rank_table", k_rm_rank_table, dim3((3 * K + 255) / 256, 12), dim3(256), 0, K, t.d_tabs, t.d_nnn);
+        MI_LAUNCH(ctx, "k_rm_rank_table", k_rm_rank_table, dim3((3 * K + 255) / 256, RM_N_COMBOS), dim3(256), 0, K, t.d_tabs, t.d_nnn);
         MI_HIP_CHECK(ctx, hipGetLastError());
         it = ctx->rm_tables.emplace(K, t).first;
     }
